@@ -12,9 +12,16 @@ its own B samples; value = N * B * K / max-over-ranks time.
   python -m torch.distributed.run --nnodes=1 --nproc-per-node N \
       --master-addr 127.0.0.1 --master-port P bench.py --gpus N --steps K --warmup W
 
-Prints ONE JSON line (rank 0) with `roofline` (dominant kernel, HIP-event timed
-inside the timed region) and, at N = 1, `cpu_baseline` (the CPU oracle in its
-reference-literal float mode on a bounded sample, host cores).
+Prints ONE JSON line (rank 0).  A plain run sets up, warms up, times the K steps and
+prints the headline (`value`, `ms_per_step`, ...); `--dump-outputs DIR` also writes
+the logits of the last timed step to DIR/logits.npy.  Everything else the benchmark
+measures runs only under `--full`: `roofline` (dominant kernel, HIP events on a second
+pass of the same steps, HBM traffic counted by rocprofv3 child runs), the other input
+formats and BASELINE configurations (`legs`), the host-fed, captured and general
+cases, the fallback / device-status checks and, at N = 1, `cpu_baseline` (the CPU
+oracle in its reference-literal float mode on a bounded sample, host cores).
+
+  python bench.py --gpus 1 --steps 20 --warmup 5 --full
 
 Other BASELINE configs: C5 (mixed 2/4-bit, 95 % pruned, T = 50, 512 samples per GPU)
   python bench.py --frames 50 --batch 512 --layer-bits 2,4,2,4 --prune 0.95 --classes 10
@@ -57,6 +64,8 @@ PMC_SUMMARY = [os.path.join(ROOT, "profiles", n) for n in ("r06_pmc_summary.json
 PARITY_VS_FLOAT = next((p for p in (os.path.join(ROOT, "profiles", n) for n in
                                     ("r05_int_vs_float.json", "r04_int_vs_float.json", "r02_int_vs_float.json"))
                         if os.path.exists(p)), os.path.join(ROOT, "profiles", "r02_int_vs_float.json"))
+# --dump-outputs writes at most this many bytes
+DUMP_LIMIT = 64 << 20
 
 
 def parse(argv=None):
@@ -99,10 +108,10 @@ def parse(argv=None):
                        "marked `pcie_inclusive`")
   ap.add_argument("--no-fed-leg", action="store_true",
                   help="skip the short host-fed leg (ev1 frames through the feeder) that the "
-                       "default run appends to the line as `fed`")
+                       "--full run appends to the line as `fed`")
   ap.add_argument("--no-legs", action="store_true",
                   help="skip the other BASELINE configurations (C2, C5, the float32 formats) that the "
-                       "default run times after the headline and reports as `legs`")
+                       "--full run times after the headline and reports as `legs`")
   ap.add_argument("--random-bn", action="store_true",
                   help="BatchNorm with random running statistics / scale / bias (a trained "
                        "model) instead of the freshly initialised one (mean 0, var 1, scale 1, "
@@ -126,10 +135,19 @@ def parse(argv=None):
                   help="print the full record on stdout instead of the compact line (tools/*.sh)")
   ap.add_argument("--no-live-traffic", action="store_true",
                   help="skip the two rocprofv3 --pmc child runs (FETCH_SIZE, WRITE_SIZE: one step each) that the "
-                       "default headline run uses to MEASURE `roofline.traffic`; the committed profiles/ "
+                       "--full headline run uses to MEASURE `roofline.traffic`; the committed profiles/ "
                        "figure is reported instead, labelled as such")
   ap.add_argument("--allow-diag", action="store_true",
                   help="accept a diagnostic libsnnqp (SNNQP_DIAG_LIB); the line is marked")
+  ap.add_argument("--full", action="store_true",
+                  help="besides the headline, measure and check everything else: per-kernel rooflines "
+                       "(a second, event-carrying pass of the steps), live HBM traffic, the u8 / captured / "
+                       "host-fed / general cases, the other BASELINE configurations, fallback counters, the "
+                       "device status word and the CPU baseline (the --no-* options above trim this run)")
+  ap.add_argument("--dump-outputs", type=str, default=None, metavar="DIR",
+                  help="after the timed steps, write what the last one returned (the gathered logits) "
+                       "to DIR/logits.npy (float32; a fixed, seeded sample of rows past %d MB)"
+                  % (DUMP_LIMIT >> 20))
   # test plumbing: the same step / fence / all-reduce code on CPU tensors over gloo with a
   # stand-in for model.apply (tests/test_host_cpu.py); never a measurement
   ap.add_argument("--backend", choices=("nccl", "gloo"), default="nccl", help=argparse.SUPPRESS)
@@ -339,6 +357,23 @@ def config_leg(base_args, overrides, dev, steps, warmup, capture):
   leg["fallbacks"] = ops.fallback_counts()
   leg["device_status"] = ops.device_status()
   return leg
+
+
+def dump_outputs(path, arrays):
+  """Writes {name: tensor} as path/<name>.npy in float32 (float64 stays float64).  Past DUMP_LIMIT
+  bytes in all, each array keeps a fixed, seeded sample of its rows, in row order."""
+  import numpy as np
+  host = {}
+  for name, t in arrays.items():
+    a = t.detach().cpu().numpy()
+    host[name] = a if a.dtype == np.float64 else a.astype(np.float32)
+  total = sum(a.nbytes for a in host.values())
+  os.makedirs(path, exist_ok=True)
+  for name, a in host.items():
+    if total > DUMP_LIMIT:
+      keep = max(1, a.shape[0] * DUMP_LIMIT // total)
+      a = a[np.sort(np.random.default_rng(20240611).choice(a.shape[0], keep, replace=False))]
+    np.save(os.path.join(path, name + ".npy"), a)
 
 
 def make_feeder(x_dev, dev, nbatches=4):
@@ -633,14 +668,15 @@ def main(argv=None):
   # The per-kernel HIP events stay OUT of the timed steps (they cost 0.8 % there, round 4): the
   # warm-up creates them once (the first timing event of a process costs tens of milliseconds on
   # a cold box), the timed region runs bare, and a second pass of the same K steps right after it
-  # carries the events the rooflines are computed from.
-  if ops is not None:
+  # carries the events the rooflines are computed from (--full).
+  full = ops is not None and args.full
+  if full:
     ops.profile_start()
   out = None
   for i in range(args.warmup):
     out = step()
   fence()
-  if ops is not None:
+  if full:
     ops.profile_stop()
   eager_step = step
   if args.graph:
@@ -668,10 +704,12 @@ def main(argv=None):
   if trace and rank == 0:
     print("enqueue done at (ms):", [round(m * 1e3, 2) for m in marks], "all done", round(dt * 1e3, 2),
           file=sys.stderr)
+  if args.dump_outputs and rank == 0:
+    dump_outputs(args.dump_outputs, {"logits": out})
   # {tag: (launches, total ms)}: a second pass of the same steps, launched eagerly with a HIP event
   # pair around every block's launch on its stream
   prof = {}
-  if ops is not None:
+  if full:
     ops.profile_start()
     for _ in range(args.steps):
       eager_step()
@@ -692,7 +730,7 @@ def main(argv=None):
   # shows in rank 0's line, not only in the maximum
   mine = {"rank": rank, "seconds": dt,
           "kernels": {tag: round(ms / max(n, 1), 5) for tag, (n, ms) in (prof or {}).items()}}
-  if ops is not None:
+  if full:
     mine["fallbacks"] = dict(ops.fallback_counts(), **ops.workqueue_stats())
     mine["device_status"] = ops.device_status(dev)
   if collective:
@@ -712,7 +750,7 @@ def main(argv=None):
   # the same steps on resident uint8 frames (the format of rounds 1 and 2's headline), when the
   # line itself is on bit-packed frames
   alt = None
-  if (gpu and ops is not None and frames_u8 is not None and args.input == "ev1"
+  if (gpu and full and frames_u8 is not None and args.input == "ev1"
       and args.feed == "resident" and not args.no_fed_leg and not args.graph):
     for _ in range(2):
       parallel.all_gather_rows(apply_fn(frames_u8))
@@ -735,7 +773,7 @@ def main(argv=None):
   # line with it, and the figure is a per-GPU one anyway (--graph runs it on every rank).
   cap_leg = None
   # (Every input format captures: float32 frames are checked on the device since round 5.)
-  if (gpu and ops is not None and not args.stand_in and not args.graph and args.feed == "resident"
+  if (gpu and full and not args.stand_in and not args.graph and args.feed == "resident"
       and not args.no_fed_leg and world == 1):
     captured = nn.capture(model, variables, x, trgt=None, train=False, rng=None)
     for _ in range(2):
@@ -754,7 +792,7 @@ def main(argv=None):
     del captured
   # the host-fed leg (every rank runs it: the step holds a collective); binary frames only
   fed = None
-  if (gpu and ops is not None and frames_u8 is not None and args.feed == "resident"
+  if (gpu and full and frames_u8 is not None and args.feed == "resident"
       and not args.no_fed_leg and not args.counts and not args.graph):
     fed = fed_leg(args, frames_u8, apply_fn, parallel, fence, dev, args.steps, min(args.warmup, 2))
     tf = torch.tensor([fed["ms_per_step"]], device=dev, dtype=torch.float64)
@@ -766,7 +804,7 @@ def main(argv=None):
   # the general case beside the headline's best case (every rank runs it: the step holds a collective)
   general = None
   notes_main = dict(ops.PROFILE_NOTES) if ops is not None else {}
-  if (gpu and ops is not None and args.model == "c3" and args.feed == "resident" and not args.no_fed_leg
+  if (gpu and full and args.model == "c3" and args.feed == "resident" and not args.no_fed_leg
       and not args.counts and not args.random_bn and not args.graph and args.input == "ev1"):
     general = general_leg(args, model, dev, B, T, parallel, fence, args.steps, min(args.warmup, 3))
     tg = torch.tensor([general["ms_per_step"]], device=dev, dtype=torch.float64)
@@ -823,7 +861,7 @@ def main(argv=None):
   line["collective"] = ("%s process group of %d rank(s): all-gather of the logits every step, "
                         "barrier + all-reduce(MAX) around the timed region" % (args.backend, world)
                         ) if collective else "none (one process, no process group)"
-  if ops is not None:
+  if full:
     line["fallbacks"] = ops.fallback_counts()      # blocks on the direct-form kernel (should be 0)
     line["fallbacks"].update(ops.workqueue_stats())   # static patch walks, arithmetic instead of table dequantisation
     line["device_status"] = ops.device_status()       # 0: no kernel reported a broken invariant
@@ -859,14 +897,15 @@ def main(argv=None):
                  + (", fed from host memory" if args.feed == "host" else ""),
         "bn_flags": "random statistics: sub, mul, add" if args.random_bn else
                     "mean 0 / bias 0 / one multiplier for every channel (as initialised): no BatchNorm "
-                    "instruction in conv1 / conv2 (the multiplier is folded into the shared table's entries)",
-        "dequant_form": {t: v.get("dequant") for t, v in notes_main.items()}}
-  # the default headline run measures the HBM bytes of its kernels itself (two counter passes of one
+                    "instruction in conv1 / conv2 (the multiplier is folded into the shared table's entries)"}
+    if full:
+      line["config"]["specialisations"]["dequant_form"] = {t: v.get("dequant") for t, v in notes_main.items()}
+  # the --full headline run measures the HBM bytes of its kernels itself (two counter passes of one
   # step each in child processes); any failure falls back to the committed figure, labelled
   default_headline = (world == 1 and args.model == "c3" and args.input == "ev1" and B == 1024 and T == 20
                       and not args.layer_bits and args.bits == 4 and not args.counts and not args.random_bn
                       and args.feed == "resident" and not args.no_fed_leg and not args.graph
-                      and not args.no_legs)
+                      and not args.no_legs and full)
   if default_headline and not args.no_live_traffic and not os.environ.get("SNNQP_BENCH_NO_PMC"):
     global LIVE_TRAFFIC
     try:
@@ -878,12 +917,13 @@ def main(argv=None):
       args._live_traffic_ok = True
     else:
       line["traffic_live"] = "not measured: %s" % src
-  line.update(rooflines_of(args, prof, B, T, lb, notes_main))
-  if os.path.exists(PARITY_VS_FLOAT):
-    with open(PARITY_VS_FLOAT) as f:
-      line["parity_vs_float"] = dict(json.load(f).get("summary") or {},
-                                     source="committed %s (CPU, oracle int vs float mode; not "
-                                            "measured in this run)" % os.path.relpath(PARITY_VS_FLOAT, ROOT))
+  if full:
+    line.update(rooflines_of(args, prof, B, T, lb, notes_main))
+    if os.path.exists(PARITY_VS_FLOAT):
+      with open(PARITY_VS_FLOAT) as f:
+        line["parity_vs_float"] = dict(json.load(f).get("summary") or {},
+                                       source="committed %s (CPU, oracle int vs float mode; not "
+                                              "measured in this run)" % os.path.relpath(PARITY_VS_FLOAT, ROOT))
   # the other single-GPU BASELINE configurations, timed in the same run: C2 as
   # BASELINE.json configs[1] names it (B = 256, T = 20, 8-bit, 50 % pruned; uint8 rows) and C5's
   # per-GPU share (B = 512, T = 50, mixed 2/4-bit, 95 % pruned, 10 classes; EV1 frames)
@@ -909,7 +949,7 @@ def main(argv=None):
         "c3_f32": config_leg(args, dict(model="c3", batch=1024, frames=20, bits=4, prune=0.9, input="f32",
                                         layer_bits=None, classes=11), dev, args.steps, 3, True),
     }
-  if world == 1 and not args.no_cpu_baseline and args.model == "c3":
+  if full and world == 1 and not args.no_cpu_baseline and args.model == "c3":
     line["cpu_baseline"] = cpu_baseline(args, variables_np)
   emit(args, line)
 
@@ -1017,7 +1057,7 @@ def live_traffic(argv_model, timeout=150.0):
     for name in ("FETCH_SIZE", "WRITE_SIZE"):
       cmd = [prof, "--kernel-trace", "--pmc", name, "--output-format", "csv", "-d", os.path.join(tmp, name.lower()),
              "--", sys.executable, os.path.abspath(__file__), "--steps", "1", "--warmup", "1", "--no-cpu-baseline",
-             "--no-fed-leg", "--no-legs", "--no-live-traffic", "--detail", os.devnull] + list(argv_model)
+             "--no-fed-leg", "--no-legs", "--no-live-traffic", "--full", "--detail", os.devnull] + list(argv_model)
       try:
         p = subprocess.run(cmd, cwd="/tmp", env=env, stdout=subprocess.DEVNULL, stderr=subprocess.PIPE,
                            timeout=max(10.0, timeout - (time.time() - t0)))

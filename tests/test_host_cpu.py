@@ -337,6 +337,46 @@ def test_bench_gpus_2_starts_its_own_ranks_on_gloo(tmp_path):
   assert err.count("bench.py rank {") >= 1
 
 
+def test_bench_dumps_the_last_timed_step_identically_from_run_to_run(tmp_path, monkeypatch):
+  """--dump-outputs DIR: rank 0 writes the gathered logits of the last timed step as DIR/logits.npy
+  (float32), every rank's rows in rank order, the same bytes in two runs with the same arguments;
+  past the size limit a fixed, seeded sample of rows is written."""
+  env = {k: v for k, v in os.environ.items()
+         if k not in ("WORLD_SIZE", "RANK", "LOCAL_RANK", "MASTER_PORT")}
+  got = []
+  for run in range(2):
+    out = tmp_path / ("out%d" % run)
+    rc, text, err = _bench(["--gpus", "2", "--backend", "gloo", "--stand-in", "--batch", "6", "--frames", "3",
+                            "--steps", "2", "--warmup", "1", "--dump-outputs", str(out)], env)
+    assert rc == 0, err
+    d = json.loads([l for l in text.splitlines() if l.startswith("{")][0])
+    assert d["steps"] == 2 and d["ms_per_step"] > 0 and d["higher_is_better"] is True and d["dtype"]
+    assert sorted(os.listdir(out)) == ["logits.npy"]
+    got.append(np.load(str(out / "logits.npy")))
+  want = []
+  for r in range(2):                   # the stand-in's per-sample function of rank r's seeded batch
+    g = torch.Generator()
+    g.manual_seed(8627169 + r)
+    x = (torch.rand((6, 3, 4, 4, 2), generator=g) < 1.0 - float(np.exp(-0.1))).to(torch.uint8)
+    f = x.reshape(6, -1).to(torch.float32).sum(1)
+    want.append(torch.stack([f * (k + 1) for k in range(11)], 1).numpy())
+  assert got[0].dtype == np.float32 and got[0].shape == (12, 11)
+  np.testing.assert_array_equal(got[0], np.concatenate(want))
+  assert got[0].tobytes() == got[1].tobytes()
+  sys.path.insert(0, ROOT)
+  import bench
+  monkeypatch.setattr(bench, "DUMP_LIMIT", 4000)
+  big = torch.arange(2000, dtype=torch.float64).reshape(1000, 2)
+  for run in range(2):
+    bench.dump_outputs(str(tmp_path / ("big%d" % run)), {"rows": big, "ids": torch.arange(1000)})
+  rows, ids = (np.load(str(tmp_path / "big0" / n)) for n in ("rows.npy", "ids.npy"))
+  assert rows.dtype == np.float64 and ids.dtype == np.float32
+  assert rows.nbytes + ids.nbytes <= 4000 and len(rows) == len(ids) > 100
+  np.testing.assert_array_equal(rows[:, 0], 2 * ids)
+  assert np.all(np.diff(ids) > 0)
+  assert rows.tobytes() == np.load(str(tmp_path / "big1" / "rows.npy")).tobytes()
+
+
 def test_bench_strong_scaling_splits_a_fixed_global_batch():
   """--scaling strong: the global batch (BASELINE config C4: 8192) is fixed and split over the
   ranks; an indivisible one is refused."""

@@ -2447,7 +2447,7 @@ def test_bench_runs_its_collectives_through_rccl_on_one_gpu(dev, tmp_path):
   env = {k: v for k, v in os.environ.items() if k not in ("WORLD_SIZE", "RANK", "LOCAL_RANK")}
   env.update(MASTER_ADDR="127.0.0.1", MASTER_PORT="29671")
   p = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--batch", "16", "--steps", "3",
-                      "--warmup", "1", "--no-cpu-baseline", "--no-fed-leg", "--single-rank-collective",
+                      "--warmup", "1", "--full", "--no-cpu-baseline", "--no-fed-leg", "--single-rank-collective",
                       "--detail", str(tmp_path / "detail.json")],
                      env=env, stdout=subprocess.PIPE, stderr=subprocess.PIPE, timeout=600, cwd=root)
   assert p.returncode == 0, p.stderr.decode()[-2000:]
@@ -2460,6 +2460,36 @@ def test_bench_runs_its_collectives_through_rccl_on_one_gpu(dev, tmp_path):
   r = d["ranks"][0]
   assert r["rccl"] not in (None, "", "unknown") and r["pci"].count(":") == 2
   assert d["fallbacks"]["conv_blocks"] == 0 and d["value"] > 0
+
+
+def test_plain_bench_run_times_the_steps_and_dumps_their_logits(dev, tmp_path):
+  """bench.py without --full: the headline keys only (no roofline pass, legs or baselines), and
+  --dump-outputs writes the logits of the last timed step -- the same numbers model.apply gives
+  on the batch bench.py builds from its seeds."""
+  import json, subprocess, sys
+  root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+  sys.path.insert(0, root)
+  import bench
+  from snnquantprune_amd import ops
+  env = {k: v for k, v in os.environ.items() if k not in ("WORLD_SIZE", "RANK", "LOCAL_RANK")}
+  argv = ["--batch", "16", "--steps", "3", "--warmup", "1"]
+  p = subprocess.run([sys.executable, os.path.join(root, "bench.py")] + argv +
+                     ["--dump-outputs", str(tmp_path / "out"), "--detail", os.devnull],
+                     env=env, stdout=subprocess.PIPE, stderr=subprocess.PIPE, timeout=600, cwd=root)
+  assert p.returncode == 0, p.stderr.decode()[-2000:]
+  short = json.loads(p.stdout.decode().rstrip("\n").splitlines()[-1])
+  assert short["steps"] == 3 and short["warmup"] == 1 and short["unit"] == "samples/s"
+  assert short["higher_is_better"] is True and short["dtype"] and short["ms_per_step"] > 0
+  assert abs(short["value"] - 16 / (short["ms_per_step"] * 1e-3)) < 1e-6 * short["value"]
+  for k in ("roofline", "roofline_dense", "legs", "cpu_baseline", "fallbacks", "kernel_ms"):
+    assert k not in short, k
+  got = np.load(str(tmp_path / "out" / "logits.npy"))
+  args = bench.parse(argv)
+  model, variables, _ = bench.build_model(args, dev)
+  x, _ = bench.build_input(args, dev, 0, 16, args.frames, 128, ops)
+  want = model.apply(variables, x, trgt=None, train=False, rng=None)[0]
+  assert got.dtype == np.float32 and got.shape == (16, 11)
+  np.testing.assert_array_equal(got, want.cpu().numpy())
 
 
 def test_eval_command_line_on_a_synthetic_workdir(dev, tmp_path):

@@ -8,7 +8,7 @@ cd /tmp && export TMPDIR=/tmp && cd "$GRAFT_REPO_ROOT"
 OUT=gpurun_out/pmc
 rm -rf $OUT          # (rocprofv3 adds files beside those of an earlier call: the summary would mix the runs)
 mkdir -p $OUT
-ARGS="--steps 1 --warmup 1 --no-cpu-baseline --no-fed-leg $@"
+ARGS="--full --steps 1 --warmup 1 --no-cpu-baseline --no-fed-leg $@"
 run() {  # name, counters...
   name=$1; shift
   rocprofv3 --kernel-trace --pmc "$@" --output-format csv -d $OUT/$name -- \
