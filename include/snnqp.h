@@ -409,6 +409,9 @@ int snnqp_dense_gated_forward(const uint32_t *s, const float *gate, int64_t NB, 
  *       frames are staged directly, 1/8 (binary) or 1/2 (counts <= 15) of the uint8 bytes;
  *       x_max / x_seen apply to EV4 as to U8), s_type BITS;
  *       any H, W, Cout and neuron kind.  SNNQP_IMPL_AUTO picks MFMA when it can.
+ *       EV1 / EV4 input is read by the MFMA kernel only: a block it does not take (s_type F32,
+ *       impl GENERIC, ...) is refused with SNNQP_EUNSUPPORTED and not counted as a fallback --
+ *       unpack the frames first (snnqp_unpack_frames).
  * x_max the largest input value the caller EXPECTS (1 for spikes and binary event frames;
  *       0 = unknown, taken as 1): with the weights' abs_sum_max it sizes the LDS tables the
  *       MFMA kernels dequantise through.  It is a hint, not a promise: the U8 kernel takes

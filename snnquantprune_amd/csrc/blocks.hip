@@ -83,6 +83,10 @@ int snnqp_conv_lif_forward(const void *x, int in_type, int64_t x_stride_t,
     return run_conv3x3_mfma(x, in_type, x_stride_t, x_stride_b, T, B, g, w, wt, bn,
                             nrn, u0, u_out, (uint32_t *)s_out, pool, x_max, x_seen, x_flags,
                             (hipStream_t)stream);
+  // the direct-form kernel reads no packed event frames: refused here, before it counts as a fallback
+  SNNQP_REQUIRE(in_type != SNNQP_EV1 && in_type != SNNQP_EV4, SNNQP_EUNSUPPORTED,
+                "conv_lif_forward: packed event frames need bit-packed spike output; unpack them first "
+                "(%s)", why ? why : "impl = GENERIC");
   SNNQP_REQUIRE(!(in_type == SNNQP_F32 && w->wtype == SNNQP_W_I8), SNNQP_EUNSUPPORTED,
                 "conv_lif_forward: float32 input into integer codes is staged by the event-layer MFMA "
                 "kernel only (%s); narrow it first (snnqp_narrow_f32 / snnqp_pack_bits_checked)",

@@ -746,6 +746,7 @@ def conv3d_lif_forward(x, geom: Conv3dGeom, weight: Weight, neuron: Optional[Neu
   if u0 is not None:
     u0 = _f32c(u0)
     assert tuple(u0.shape) == (B, OD, OH, OW, geom.Cout), (u0.shape, (B, OD, OH, OW, geom.Cout))
+  _zero_step_carry(u_out, u0, T)
   n = neuron.struct()
   with _timed("conv3d[%s]" % geom.tag()):
     L.check(L.lib().snnqp_conv3d_lif_forward(_ptr(pred), _ptr(xt), in_type, B * unit, unit, T, B, ctypes.byref(g),
@@ -905,6 +906,16 @@ def _tb_strides(x, T, B, time_major: bool, unit: int):
   return unit, T * unit
 
 
+def _zero_step_carry(u_out: Optional[torch.Tensor], u0: Optional[torch.Tensor], T: int):
+  """A scan over zero time steps returns its carry (spiking_learning.py:446-462): u0, or the zeros of
+  initialize_carry.  The kernels launch nothing for T = 0, so the state is written here."""
+  if u_out is not None and T == 0:
+    if u0 is None:
+      u_out.zero_()
+    else:
+      u_out.copy_(u0)
+
+
 def conv_lif_forward(x, geom: ConvGeom, weight: Weight, neuron: Neuron,
                      bn: Optional[BnCoeffs] = None, u0: Optional[torch.Tensor] = None,
                      want_u: bool = True, packed_out: bool = False, pool: int = 1,
@@ -947,6 +958,7 @@ def conv_lif_forward(x, geom: ConvGeom, weight: Weight, neuron: Neuron,
   if u0 is not None:
     u0 = _f32c(u0)
     assert tuple(u0.shape) == (B, OH, OW, geom.Cout), (u0.shape, (B, OH, OW, geom.Cout))
+  _zero_step_carry(u_out, u0, T)
   oshape = (T, B, OH // pool, OW // pool)
   if packed_out:
     s = torch.empty(oshape + ((geom.Cout + 31) // 32,), dtype=torch.int32, device=dev)
@@ -957,22 +969,31 @@ def conv_lif_forward(x, geom: ConvGeom, weight: Weight, neuron: Neuron,
   tag = "conv%dx%d[%dx%dx%d->%d]" % (geom.KH, geom.KW, geom.H, geom.W, geom.Cin, geom.Cout)
   if _PROFILE is not None and in_type == L.BITS and weight.is_int and tag not in PROFILE_NOTES:
     PROFILE_NOTES[tag] = {"dequant": conv_dequant_form(weight, neuron)}
-  speculate = (binary_first and not isinstance(x, (PackedFrames, PackedSpikes)) and in_type in (L.U8, L.F32)
-               and geom.Cin == 2 and weight.is_int and impl != L.IMPL_GENERIC and xt.ndim == 5)
+  # (the bit-packed variant writes bit-packed spikes only: float32 spikes take the frames as they are)
+  speculate = (binary_first and packed_out and not isinstance(x, (PackedFrames, PackedSpikes))
+               and in_type in (L.U8, L.F32) and geom.Cin == 2 and weight.is_int and impl != L.IMPL_GENERIC
+               and xt.ndim == 5)
   with _timed(tag):
     if speculate:
       pf, not_binary = pack_frames_checked(xt)
       ps_t, ps_b = _tb_strides(pf.data, T, B, time_major, pf.data.shape[-1])
-      L.check(L.lib().snnqp_conv_lif_forward(
-          _ptr(pf.data), L.EV1, ps_t, ps_b, T, B, ctypes.byref(g), ctypes.byref(w),
-          _ptr(weight.wt), ctypes.byref(b) if b is not None else None, ctypes.byref(n),
-          _ptr(u0), _ptr(u_out), _ptr(s), L.BITS if packed_out else L.F32, pool, impl,
-          1, None, None, _stream()))
+      try:
+        L.check(L.lib().snnqp_conv_lif_forward(
+            _ptr(pf.data), L.EV1, ps_t, ps_b, T, B, ctypes.byref(g), ctypes.byref(w),
+            _ptr(weight.wt), ctypes.byref(b) if b is not None else None, ctypes.byref(n),
+            _ptr(u0), _ptr(u_out), _ptr(s), L.BITS, pool, impl, 1, None, None, _stream()))
+      except L.SnnqpError as e:
+        # the bit-packed variant refused the block: nothing has been written to the outputs (only
+        # the checked pass has run, into its own buffers) -- the frames go in as they are
+        if e.code != L.EUNSUPPORTED:
+          raise
+        speculate = False
+    if speculate:
       # ... and the frames as they are, iff a value was not 0 or 1
       L.check(L.lib().snnqp_conv_lif_forward_pred(
           _ptr(not_binary), _ptr(xt), in_type, xs_t, xs_b, T, B, ctypes.byref(g), ctypes.byref(w),
           _ptr(weight.wt), ctypes.byref(b) if b is not None else None, ctypes.byref(n),
-          _ptr(u0), _ptr(u_out), _ptr(s), L.BITS if packed_out else L.F32, pool,
+          _ptr(u0), _ptr(u_out), _ptr(s), L.BITS, pool,
           int(x_max), _ptr(x_seen), _ptr(x_flags), _stream()))
     else:
       L.check(L.lib().snnqp_conv_lif_forward(
@@ -1014,6 +1035,7 @@ def dense_lif_forward(x, weight: Weight, K: int, N: int, neuron: Neuron,
   if u0 is not None:
     u0 = _f32c(u0)
     assert tuple(u0.shape) == (B, N)
+  _zero_step_carry(u_out, u0, T)
   if packed_out:
     s = torch.empty((T, B, (N + 31) // 32), dtype=torch.int32, device=dev)
   else:
@@ -1203,6 +1225,7 @@ def lif_forward(x: torch.Tensor, neuron: Neuron, bn: Optional[BnCoeffs] = None,
   if u0 is not None:
     u0 = _f32c(u0)
     assert tuple(u0.shape) == tuple(x.shape[1:])
+  _zero_step_carry(u_out, u0, T)
   if packed_out:
     s = torch.empty(tuple(x.shape[:-1]) + ((C + 31) // 32,), dtype=torch.int32,
                     device=x.device)

@@ -384,9 +384,10 @@ class SpikingBlock(nn.Module):
     # Packed event frames (the host feed's wire formats): the fused 3x3 event layer stages
     # them directly, bit-packed binary frames (EV1) and nibble-packed count frames (EV4); every
     # other consumer -- other geometries, the float32 and direct-form kernels -- gets the uint8
-    # frames back with one device pass.
+    # frames back with one device pass.  (The fused layer writes bit-packed spikes only: float32 spikes
+    # are the direct-form kernel's, which reads uint8 frames.)
     if isinstance(x, ops.PackedFrames):
-      direct = (not is_dense and w.wtype == L.W_I8
+      direct = (not is_dense and w.wtype == L.W_I8 and packed_out
                 and self.impl != L.IMPL_GENERIC and x.ndim == 5
                 and self._event_layer_geometry(conn.geometry(tuple(x.shape[2:-1]), cin)))
       if not direct:
@@ -450,8 +451,9 @@ class SpikingBlock(nn.Module):
       x_max = hint.current()
       # byte / float32 frames that have been binary so far: packed to bits in one checked pass, the
       # event layer on its bit-packed variant, the frames as they are behind it iff the check fails
-      binary_first = (isinstance(x, torch.Tensor) and self.impl != L.IMPL_GENERIC and hint.binary_so_far()
-                      and self._event_layer_geometry(geom) and w.is_int)
+      # (bit-packed spikes only: that variant writes no float32 spikes)
+      binary_first = (isinstance(x, torch.Tensor) and packed_out and self.impl != L.IMPL_GENERIC
+                      and hint.binary_so_far() and self._event_layer_geometry(geom) and w.is_int)
     elif isinstance(x, ops.PackedFrames):
       x_max = 1                          # EV1: binary by construction
     else:
