@@ -203,9 +203,10 @@ typedef struct {
  * predicated snnqp_*_if entry points, snnqp_pack_bits_checked, snnqp_conv_gated_forward,
  * snnqp_dense_gated_forward, snnqp_quantize_ex, snnqp_conv_forward_if,
  * snnqp_conv3d_*; 501: snnqp_weight_t.ch_stack_max / ch_slots, the *_gated_*_ex pack calls; 502:
- * snnqp_pack_frames_checked, snnqp_conv_lif_forward_pred, SNNQP_BN_MUL_UNIFORM).  A binding compares snnqp_version()
+ * snnqp_pack_frames_checked, snnqp_conv_lif_forward_pred, SNNQP_BN_MUL_UNIFORM; 503:
+ * snnqp_scatter_spike_channels).  A binding compares snnqp_version()
  * with the SNNQP_VERSION it was written against and refuses a library of another version (_lib.py does). */
-#define SNNQP_VERSION 502
+#define SNNQP_VERSION 503
 int snnqp_version(void);
 const char *snnqp_last_error(void);
 /* Extra compiler flags the library was built with: "" for the product build
@@ -683,6 +684,14 @@ int snnqp_vote(const void *s, int type, int32_t T, int32_t B, int32_t N,
 /* executed only if *pred != 0 (snnqp_conv_lif_forward_if) */
 int snnqp_vote_if(const int32_t *pred, const void *s, int type, int32_t T, int32_t B, int32_t N,
                   int32_t group, float *logits, snnqp_stream_t stream);
+
+/* replaces: nothing in the reference (it computes every output channel); the blocks of a model
+ * whose pruned channels cannot fire compute the others only, and this restores the
+ * full raster where one is sown: bit-packed s [npix][ceil(cin/32)] -> out [npix][ceil(cout/32)],
+ * input channel c to output channel map[c] (int32 [cin]; entries outside [0, cout) are dropped),
+ * every other channel zero. */
+int snnqp_scatter_spike_channels(const uint32_t *s, int64_t npix, int32_t cin, const int32_t *map,
+                                 int32_t cout, uint32_t *out, snnqp_stream_t stream);
 
 #ifdef __cplusplus
 }

@@ -16,7 +16,7 @@ _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.path.join(_HERE, "csrc", "libsnnqp.so")
 
 # include/snnqp.h SNNQP_VERSION the prototypes below were written against
-ABI_VERSION = 502
+ABI_VERSION = 503
 
 # enums of include/snnqp.h
 F32, U8, BITS, EV1, EV4 = 0, 1, 2, 3, 4
@@ -168,6 +168,8 @@ _PROTOTYPES = {
                            c_void_p, c_void_p]),
     "snnqp_vote_if": (c_int, [c_void_p, c_void_p, c_int, c_int32, c_int32, c_int32, c_int32,
                               c_void_p, c_void_p]),
+    "snnqp_scatter_spike_channels": (c_int, [c_void_p, c_int64, c_int32, c_void_p, c_int32,
+                                             c_void_p, c_void_p]),
 }
 
 EXPORTED_SYMBOLS = tuple(_PROTOTYPES)

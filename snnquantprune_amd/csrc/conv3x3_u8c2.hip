@@ -481,8 +481,12 @@ conv3x3_u8c2_kernel(ConvMfmaArgs a) {
       const v4i bw = OFFS ? bfg : bf;
       for (int tf = 0; tf < nt; tf += FL) {          // FL steps, then flush
         const int nf = min(FL, nt - tf);
+        // a wave beyond Cout (a launch of 32, 64 or 96 channels: a compacted block)
+        // has no channel to compute: it stages, flushes and takes the barriers, nothing else.  The
+        // waves of a workgroup start on a varying SIMD, so the freed issue slots spread evenly
+        // over the SIMDs (a scalar branch: `wave` and Cout are uniform)
 #pragma unroll 1
-        for (int tt = tf; tt < tf + nf; ++tt) {
+        for (int tt = tf; tt < (wave_on ? tf + nf : tf); ++tt) {
           const uint32_t img = (uint32_t)(tt * HIMG2);
           uint32_t words[2];
 #pragma unroll

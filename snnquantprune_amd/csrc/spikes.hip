@@ -189,6 +189,29 @@ maxpool_bits_kernel(const uint32_t *__restrict__ x, int64_t NB, int32_t H,
   }
 }
 
+// channel scatter of bit-packed spikes: one thread per output word; input channel c lands on
+// output channel map[c] (entries outside [0, cout) are dropped), every other bit is zero.
+__global__ void __launch_bounds__(256)
+scatter_spike_channels_kernel(const uint32_t *__restrict__ s, int64_t npix, int32_t cin,
+                              const int32_t *__restrict__ map, int32_t cout,
+                              uint32_t *__restrict__ out) {
+  const int32_t CWi = (cin + 31) / 32, CWo = (cout + 31) / 32;
+  const int64_t n = npix * CWo;
+  for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n;
+       i += (int64_t)gridDim.x * blockDim.x) {
+    const int64_t p = i / CWo;
+    const int32_t wo = (int32_t)(i - p * CWo);
+    const uint32_t *src = s + p * CWi;
+    uint32_t w = 0;
+    for (int32_t c = 0; c < cin; ++c) {
+      const int32_t m = map[c];
+      if (m >= 0 && m < cout && (m >> 5) == wo && ((src[c >> 5] >> (c & 31)) & 1u))
+        w |= 1u << (m & 31);
+    }
+    out[i] = w;
+  }
+}
+
 template <bool BITS>
 __global__ void __launch_bounds__(256)
 vote_kernel(const void *__restrict__ s, int32_t T, int32_t B, int32_t N,
@@ -544,6 +567,18 @@ int snnqp_density(const void *x, int type, int64_t NB, int64_t n, int32_t C, int
     hipLaunchKernelGGL(density_kernel<SNNQP_F32>, dim3(grid_for(NB * units)), dim3(256), 0, st, x,
                        NB, n, C, nnz);
   SNNQP_CHECK_LAUNCH("density_kernel");
+  return SNNQP_OK;
+}
+
+int snnqp_scatter_spike_channels(const uint32_t *s, int64_t npix, int32_t cin, const int32_t *map,
+                                  int32_t cout, uint32_t *out, snnqp_stream_t stream) {
+  SNNQP_REQUIRE(npix >= 0 && cin > 0 && cout > 0 && ((s && map && out) || npix == 0), SNNQP_EINVAL,
+                "scatter_spike_channels: bad argument");
+  if (npix == 0) return SNNQP_OK;
+  const int64_t n = npix * ((cout + 31) / 32);
+  hipLaunchKernelGGL(scatter_spike_channels_kernel, dim3(grid_for(n)), dim3(256), 0,
+                     (hipStream_t)stream, s, npix, cin, map, cout, out);
+  SNNQP_CHECK_LAUNCH("scatter_spike_channels_kernel");
   return SNNQP_OK;
 }
 

@@ -126,6 +126,23 @@ def set_compute_dtype_policy(policy: str):
   _DTYPE_POLICY = policy
 
 
+# Channel compaction: a model's conv blocks compute only the output channels their
+# pruned codes leave able to fire (prune_utils.channel_liveness), padded to a multiple of 32, and
+# the next block reads only those rows.  Same spikes, same logits; on by default.
+_CHANNEL_COMPACTION = True
+
+
+def set_channel_compaction(enabled: bool):
+  """True (default): the models' plain conv blocks skip the output channels that provably never
+  fire.  False: every channel is computed (the A side of an A/B; the results are the same)."""
+  global _CHANNEL_COMPACTION
+  _CHANNEL_COMPACTION = bool(enabled)
+
+
+def channel_compaction() -> bool:
+  return _CHANNEL_COMPACTION
+
+
 def check_compute_dtype(dtype, who: str):
   global _dtype_warned
   if dtype in (torch.float32, None, "float32"):

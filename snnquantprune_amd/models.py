@@ -41,10 +41,14 @@ def flatten_channel_major(x):
   if isinstance(x, ops.PackedSpikes):
     T, B, H, W, C = x.shape
     if C % 32:
+      x = ops.expand_channels(x)
+      C = x.channels
+    if C % 32:
       d = x.to_dense().permute(0, 1, 4, 2, 3).reshape(T, B, C * H * W)
       return ops.pack_bits(d.contiguous())
     out = ops.PackedSpikes(x.bits.reshape(T, B, H * W * (C // 32)), H * W * C)
     out.flat_perm = (C, H, W)
+    out.chan_map = x.chan_map      # a compacted raster: the read-out takes its rows
     return out
   x = x.permute(0, 1, 4, 2, 3)
   return x.reshape(x.shape[0], x.shape[1], x.shape[2] * x.shape[3] * x.shape[4]).contiguous()   # (no -1: B may be 0)
@@ -74,6 +78,18 @@ def _probing(mod, cfg):
   probe is a kernel launch, and the `*_out_*` probes need the UNPOOLED raster, so the blocks
   then run with the 2x2 max-pool as a separate pass."""
   return bool(cfg.get("density_probes", False)) and mod.is_mutable_collection("intermediates")
+
+
+def _compacting(mod, cfg, u_state):
+  """Whether the plain conv blocks compute only the channels that can fire:
+  nn.set_channel_compaction (default on), off while density probes run or a state carry is given."""
+  return nn.channel_compaction() and not _probing(mod, cfg) and u_state is None
+
+
+def _sow_raster(mod, name, x):
+  """Sows a block's spikes at their logical width (a compacted raster is scattered back)."""
+  if mod.is_mutable_collection("intermediates"):
+    mod.sow("intermediates", name, ops.expand_channels(x))
 
 
 def _sow_density(mod, name, x, lead_dims=2):
@@ -205,6 +221,7 @@ class ConvDenseSNN(nn.Module):
                                 epsilon=1e-5, use_bias=True, use_scale=True,
                                 dtype=self.dtype)
     probe = _probing(self, cfg)
+    compact = _compacting(self, cfg, u_state)
     for i in range(nblocks):
       layer = SpikingBlock(
           connection_fn=QuantConv(features=cfg.channels, kernel_size=(3, 3),
@@ -215,14 +232,15 @@ class ConvDenseSNN(nn.Module):
           norm_fn=norm(),
           pool=1 if probe else 2,       # the reduce_window max of models.py:145-147
           return_state=False,
-          batch_major_input=(i == 0))   # models.py:109 swapaxes, done by strides
+          batch_major_input=(i == 0),   # models.py:109 swapaxes, done by strides
+          compact=compact)
       if probe:
         _sow_density(self, "conv_%d_inpt" % i, x)
       _, x = layer(None, x)
       if probe:
         _sow_density(self, "conv_%d_out" % i, x)
         x = ops.maxpool2x2(x)
-      self.sow("intermediates", "pool%d" % i, x)
+      _sow_raster(self, "pool%d" % i, x)
     x = flatten_channel_major(x)
     if probe:
       _sow_density(self, "dense1_inpt", x)
@@ -292,7 +310,9 @@ class CextNet(nn.Module):
         return ops.GatedSpikes(pooled, gate)
       return ops.apply_gate(pooled, gate)   # [T, B, H/2, W/2, C] float32
 
-    def conv_block(x, first, pool, packed=None):
+    compact = _compacting(self, cfg, u_state)
+
+    def conv_block(x, first, pool, packed=None, compact=False):
       layer = SpikingBlock(
           connection_fn=QuantConv(features=cfg.channels, kernel_size=(3, 3),
                                   padding=((1, 1), (1, 1)), use_bias=False,
@@ -301,7 +321,7 @@ class CextNet(nn.Module):
           neural_dynamics=cfg.neuron_dynamics(dtype=self.dtype),
           norm_fn=nn.BatchNorm(use_running_average=not train, momentum=0.9, epsilon=1e-5,
                                use_bias=True, use_scale=True, dtype=self.dtype),
-          pool=pool, return_state=False, batch_major_input=first, packed=packed)
+          pool=pool, return_state=False, batch_major_input=first, packed=packed, compact=compact)
       return layer(None, x)[1]
 
     def dense_block(x, features, packed=None):
@@ -316,11 +336,13 @@ class CextNet(nn.Module):
     for i in range(3):                                  # models.py:111-147
       if probe:
         _sow_density(self, "conv_%d_inpt" % i, x)
-      x = conv_block(x, first=(i == 0), pool=1 if probe else 2)
+      # (the plain blocks feed 3x3 conv blocks: they may compact; conv_t_0 / 1 feed the TCJA gates,
+      # whose channel-axis convolution needs every channel)
+      x = conv_block(x, first=(i == 0), pool=1 if probe else 2, compact=compact)
       if probe:
         _sow_density(self, "conv_%d_out" % i, x)
         x = ops.maxpool2x2(x)
-      self.sow("intermediates", "pool%d" % i, x)
+      _sow_raster(self, "pool%d" % i, x)
     real_valued = False
     for i in range(2):                                  # models.py:149-187
       if probe:

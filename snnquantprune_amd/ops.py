@@ -35,6 +35,9 @@ class PackedSpikes:
     # [T, B, H, W, C] block whose logical order is channel-major
     # (examples/tcja/models.py:189-190); consumers permute weight rows instead.
     self.flat_perm = None
+    # ChannelMap when these are the computed channels of a compacted block: channel i
+    # here is channel chan_map.index[i] of the block's logical output; the others never fire
+    self.chan_map = None
 
   @property
   def shape(self):
@@ -53,10 +56,14 @@ class PackedSpikes:
     if not isinstance(idx, tuple):
       idx = (idx,)
     assert len(idx) < self.bits.ndim, "cannot index the packed channel axis"
-    return PackedSpikes(self.bits[idx].contiguous(), self.channels)
+    out = PackedSpikes(self.bits[idx].contiguous(), self.channels)
+    out.chan_map = self.chan_map
+    return out
 
   def reshape_leading(self, *lead):
-    return PackedSpikes(self.bits.reshape(*lead, self.bits.shape[-1]), self.channels)
+    out = PackedSpikes(self.bits.reshape(*lead, self.bits.shape[-1]), self.channels)
+    out.chan_map = self.chan_map
+    return out
 
   def to_dense(self) -> torch.Tensor:
     return unpack_bits(self)
@@ -161,6 +168,65 @@ class GatedSpikes:
       x = x.permute(0, 1, 4, 2, 3)
       x = x.reshape(x.shape[0], x.shape[1], x.shape[2] * x.shape[3] * x.shape[4]).contiguous()
     return x
+
+
+class ChannelMap:
+  """The channels a compacted block computes: `index` int64 [n], the logical output
+  channel of computed channel i (live ones first, in their order, then silent ones as padding);
+  `live` bool [n], which of them can fire; `full` the block's logical channel count."""
+
+  def __init__(self, index, live, full: int):
+    import numpy as np
+    self.index = np.asarray(index, np.int64)
+    self.live = np.asarray(live, bool)
+    self.full = int(full)
+    self._dev = {}
+
+  def device_index(self, device) -> torch.Tensor:
+    """int32 [n] on `device` (made once per device)."""
+    key = str(device)
+    t = self._dev.get(key)
+    if t is None:
+      t = self._dev[key] = torch.from_numpy(self.index.astype("int32")).to(device)
+    return t
+
+  def __repr__(self):
+    return "ChannelMap(%d of %d, %d live)" % (self.index.size, self.full, int(self.live.sum()))
+
+
+def scatter_spike_channels(s: "PackedSpikes", channel_map: torch.Tensor, cout: int) -> "PackedSpikes":
+  """Bit-packed spikes [..., cin] -> [..., cout]: input channel c to output channel channel_map[c]
+  (int32 device [cin]; entries outside [0, cout) dropped), every other channel zero
+  (snnqp_scatter_spike_channels)."""
+  bits = s.bits.contiguous()
+  _require_gpu(bits, channel_map)
+  assert channel_map.dtype == torch.int32 and channel_map.numel() == s.channels
+  cw = (int(cout) + 31) // 32
+  npix = bits.numel() // max(bits.shape[-1], 1) if bits.ndim else 0
+  out = torch.empty(tuple(bits.shape[:-1]) + (cw,), dtype=torch.int32, device=bits.device)
+  L.check(L.lib().snnqp_scatter_spike_channels(_ptr(bits), npix, s.channels,
+                                                _ptr(channel_map.contiguous()), int(cout), _ptr(out),
+                                                _stream()))
+  return PackedSpikes(out, int(cout))
+
+
+def expand_channels(x):
+  """A compacted raster (PackedSpikes with a chan_map) at its logical width, channels in their
+  original order, the ones not computed zero; anything else is returned as it is.  A flattened
+  raster (flat_perm) is expanded as the [.., H, W, C] block it stands for and flattened again."""
+  cm = getattr(x, "chan_map", None)
+  if cm is None:
+    return x
+  flat = x.flat_perm
+  if flat is not None:
+    c, h, w = flat
+    lead = tuple(x.bits.shape[:-1])
+    blk = PackedSpikes(x.bits.reshape(*lead, h, w, c // 32).contiguous(), c)
+    full = scatter_spike_channels(blk, cm.device_index(x.device), cm.full)
+    out = PackedSpikes(full.bits.reshape(*lead, h * w * ((cm.full + 31) // 32)), h * w * cm.full)
+    out.flat_perm = (cm.full, h, w)
+    return out
+  return scatter_spike_channels(x, cm.device_index(x.device), cm.full)
 
 
 def frame_units(H: int, W: int, fmt: int) -> int:
@@ -921,7 +987,8 @@ def conv_lif_forward(x, geom: ConvGeom, weight: Weight, neuron: Neuron,
                      want_u: bool = True, packed_out: bool = False, pool: int = 1,
                      impl: int = L.IMPL_AUTO, time_major: bool = True, x_max: int = 0,
                      x_seen: Optional[torch.Tensor] = None,
-                     fallback: Optional[FloatFallback] = None, binary_first: bool = False):
+                     fallback: Optional[FloatFallback] = None, binary_first: bool = False,
+                     logical: Optional[Tuple[int, int, int]] = None):
   """x [T, B, H, W, Cin] (or [B, T, ...] with time_major=False) ->
   (u_T [B, OH, OW, Cout] | None, spikes [T, B, OH/pool, OW/pool, Cout]).
   x_max: the largest input value expected (a hint, snnqp.h); x_seen: eight int32 device words
@@ -932,7 +999,10 @@ def conv_lif_forward(x, geom: ConvGeom, weight: Weight, neuron: Neuron,
   (ops.CountHint.binary_so_far): one checked pass packs them to bits, the event layer runs its
   bit-packed variant on 1/8 (1/32) of the bytes, and a predicated launch on the frames as they are
   redoes the block iff a value was not 0 or 1 (snnqp_pack_frames_checked,
-  snnqp_conv_lif_forward_pred) -- same results whatever the frames hold, nothing read back."""
+  snnqp_conv_lif_forward_pred) -- same results whatever the frames hold, nothing read back.
+  logical: (Cin, Cout, live outputs) of a compacted block, whose launch computes
+  geom.Cin x geom.Cout channels: the profile tag keeps the logical geometry, PROFILE_NOTES[tag]
+  gets the computed and live counts."""
   xt, in_type = _in_desc(x)
   xt = xt.contiguous()
   _require_gpu(xt, weight.w, u0)
@@ -966,9 +1036,13 @@ def conv_lif_forward(x, geom: ConvGeom, weight: Weight, neuron: Neuron,
     s = torch.empty(oshape + (geom.Cout,), dtype=torch.float32, device=dev)
   g, w, n = geom.struct(), weight.struct(), neuron.struct()
   b = bn.struct() if bn is not None else None
-  tag = "conv%dx%d[%dx%dx%d->%d]" % (geom.KH, geom.KW, geom.H, geom.W, geom.Cin, geom.Cout)
-  if _PROFILE is not None and in_type == L.BITS and weight.is_int and tag not in PROFILE_NOTES:
-    PROFILE_NOTES[tag] = {"dequant": conv_dequant_form(weight, neuron)}
+  cin_l, cout_l = (geom.Cin, geom.Cout) if logical is None else logical[:2]
+  tag = "conv%dx%d[%dx%dx%d->%d]" % (geom.KH, geom.KW, geom.H, geom.W, cin_l, cout_l)
+  if _PROFILE is not None and in_type == L.BITS and weight.is_int and "dequant" not in PROFILE_NOTES.get(tag, {}):
+    PROFILE_NOTES.setdefault(tag, {})["dequant"] = conv_dequant_form(weight, neuron)
+  if _PROFILE is not None and logical is not None:
+    PROFILE_NOTES.setdefault(tag, {})["channels"] = {
+        "cin": geom.Cin, "cout": geom.Cout, "live_out": int(logical[2])}
   # (the bit-packed variant writes bit-packed spikes only: float32 spikes take the frames as they are)
   speculate = (binary_first and packed_out and not isinstance(x, (PackedFrames, PackedSpikes))
                and in_type in (L.U8, L.F32) and geom.Cin == 2 and weight.is_int and impl != L.IMPL_GENERIC

@@ -84,6 +84,25 @@ def table_slots(ranges):
   return slots, worst
 
 
+def _int_weight_of(codes: torch.Tensor, Lq: float, m: float) -> ops.Weight:
+  """ops.Weight of integer codes in the kernel's layout, with the per-channel statistics the
+  kernels want."""
+  c2 = codes.reshape(-1, codes.shape[-1]).to(torch.int32)
+  # inputs of the integer kernels are never negative (spikes, event counts), so an
+  # accumulator lies in [-sum of |negative codes|, +sum of positive codes] * x_max: the
+  # larger one-sided sum over the outputs bounds |acc| (about half of sum |code|)
+  side = torch.maximum(c2.clamp(min=0).sum(0).max(), (-c2).clamp(min=0).sum(0).max())
+  stats = torch.stack([side, c2.abs().max()]).tolist()             # one readback
+  # dense kernels: column sums of the codes, for uint8 rows read as x - 128 (snnqp.h col_sum)
+  col = c2.sum(0).to(torch.int32).contiguous() if codes.ndim == 2 else None
+  slots, stack = None, 0
+  if codes.ndim == 4 and codes.shape[2] == 2:
+    slots, stack = table_slots(c2.abs().sum(0).cpu().numpy())
+    slots = torch.from_numpy(slots).to(codes.device)
+  return ops.Weight(L.W_I8, codes, Lq, m, abs_sum_max=int(stats[0]),
+                    code_max=int(stats[1]), col_sum=col, ch_stack_max=stack, ch_slots=slots)
+
+
 class PackedKernel:
   def __init__(self, kernel: torch.Tensor, desc: Optional[QuantDesc],
                mask: Optional[torch.Tensor]):
@@ -107,21 +126,35 @@ class PackedKernel:
                                    want_fq=False, want_codes=True, sign=d.sign)
     if int(flags.item()) & (L.FLAG_CODE_OVERFLOW | L.FLAG_MASK_NOT_BINARY):
       return None
-    c2 = codes.reshape(-1, codes.shape[-1]).to(torch.int32)
-    # inputs of the integer kernels are never negative (spikes, event counts), so an
-    # accumulator lies in [-sum of |negative codes|, +sum of positive codes] * x_max: the
-    # larger one-sided sum over the outputs bounds |acc| (about half of sum |code|)
-    side = torch.maximum(c2.clamp(min=0).sum(0).max(), (-c2).clamp(min=0).sum(0).max())
-    stats = torch.stack([side, c2.abs().max()]).tolist()             # one readback
-    # dense kernels: column sums of the codes, for uint8 rows read as x - 128 (snnqp.h col_sum)
-    col = c2.sum(0).to(torch.int32).contiguous() if self.kernel.ndim == 2 else None
-    slots, stack = None, 0
-    if self.kernel.ndim == 4 and self.kernel.shape[2] == 2:
-      slots, stack = table_slots(c2.abs().sum(0).cpu().numpy())
-      slots = torch.from_numpy(slots).to(codes.device)
-    self._int = ops.Weight(L.W_I8, codes, d.L, d.m, abs_sum_max=int(stats[0]),
-                           code_max=int(stats[1]), col_sum=col, ch_stack_max=stack, ch_slots=slots)
+    self._int = _int_weight_of(codes, d.L, d.m)
     return self._int
+
+  def sliced(self, rows, cols) -> "PackedKernel":
+    """The integer codes restricted to input rows `rows` (conv: channels of the Cin axis; dense:
+    rows of K) and output channels `cols` (int64 numpy indices, None = all), as a PackedKernel of
+    their own (cached): what a compacted block launches with.  Codes are
+    elementwise in the per-tensor a, c: slicing after quantisation is exact."""
+    base = self.int_weight()
+    assert base is not None, "only integer codes are sliced"
+    import numpy as np
+    key = ("_sliced", None if rows is None else np.asarray(rows).tobytes(),
+           None if cols is None else np.asarray(cols).tobytes())
+    pk = self._wt.get(key)
+    if pk is None:
+      codes = base.w
+      dev = codes.device
+      if rows is not None:
+        codes = codes.index_select(codes.ndim - 2, torch.as_tensor(np.asarray(rows), device=dev))
+      if cols is not None:
+        codes = codes.index_select(codes.ndim - 1, torch.as_tensor(np.asarray(cols), device=dev))
+      pk = self._wt[key] = _SlicedKernel(codes.contiguous(), self.desc, base)
+    return pk
+
+  def host_codes(self):
+    """The integer codes as int64 numpy (one read-back per weight version)."""
+    if "_host" not in self._wt:
+      self._wt["_host"] = self.int_weight().w.cpu().numpy().astype("int64")
+    return self._wt["_host"]
 
   def gated_codes(self):
     """The codes in the operand layout of ops.conv_gated_forward (3x3 kernels: e2m3 for codes up to 7,
@@ -203,6 +236,19 @@ class PackedKernel:
                      ch_slots=base.ch_slots)
       self._wt[key] = w
     return w
+
+
+class _SlicedKernel(PackedKernel):
+  """Integer codes sliced out of another PackedKernel (PackedKernel.sliced): `kernel` holds the
+  codes themselves (only its layout is read), there is no float32 form."""
+
+  def __init__(self, codes: torch.Tensor, desc, base: ops.Weight):
+    super().__init__(codes, desc, None)
+    self._int = _int_weight_of(codes, base.L, base.m)
+    self._int_done = True
+
+  def float_weight(self):
+    raise RuntimeError("a sliced kernel has integer codes only")
 
 
 _cache = TensorCache(128)

@@ -99,3 +99,181 @@ def prepare_params(params, config):
   if "start_epoch" not in q or q.start_epoch == -1:
     params = update_quant_params(params, q.init_fn, q.bits)
   return params
+
+
+# ---------------------------------------------------------------------------
+# Channel liveness: output channels the prune mask leaves unable to spike
+# ---------------------------------------------------------------------------
+#
+# An output channel whose largest reachable input current keeps the membrane below threshold
+# never fires, whatever the input; its spikes are zeros that the next layer multiplies by its
+# codes.  The rule and its float32 proof are DESIGN.md section 9.  Everything below is host-side
+# numpy on the packed codes and the folded BatchNorm constants, run once per weight version.
+
+_EPS32 = 2.0 ** -24          # unit roundoff of float32
+_ETA32 = 2.0 ** -126         # absolute error of one float32 operation near zero (subnormals, FTZ)
+_K_MIN = 2.0 ** -16          # smallest convex factor the slack below is derived for
+
+
+def _np(a):
+  if a is None:
+    return None
+  if isinstance(a, torch.Tensor):
+    return a.detach().cpu().numpy()
+  return np.asarray(a)
+
+
+def _current_f32(acc, L, m, bn):
+  """Input current of integer accumulators `acc` (int64 [C]) in the kernels' and the oracle's
+  float32 operation order: y = fl(fl(acc / L) * m), then fl(fl(fl(y - mean) * mul) + bias)."""
+  f = np.float32
+  y = (acc.astype(f) / f(L)) * f(m)
+  if bn is not None:
+    mean, mul, bias = bn
+    y = ((y - mean.astype(f)) * mul.astype(f)) + bias.astype(f)
+  return y.astype(f)
+
+
+def _neuron_factor(neuron):
+  """(convex factor k in (0, 1] of the membrane update, v_threshold, v_reset), or None when the
+  update is not a convex combination the proof covers."""
+  from . import _lib as L
+  kind = getattr(neuron, "kind", None)
+  vth, vr = float(np.float32(neuron.v_threshold)), float(np.float32(neuron.v_reset))
+  if kind == L.NEURON_MULTI_STEP_LIF:
+    tau = float(np.float32(neuron.k))
+    if not tau >= 1.0:
+      return None
+    k = 1.0 / tau
+  elif kind == L.NEURON_PARAMETRIC_LEAKY_IF:
+    k = float(np.float32(neuron.k))      # sigmoid(tau), rounded to float32: (0, 1]
+    if not 0.0 < k <= 1.0:
+      return None
+  else:
+    return None                          # LIF: u * k + x is not convex in (u, x)
+  if k < _K_MIN:
+    return None
+  return k, vth, vr
+
+
+def channel_liveness(kernel_codes, dequant, bn, neuron, x_max, live_in=None, u0=None):
+  """Output channels that can fire: bool numpy [Cout] (True = live).
+
+  kernel_codes  integer codes * mask, input channels on axis -2 and output channels on axis -1
+                (HWIO conv or [K, N] dense)
+  dequant       (L, m) of y = fl(fl(acc / L) * m); None for float (fake-quantised) weights
+  bn            (mean, mul, bias) float32 [Cout] of the folded eval BatchNorm
+                (linen.BatchNorm.coeffs; ops.BnCoeffs is taken too), or None
+  neuron        ops.Neuron of the block
+  x_max         largest input value: 1 spikes / EV1 frames, 15 EV4, 255 uint8 frames
+  live_in       bool [Cin]: input channels that may be non-zero (None: all)
+  u0            a carried-in membrane state (anything but None: nothing is provably silent)
+
+  A channel is silent when the block starts from zero state, its neuron update is convex
+  (multi_step_LIF with tau >= 1, parametric_leaky_IF) and max(0, x_hi + v_reset) plus the float32
+  rounding slack of DESIGN.md 9 stays below v_threshold, x_hi being the largest current its
+  reachable accumulators [-neg * x_max, pos * x_max] give.  In every other case every channel is
+  live."""
+  codes = _np(kernel_codes)
+  live = np.ones(codes.shape[-1], bool)
+  if dequant is None:
+    return live
+  nf = _neuron_factor(neuron)
+  if nf is None or u0 is not None:
+    return live
+  k, vth, vr = nf
+  if not vth > 0.0:
+    return live
+  c = codes.reshape((-1,) + codes.shape[-2:]).astype(np.int64)       # [taps, Cin, Cout]
+  if live_in is not None:
+    li = np.asarray(_np(live_in), bool)
+    assert li.shape == (c.shape[1],), (li.shape, c.shape)
+    c = c * li[None, :, None]
+  pos = np.clip(c, 0, None).sum((0, 1))
+  neg = np.clip(-c, 0, None).sum((0, 1))
+  if isinstance(bn, (tuple, list)) or bn is None:
+    bnn = None if bn is None else tuple(_np(v).astype(np.float32) for v in bn)
+  else:
+    bnn = (_np(bn.mean).astype(np.float32), _np(bn.mul).astype(np.float32),
+           _np(bn.bias).astype(np.float32))
+  L_, m_ = dequant
+  xm = int(x_max)
+  # dequantisation and BatchNorm are monotone in the accumulator: the extremes of the current are
+  # at the two ends of the reachable accumulator range
+  e1 = _current_f32(pos * xm, L_, m_, bnn).astype(np.float64)
+  e0 = _current_f32(-neg * xm, L_, m_, bnn).astype(np.float64)
+  x_hi, x_lo = np.maximum(e0, e1), np.minimum(e0, e1)
+  fin = np.isfinite(x_hi) & np.isfinite(x_lo)       # (a NaN / inf current proves nothing)
+  # exact in float64: both terms are float32
+  bound = np.maximum(0.0, x_hi + vr)
+  S = np.maximum(np.abs(x_hi), np.abs(x_lo)) + abs(vr)
+  slack = (32.0 * _EPS32 * S + 8.0 * _ETA32) / k
+  silent = fin & (bound + slack + 2.0 * _ETA32 < vth)
+  return ~silent
+
+
+def computed_channels(live, multiple: int = 32):
+  """The channel set a compacted block computes: its live channels in their original order,
+  padded with silent ones (appended in original order) to a multiple of `multiple` (at least
+  one multiple).  int64 numpy indices."""
+  live = np.asarray(live, bool)
+  idx = np.flatnonzero(live)
+  n = max(multiple, -(-idx.size // multiple) * multiple)
+  n = min(n, live.size)
+  pad = np.flatnonzero(~live)[:n - idx.size]
+  return np.concatenate([idx, pad]).astype(np.int64)
+
+
+def _host_codes(leaf, bits):
+  """DuQ codes * mask of a layer leaf on the host (round half to even of hard_tanh(w / a) * L,
+  float32), and (L, m); None when the layer is not integer-coded (a == -1, bits > 8)."""
+  f = np.float32
+  w = _np(leaf["kernel"]).astype(f)
+  a = f(_np(leaf["DuQ_0"]["a"]).reshape(-1)[0])
+  c = f(_np(leaf["DuQ_0"]["c"]).reshape(-1)[0])
+  if a == f(-1) or bits == -1 or bits > 8:
+    return None
+  L_ = f(2 ** (bits - 1) - 1)
+  q = np.rint(np.clip(w / a, f(-1), f(1)) * L_)
+  if "prune_0" in leaf:
+    q = q * _np(leaf["prune_0"]["mask"]).astype(f)
+  return q.astype(np.int64), (float(L_), float(c))
+
+
+def _host_bn(params, stats, name, eps=1e-5):
+  f = np.float32
+  mean = _np(stats[name]["mean"]).astype(f)
+  var = _np(stats[name]["var"]).astype(f)
+  mul = f(1) / np.sqrt(var + f(eps))
+  if "scale" in params[name]:
+    mul = mul * _np(params[name]["scale"]).astype(f)
+  bias = _np(params[name]["bias"]).astype(f) if "bias" in params[name] else np.zeros_like(mean)
+  return mean, mul.astype(f), bias
+
+
+def conv_net_liveness(variables, config, x_max, nblocks: int = 3, neuron=None):
+  """Liveness of the conv blocks QuantConv_0 .. nblocks-1 of models.ConvDenseSNN (or the three
+  plain conv blocks of models.CextNet) for model inputs bounded by `x_max`, cascaded: a block's
+  live input rows are the previous block's live outputs.  Returns a list of bool [Cout] arrays.
+  `neuron` (ops.Neuron) defaults to the config's multi_step_LIF."""
+  from . import _lib as L
+  from . import ops
+  params, stats = variables["params"], variables.get("batch_stats", {})
+  if neuron is None:
+    nd = config.neuron_dynamics
+    kw = dict(getattr(nd, "keywords", {}) or {})
+    neuron = ops.Neuron(L.NEURON_MULTI_STEP_LIF, float(np.float32(kw.get("tau", 2.0))),
+                        float(kw.get("v_threshold", 1.0)), float(kw.get("v_reset", 0.0)))
+  q = config.quant
+  out, live_in, xm = [], None, int(x_max)
+  for i in range(nblocks):
+    bits = int(q.layer_bits[i]) if ("layer_bits" in q and q.layer_bits is not None) else q.bits
+    hc = _host_codes(params["QuantConv_%d" % i], bits) if "weight" in q else None
+    if hc is None:
+      live = np.ones(_np(params["QuantConv_%d" % i]["kernel"]).shape[-1], bool)
+    else:
+      live = channel_liveness(hc[0], hc[1], _host_bn(params, stats, "BatchNorm_%d" % i), neuron,
+                              xm, live_in)
+    out.append(live)
+    live_in, xm = live, 1                # spikes from here on
+  return out

@@ -13,6 +13,7 @@ Out of scope (training / unused): surrogate-gradient backward rules
 
 from __future__ import annotations
 
+import dataclasses
 import math
 from typing import Any, Callable, Optional
 
@@ -181,6 +182,20 @@ class ZeroCarry:
 
 
 _flat_perm_cache = {}
+_plan_cache = TensorCache(256)
+_bn_slice_cache = TensorCache(256)
+
+
+def _sliced_bn(bn: ops.BnCoeffs, cmap: ops.ChannelMap) -> ops.BnCoeffs:
+  """The BatchNorm constants of the computed channels (cached per BatchNorm version and map)."""
+  extra = cmap.index.tobytes()
+  hit = _bn_slice_cache.get((bn.mean, bn.mul, bn.bias), extra)
+  if hit is None:
+    idx = cmap.device_index(bn.mean.device).long()
+    hit = _bn_slice_cache.put((bn.mean, bn.mul, bn.bias), extra, ops.BnCoeffs(
+        bn.mean.index_select(0, idx).contiguous(), bn.mul.index_select(0, idx).contiguous(),
+        bn.bias.index_select(0, idx).contiguous(), bn.flags))
+  return hit
 
 
 def _flat_perm(c, h, w, device):
@@ -265,6 +280,10 @@ class SpikingBlock(nn.Module):
     impl          kernel choice, _lib.IMPL_*
     batch_major_input  inputs are [B, T, ...] (the model's input layout,
                   models.py:109 swaps axes first); the kernels read it by strides
+    compact       True: a 2-D conv block on integer codes computes only the output
+                  channels that can fire for its input's format and
+                  returns them with their ChannelMap (PackedSpikes.chan_map); its
+                  consumer reads just those rows.  Same spikes, fewer channels.
   """
   connection_fn: Callable
   neural_dynamics: Callable
@@ -274,6 +293,7 @@ class SpikingBlock(nn.Module):
   packed: Optional[bool] = None
   impl: int = L.IMPL_AUTO
   batch_major_input: bool = False
+  compact: bool = False
 
   def _fusable(self):
     conn, nrn, norm = self.connection_fn, self.neural_dynamics, self.norm_fn
@@ -298,7 +318,40 @@ class SpikingBlock(nn.Module):
       raise ValueError("pool must be 1 or 2")
     if self._fusable():
       return self._fused(u, inputs)
-    return self._composed(u, inputs)
+    return self._composed(u, ops.expand_channels(inputs))
+
+  # -- channel compaction ---------------------------------------------------
+  @staticmethod
+  def _input_bound(x):
+    """Largest value the block's input format can hold, or None (float32: no bound)."""
+    if isinstance(x, ops.PackedFrames):
+      return 1 if x.fmt == L.EV1 else 15
+    if isinstance(x, ops.PackedSpikes):
+      return 1
+    if isinstance(x, torch.Tensor) and x.dtype == torch.uint8:
+      return 255
+    return None
+
+  def _channel_plan(self, pk, nrn, bn, x_max, cmap_in):
+    """ChannelMap of the output channels to compute, or None when all of them are."""
+    from . import prune_utils
+    w = pk.int_weight()
+    full_in = w.w.shape[-2]
+    live_in = None
+    if cmap_in is not None:
+      live_in = np.zeros(full_in, bool)
+      live_in[cmap_in.index[cmap_in.live]] = True
+    key = (w.w,) + ((bn.mean, bn.mul, bn.bias) if bn is not None else (None, None, None))
+    extra = (int(x_max), None if live_in is None else live_in.tobytes(), nrn.kind, float(nrn.k),
+             float(nrn.v_threshold), float(nrn.v_reset))
+    plan = _plan_cache.get(key, extra)
+    if plan is None:
+      bnh = None if bn is None else (bn.mean.cpu().numpy(), bn.mul.cpu().numpy(), bn.bias.cpu().numpy())
+      live = prune_utils.channel_liveness(pk.host_codes(), (w.L, w.m), bnh, nrn, x_max, live_in)
+      idx = prune_utils.computed_channels(live)
+      plan = _plan_cache.put(key, extra, (ops.ChannelMap(idx, live[idx], live.size),)
+                             if idx.size < live.size else (None,))
+    return plan[0]
 
   # -- one launch ---------------------------------------------------------------
   def _fused(self, u, inputs):
@@ -317,10 +370,38 @@ class SpikingBlock(nn.Module):
       x.flat_perm = flat
     u0 = None if (u is None or isinstance(u, ZeroCarry)) else u
     tm = not self.batch_major_input
-    cin = x.shape[-1]
-    pk = conn.packed_kernel(cin)
-    packed_out = bool(integer) if self.packed is None else bool(self.packed)
     is_dense = isinstance(conn, QuantDense)
+    cmap_in = getattr(x, "chan_map", None)
+    if cmap_in is not None:
+      # a compacted raster: the block reads the rows of the computed channels only -- a conv
+      # block its Cin axis, the read-out its channel-major rows c * HW + hw -- when it has
+      # integer codes for them; anything else reads the raster at its logical width
+      full_cin = cmap_in.full if flat is None else cmap_in.full * flat[1] * flat[2]
+      pk = conn.packed_kernel(full_cin)
+      if not (integer and pk.int_weight() is not None and is_dense == (flat is not None)
+              and (is_dense or len(conn._ksize()) == 2)):
+        x = ops.expand_channels(x)
+        flat = x.flat_perm
+        cmap_in = None
+    cin = x.shape[-1]
+    pk = conn.packed_kernel(cin if cmap_in is None else full_cin)
+    packed_out = bool(integer) if self.packed is None else bool(self.packed)
+    rows = None
+    if cmap_in is not None:
+      rows = cmap_in.index
+      if flat is not None:
+        hw = flat[1] * flat[2]
+        rows = (rows[:, None] * hw + np.arange(hw)[None, :]).reshape(-1)
+    cmap_out = None
+    x_bound = self._input_bound(x)
+    if (self.compact and nn.channel_compaction() and not is_dense and integer is True and u0 is None
+        and not self.return_state and packed_out and len(conn._ksize()) == 2 and x_bound is not None
+        and self.impl != L.IMPL_GENERIC and pk.int_weight() is not None):
+      cmap_out = self._channel_plan(pk, self.neural_dynamics.neuron(conn.features),
+                                    self.norm_fn.coeffs(conn.features) if self.norm_fn is not None else None,
+                                    x_bound, cmap_in)
+    if rows is not None or cmap_out is not None:
+      pk = pk.sliced(rows, None if cmap_out is None else cmap_out.index)
     w = None
     if integer:
       if is_dense:
@@ -380,6 +461,8 @@ class SpikingBlock(nn.Module):
       x = d.reshape(d.shape[0], d.shape[1], c * h * ww).contiguous()
     nrn = self.neural_dynamics.neuron(conn.features)
     bn = norm.coeffs(conn.features) if norm is not None else None
+    if cmap_out is not None and bn is not None:
+      bn = _sliced_bn(bn, cmap_out)
 
     # Packed event frames (the host feed's wire formats): the fused 3x3 event layer stages
     # them directly, bit-packed binary frames (EV1) and nibble-packed count frames (EV4); every
@@ -440,6 +523,12 @@ class SpikingBlock(nn.Module):
       raise ValueError("QuantConv block expects [T, B, spatial..., C] inputs, got %s"
                        % (x.shape,))
     geom = conn.geometry(tuple(x.shape[2:-1]), cin)
+    logical = None
+    if cmap_in is not None or cmap_out is not None:
+      logical = (cin if cmap_in is None else cmap_in.full, geom.Cout,
+                 geom.Cout if cmap_out is None else int(cmap_out.live.sum()))
+      if cmap_out is not None:
+        geom = dataclasses.replace(geom, Cout=int(cmap_out.index.size))
     hint = None
     binary_first = False
     if (integer and cin == 2 and nsp == 2 and
@@ -476,7 +565,6 @@ class SpikingBlock(nn.Module):
         and 0 < w.abs_sum_max < (1 << 22) and impl != L.IMPL_GENERIC and u0 is None):
       # let the kernel fuse the membrane update where BatchNorm of every reachable
       # dequantised accumulator value proves that exact (snnqp.h, min_current_bits)
-      import dataclasses
       w = dataclasses.replace(w, min_current_bits=ops.current_min_bits(
           w, bn, int(w.abs_sum_max), geom.Cout))
     x_seen = hint.seen_word() if hint is not None else None
@@ -485,7 +573,8 @@ class SpikingBlock(nn.Module):
         u_out, s = ops.conv_lif_forward(x, geom, w, nrn, bn=bn, u0=u0,
                                         want_u=self.return_state, packed_out=packed_out,
                                         pool=self.pool, impl=impl, time_major=tm,
-                                        x_max=x_max, x_seen=x_seen, fallback=fb, binary_first=binary_first)
+                                        x_max=x_max, x_seen=x_seen, fallback=fb, binary_first=binary_first,
+                                        logical=logical)
         break
       except L.SnnqpError as e:
         if (e.code == L.EUNSUPPORTED and spec and attempt == 0 and isinstance(x, torch.Tensor)
@@ -502,11 +591,14 @@ class SpikingBlock(nn.Module):
         u_out, s = ops.conv_lif_forward(x, geom, w, nrn, bn=bn, u0=u0,
                                         want_u=self.return_state, packed_out=packed_out,
                                         pool=1, impl=impl, time_major=tm, x_max=x_max,
-                                        x_seen=x_seen, fallback=fb, binary_first=binary_first)
+                                        x_seen=x_seen, fallback=fb, binary_first=binary_first,
+                                        logical=logical)
         s = ops.maxpool2x2(s)
         break
     if hint is not None:
       hint.launched()
+    if cmap_out is not None:
+      s.chan_map = cmap_out
     return self._finish_conv((u_out, s), nsp, T, B)
 
   @staticmethod
