@@ -134,6 +134,9 @@ typedef struct {
                           32 different columns and no slot twice -- a balanced assignment keeps
                           the tallest column, hence the table, small.  NULL: column n = c mod 32,
                           position w */
+  int32_t wt_cin;      /* W_I8, 3x3 conv blocks over bit-packed spikes: the input-channel count
+                          `wt` was zero-padded to (snnqp_conv_lif_forward), a multiple of 32 in
+                          [Cin, 128]; 0 = 32 ceil(Cin / 32), the packing rule */
 } snnqp_weight_t;
 
 /* Eval-mode BatchNorm folded on the host: y = fl(fl(fl(x - mean) * mul) + bias),
@@ -206,7 +209,7 @@ typedef struct {
  * snnqp_pack_frames_checked, snnqp_conv_lif_forward_pred, SNNQP_BN_MUL_UNIFORM; 503:
  * snnqp_scatter_spike_channels).  A binding compares snnqp_version()
  * with the SNNQP_VERSION it was written against and refuses a library of another version (_lib.py does). */
-#define SNNQP_VERSION 503
+#define SNNQP_VERSION 504
 int snnqp_version(void);
 const char *snnqp_last_error(void);
 /* Extra compiler flags the library was built with: "" for the product build
@@ -403,8 +406,9 @@ int snnqp_dense_gated_forward(const uint32_t *s, const float *gate, int64_t NB, 
  *       SNNQP_IMPL_MFMA: MFMA implicit GEMM (fp6 codes x fp4 spikes when
  *       code_max <= 7, else int8); needs W_I8, 3x3 / stride 1 / pad 1 / no
  *       dilation / groups 1 and (BITS input with Cin <= 128 and `wt` = the codes
- *       of the kernel zero-padded along Cin to Cpad = 64 (Cin <= 64) or 128,
- *       tiled by snnqp_pack_codes_mfma with K = 9 * Cpad (row = tap * Cpad + cin);
+ *       of the kernel zero-padded along Cin to Cpad = 32 ceil(Cin / 32) (or to
+ *       w->wt_cin, a wider multiple of 32 up to 128), tiled by snnqp_pack_codes_mfma
+ *       with K = 9 * Cpad (row = tap * Cpad + cin: int8 tile tap * Cpad / 32 + group);
  *       a pixel keeps its ceil(Cin / 32) spike words, zero bits beyond Cin --
  *       or U8 input with Cin == 2, any count 0..255; or EV1 / EV4 input, Cin == 2: the packed
  *       frames are staged directly, 1/8 (binary) or 1/2 (counts <= 15) of the uint8 bytes;

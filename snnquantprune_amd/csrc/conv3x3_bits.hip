@@ -10,7 +10,11 @@
 //    2^24 -- the same integer an int8 MFMA accumulates, at half the A bytes per MAC
 //    through LDS and twice the matrix rate;
 //  * wider codes (8-bit DuQ, the reference's shipped configs): v_mfma_i32_32x32x32_i8,
-//    A = spikes as bytes, B = the int8 codes, 36 k-steps instead of 18.
+//    A = spikes as bytes, B = the int8 codes, 36 k-steps instead of 18 (Cin = 128).
+//
+// K runs over (tap, 32-channel group) pairs: CIN = 32 G input channels (the codes are padded to
+// that, snnqp.h), 9 G pairs, two per fp6 k-step (5 / 9 / 14 / 18 k-steps for G = 1 .. 4), one per
+// int8 k-step.
 //
 // A workgroup is 4 waves on one 4x8-pixel tile (patch), two workgroups per CU = two waves
 // per SIMD: wave w owns output channels [32 w, +32) of the tile, its B fragments for
@@ -27,9 +31,11 @@
 // the previous one, so the A fragments of step s + 1 are requested during the last slots of
 // step s and the matrix pipe does not drain at a step boundary (with two buffers and the
 // barrier at the end of the step every step began with an LDS round trip).
-// LDS image: one plane per k-step of a tap (64 fp4 / 32 byte channels = 32 B per pixel),
-// rows of 12 pixels, the two 16-byte lane halves swapped on odd rows: every tap/half offset
-// is an instruction immediate and the reads are bank-conflict free.
+// LDS image: one plane per 64 fp4 / 32 byte channels (32 B per pixel), rows of 12 pixels, the
+// two 16-byte halves (fp4: channel groups 2 p, 2 p + 1) swapped on odd rows: every tap/half
+// offset is an instruction immediate and the reads are bank-conflict free.  An odd fp6 G leaves
+// group G - 1 alone in the first half of the last plane; its k-steps pair two taps instead
+// (pair_tap) and read it through lane bases of their own.
 #include <type_traits>
 
 #include "conv_tile.h"
@@ -113,23 +119,29 @@ enum { FMT_FP6 = 0, FMT_I8 = 1 };
 
 constexpr int F6_WR_SLOT = 2;    // slot of a step after which the staged halo is written
 constexpr int F6_BAR_SLOT = 4;   // slot of a step after which the step's barrier sits
-constexpr int F6_PF = 4;         // A fragments in flight (ring of 6); 2 when a step has 9 slots
+constexpr int F6_PF = 4;         // A fragments in flight (ring of 6 or 7); 2 with a ring of 3 or 5
+
+// fp6, odd G: the tap lane half h reads in pair k-step p of the last group -- (0, 3), (1, 4),
+// (2, 5) one halo row apart, (6, 7), (8, -) one pixel apart; "tap 9" has zero codes
+__host__ __device__ constexpr int pair_tap(int p, int h) { return p < 3 ? p + 3 * h : 2 * p + h; }
 
 template <int FMT, int CIN, int NF, bool POOL, int DQ, bool FMA = false, bool BNF = false, bool BNU = false>
 __global__ void __launch_bounds__(F6_NT, 2)
 conv3x3_bits_kernel(ConvMfmaArgs a) {
-  static_assert(CIN == 64 || CIN == 128, "one or two 64-channel planes");
+  static_assert(CIN == 32 || CIN == 64 || CIN == 96 || CIN == 128, "one to four 32-channel groups");
   static_assert(!BNU || (BNF && DQ == DQ_TABLE), "the uniform multiplier folds into the shared table");
   static_assert(DQ == DQ_ARITH || DQ == DQ_ONE || DQ == DQ_TABLE, "dequantisation mode");
   constexpr bool I8 = FMT == FMT_I8;
   constexpr bool TABLE = DQ == DQ_TABLE;
   static_assert(!(TABLE && I8), "the table is addressed by a float32 accumulator");
   typedef typename std::conditional<I8, v16i, v16f>::type acc_t;
-  constexpr int KCH = I8 ? 32 : 64;              // input channels of one k-step
   constexpr int BR = I8 ? 4 : 6;                 // registers of one B fragment
-  constexpr int NP = CIN / KCH;                  // planes of the halo image
-  constexpr int WPP = CIN / 32;                  // spike words per pixel
-  constexpr int KS = 9 * NP;                     // MFMAs (slots) of one timestep
+  constexpr int WPP = CIN / 32;                  // spike words (32-channel groups) per pixel
+  constexpr int NP = I8 ? WPP : (WPP + 1) / 2;   // planes of the halo image
+  constexpr int NPL = I8 ? WPP : WPP / 2;        // planes read whole: both lane halves at one tap
+  constexpr int PAIRS = I8 || WPP % 2 == 0 ? 0 : 5;   // k-steps over group G - 1 alone (pair_tap)
+  constexpr int KS = 9 * NPL + PAIRS;            // MFMAs (slots) of one timestep
+  constexpr int NPD = NPL > 0 ? NPL : 1;         // (divisor of the whole-plane k-step index)
   constexpr int HALO_B = NP * F6_PLANE;          // one halo image
   constexpr int FL = POOL ? 16 : 4;              // timesteps per flush block
   constexpr int SLOTS = 2 * FL;                  // ring of staged spike words
@@ -161,8 +173,9 @@ conv3x3_bits_kernel(ConvMfmaArgs a) {
       ((uint32_t *)(lds + TAB_OFF))[i] = v;
     }
   }
-  // B operand: k-step ks = NP tap + kk covers channels 64 kk .. +63 of the tap; lane
-  // (n, h) holds k = 32 h + j, i.e. both 16-byte halves of int8 tile WPP tap + 2 kk + h
+  // B operand: k-step ks = NPL tap + kk (< 9 NPL) covers channels 64 kk .. +63 of the tap; lane
+  // (n, h) holds k = 32 h + j, i.e. both 16-byte halves of int8 tile WPP tap + 2 kk + h; pair
+  // k-step 9 NPL + p: lane half h holds group WPP - 1 of tap pair_tap(p, h)
   // (int8: k-step ks = WPP tap + kk is int8 tile ks as it is, lane (n, h) holds k = 16 h + j)
   int bf[KS][BR];
   {
@@ -173,9 +186,11 @@ conv3x3_bits_kernel(ConvMfmaArgs a) {
         const v4i t = wave_on ? wtile[ks * 64 + lane] : v4i{0, 0, 0, 0};
         bf[ks][0] = t.x; bf[ks][1] = t.y; bf[ks][2] = t.z; bf[ks][3] = t.w;
       } else {
-        const int ks8 = (ks / NP) * WPP + (ks % NP) * 2 + h;
+        const int ptap = pair_tap(ks - 9 * NPL, h);
+        const bool pair = ks >= 9 * NPL;
+        const int ks8 = pair ? ptap * WPP + WPP - 1 : (ks / NPD) * WPP + (ks % NPD) * 2 + h;
         v4i lo = {0, 0, 0, 0}, hi = {0, 0, 0, 0};
-        if (wave_on) {
+        if (wave_on && !(pair && ptap >= 9)) {
           lo = wtile[ks8 * 64 + n];
           hi = wtile[ks8 * 64 + 32 + n];
         }
@@ -216,12 +231,17 @@ conv3x3_bits_kernel(ConvMfmaArgs a) {
   const uint32_t pixb = lds0 + (uint32_t)((ty * F6_PITCH + tx) * 32);
   const uint32_t abase_even = pixb + (uint32_t)((h ^ (ty & 1)) * 16);       // dy = 0, 2
   const uint32_t abase_odd = pixb + (uint32_t)((h ^ (ty & 1) ^ 1) * 16);    // dy = 1
+  // pair k-steps (first half of plane NPL): half h one halo row lower (taps p, p + 3) or one
+  // pixel to the right (taps 6 + 2q, 7 + 2q); the same swizzle, so still conflict free
+  const uint32_t abase_pv = pixb + (uint32_t)(h * F6_PITCH * 32 + ((ty ^ h) & 1) * 16);
+  const uint32_t abase_ph = pixb + (uint32_t)(h * 32 + (ty & 1) * 16);
+  struct Bases { uint32_t e, o, pv, ph; };       // lane bases of one halo image
 
   // staging task of this thread: word wi of halo pixel pix
   const int s_pix = tid / WPP, s_wi = tid % WPP;
   const bool s_task = tid < F6_ROWS * HALO * WPP;
-  // a pixel has ceil(Cin / 32) spike words in memory; the planes beyond them (Cin below
-  // the template's 64 / 128) are zero spikes against zero codes
+  // a pixel has ceil(Cin / 32) spike words in memory; the groups beyond them (codes padded
+  // wider than that, snnqp_weight_t.wt_cin) are zero spikes against zero codes
   const int wpm = (a.Cin + 31) >> 5;
   const int s_hy = s_pix / HALO, s_hx = s_pix % HALO;
   // fp4: word wi = half wi & 1 of plane wi >> 1; bytes: word wi = both halves of plane wi
@@ -298,11 +318,16 @@ conv3x3_bits_kernel(ConvMfmaArgs a) {
         *(lds_v4i_t *)(uintptr_t)(s_dst + bufoff) = s_exp;
       }
     };
-    // A fragment of k-step ks from the halo image whose lane bases are (aeven, aodd)
-    auto a_read = [&](uint32_t aeven, uint32_t aodd, int ks) -> v4i {
-      const int tap = ks / NP;
-      const uint32_t off = (uint32_t)((ks % NP) * F6_PLANE + ((tap / 3) * F6_PITCH + tap % 3) * 32);
-      return *(lds_cv4i_t *)(uintptr_t)(((tap / 3) & 1 ? aodd : aeven) + off);
+    // A fragment of k-step ks from the halo image whose lane bases are ib
+    auto a_read = [&](const Bases &ib, int ks) -> v4i {
+      if (ks >= 9 * NPL) {                        // pair k-step: the padding half ("tap 9")
+        const int p = ks - 9 * NPL;               // reads pixel (2, 3), inside the image
+        const uint32_t off = (uint32_t)(NPL * F6_PLANE + (p < 3 ? p : 2 * F6_PITCH + 2 * (p - 3)) * 32);
+        return *(lds_cv4i_t *)(uintptr_t)((p < 3 ? ib.pv : ib.ph) + off);
+      }
+      const int tap = ks / NPD;
+      const uint32_t off = (uint32_t)((ks % NPD) * F6_PLANE + ((tap / 3) * F6_PITCH + tap % 3) * 32);
+      return *(lds_cv4i_t *)(uintptr_t)(((tap / 3) & 1 ? ib.o : ib.e) + off);
     };
     auto mfma_acc = [&](int ks, const v4i &av, const acc_t &c) -> acc_t {
       if constexpr (I8) {
@@ -432,22 +457,25 @@ conv3x3_bits_kernel(ConvMfmaArgs a) {
     };
 
     // ---- A-fragment ring: PF fragments in flight, across step boundaries ----------------
-    constexpr int RING = KS % 6 == 0 && !TABLE ? 6 : 3;    // divides KS (9, 18, 36): static indices
-    constexpr int PF = RING == 6 ? F6_PF : 2;
+    // the ring divides KS (5, 9, 14, 18, 27, 36): static indices
+    constexpr int RING = KS % 6 == 0 && !TABLE ? 6 : KS % 3 == 0 ? 3 : KS % 7 == 0 ? 7 : KS;
+    constexpr int PF = RING == 6 || (RING == 7 && !TABLE) ? F6_PF : 2;
     static_assert(KS % RING == 0 && PF < RING, "ring indices must repeat every step");
     v4i A[RING];
 
-    // One pipelined step s: MFMA(s + 1) from the image (rd_e, rd_o) while the epilogue of
-    // timestep s runs on accC; halo(s + 2) is written early, the barrier follows two slots
-    // later; the last PF slots request the first fragments of the NEXT step from (rn_e, rn_o).
+    // One pipelined step s: MFMA(s + 1) from the image rd while the epilogue of timestep s
+    // runs on accC; halo(s + 2) is written early, the barrier follows two slots later; the
+    // last PF slots request the first fragments of the NEXT step from the image rn.
     // The table form and the int8 instruction want both late (write after 5/9 of the slots,
     // barrier after 5/6, right before the next step's first fragments are requested): conv1
     // 5.19 ms against 5.28 with the early pair (5.28 again with the write one slot before the
     // barrier), 8-bit codes 8.70 against 8.89; the fp6 kernel with arithmetic dequantisation
     // keeps the early pair (2-bit layer of C5: 1.50 against 1.53 ms late).
+    // (14 slots: write after slot 7, barrier after 11; 5 slots: 1 and 2)
     constexpr bool LATE = TABLE || I8;
     constexpr int BAR_LATE = KS * 5 / 6 < KS - PF ? KS * 5 / 6 : KS - PF - 1;
-    constexpr int WR_SLOT = LATE ? KS * 5 / 9 : F6_WR_SLOT < KS - PF - 2 ? F6_WR_SLOT : 1;
+    constexpr int WR_LATE = KS * 5 / 9 < BAR_LATE ? KS * 5 / 9 : BAR_LATE - 1;
+    constexpr int WR_SLOT = LATE ? WR_LATE : F6_WR_SLOT < KS - PF - 2 ? F6_WR_SLOT : 1;
     constexpr int BAR_SLOT = LATE ? BAR_LATE : F6_BAR_SLOT < KS - PF ? F6_BAR_SLOT : WR_SLOT + 1;
     static_assert(WR_SLOT < BAR_SLOT && BAR_SLOT < KS - PF,
                   "the halo is written before the barrier, the next step's fragments read after it");
@@ -462,8 +490,8 @@ conv3x3_bits_kernel(ConvMfmaArgs a) {
           }
       return n;
     }();
-    auto fused_step = [&](acc_t &accN, acc_t &accC, int s, uint32_t rd_e, uint32_t rd_o,
-                          uint32_t rn_e, uint32_t rn_o, uint32_t wr_off, int par, bool more) {
+    auto fused_step = [&](acc_t &accN, acc_t &accC, int s, const Bases &rd, const Bases &rn,
+                          uint32_t wr_off, int par, bool more) {
       if (s + 2 < a.T) stage_expand(par);
       if (s + 4 < a.T) stage_load(s + 4, par);
       ETmp e;
@@ -474,8 +502,8 @@ conv3x3_bits_kernel(ConvMfmaArgs a) {
         else accN = mfma_acc(ks, A[ks % RING], accN);                   // the chain constants)
         __builtin_amdgcn_sched_barrier(0);
         // the slot's A read: PF slots ahead, wrapping into the next step's image
-        if (ks + PF < KS) A[(ks + PF) % RING] = a_read(rd_e, rd_o, ks + PF);
-        else if (more) A[(ks + PF) % RING] = a_read(rn_e, rn_o, ks + PF - KS);
+        if (ks + PF < KS) A[(ks + PF) % RING] = a_read(rd, ks + PF);
+        else if (more) A[(ks + PF) % RING] = a_read(rn, ks + PF - KS);
         // an even share of the epilogue stages
         {
           const int lo = ks * NSTAGES / KS, hi = (ks + 1) * NSTAGES / KS;
@@ -523,8 +551,10 @@ conv3x3_bits_kernel(ConvMfmaArgs a) {
     };
 
     // lane bases of the halo images: halo(t) lives in image t % 3 of the ring
-    auto img_e = [&](int k) { return abase_even + (uint32_t)(k * HALO_B); };
-    auto img_o = [&](int k) { return abase_odd + (uint32_t)(k * HALO_B); };
+    auto img = [&](int k) {
+      const uint32_t d = (uint32_t)(k * HALO_B);
+      return Bases{abase_even + d, abase_odd + d, abase_pv + d, abase_ph + d};
+    };
 
     // pipeline prologue: halo(0), halo(1) staged; MFMA(0) alone
     acc_t accA, accB;
@@ -542,15 +572,15 @@ conv3x3_bits_kernel(ConvMfmaArgs a) {
     // (every wave has read the previous patch's claim: behind the barrier above)
     if (pw.queue && tid == 0) nxt[0] = (uint32_t)claimed;
     {
-      const uint32_t e0 = img_e(0), o0 = img_o(0), e1 = img_e(1), o1 = img_o(1);
+      const Bases i0 = img(0), i1 = img(1);
 #pragma unroll
-      for (int i = 0; i < PF; ++i) A[i] = a_read(e0, o0, i);
+      for (int i = 0; i < PF; ++i) A[i] = a_read(i0, i);
 #pragma unroll
       for (int ks = 0; ks < KS; ++ks) {
         if (ks == 0) accA = mfma_acc(0, A[0], TABLE ? cblk : zero16);
         else accA = mfma_acc(ks, A[ks % RING], accA);
-        if (ks + PF < KS) A[(ks + PF) % RING] = a_read(e0, o0, ks + PF);
-        else if (a.T > 1) A[(ks + PF) % RING] = a_read(e1, o1, ks + PF - KS);
+        if (ks + PF < KS) A[(ks + PF) % RING] = a_read(i0, ks + PF);
+        else if (a.T > 1) A[(ks + PF) % RING] = a_read(i1, ks + PF - KS);
         __builtin_amdgcn_sched_barrier(0);
       }
     }
@@ -560,17 +590,14 @@ conv3x3_bits_kernel(ConvMfmaArgs a) {
     int s = 0;
     int k1 = 1, k2 = 2;                  // images of halo(s + 1), halo(s + 2)
     for (; s + 2 < a.T; s += 2) {
-      fused_step(accB, accA, s, img_e(k1), img_o(k1), img_e(k2), img_o(k2), (uint32_t)(k2 * HALO_B),
-                 0, true);
+      fused_step(accB, accA, s, img(k1), img(k2), (uint32_t)(k2 * HALO_B), 0, true);
       const int k3 = k1 == 0 ? 2 : k1 - 1;        // image of halo(s + 3)
-      fused_step(accA, accB, s + 1, img_e(k2), img_o(k2), img_e(k3), img_o(k3),
-                 (uint32_t)(k3 * HALO_B), 1, s + 3 < a.T);
+      fused_step(accA, accB, s + 1, img(k2), img(k3), (uint32_t)(k3 * HALO_B), 1, s + 3 < a.T);
       k1 = k3;
       k2 = k3 == 2 ? 0 : k3 + 1;
     }
     if (s + 1 < a.T) {
-      fused_step(accB, accA, s, img_e(k1), img_o(k1), img_e(k2), img_o(k2), (uint32_t)(k2 * HALO_B),
-                 0, false);
+      fused_step(accB, accA, s, img(k1), img(k2), (uint32_t)(k2 * HALO_B), 0, false);
       epilogue(accB, s + 1);
     } else {
       epilogue(accA, s);
@@ -633,19 +660,24 @@ static void launch_bits_nf(const ConvMfmaArgs &a, int nf, bool pool, int dq, boo
 // i8: codes wider than fp6 holds (|code| > 7) -> the int8 instruction
 // dq: DQ_ARITH / DQ_ONE (conv_tile.h; ONE is a shortcut, ARITH with L = 1 computes the same);
 // fma: NF_MUL0 with the fused membrane update; bnf: BatchNorm means and biases all zero
-void launch_conv3x3_bits(const ConvMfmaArgs &a0, bool i8, int nf, bool pool, int dq, bool fma,
-                         bool bnf, unsigned gy, hipStream_t st) {
+// cin_pad: the input channels the codes `wt` are padded to (32, 64, 96 or 128): the template
+template <int FMT>
+static void launch_bits_cin(const ConvMfmaArgs &a, int cin_pad, int nf, bool pool, int dq, bool fma,
+                            bool bnf, unsigned gy, hipStream_t st) {
+  if (cin_pad == 32) launch_bits_nf<FMT, 32>(a, nf, pool, dq, fma, bnf, gy, st);
+  else if (cin_pad == 64) launch_bits_nf<FMT, 64>(a, nf, pool, dq, fma, bnf, gy, st);
+  else if (cin_pad == 96) launch_bits_nf<FMT, 96>(a, nf, pool, dq, fma, bnf, gy, st);
+  else launch_bits_nf<FMT, 128>(a, nf, pool, dq, fma, bnf, gy, st);
+}
+
+void launch_conv3x3_bits(const ConvMfmaArgs &a0, int cin_pad, bool i8, int nf, bool pool, int dq,
+                         bool fma, bool bnf, unsigned gy, hipStream_t st) {
   ConvMfmaArgs a = a0;                       // this kernel's patch: one tile of 4x8 pixels
   a.patch_h = 4;
   a.tiles_y = (a.H + 3) / 4;
   a.npatch = (int64_t)a.B * a.tiles_y * a.tiles_x;
-  if (i8) {
-    if (a.Cin <= 64) launch_bits_nf<FMT_I8, 64>(a, nf, pool, dq, fma, bnf, gy, st);
-    else launch_bits_nf<FMT_I8, 128>(a, nf, pool, dq, fma, bnf, gy, st);
-  } else {
-    if (a.Cin <= 64) launch_bits_nf<FMT_FP6, 64>(a, nf, pool, dq, fma, bnf, gy, st);
-    else launch_bits_nf<FMT_FP6, 128>(a, nf, pool, dq, fma, bnf, gy, st);
-  }
+  if (i8) launch_bits_cin<FMT_I8>(a, cin_pad, nf, pool, dq, fma, bnf, gy, st);
+  else launch_bits_cin<FMT_FP6>(a, cin_pad, nf, pool, dq, fma, bnf, gy, st);
 }
 
 }  // namespace snnqp

@@ -759,8 +759,8 @@ const char *conv3x3_mfma_unsupported(int in_type, const snnqp_conv_geom_t *g,
   if (g->Cout <= 0) return "no output channels";    // any count: the last word is masked
   if (s_type != SNNQP_BITS) return "spike output must be bit-packed";
   if (in_type == SNNQP_BITS) {
-    // any width up to 128: `wt` is tiled from the kernel zero-padded along Cin to 64
-    // (Cin <= 64) or 128; the spike words beyond ceil(Cin / 32) are not read
+    // any width up to 128: `wt` is tiled from the kernel zero-padded along Cin to
+    // 32 ceil(Cin / 32) (or wt_cin); the spike words beyond ceil(Cin / 32) are not read
     if (g->Cin < 1 || g->Cin > 128) return "bit input needs Cin <= 128";
   } else if (in_type == SNNQP_U8) {     // any count 0..255 (taken as x - 128 without a table)
     if (g->Cin != 2) return "u8 input needs Cin == 2";
@@ -802,6 +802,10 @@ int run_conv3x3_mfma(const void *x, int in_type, int64_t xs_t, int64_t xs_b,
                 "conv3x3 mfma: only the event layer on byte / nibble / float32 frames takes a predicate");   // (an empty batch has no buffers)
   SNNQP_REQUIRE(in_type != SNNQP_BITS || wt, SNNQP_EINVAL,
                 "conv3x3 mfma: bit input needs the MFMA-tiled codes `wt`");
+  // the input channels `wt` is padded to: one 32-channel group per int8 tile of a tap
+  const int cin_pad = w->wt_cin ? w->wt_cin : (g->Cin + 31) / 32 * 32;
+  SNNQP_REQUIRE(in_type != SNNQP_BITS || (cin_pad % 32 == 0 && cin_pad >= g->Cin && cin_pad <= 128),
+                SNNQP_EINVAL, "conv3x3 mfma: wt_cin must be a multiple of 32 in [Cin, 128]");
   SNNQP_REQUIRE(T >= 0 && B >= 0, SNNQP_EINVAL, "conv3x3 mfma: negative T/B");
   SNNQP_REQUIRE(w->L >= 1.0f, SNNQP_EINVAL, "dequant L must be >= 1");
   SNNQP_CHECK_BN(bn);
@@ -902,7 +906,7 @@ int run_conv3x3_mfma(const void *x, int in_type, int64_t xs_t, int64_t xs_b,
     a.lut_bound = tab ? (int32_t)w->abs_sum_max : 0;
     if (tab) check_code_bound_once(stream_device(st), (const int8_t *)w->w, (int64_t)9 * g->Cin, g->Cout,
                                    w->abs_sum_max, st);
-    launch_conv3x3_bits(a, i8, nf, pl, dq, fma, bnf, gy, st);
+    launch_conv3x3_bits(a, cin_pad, i8, nf, pl, dq, fma, bnf, gy, st);
   } else {
     const int lm = lutc ? LUT_CHANNEL : lut ? LUT_SHARED : LUT_NONE;
     if (lut) check_code_bound_once(stream_device(st), (const int8_t *)w->w, (int64_t)9 * g->Cin, g->Cout,

@@ -649,9 +649,10 @@ static inline void launch_persistent(K kernel, ConvMfmaArgs a, unsigned gy, hipS
 // fma: the membrane update as one fused multiply-add (NF_MUL0, proven exact for this launch
 // by the caller: snnqp_weight_t.min_current_bits + lif_fma_is_exact)
 // bnf: every BatchNorm mean and bias is zero (snnqp_bn_t.flags): x = y * mul
+// cin_pad: the input channels `wt` is padded to, 32 / 64 / 96 / 128 (snnqp_weight_t.wt_cin)
 enum { DQ_ARITH = 1, DQ_ONE = 2, DQ_TABLE = 3 };
 constexpr int DQT_MAXA = 2047;
-void launch_conv3x3_bits(const ConvMfmaArgs &a, bool i8, int nf, bool pool, int dq, bool fma,
-                         bool bnf, unsigned gy, hipStream_t st);
+void launch_conv3x3_bits(const ConvMfmaArgs &a, int cin_pad, bool i8, int nf, bool pool, int dq,
+                         bool fma, bool bnf, unsigned gy, hipStream_t st);
 
 }  // namespace snnqp

@@ -143,6 +143,24 @@ def channel_compaction() -> bool:
   return _CHANNEL_COMPACTION
 
 
+# K packing of the 3x3 convs over bit-packed spikes: their codes are padded along
+# Cin to the next multiple of 32 and the kernel walks (tap, 32-channel group) pairs.  On by default.
+_CONV_KPACK = True
+
+
+def set_conv_kpack(enabled: bool):
+  """True (default): a conv block over bit-packed spikes pads its input channels to a multiple of
+  32.  False: to 64 or 128, the wider layout of earlier versions (the A side of an A/B; the
+  results are the same).  Applies to weights packed afterwards (the packed forms are cached per
+  setting)."""
+  global _CONV_KPACK
+  _CONV_KPACK = bool(enabled)
+
+
+def conv_kpack() -> bool:
+  return _CONV_KPACK
+
+
 def check_compute_dtype(dtype, who: str):
   global _dtype_warned
   if dtype in (torch.float32, None, "float32"):

@@ -365,6 +365,7 @@ class Weight:
   wt6: Optional[torch.Tensor] = None       # dense, code_max <= 7: fp6 MFMA tiles (pack_codes_fp6)
   ch_stack_max: int = 0     # event layer: largest stacked per-channel code range (snnqp.h), 0 = unknown
   ch_slots: Optional[torch.Tensor] = None  # event layer: int32 [padded Cout] table slots (packing.table_slots)
+  wt_cin: int = 0           # 3x3 conv over bits: the Cin `wt` is padded to (snnqp.h), 0 = 32 ceil(Cin / 32)
 
   def struct(self) -> L.WeightT:
     # (built once per object: a Weight is not modified after the pack step made it --
@@ -376,7 +377,7 @@ class Weight:
                      None if self.col_sum is None else self.col_sum.data_ptr(),
                      None if self.wt6 is None else self.wt6.data_ptr(),
                      int(self.min_current_bits), int(self.ch_stack_max),
-                     None if self.ch_slots is None else self.ch_slots.data_ptr())
+                     None if self.ch_slots is None else self.ch_slots.data_ptr(), int(self.wt_cin))
       self.__dict__["_cstruct"] = st
     return st
 

@@ -15,6 +15,7 @@ from typing import Optional
 import torch
 
 from . import _lib as L
+from . import linen as _nn
 from . import ops
 from ._cache import TensorCache
 from .quant import QuantDesc
@@ -101,6 +102,17 @@ def _int_weight_of(codes: torch.Tensor, Lq: float, m: float) -> ops.Weight:
     slots = torch.from_numpy(slots).to(codes.device)
   return ops.Weight(L.W_I8, codes, Lq, m, abs_sum_max=int(stats[0]),
                     code_max=int(stats[1]), col_sum=col, ch_stack_max=stack, ch_slots=slots)
+
+
+def conv_cin_pad(cin: int, kpack: bool = True) -> int:
+  """The input channels the MFMA tiles of a 3x3 conv over bit-packed spikes are padded to
+  (snnqp.h, `wt` of a conv block): the next multiple of 32, the groups the bits kernel walks K
+  in; kpack=False (nn.set_conv_kpack): 64 or 128."""
+  if not 0 < cin <= 128:
+    raise ValueError("bit-input conv blocks take 1 to 128 input channels")
+  if kpack:
+    return (cin + 31) // 32 * 32
+  return 64 if cin <= 64 else 128
 
 
 class PackedKernel:
@@ -201,28 +213,32 @@ class PackedKernel:
     base = self.int_weight()
     if base is None:
       return None
-    key = (n_pad, perm_key)
+    kpack = _nn.conv_kpack()
+    key = (n_pad, perm_key, kpack)
     w = self._wt.get(key)
     if w is None:
       codes = base.w.reshape(-1, base.w.shape[-1])
       if row_perm is not None:
         codes = codes.index_select(0, row_perm)
       codes = codes.contiguous()
+      wt_cin = 0
       if self.kernel.ndim == 2 and codes.shape[0] % 32:
         # dense layers: zero rows up to a multiple of 32 (the packed input rows carry
         # zero bits there), so K = 784 etc. stay on the MFMA kernel
         pad = 32 - codes.shape[0] % 32
         tiles_src = torch.cat([codes, codes.new_zeros((pad, codes.shape[1]))], 0)
-      elif (self.kernel.ndim == 4 and row_perm is None and 2 < base.w.shape[2] <= 128
-            and base.w.shape[2] not in (64, 128)):
-        # convolution over bit-packed spikes: the MFMA kernels walk 64 or 128 input
-        # channels per tap; other widths (config.channels = 100, 96, 48 ...) get zero
-        # codes up to the next of the two (the spike words carry zero bits there)
+      elif (self.kernel.ndim == 4 and row_perm is None and (0 if kpack else 2) < base.w.shape[2] <= 128
+            and base.w.shape[2] % (32 if kpack else 64)):
+        # convolution over bit-packed spikes: the MFMA kernels walk the input channels of a
+        # tap in groups of 32; other widths (config.channels = 100, 79 live of 128 ...) get
+        # zero codes up to the next multiple of 32 (the spike words carry zero bits there).
+        # nn.set_conv_kpack(False): up to 64 or 128, the layout of earlier versions
         kh, kw, ci, co = base.w.shape
-        cpad = 64 if ci <= 64 else 128          # snnqp.h: `wt` of a conv block
+        cpad = conv_cin_pad(ci, kpack)          # snnqp.h: `wt` of a conv block
         padded = base.w.new_zeros((kh, kw, cpad, co))
         padded[:, :, :ci] = base.w
         tiles_src = padded.reshape(-1, co)
+        wt_cin = cpad
       else:
         tiles_src = codes
       wt = ops.pack_codes_mfma(tiles_src, n_pad) if tiles_src.shape[0] % 32 == 0 else None
@@ -233,7 +249,7 @@ class PackedKernel:
         wt6 = ops.pack_codes_fp6(codes, n_pad)
       w = ops.Weight(L.W_I8, codes, base.L, base.m, wt=wt, abs_sum_max=base.abs_sum_max,
                      code_max=base.code_max, col_sum=base.col_sum, wt6=wt6, ch_stack_max=base.ch_stack_max,
-                     ch_slots=base.ch_slots)
+                     ch_slots=base.ch_slots, wt_cin=wt_cin)
       self._wt[key] = w
     return w
 

@@ -1,0 +1,103 @@
+"""Conv K packing A/B: the same model, weights and batch with nn.set_conv_kpack off
+(codes of the bit-input convs padded to 64 / 128 input channels) and on (to a multiple of 32), in
+one process, alternating; per-kernel device time from the HIP-event profile and the whole apply.
+Checks that logits are bit-equal.
+
+  python tools/kpack_ab.py [--B 1024] [--T 20] [--reps 5] [--out FILE.json]
+"""
+import argparse
+import json
+import os
+import sys
+
+import numpy as np
+import torch
+
+sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
+from snnquantprune_amd import _lib as L, linen as nn, models, ops, synthetic as syn  # noqa: E402
+
+LEGS = [  # name, bits, prune, layer_bits, input
+    ("C3", 4, 0.9, None, "ev1"),
+    ("C3", 4, 0.9, None, "u8"),
+    ("C5", 4, 0.95, (2, 4, 2, 4), "ev1"),
+    ("8bit_30", 8, 0.3, None, "ev1"),
+]
+
+
+def leg(name, bits, prune, lb, inp, B, T, reps, dev):
+  cfg = syn.make_config(bits=bits, prune_percentage=prune)
+  if lb:
+    cfg.quant.layer_bits = tuple(lb)
+  model = models.ConvDenseSNN(num_classes=11, config=cfg)
+  variables = nn.tree_from_numpy(syn.conv_net_variables(prune_p=prune, out=110), dev)
+  gen = torch.Generator(device=dev)
+  gen.manual_seed(8627169)
+  x = (torch.rand((B, T, 128, 128, 2), device=dev, generator=gen) < 1.0 - np.exp(-0.1)).to(torch.uint8)
+  if inp == "ev1":
+    x = ops.pack_frames(x, L.EV1)
+
+  def run(kpack):
+    nn.set_conv_kpack(kpack)
+    return model.apply(variables, x, trgt=None, train=False, rng=None)[0]
+
+  out = {}
+  ref = {}
+  for kpack in (False, True):
+    ref[kpack] = run(kpack).cpu().numpy()
+    run(kpack)
+  torch.cuda.synchronize()
+  sums = {False: {}, True: {}}
+  steps = {False: [], True: []}
+  for _ in range(reps):
+    for kpack in (False, True):
+      run(kpack)
+      torch.cuda.synchronize()
+      a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+      ops.profile_start()
+      a.record()
+      run(kpack)
+      b.record()
+      prof = ops.profile_stop()
+      steps[kpack].append(a.elapsed_time(b))
+      for tag, (n, ms) in prof.items():
+        sums[kpack].setdefault(tag, []).append(ms / max(n, 1))
+      if kpack:
+        out["notes"] = {t: v for t, v in ops.PROFILE_NOTES.items() if "channels" in v}
+  for kpack in (False, True):
+    key = "on" if kpack else "off"
+    out[key] = {"step_ms_median": float(np.median(steps[kpack])),
+                "kernel_ms_median": {t: float(np.median(v)) for t, v in sorted(sums[kpack].items())}}
+  out["ratio_on_off"] = {t: out["on"]["kernel_ms_median"][t] / out["off"]["kernel_ms_median"][t]
+                         for t in out["on"]["kernel_ms_median"] if t in out["off"]["kernel_ms_median"]}
+  out["step_ratio_on_off"] = out["on"]["step_ms_median"] / out["off"]["step_ms_median"]
+  out["logits_bit_equal"] = bool(np.array_equal(ref[False], ref[True]))
+  nn.set_conv_kpack(True)
+  return out
+
+
+def main():
+  ap = argparse.ArgumentParser()
+  ap.add_argument("--B", type=int, default=1024)
+  ap.add_argument("--T", type=int, default=20)
+  ap.add_argument("--reps", type=int, default=5)
+  ap.add_argument("--out", default=None)
+  args = ap.parse_args()
+  dev = torch.device("cuda:0")
+  res = {"B": args.B, "T": args.T, "reps": args.reps, "device": torch.cuda.get_device_name(0), "legs": {}}
+  for name, bits, prune, lb, inp in LEGS:
+    r = leg(name, bits, prune, lb, inp, args.B, args.T, args.reps, dev)
+    res["legs"]["%s_%s" % (name, inp)] = r
+    print("%-8s %-4s step %.2f -> %.2f ms (x%.3f)  %s  bit-equal %s" % (
+        name, inp, r["off"]["step_ms_median"], r["on"]["step_ms_median"], r["step_ratio_on_off"],
+        " ".join("%s %.3f->%.3f x%.3f" % (t, r["off"]["kernel_ms_median"][t], r["on"]["kernel_ms_median"][t], v)
+                 for t, v in r["ratio_on_off"].items() if t.startswith("conv3x3")),
+        r["logits_bit_equal"]), flush=True)
+    torch.cuda.empty_cache()
+  res["fallback_counts"] = ops.fallback_counts()
+  if args.out:
+    with open(args.out, "w") as f:
+      json.dump(res, f, indent=1, sort_keys=True)
+
+
+if __name__ == "__main__":
+  main()
