@@ -68,6 +68,14 @@ enum {
   SNNQP_NEURON_PARAMETRIC_LEAKY_IF = 2, /* spiking_learning.py:357-387 */
   SNNQP_NEURON_LIF = 3                  /* spiking_learning.py:419-438 */
 };
+/* surrogate derivatives of the spike functions, spiking_learning.py:139-241 (training) */
+enum {
+  SNNQP_SURR_FAST_SIGMOID = 0,   /* 1 / (10 |x| + 1)^2       */
+  SNNQP_SURR_ATAN = 1,           /* 1 / (1 + (pi x)^2)        */
+  SNNQP_SURR_SLAYER = 2,         /* exp(-5 |x|)               */
+  SNNQP_SURR_SMOOTH_STEP = 3,    /* 1 on [-0.5, 0.5), else 0  */
+  SNNQP_SURR_PIECEWISE_LINEAR = 4 /* relu(1 - 2 |x|)          */
+};
 /* quantisers, quant.py */
 enum {
   SNNQP_Q_DUQ = 0,              /* quant.py:428-469  p0 = a, p1 = c           */
@@ -207,9 +215,11 @@ typedef struct {
  * snnqp_dense_gated_forward, snnqp_quantize_ex, snnqp_conv_forward_if,
  * snnqp_conv3d_*; 501: snnqp_weight_t.ch_stack_max / ch_slots, the *_gated_*_ex pack calls; 502:
  * snnqp_pack_frames_checked, snnqp_conv_lif_forward_pred, SNNQP_BN_MUL_UNIFORM; 503:
- * snnqp_scatter_spike_channels).  A binding compares snnqp_version()
+ * snnqp_scatter_spike_channels; 505: training of the dense blocks -- SNNQP_SURR_*,
+ * snnqp_lif_forward_save, snnqp_lif_backward, snnqp_dense_weight_grad, snnqp_dense_input_grad).
+ * A binding compares snnqp_version()
  * with the SNNQP_VERSION it was written against and refuses a library of another version (_lib.py does). */
-#define SNNQP_VERSION 504
+#define SNNQP_VERSION 505
 int snnqp_version(void);
 const char *snnqp_last_error(void);
 /* Extra compiler flags the library was built with: "" for the product build
@@ -696,6 +706,34 @@ int snnqp_vote_if(const int32_t *pred, const void *s, int type, int32_t T, int32
  * every other channel zero. */
 int snnqp_scatter_spike_channels(const uint32_t *s, int64_t npix, int32_t cin, const int32_t *map,
                                  int32_t cout, uint32_t *out, snnqp_stream_t stream);
+
+/* ---- training of the dense blocks (csrc/train_dense.hip) ------------------------------------
+ * The surrogate-gradient backward of SpikingBlock(QuantDense, multi_step_LIF) as jax.grad
+ * differentiates examples/tcja/models.py:191-255.  All tensors float32, time-major.
+ *
+ * replaces: the scan of spiking_learning.py:403-416 in train mode, keeping its residual:
+ *           x [T][R][C] currents, zero initial state -> h_out [T][R][C] the potential before
+ *           the reset (u + (x - (u - v_reset)) / tau), s_out [T][R][C] spikes 0.0 / 1.0 -- the
+ *           same arithmetic as snnqp_lif_forward.  multi_step_LIF only (else SNNQP_EUNSUPPORTED). */
+int snnqp_lif_forward_save(const float *x, int32_t T, int64_t R, int32_t C,
+                           const snnqp_neuron_t *nrn, float *h_out, float *s_out,
+                           snnqp_stream_t stream);
+/* the backward of that scan, t = T-1 .. 0, with gu_T = 0 and no gradient through the reset:
+ *   gh_t = gs_t sigma'(h_t - v_th) + gu_t (1 - s_t),  gI_t = gh_t / tau,  gu_{t-1} = gh_t (1 - 1/tau)
+ * sigma' = SNNQP_SURR_*.  Upstream either gs [T][R][C] or, with the vote of
+ * examples/tcja/models.py:253-255 fused, glogits [R][C / group]: gs_t[r][c] = glogits[r][c / group]
+ * / (group T) (exactly one of the two is non-null).  gI [T][R][C]. */
+int snnqp_lif_backward(const float *h, const float *gs, const float *glogits, int32_t group,
+                       int32_t T, int64_t R, int32_t C, const snnqp_neuron_t *nrn,
+                       int surrogate, float *gI, snnqp_stream_t stream);
+/* gw [K][N] = sum_m x[m][k] gI[m][n] over x [M][K], gI [M][N], m ascending (exact f32 MFMA,
+ * one fixed order: bitwise reproducible). */
+int snnqp_dense_weight_grad(const float *x, const float *gI, int64_t M, int32_t K, int32_t N,
+                            float *gw, snnqp_stream_t stream);
+/* gx [M][K] = (sum_n gI[m][n] w[k][n]) * mask[m][k] over gI [M][N], w [K][N]; mask [M][K]
+ * optional (the dropout mask of the block's input). */
+int snnqp_dense_input_grad(const float *gI, const float *w, const float *mask, int64_t M,
+                           int32_t K, int32_t N, float *gx, snnqp_stream_t stream);
 
 #ifdef __cplusplus
 }

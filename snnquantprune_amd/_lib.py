@@ -16,12 +16,13 @@ _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.path.join(_HERE, "csrc", "libsnnqp.so")
 
 # include/snnqp.h SNNQP_VERSION the prototypes below were written against
-ABI_VERSION = 504
+ABI_VERSION = 505
 
 # enums of include/snnqp.h
 F32, U8, BITS, EV1, EV4 = 0, 1, 2, 3, 4
 W_F32, W_I8 = 0, 1
 NEURON_NONE, NEURON_MULTI_STEP_LIF, NEURON_PARAMETRIC_LEAKY_IF, NEURON_LIF = 0, 1, 2, 3
+SURR_FAST_SIGMOID, SURR_ATAN, SURR_SLAYER, SURR_SMOOTH_STEP, SURR_PIECEWISE_LINEAR = 0, 1, 2, 3, 4
 Q_DUQ, Q_UNIFORM_STATIC, Q_PARAMETRIC_D, Q_PARAMETRIC_D_XMAX = 0, 1, 2, 3
 IMPL_AUTO, IMPL_GENERIC, IMPL_MFMA = 0, 1, 2
 FLAG_CODE_OVERFLOW, FLAG_MASK_NOT_BINARY = 1, 2
@@ -170,6 +171,14 @@ _PROTOTYPES = {
                               c_void_p, c_void_p]),
     "snnqp_scatter_spike_channels": (c_int, [c_void_p, c_int64, c_int32, c_void_p, c_int32,
                                              c_void_p, c_void_p]),
+    "snnqp_lif_forward_save": (c_int, [c_void_p, c_int32, c_int64, c_int32, POINTER(NeuronT),
+                                       c_void_p, c_void_p, c_void_p]),
+    "snnqp_lif_backward": (c_int, [c_void_p, c_void_p, c_void_p, c_int32, c_int32, c_int64,
+                                   c_int32, POINTER(NeuronT), c_int, c_void_p, c_void_p]),
+    "snnqp_dense_weight_grad": (c_int, [c_void_p, c_void_p, c_int64, c_int32, c_int32, c_void_p,
+                                        c_void_p]),
+    "snnqp_dense_input_grad": (c_int, [c_void_p, c_void_p, c_void_p, c_int64, c_int32, c_int32,
+                                       c_void_p, c_void_p]),
 }
 
 EXPORTED_SYMBOLS = tuple(_PROTOTYPES)

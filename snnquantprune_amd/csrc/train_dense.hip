@@ -1,0 +1,292 @@
+// Training of the dense SNN (DenseSNN, configs C1 / C2): the pieces of the surrogate-gradient
+// backward pass through time (examples/tcja/models.py:191-255 differentiated by jax.grad).
+//
+//   snnqp_lif_forward_save   multi_step_LIF scan over float32 currents that also writes the
+//                            pre-reset potential h_t (the residual of the backward)
+//   snnqp_lif_backward       the time-reversed scan, one lane per (row, feature), with the
+//                            surrogate derivative as a template and the vote backward fused
+//   snnqp_dense_weight_grad  gW[k][n] = sum_m x[m][k] gI[m][n]       (f32-input MFMA)
+//   snnqp_dense_input_grad   gx[m][k] = (sum_n gI[m][n] w[k][n]) * mask[m][k]
+//
+// Both products run on v_mfma_f32_16x16x4_f32, which is an exact k-ordered fmaf chain; every
+// output element is reduced by one wave in one fixed order (no atomics), so gradients are
+// bitwise reproducible run to run.
+#include "common.h"
+
+namespace snnqp {
+namespace {
+
+// ---- surrogate derivatives, spiking_learning.py:139-241 -------------------------------------
+template <int S>
+__device__ __forceinline__ float surrogate_grad(float x) {
+  if constexpr (S == SNNQP_SURR_FAST_SIGMOID) {        // :151-156, alpha = 10
+    float d = 10.0f * fabsf(x) + 1.0f;
+    return 1.0f / (d * d);
+  } else if constexpr (S == SNNQP_SURR_ATAN) {         // :226-233, alpha = 2
+    float p = 3.14159265358979323846f * x;
+    return 1.0f / (1.0f + p * p);
+  } else if constexpr (S == SNNQP_SURR_SLAYER) {       // :170-174
+    return expf(-5.0f * fabsf(x));
+  } else if constexpr (S == SNNQP_SURR_SMOOTH_STEP) {  // :188-192, [-0.5, 0.5)
+    return (x < 0.5f && x >= -0.5f) ? 1.0f : 0.0f;
+  } else {                                             // :206-211 piecewise_linear
+    return fmaxf(1.0f - 2.0f * fabsf(x), 0.0f);
+  }
+}
+
+// The forward of neuron_step (common.h) for MULTI_STEP_LIF, keeping h before the reset.
+__global__ void lif_save_kernel(const float *__restrict__ x, int32_t T, int64_t n,
+                                NeuronP p, float *__restrict__ h_out, float *__restrict__ s_out) {
+  const int64_t e = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (e >= n) return;
+  float u = 0.0f;
+  for (int32_t t = 0; t < T; ++t) {
+    const int64_t o = (int64_t)t * n + e;
+    float d = x[o] - (u - p.vr);                                     // :410
+    float h = u + (p.inv_k != 0.0f ? d * p.inv_k : d / p.k);
+    bool s = (h - p.vth) >= 0.0f;                                    // :412
+    h_out[o] = h;
+    s_out[o] = s ? 1.0f : 0.0f;
+    u = s ? p.vr : h;                                                // :414
+  }
+}
+
+// gh_t = gs_t sigma'(h_t - vth) + gu_t (1 - s_t);  gI_t = gh_t / tau;  gu_{t-1} = gh_t (1 - 1/tau).
+// VOTE: gs_t[r][c] = glogits[r][c / group] / (group T) (models.py:253-255), no [T][R][C] upstream.
+template <int S, bool VOTE>
+__global__ void lif_backward_kernel(const float *__restrict__ h, const float *__restrict__ gs,
+                                    const float *__restrict__ glogits, int32_t group,
+                                    int32_t T, int64_t R, int32_t C, NeuronP p,
+                                    float *__restrict__ gI) {
+  const int64_t n = R * C;
+  const int64_t e = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (e >= n) return;
+  const float inv = p.inv_k != 0.0f ? p.inv_k : 1.0f / p.k;
+  const float keep = 1.0f - inv;
+  float gv = 0.0f;
+  if constexpr (VOTE) {
+    const int64_t r = e / C;
+    const int32_t c = (int32_t)(e - r * C);
+    gv = glogits[r * (C / group) + c / group] / (float)((int64_t)group * T);
+  }
+  float gu = 0.0f;                                                   // gu_T = 0
+  for (int32_t t = T - 1; t >= 0; --t) {
+    const int64_t o = (int64_t)t * n + e;
+    const float x = h[o] - p.vth;
+    const float s = x >= 0.0f ? 1.0f : 0.0f;                          // the forward's spike
+    const float g = VOTE ? gv : gs[o];
+    const float gh = g * surrogate_grad<S>(x) + gu * (1.0f - s);
+    gI[o] = p.inv_k != 0.0f ? gh * p.inv_k : gh / p.k;
+    gu = gh * keep;
+  }
+}
+
+template <int S>
+int launch_backward(const float *h, const float *gs, const float *glogits, int32_t group,
+                    int32_t T, int64_t R, int32_t C, const NeuronP &p, float *gI,
+                    hipStream_t st) {
+  const int64_t blocks = ceil_div64(R * C, 256);
+  if (glogits)
+    hipLaunchKernelGGL((lif_backward_kernel<S, true>), dim3((unsigned)blocks), dim3(256), 0, st,
+                       h, gs, glogits, group, T, R, C, p, gI);
+  else
+    hipLaunchKernelGGL((lif_backward_kernel<S, false>), dim3((unsigned)blocks), dim3(256), 0, st,
+                       h, gs, glogits, group, T, R, C, p, gI);
+  SNNQP_CHECK_LAUNCH("lif_backward_kernel");
+  return SNNQP_OK;
+}
+
+// ---- C[i][j] = sum_r A(r, i) B(r, j) (* mask[i][j]) -----------------------------------------
+// A(r, i) = a[r * a_sr + i * a_si], B(r, j) = b[r * b_sr + j * b_sj]; C row-major [I][J].
+// 256 threads, a 64 x 64 tile of C per workgroup, 32 x 32 per wave (2 x 2 16x16x4 MFMAs);
+// r walks in chunks of 16 through LDS, the next chunk held in registers while this one computes.
+constexpr int GT = 64;     // tile edge
+constexpr int GR = 16;     // r per chunk
+constexpr int GLD = GT + 4;
+
+using f32x4 = __attribute__((ext_vector_type(4))) float;
+
+// Element q (0..3) of this thread's share of one GR x GT operand chunk: (rr, ii) in the chunk.
+// When the r axis is the contiguous one, neighbouring threads walk r; else they walk i.
+__device__ __forceinline__ void chunk_coord(int tid, int q, bool r_contig, int &rr, int &ii) {
+  const int idx = tid + 256 * q;
+  if (r_contig) {
+    rr = idx % GR;
+    ii = idx / GR;
+  } else {
+    rr = idx / GT;
+    ii = idx % GT;
+  }
+}
+
+__device__ __forceinline__ void load_chunk(const float *__restrict__ a, int64_t sr, int64_t si,
+                                           int64_t r0, int64_t Rn, int64_t i0, int64_t I,
+                                           bool r_contig, int tid, float (&reg)[4]) {
+#pragma unroll
+  for (int q = 0; q < 4; ++q) {
+    int rr, ii;
+    chunk_coord(tid, q, r_contig, rr, ii);
+    const int64_t r = r0 + rr, i = i0 + ii;
+    reg[q] = (r < Rn && i < I) ? a[r * sr + i * si] : 0.0f;
+  }
+}
+
+__device__ __forceinline__ void store_chunk(float (*lds)[GLD], bool r_contig, int tid,
+                                            const float (&reg)[4]) {
+#pragma unroll
+  for (int q = 0; q < 4; ++q) {
+    int rr, ii;
+    chunk_coord(tid, q, r_contig, rr, ii);
+    lds[rr][ii] = reg[q];
+  }
+}
+
+__global__ __launch_bounds__(256) void grad_gemm_kernel(
+    const float *__restrict__ a, int64_t a_sr, int64_t a_si,
+    const float *__restrict__ b, int64_t b_sr, int64_t b_sj,
+    int64_t I, int64_t J, int64_t Rn, const float *__restrict__ mask, float *__restrict__ c) {
+  __shared__ float As[GR][GLD];
+  __shared__ float Bs[GR][GLD];
+  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+  const int64_t i0 = (int64_t)blockIdx.y * GT, j0 = (int64_t)blockIdx.x * GT;
+  const int wi = (wave & 1) * 32, wj = (wave >> 1) * 32;
+  const bool a_rc = a_sr == 1 && a_si != 1, b_rc = b_sr == 1 && b_sj != 1;
+  f32x4 acc[2][2];
+#pragma unroll
+  for (int x = 0; x < 2; ++x)
+#pragma unroll
+    for (int y = 0; y < 2; ++y) acc[x][y] = f32x4{0.0f, 0.0f, 0.0f, 0.0f};
+  float ra[4], rb[4];
+  load_chunk(a, a_sr, a_si, 0, Rn, i0, I, a_rc, tid, ra);
+  load_chunk(b, b_sr, b_sj, 0, Rn, j0, J, b_rc, tid, rb);
+  const int kl = lane >> 4, il = lane & 15;
+  for (int64_t r0 = 0; r0 < Rn; r0 += GR) {
+    __syncthreads();                       // the previous chunk's reads are done
+    store_chunk(As, a_rc, tid, ra);
+    store_chunk(Bs, b_rc, tid, rb);
+    __syncthreads();
+    if (r0 + GR < Rn) {
+      load_chunk(a, a_sr, a_si, r0 + GR, Rn, i0, I, a_rc, tid, ra);
+      load_chunk(b, b_sr, b_sj, r0 + GR, Rn, j0, J, b_rc, tid, rb);
+    }
+#pragma unroll
+    for (int kk = 0; kk < GR; kk += 4) {
+      // 16x16x4: lane l holds A[i = l & 15][k = l >> 4] and B[k = l >> 4][j = l & 15]
+      float av[2], bv[2];
+#pragma unroll
+      for (int x = 0; x < 2; ++x) av[x] = As[kk + kl][wi + 16 * x + il];
+#pragma unroll
+      for (int y = 0; y < 2; ++y) bv[y] = Bs[kk + kl][wj + 16 * y + il];
+#pragma unroll
+      for (int x = 0; x < 2; ++x)
+#pragma unroll
+        for (int y = 0; y < 2; ++y)
+          acc[x][y] = __builtin_amdgcn_mfma_f32_16x16x4f32(av[x], bv[y], acc[x][y], 0, 0, 0);
+    }
+  }
+  // C/D: col = lane & 15, row = (lane >> 4) * 4 + reg
+#pragma unroll
+  for (int x = 0; x < 2; ++x)
+#pragma unroll
+    for (int y = 0; y < 2; ++y)
+#pragma unroll
+      for (int g = 0; g < 4; ++g) {
+        const int64_t i = i0 + wi + 16 * x + kl * 4 + g;
+        const int64_t j = j0 + wj + 16 * y + il;
+        if (i < I && j < J) {
+          float v = acc[x][y][g];
+          if (mask) v = v * mask[i * J + j];
+          c[i * J + j] = v;
+        }
+      }
+}
+
+int launch_gemm(const float *a, int64_t a_sr, int64_t a_si, const float *b, int64_t b_sr,
+                int64_t b_sj, int64_t I, int64_t J, int64_t Rn, const float *mask, float *c,
+                hipStream_t st, const char *name) {
+  const int64_t gx = ceil_div64(J, GT), gy = ceil_div64(I, GT);
+  SNNQP_REQUIRE(gx < 65536 && gy < 65536, SNNQP_EINVAL, "%s: grid too large", name);
+  hipLaunchKernelGGL(grad_gemm_kernel, dim3((unsigned)gx, (unsigned)gy), dim3(256), 0, st,
+                     a, a_sr, a_si, b, b_sr, b_sj, I, J, Rn, mask, c);
+  SNNQP_CHECK_LAUNCH(name);
+  return SNNQP_OK;
+}
+
+}  // namespace
+}  // namespace snnqp
+
+using namespace snnqp;
+
+extern "C" {
+
+int snnqp_lif_forward_save(const float *x, int32_t T, int64_t R, int32_t C,
+                           const snnqp_neuron_t *nrn, float *h_out, float *s_out,
+                           snnqp_stream_t stream) {
+  SNNQP_REQUIRE(T >= 0 && R >= 0 && C > 0, SNNQP_EINVAL, "lif_forward_save: bad shape");
+  SNNQP_REQUIRE(nrn && nrn->kind == SNNQP_NEURON_MULTI_STEP_LIF, SNNQP_EUNSUPPORTED,
+                "lif_forward_save: multi_step_LIF only");
+  const int64_t n = R * C;
+  if (n == 0 || T == 0) return SNNQP_OK;
+  SNNQP_REQUIRE(x && h_out && s_out, SNNQP_EINVAL, "lif_forward_save: null argument");
+  const int64_t blocks = ceil_div64(n, 256);
+  SNNQP_REQUIRE(blocks < (1ll << 31), SNNQP_EINVAL, "lif_forward_save: grid too large");
+  hipLaunchKernelGGL(lif_save_kernel, dim3((unsigned)blocks), dim3(256), 0,
+                     (hipStream_t)stream, x, T, n, make_neuron(nrn), h_out, s_out);
+  SNNQP_CHECK_LAUNCH("lif_save_kernel");
+  return SNNQP_OK;
+}
+
+int snnqp_lif_backward(const float *h, const float *gs, const float *glogits, int32_t group,
+                       int32_t T, int64_t R, int32_t C, const snnqp_neuron_t *nrn,
+                       int surrogate, float *gI, snnqp_stream_t stream) {
+  SNNQP_REQUIRE(T >= 0 && R >= 0 && C > 0, SNNQP_EINVAL, "lif_backward: bad shape");
+  SNNQP_REQUIRE(nrn && nrn->kind == SNNQP_NEURON_MULTI_STEP_LIF, SNNQP_EUNSUPPORTED,
+                "lif_backward: multi_step_LIF only");
+  SNNQP_REQUIRE((gs == nullptr) != (glogits == nullptr), SNNQP_EINVAL,
+                "lif_backward: exactly one of gs / glogits");
+  SNNQP_REQUIRE(!glogits || (group > 0 && C % group == 0), SNNQP_EINVAL,
+                "lif_backward: %d features not divisible by group %d", C, group);
+  const int64_t n = R * C;
+  if (n == 0 || T == 0) return SNNQP_OK;
+  SNNQP_REQUIRE(h && gI, SNNQP_EINVAL, "lif_backward: null argument");
+  SNNQP_REQUIRE(ceil_div64(n, 256) < (1ll << 31), SNNQP_EINVAL, "lif_backward: grid too large");
+  const NeuronP p = make_neuron(nrn);
+  hipStream_t st = (hipStream_t)stream;
+  switch (surrogate) {
+    case SNNQP_SURR_FAST_SIGMOID:
+      return launch_backward<SNNQP_SURR_FAST_SIGMOID>(h, gs, glogits, group, T, R, C, p, gI, st);
+    case SNNQP_SURR_ATAN:
+      return launch_backward<SNNQP_SURR_ATAN>(h, gs, glogits, group, T, R, C, p, gI, st);
+    case SNNQP_SURR_SLAYER:
+      return launch_backward<SNNQP_SURR_SLAYER>(h, gs, glogits, group, T, R, C, p, gI, st);
+    case SNNQP_SURR_SMOOTH_STEP:
+      return launch_backward<SNNQP_SURR_SMOOTH_STEP>(h, gs, glogits, group, T, R, C, p, gI, st);
+    case SNNQP_SURR_PIECEWISE_LINEAR:
+      return launch_backward<SNNQP_SURR_PIECEWISE_LINEAR>(h, gs, glogits, group, T, R, C, p, gI,
+                                                          st);
+    default:
+      set_error("lif_backward: unknown surrogate %d", surrogate);
+      return SNNQP_EINVAL;
+  }
+}
+
+int snnqp_dense_weight_grad(const float *x, const float *gI, int64_t M, int32_t K, int32_t N,
+                            float *gw, snnqp_stream_t stream) {
+  SNNQP_REQUIRE(M >= 0 && K > 0 && N > 0, SNNQP_EINVAL, "dense_weight_grad: bad shape");
+  SNNQP_REQUIRE(gw && ((x && gI) || M == 0), SNNQP_EINVAL, "dense_weight_grad: null argument");
+  // C[k][n] = sum_m x[m][k] gI[m][n]
+  return launch_gemm(x, K, 1, gI, N, 1, K, N, M, nullptr, gw, (hipStream_t)stream,
+                     "dense_weight_grad");
+}
+
+int snnqp_dense_input_grad(const float *gI, const float *w, const float *mask, int64_t M,
+                           int32_t K, int32_t N, float *gx, snnqp_stream_t stream) {
+  SNNQP_REQUIRE(M >= 0 && K > 0 && N > 0, SNNQP_EINVAL, "dense_input_grad: bad shape");
+  SNNQP_REQUIRE((gI && w && gx) || M == 0, SNNQP_EINVAL, "dense_input_grad: null argument");
+  if (M == 0) return SNNQP_OK;
+  // C[m][k] = sum_n gI[m][n] w[k][n]: r = n, i = m, j = k
+  return launch_gemm(gI, 1, N, w, 1, N, M, K, N, mask, gx, (hipStream_t)stream,
+                     "dense_input_grad");
+}
+
+}  // extern "C"

@@ -28,6 +28,7 @@ from . import ops
 from . import packing
 from .flax_qconv import QuantConv
 from .flax_qdense import QuantDense
+from .quant import DuQ
 from .spiking_learning import SpikingBlock, fused_dense_head
 
 
@@ -152,7 +153,8 @@ class DenseSNN(nn.Module):
 
   def __call__(self, inputs, trgt=None, train: bool = False, rng: Any = None,
                u_state=None, online=False):
-    _require_eval(train)
+    if train:
+      return self._train_forward(inputs, rng, u_state, online)
     cfg = self.config
     x = _as_input(inputs)
     hidden = cfg.hidden if "hidden" in cfg else cfg.channels * 2 * 2
@@ -203,6 +205,70 @@ class DenseSNN(nn.Module):
     if probe:
       _sow_density(self, "dense2_out", x)
     return ops.vote(x, 10), None                       # models.py:253-255
+
+  def _train_forward(self, inputs, rng, u_state, online):
+    """The training forward of models.py:191-255 (dropout masks M0 on the input and M1 on the
+    hidden spikes, keep probability config.dropout, not rescaled), attached to torch autograd
+    through the parameter leaves (dense_train.py).  Same spikes and logits as the eval forward
+    when every mask is one."""
+    from . import dense_train as dt
+    cfg = self.config
+    if rng is None:
+      raise NotImplementedError("train=True needs an rng (an int seed or a torch.Generator) for "
+                                "the dropout masks; the reference splits it unconditionally")
+    if u_state is not None or online:
+      raise NotImplementedError("training: the online mode and a carried state are not supported")
+    if _probing(self, cfg):
+      raise NotImplementedError("training: density probes are not supported")
+    if "dropout" not in cfg:
+      raise ValueError("train=True needs config.dropout (the keep probability of the dropout "
+                       "masks, models.py:193-197)")
+    qw = cfg.quant.get("weight")
+    if qw is not None and getattr(qw, "func", qw) is not DuQ:
+      raise NotImplementedError("training supports the DuQ weight quantiser or none, not %r" % (qw,))
+    if not (isinstance(inputs, torch.Tensor) or hasattr(inputs, "__array__")) or isinstance(
+        inputs, (ops.PackedSpikes, ops.PackedFrames, ops.GatedSpikes)):
+      raise NotImplementedError("training takes uint8 or float32 [B, T, K] tensors")
+    x = _as_input(inputs)
+    if x.ndim != 3:
+      raise ValueError("DenseSNN expects [B, T, K] inputs, got %s" % (tuple(x.shape),))
+    hidden = cfg.hidden if "hidden" in cfg else cfg.channels * 2 * 2
+    layer = SpikingBlock(
+        connection_fn=QuantDense(hidden, use_bias=False, dtype=self.dtype,
+                                 config=cfg.quant, bits=_layer_bits(cfg, 0),
+                                 g_scale=cfg.quant.g_scale),
+        neural_dynamics=cfg.neuron_dynamics(dtype=self.dtype),
+        return_state=False, batch_major_input=True)
+    layer2 = SpikingBlock(
+        connection_fn=QuantDense(self.num_classes * 10, use_bias=False,
+                                 dtype=self.dtype, config=cfg.quant,
+                                 bits=_layer_bits(cfg, 1), g_scale=cfg.quant.g_scale),
+        neural_dynamics=cfg.neuron_dynamics(dtype=self.dtype),
+        return_state=False)
+    surr1 = dt.surrogate_of(layer.neural_dynamics)
+    surr2 = dt.surrogate_of(layer2.neural_dynamics)
+    c1, c2 = layer.connection_fn, layer2.connection_fn
+    K = x.shape[-1]
+    pk1 = c1.packed_kernel(K)
+    pk2 = c2.packed_kernel(hidden)
+    params = self._root.variables["params"]
+    gen = dt.generator_of(rng, x.device)
+    m0 = dt.dropout_mask(x.shape, cfg.dropout, gen, x.device)           # models.py:193-197
+    x0 = dt.input_time_major(dt.apply_input_mask(x, m0))
+    wq1 = dt.transformed_kernel(params["QuantDense_0"], pk1)
+    s1, h1 = dt.DenseBlock1.apply(wq1, x0, pk1, layer.neural_dynamics.neuron(hidden), surr1)
+    m1 = dt.dropout_mask(s1.shape, cfg.dropout, gen, x.device)          # models.py:219-224
+    wq2 = dt.transformed_kernel(params["QuantDense_1"], pk2)
+    logits, s2, h2 = dt.DenseBlock2.apply(s1, wq2, m1, pk2, layer2.neural_dynamics.neuron(
+        self.num_classes * 10), surr2, 10)
+    if self.is_mutable_collection("intermediates"):
+      self.sow("intermediates", "dropout_0", m0)
+      self.sow("intermediates", "dropout_1", m1)
+      self.sow("intermediates", "dense1_out", s1.detach())
+      self.sow("intermediates", "dense1_h", h1)
+      self.sow("intermediates", "dense2_out", s2)
+      self.sow("intermediates", "dense2_h", h2)
+    return logits, None
 
 
 class ConvDenseSNN(nn.Module):

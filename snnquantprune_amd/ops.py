@@ -1452,3 +1452,65 @@ def vote(s, group: int = 10) -> torch.Tensor:
   out = torch.empty((B, N // group), dtype=torch.float32, device=t.device)
   L.check(L.lib().snnqp_vote(_ptr(t), typ, T, B, N, group, _ptr(out), _stream()))
   return out
+
+
+# ---------------------------------------------------------------------------
+# training of the dense blocks (csrc/train_dense.hip)
+# ---------------------------------------------------------------------------
+
+
+def lif_forward_save(x: torch.Tensor, neuron: Neuron):
+  """currents float32 [T, ..., C] -> (h, s) float32 [T, ..., C]: the multi_step_LIF potential
+  before the reset and the spikes, from a zero state (the arithmetic of lif_forward)."""
+  x = _f32c(x)
+  _require_gpu(x)
+  T, C = x.shape[0], x.shape[-1]
+  R = (x.numel() // (T * C)) if T * C else 0
+  h = torch.empty_like(x)
+  s = torch.empty_like(x)
+  L.check(L.lib().snnqp_lif_forward_save(_ptr(x), T, R, C, ctypes.byref(neuron.struct()),
+                                         _ptr(h), _ptr(s), _stream()))
+  return h, s
+
+
+def lif_backward(h: torch.Tensor, neuron: Neuron, surrogate: int, gs: Optional[torch.Tensor] = None,
+                 glogits: Optional[torch.Tensor] = None, group: int = 10) -> torch.Tensor:
+  """BPTT of the multi_step_LIF scan: h [T, R, C] -> gI [T, R, C], from the spikes' gradient
+  gs [T, R, C] or, through the vote, from the logits' gradient glogits [R, C // group]."""
+  h = _f32c(h)
+  gs = None if gs is None else _f32c(gs)
+  glogits = None if glogits is None else _f32c(glogits)
+  _require_gpu(h, gs, glogits)
+  T, C = h.shape[0], h.shape[-1]
+  R = (h.numel() // (T * C)) if T * C else 0
+  gI = torch.empty_like(h)
+  L.check(L.lib().snnqp_lif_backward(_ptr(h), _ptr(gs), _ptr(glogits), int(group), T, R, C,
+                                     ctypes.byref(neuron.struct()), int(surrogate), _ptr(gI),
+                                     _stream()))
+  return gI
+
+
+def dense_weight_grad(x: torch.Tensor, gI: torch.Tensor) -> torch.Tensor:
+  """x [M, K], gI [M, N] -> x^T gI [K, N] (float32 MFMA, one fixed reduction order)."""
+  x, gI = _f32c(x), _f32c(gI)
+  _require_gpu(x, gI)
+  M, K = x.shape
+  N = gI.shape[1]
+  assert gI.shape[0] == M
+  gw = torch.empty((K, N), dtype=torch.float32, device=x.device)
+  L.check(L.lib().snnqp_dense_weight_grad(_ptr(x), _ptr(gI), M, K, N, _ptr(gw), _stream()))
+  return gw
+
+
+def dense_input_grad(gI: torch.Tensor, w: torch.Tensor, mask: Optional[torch.Tensor] = None) -> torch.Tensor:
+  """gI [M, N], w [K, N] -> (gI w^T) * mask [M, K]."""
+  gI, w = _f32c(gI), _f32c(w)
+  mask = None if mask is None else _f32c(mask)
+  _require_gpu(gI, w, mask)
+  M, N = gI.shape
+  K = w.shape[0]
+  assert w.shape[1] == N and (mask is None or tuple(mask.shape) == (M, K))
+  gx = torch.empty((M, K), dtype=torch.float32, device=gI.device)
+  L.check(L.lib().snnqp_dense_input_grad(_ptr(gI), _ptr(w), _ptr(mask), M, K, N, _ptr(gx),
+                                         _stream()))
+  return gx

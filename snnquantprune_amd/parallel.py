@@ -74,3 +74,22 @@ def sharded_logits(apply_fn, variables, inputs, rank: int, world: int, group=Non
   if isinstance(logits, tuple):
     logits = logits[0]
   return all_gather_rows(logits, group)
+
+
+def mean_over_ranks(tensors, group=None):
+  """Averages a list of tensors over the ranks with ONE all-reduce (the reference's
+  lax.pmean(grads, "batch"), examples/train_utils.py:352): the tensors are flattened into one
+  float32 buffer, summed, divided by the world size and written back in place.  A no-op when
+  torch.distributed is not initialised."""
+  if not dist.is_initialized() or not tensors:
+    return tensors
+  world = dist.get_world_size(group)
+  flat = torch.cat([t.reshape(-1).to(torch.float32) for t in tensors])
+  dist.all_reduce(flat, op=dist.ReduceOp.SUM, group=group)
+  flat /= world
+  off = 0
+  for t in tensors:
+    n = t.numel()
+    t.copy_(flat[off:off + n].view_as(t))
+    off += n
+  return tensors

@@ -1,13 +1,15 @@
-"""Eval-side step functions -- mirror of examples/train_utils.py (eval_step
-:370-390, compute_metrics :220-225, mse_loss :210-217, cross_entropy_loss
-:196-207, create_model :133-134).  Training (train_step, optimisers, LR
-schedules, checkpoint writing) is out of scope.
+"""Step functions -- mirror of examples/train_utils.py (eval_step :370-390, compute_metrics
+:220-225, mse_loss :210-217, cross_entropy_loss :196-207, create_model :133-134, and for the
+models that train here (DenseSNN) create_train_state :161-195, weight_decay_fn :228-234 and the
+offline branch of train_step :249-368).  Not ported: the optax learning-rate schedules (any
+step -> lr callable is taken), the online branch, checkpoint writing.
 """
 
 from __future__ import annotations
 
+import dataclasses
 from dataclasses import dataclass
-from typing import Any, Callable
+from typing import Any, Callable, Optional
 
 import torch
 
@@ -53,3 +55,117 @@ def eval_step(state, batch, rng, smoothing, loss_type, burnin=0):
       variables, batch["dvs_matrix"], trgt=batch["label"], train=False,
       online=False, rng=rng, mutable=["batch_stats"], rngs={"dropout": rng})
   return compute_metrics(logits, batch["label"], smoothing, loss_type)
+
+
+# ---------------------------------------------------------------------------
+# training (offline branch)
+# ---------------------------------------------------------------------------
+
+
+def _flatten(tree, prefix=()):
+  """[(path tuple, tensor)] of a nested dict, in insertion order."""
+  out = []
+  for k, v in tree.items():
+    if isinstance(v, dict):
+      out.extend(_flatten(v, prefix + (k,)))
+    else:
+      out.append((prefix + (k,), v))
+  return out
+
+
+def _unflatten(items):
+  tree = {}
+  for path, v in items:
+    node = tree
+    for k in path[:-1]:
+      node = node.setdefault(k, {})
+    node[path[-1]] = v
+  return tree
+
+
+def weight_decay_fn(params):
+  """0.5 * sum p^2 over every parameter whose path names no BatchNorm (train_utils.py:228-234;
+  DuQ's a, c and the prune mask included, as there)."""
+  terms = [torch.sum(torch.square(p)) for path, p in _flatten(params)
+           if "BatchNorm" not in str(path) and "bn_init" not in str(path)]
+  if not terms:
+    return torch.zeros(())
+  return 0.5 * sum(terms)
+
+
+@dataclass
+class TrainState(EvalState):
+  """The reference's TrainState (flax.training.train_state + batch_stats): `params` holds
+  {'params': tree} as plain tensors that `tx` updates in place; `step` counts the updates."""
+  tx: Any = None
+  step: int = 0
+
+
+def make_optimizer(config, tensors):
+  """optax.adam (defaults: b1 0.9, b2 0.999, eps 1e-8) or optax.sgd(momentum, nesterov) over the
+  given tensors, as torch.optim; the learning rate is set by train_step each step."""
+  name = config.optimizer
+  if name == "adam":
+    return torch.optim.Adam(tensors, lr=0.0, betas=(0.9, 0.999), eps=1e-8)
+  if name == "sgd":
+    momentum = float(config.get("momentum", 0.0) or 0.0)
+    return torch.optim.SGD(tensors, lr=0.0, momentum=momentum,
+                           nesterov=bool(config.get("nesterov", False)))
+  raise ValueError("Unknown optimizer in config: " + str(name))
+
+
+def create_train_state(variables, config, model) -> TrainState:
+  """A TrainState over existing variables (model.init's, or a loaded checkpoint's): the params
+  are taken over as they are and updated in place (train_utils.py:161-195 creates them with
+  model.init first)."""
+  params = variables["params"]
+  tensors = []
+  for _, p in _flatten(params):
+    if p.requires_grad:
+      p.requires_grad_(False)
+    tensors.append(p)
+  tx = make_optimizer(config, tensors)
+  return TrainState(apply_fn=model.apply, params={"params": params},
+                    batch_stats=variables.get("batch_stats", {}), tx=tx, step=0)
+
+
+def train_step(state: TrainState, batch, rng, learning_rate_fn, weight_decay, smoothing,
+               loss_type, online=False, burnin=0, return_grads=False):
+  """One offline step (train_utils.py:249-368): loss = loss_type(logits, labels, smoothing) +
+  weight_decay * weight_decay_fn(params); gradients by the model's backward (DenseSNN:
+  dense_train.py), averaged over ranks when torch.distributed is initialised; then one update.
+  Returns (state, metrics) -- metrics with loss, accuracy, learning_rate and logits --, and the
+  gradient tree as a third element when return_grads."""
+  if online:
+    raise NotImplementedError("the online branch of train_step is not supported")
+  from .parallel import mean_over_ranks
+  params = state.params["params"]
+  items = _flatten(params)
+  leaves = [(path, p.detach().requires_grad_(True)) for path, p in items]
+  ptree = _unflatten(leaves)
+  (logits, _), _ = state.apply_fn(
+      {"params": ptree, "batch_stats": state.batch_stats}, batch["dvs_matrix"],
+      trgt=batch["label"], train=True, rng=rng, mutable=["batch_stats"], rngs={"dropout": rng})
+  loss = loss_type(logits, batch["label"], smoothing)
+  if weight_decay:
+    loss = loss + weight_decay * weight_decay_fn(ptree)
+  loss.backward()
+  grads = [torch.zeros_like(p) if p.grad is None else p.grad for _, p in leaves]
+  mean_over_ranks(grads)
+  lr = learning_rate_fn(state.step)
+  with torch.no_grad():
+    for (_, p), g in zip(items, grads):
+      p.grad = g.detach()
+    for group in state.tx.param_groups:
+      group["lr"] = float(lr)
+    state.tx.step()
+    for _, p in items:
+      p.grad = None
+  logits = logits.detach()
+  metrics = compute_metrics(logits, batch["label"], smoothing, loss_type)
+  metrics["learning_rate"] = lr
+  metrics["logits"] = logits
+  new_state = dataclasses.replace(state, step=state.step + 1)
+  if return_grads:
+    return new_state, metrics, _unflatten([(path, g) for (path, _), g in zip(items, grads)])
+  return new_state, metrics

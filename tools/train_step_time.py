@@ -1,0 +1,136 @@
+"""Times one DenseSNN train_step at config C2 (B = 256, T = 20, 2048 -> 512 -> 110, 8-bit DuQ,
+50 % pruned, uint8 spikes, atan surrogate, Adam) on the HIP path, per step and per backward
+kernel, against a plain PyTorch-eager float32 autograd statement of the same step on the same GPU
+(the reference's own training comparison is against a PyTorch SNN, examples/norse_cmp).
+Prints one JSON line.
+
+  python tools/train_step_time.py [--steps 20] [--warmup 5] [--batch 256] [--frames 20]
+"""
+import argparse
+import json
+import os
+import sys
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, ROOT)
+
+import torch  # noqa: E402
+
+
+def _time(fn, steps, warmup):
+  for _ in range(warmup):
+    fn()
+  torch.cuda.synchronize()
+  a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+  a.record()
+  for _ in range(steps):
+    fn()
+  b.record()
+  torch.cuda.synchronize()
+  return a.elapsed_time(b) / steps
+
+
+class _Spike(torch.autograd.Function):
+  @staticmethod
+  def forward(ctx, x):
+    ctx.save_for_backward(x)
+    return (x >= 0).to(x.dtype)
+
+  @staticmethod
+  def backward(ctx, g):
+    (x,) = ctx.saved_tensors
+    return g / (1 + (torch.pi * x) ** 2)
+
+
+def _eager_loss(params, x, labels, tau=2.0, L=127.0):
+  """The same step as float32 torch autograd: DuQ + prune, two dense blocks, LIF, vote, MSE."""
+  def wq(leaf):
+    w, a, c, m = leaf["kernel"], leaf["DuQ_0"]["a"], leaf["DuQ_0"]["c"], leaf["prune_0"]["mask"]
+    y = torch.nn.functional.hardtanh(w / a)
+    y = y + (torch.round(y * L) / L - y).detach()
+    return y * c * m
+
+  def block(xs, w):
+    cur = torch.einsum("tbk,kn->tbn", xs, w)
+    u = torch.zeros_like(cur[0])
+    out = []
+    for t in range(cur.shape[0]):
+      u = u + (cur[t] - u) / tau
+      s = _Spike.apply(u - 1.0)
+      u = u * (1 - s.detach())
+      out.append(s)
+    return torch.stack(out)
+
+  x0 = x.transpose(0, 1).to(torch.float32)
+  s1 = block(x0, wq(params["QuantDense_0"]))
+  s2 = block(s1, wq(params["QuantDense_1"]))
+  logits = s2.mean(0).reshape(s2.shape[1], -1, 10).mean(-1)
+  oh = torch.nn.functional.one_hot(labels, logits.shape[1]).to(torch.float32)
+  return torch.mean(torch.square(logits - oh))
+
+
+def main():
+  ap = argparse.ArgumentParser()
+  ap.add_argument("--steps", type=int, default=20)
+  ap.add_argument("--warmup", type=int, default=5)
+  ap.add_argument("--batch", type=int, default=256)
+  ap.add_argument("--frames", type=int, default=20)
+  args = ap.parse_args()
+  from snnquantprune_amd import linen as nn
+  from snnquantprune_amd import models, ops, synthetic as syn, train_utils as tu
+  dev = torch.device("cuda:0")
+  B, T, K, H, N = args.batch, args.frames, 2048, 512, 110
+  cfg = syn.make_config(bits=8, prune_percentage=0.5, hidden=H, dropout=0.9)
+  cfg.optimizer = "adam"
+  model = models.DenseSNN(num_classes=11, config=cfg)
+  v = syn.dense_net_variables(K, H, N, True, 0.5)
+  variables = nn.tree_from_numpy(v, dev)
+  x = torch.from_numpy(syn.poisson_spikes((B, T, K), 0.1, seed=941)).to(dev)
+  labels = torch.arange(B, device=dev) % 11
+  batch = {"dvs_matrix": x, "label": labels}
+  state = tu.create_train_state(variables, cfg, model)
+  box = [state]
+
+  def hip_step():
+    box[0], _ = tu.train_step(box[0], batch, 0, lambda s: 1e-4, 0.0, 0.0, tu.mse_loss)
+
+  hip_ms = _time(hip_step, args.steps, args.warmup)
+
+  # the backward kernels alone, on the step's shapes
+  nrn = ops.Neuron(1, 2.0, 1.0, 0.0)
+  h1 = torch.randn((T, B, H), device=dev)
+  h2 = torch.randn((T, B, N), device=dev)
+  gl = torch.randn((B, 11), device=dev)
+  x0 = x.transpose(0, 1).reshape(T * B, K).to(torch.float32)
+  x1 = (torch.rand((T * B, H), device=dev) < 0.2).to(torch.float32)
+  w2 = torch.randn((H, N), device=dev)
+  gI1, gI2 = torch.randn((T * B, H), device=dev), torch.randn((T * B, N), device=dev)
+  kern = {
+      "lif_backward_vote_ms": _time(lambda: ops.lif_backward(h2, nrn, 1, glogits=gl), args.steps, 2),
+      "lif_backward_ms": _time(lambda: ops.lif_backward(h1, nrn, 1, gs=h1), args.steps, 2),
+      "weight_grad_1_ms": _time(lambda: ops.dense_weight_grad(x0, gI1), args.steps, 2),
+      "weight_grad_2_ms": _time(lambda: ops.dense_weight_grad(x1, gI2), args.steps, 2),
+      "input_grad_2_ms": _time(lambda: ops.dense_input_grad(gI2, w2, x1), args.steps, 2),
+  }
+
+  eparams = {k: {kk: ({kkk: t.detach().clone().requires_grad_(True) for kkk, t in vv.items()}
+                      if isinstance(vv, dict) else vv.detach().clone().requires_grad_(True))
+                 for kk, vv in leaf.items()} for k, leaf in nn.tree_from_numpy(v, dev)["params"].items()}
+  flat = [t for _, t in tu._flatten(eparams)]
+  opt = torch.optim.Adam(flat, lr=1e-4, eps=1e-8)
+
+  def eager_step():
+    opt.zero_grad(set_to_none=True)
+    _eager_loss(eparams, x, labels).backward()
+    opt.step()
+
+  eager_ms = _time(eager_step, args.steps, args.warmup)
+  print(json.dumps({"workload": "dense_snn_c2_train_step", "batch": B, "frames": T,
+                    "hip_train_step_ms": round(hip_ms, 3), "eager_torch_train_step_ms": round(eager_ms, 3),
+                    "speedup_vs_eager": round(eager_ms / hip_ms, 2),
+                    "samples_per_s": round(B / hip_ms * 1e3, 1),
+                    **{k: round(val, 4) for k, val in kern.items()}}))
+
+
+if __name__ == "__main__":
+  main()
