@@ -144,7 +144,10 @@ typedef struct {
                           position w */
   int32_t wt_cin;      /* W_I8, 3x3 conv blocks over bit-packed spikes: the input-channel count
                           `wt` was zero-padded to (snnqp_conv_lif_forward), a multiple of 32 in
-                          [Cin, 128]; 0 = 32 ceil(Cin / 32), the packing rule */
+                          [Cin, 128]; 0 = 32 ceil(Cin / 32), the packing rule.  Where Cin leaves the
+                          upper 16 channels of the last 32-channel group empty (16 ceil(Cin / 16)
+                          + 16 equals the padding), the upper 16 rows of that group's tiles are
+                          not read (snnqp_set_conv_k16) */
 } snnqp_weight_t;
 
 /* Eval-mode BatchNorm folded on the host: y = fl(fl(fl(x - mean) * mul) + bias),
@@ -229,6 +232,15 @@ const char *snnqp_last_error(void);
 const char *snnqp_build_flags(void);
 
 /* Output spatial size of `g` (same rule as lax.conv_general_dilated). */
+/* The K walk of the bit-input 3x3 conv kernel (snnqp_conv_lif_forward, SNNQP_IMPL_MFMA, BITS
+ * input).  1 (the default): when Cin mod 32 is in 1..16 the kernel walks the last 32-channel group
+ * in 16-channel units and reads neither the upper 16 rows of that group's tiles in `wt` nor bits
+ * 16..31 of a pixel's last spike word.  0: it walks whole groups (the same results: those bits are
+ * zero by the contract of the input, those rows zero by the packing rule).  Process-wide, for the
+ * launches enqueued after the call; returns the previous setting.  A negative argument only
+ * queries. */
+int snnqp_set_conv_k16(int enabled);
+
 int snnqp_conv_out_shape(const snnqp_conv_geom_t *g, int32_t *OH, int32_t *OW);
 
 /* ---- weight transforms --------------------------------------------------
@@ -419,7 +431,8 @@ int snnqp_dense_gated_forward(const uint32_t *s, const float *gate, int64_t NB, 
  *       of the kernel zero-padded along Cin to Cpad = 32 ceil(Cin / 32) (or to
  *       w->wt_cin, a wider multiple of 32 up to 128), tiled by snnqp_pack_codes_mfma
  *       with K = 9 * Cpad (row = tap * Cpad + cin: int8 tile tap * Cpad / 32 + group);
- *       a pixel keeps its ceil(Cin / 32) spike words, zero bits beyond Cin --
+ *       a pixel keeps its ceil(Cin / 32) spike words, zero bits beyond Cin (bits 16..31 of the
+ *       last word are not even read when Cin mod 32 is in 1..16, snnqp_set_conv_k16) --
  *       or U8 input with Cin == 2, any count 0..255; or EV1 / EV4 input, Cin == 2: the packed
  *       frames are staged directly, 1/8 (binary) or 1/2 (counts <= 15) of the uint8 bytes;
  *       x_max / x_seen apply to EV4 as to U8), s_type BITS;

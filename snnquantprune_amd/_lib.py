@@ -67,6 +67,7 @@ _PROTOTYPES = {
     "snnqp_version": (c_int, []),
     "snnqp_last_error": (c_char_p, []),
     "snnqp_build_flags": (c_char_p, []),
+    "snnqp_set_conv_k16": (c_int, [c_int]),
     "snnqp_conv_out_shape": (c_int, [POINTER(ConvGeomT), POINTER(c_int32),
                                      POINTER(c_int32)]),
     "snnqp_quantize": (c_int, [c_int, c_void_p, c_void_p, c_int64, c_int, c_float,

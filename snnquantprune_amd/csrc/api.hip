@@ -1,7 +1,12 @@
 // libsnnqp: version, thread-local error string, geometry helper.
+#include <atomic>
+
 #include "common.h"
 
 namespace snnqp {
+
+static std::atomic<int> g_conv_k16{1};
+bool conv_k16_enabled() { return g_conv_k16.load(std::memory_order_relaxed) != 0; }
 
 static thread_local std::string g_last_error;
 
@@ -26,6 +31,11 @@ const char *snnqp_last_error(void) { return snnqp::g_last_error.c_str(); }
 #define SNNQP_BUILD_FLAGS ""
 #endif
 const char *snnqp_build_flags(void) { return SNNQP_BUILD_FLAGS; }
+
+int snnqp_set_conv_k16(int enabled) {
+  if (enabled < 0) return snnqp::conv_k16_enabled() ? 1 : 0;
+  return snnqp::g_conv_k16.exchange(enabled ? 1 : 0, std::memory_order_relaxed);
+}
 
 int snnqp_conv_out_shape(const snnqp_conv_geom_t *g, int32_t *OH, int32_t *OW) {
   SNNQP_REQUIRE(g && OH && OW, SNNQP_EINVAL, "conv_out_shape: null argument");

@@ -12,9 +12,12 @@
 //  * wider codes (8-bit DuQ, the reference's shipped configs): v_mfma_i32_32x32x32_i8,
 //    A = spikes as bytes, B = the int8 codes, 36 k-steps instead of 18 (Cin = 128).
 //
-// K runs over (tap, 32-channel group) pairs: CIN = 32 G input channels (the codes are padded to
-// that, snnqp.h), 9 G pairs, two per fp6 k-step (5 / 9 / 14 / 18 k-steps for G = 1 .. 4), one per
-// int8 k-step.
+// K runs over (tap, 32-channel group) pairs: the codes are padded to 32 G input channels
+// (snnqp.h), 9 G pairs, two per fp6 k-step (5 / 9 / 14 / 18 k-steps for G = 1 .. 4), one per
+// int8 k-step.  A last group of which only the lower 16 channels can spike (CIN = 16, 48, 80, 112:
+// Cin mod 32 in 1 .. 16) is walked in (tap, 16-channel) units instead and the upper 16 rows of its
+// tiles are not read: fp6 three k-steps of three units (k16_tap; 3 / 8 / 12 / 17 k-steps), int8
+// the five k-steps of the pair walk, one unit per lane half (5 / 14 / 23 / 32).
 //
 // A workgroup is 4 waves on one 4x8-pixel tile (patch), two workgroups per CU = two waves
 // per SIMD: wave w owns output channels [32 w, +32) of the tile, its B fragments for
@@ -35,13 +38,16 @@
 // two 16-byte halves (fp4: channel groups 2 p, 2 p + 1) swapped on odd rows: every tap/half
 // offset is an instruction immediate and the reads are bank-conflict free.  An odd fp6 G leaves
 // group G - 1 alone in the first half of the last plane; its k-steps pair two taps instead
-// (pair_tap) and read it through lane bases of their own.
+// (pair_tap) and read it through lane bases of their own.  A 16-channel last group (fp6) is staged
+// with its 8 bytes in both halves of its 16-byte slot; the two 8-byte pieces of a lane (k16_tap)
+// come from the half that keeps the 32 lanes of a ds_read_b64 group on 64 different banks.
 #include <type_traits>
 
 #include "conv_tile.h"
 
 namespace snnqp {
 
+typedef int v2i __attribute__((ext_vector_type(2)));
 typedef int v8i __attribute__((ext_vector_type(8)));
 typedef float v16f __attribute__((ext_vector_type(16)));
 typedef __attribute__((address_space(3))) const v4i lds_cv4i_t;
@@ -124,11 +130,26 @@ constexpr int F6_PF = 4;         // A fragments in flight (ring of 6 or 7); 2 wi
 // fp6, odd G: the tap lane half h reads in pair k-step p of the last group -- (0, 3), (1, 4),
 // (2, 5) one halo row apart, (6, 7), (8, -) one pixel apart; "tap 9" has zero codes
 __host__ __device__ constexpr int pair_tap(int p, int h) { return p < 3 ? p + 3 * h : 2 * p + h; }
+// fp6, 16-channel last group: the tap of piece i (k rows 32 h + 16 i .. + 15) of lane half h in
+// k-step q = 0 .. 2 of that group -- h = 0: taps q and 6 + q (two halo rows apart), h = 1: tap
+// 3 + q and nothing ("tap 9": zero codes; the piece re-reads tap 6 + q)
+__host__ __device__ constexpr int k16_tap(int q, int h, int i) { return i == 0 ? q + 3 * h : h == 0 ? 6 + q : 9; }
+
+// The A ring: the fragment of k-step k lives in entry k % ring, requested pf slots ahead.  True
+// when no request overwrites an entry that is still waiting for its MFMA (always so when the ring
+// divides ks; otherwise the wrap into the next timestep has to be checked)
+constexpr bool ring_ok(int ks, int ring, int pf) {
+  if (pf >= ring || pf >= ks) return false;
+  for (int k = 0; k < ks; ++k)
+    for (int j = 1; j < pf; ++j)
+      if ((k + pf) % ks % ring == (k + j) % ks % ring) return false;
+  return true;
+}
 
 template <int FMT, int CIN, int NF, bool POOL, int DQ, bool FMA = false, bool BNF = false, bool BNU = false>
 __global__ void __launch_bounds__(F6_NT, 2)
 conv3x3_bits_kernel(ConvMfmaArgs a) {
-  static_assert(CIN == 32 || CIN == 64 || CIN == 96 || CIN == 128, "one to four 32-channel groups");
+  static_assert(CIN % 16 == 0 && CIN >= 16 && CIN <= 128, "one to eight 16-channel half groups");
   static_assert(!BNU || (BNF && DQ == DQ_TABLE), "the uniform multiplier folds into the shared table");
   static_assert(DQ == DQ_ARITH || DQ == DQ_ONE || DQ == DQ_TABLE, "dequantisation mode");
   constexpr bool I8 = FMT == FMT_I8;
@@ -136,11 +157,17 @@ conv3x3_bits_kernel(ConvMfmaArgs a) {
   static_assert(!(TABLE && I8), "the table is addressed by a float32 accumulator");
   typedef typename std::conditional<I8, v16i, v16f>::type acc_t;
   constexpr int BR = I8 ? 4 : 6;                 // registers of one B fragment
-  constexpr int WPP = CIN / 32;                  // spike words (32-channel groups) per pixel
+  constexpr int WPP = (CIN + 31) / 32;           // spike words (32-channel groups) per pixel
+  constexpr int GW = CIN / 32;                   // groups walked whole
+  constexpr bool HALF = CIN % 32 != 0;           // group GW: its lower 16 channels only
   constexpr int NP = I8 ? WPP : (WPP + 1) / 2;   // planes of the halo image
-  constexpr int NPL = I8 ? WPP : WPP / 2;        // planes read whole: both lane halves at one tap
-  constexpr int PAIRS = I8 || WPP % 2 == 0 ? 0 : 5;   // k-steps over group G - 1 alone (pair_tap)
-  constexpr int KS = 9 * NPL + PAIRS;            // MFMAs (slots) of one timestep
+  constexpr int NPL = I8 ? GW : GW / 2;          // planes read whole: both lane halves at one tap
+  // k-steps of the pair walk (pair_tap) over the first half of plane NPL: fp6, the last whole
+  // group when their number is odd; int8, the lower 16 channels of a 16-channel last group
+  constexpr int PAIRS = (I8 ? HALF : GW % 2 == 1) ? 5 : 0;
+  constexpr int PGRP = I8 ? GW : GW - 1;         // the group the pair walk covers
+  constexpr int K16 = !I8 && HALF ? 3 : 0;       // fp6 k-steps over a 16-channel last group (k16_tap)
+  constexpr int KS = 9 * NPL + PAIRS + K16;      // MFMAs (slots) of one timestep
   constexpr int NPD = NPL > 0 ? NPL : 1;         // (divisor of the whole-plane k-step index)
   constexpr int HALO_B = NP * F6_PLANE;          // one halo image
   constexpr int FL = POOL ? 16 : 4;              // timesteps per flush block
@@ -176,19 +203,32 @@ conv3x3_bits_kernel(ConvMfmaArgs a) {
   // B operand: k-step ks = NPL tap + kk (< 9 NPL) covers channels 64 kk .. +63 of the tap; lane
   // (n, h) holds k = 32 h + j, i.e. both 16-byte halves of int8 tile WPP tap + 2 kk + h; pair
   // k-step 9 NPL + p: lane half h holds group WPP - 1 of tap pair_tap(p, h)
-  // (int8: k-step ks = WPP tap + kk is int8 tile ks as it is, lane (n, h) holds k = 16 h + j)
+  // k16 k-step 9 NPL + PAIRS + q: lane half h holds rows 0 .. 15 of group GW's tiles of taps
+  // k16_tap(q, h, 0) and k16_tap(q, h, 1)
+  // (int8: k-step ks = GW tap + kk is int8 tile WPP tap + kk as it is, lane (n, h) holds
+  // k = 16 h + j; pair k-step p: rows 0 .. 15 of group GW's tile of tap pair_tap(p, h))
   int bf[KS][BR];
   {
     const v4i *wtile = (const v4i *)a.wt + (int64_t)(cout_base >> 5) * (9 * WPP) * 64;
 #pragma unroll
     for (int ks = 0; ks < KS; ++ks) {
       if constexpr (I8) {
-        const v4i t = wave_on ? wtile[ks * 64 + lane] : v4i{0, 0, 0, 0};
+        const int ptap = pair_tap(ks - 9 * NPL, h);
+        const bool pair = ks >= 9 * NPL;
+        const int idx = pair ? (ptap * WPP + GW) * 64 + n : ((ks / NPD) * WPP + ks % NPD) * 64 + lane;
+        const v4i t = wave_on && !(pair && ptap >= 9) ? wtile[idx] : v4i{0, 0, 0, 0};
         bf[ks][0] = t.x; bf[ks][1] = t.y; bf[ks][2] = t.z; bf[ks][3] = t.w;
+      } else if (ks >= 9 * NPL + PAIRS) {
+        const int q = ks - 9 * NPL - PAIRS;
+        const int t0 = k16_tap(q, h, 0), t1 = k16_tap(q, h, 1);
+        v4i lo = {0, 0, 0, 0}, hi = {0, 0, 0, 0};
+        if (wave_on) lo = wtile[(t0 * WPP + GW) * 64 + n];
+        if (wave_on && t1 < 9) hi = wtile[(t1 * WPP + GW) * 64 + n];
+        fp6_pack32(lo, hi, bf[ks]);
       } else {
         const int ptap = pair_tap(ks - 9 * NPL, h);
         const bool pair = ks >= 9 * NPL;
-        const int ks8 = pair ? ptap * WPP + WPP - 1 : (ks / NPD) * WPP + (ks % NPD) * 2 + h;
+        const int ks8 = pair ? ptap * WPP + PGRP : (ks / NPD) * WPP + (ks % NPD) * 2 + h;
         v4i lo = {0, 0, 0, 0}, hi = {0, 0, 0, 0};
         if (wave_on && !(pair && ptap >= 9)) {
           lo = wtile[ks8 * 64 + n];
@@ -235,7 +275,15 @@ conv3x3_bits_kernel(ConvMfmaArgs a) {
   // pixel to the right (taps 6 + 2q, 7 + 2q); the same swizzle, so still conflict free
   const uint32_t abase_pv = pixb + (uint32_t)(h * F6_PITCH * 32 + ((ty ^ h) & 1) * 16);
   const uint32_t abase_ph = pixb + (uint32_t)(h * 32 + (ty & 1) * 16);
-  struct Bases { uint32_t e, o, pv, ph; };       // lane bases of one halo image
+  // k16 k-steps (group GW: half GW & 1 of plane GW / 2, its 8 bytes in both halves of the 16-byte
+  // slot): piece 0 at taps q / 3 + q (half h one halo row lower), piece 1 at tap 6 + q for both
+  // halves.  The 8-byte half alternates every two halo rows, so that with the 16-byte swizzle the
+  // four rows of a 32-lane group sit in four different quarters of a pixel's 32 bytes: every
+  // ds_read_b64 is bank-conflict free (tests/test_conv_k16_cpu.py)
+  const uint32_t abase_ka = pixb + (uint32_t)(h * F6_PITCH * 32 + (((GW ^ ty ^ h) & 1) * 16) +
+                                              (((ty + h) >> 1) & 1) * 8);
+  const uint32_t abase_kb = pixb + (uint32_t)((((GW ^ ty) & 1) * 16) + (((ty >> 1) & 1) ^ 1) * 8);
+  struct Bases { uint32_t e, o, pv, ph, ka, kb; };   // lane bases of one halo image
 
   // staging task of this thread: word wi of halo pixel pix
   const int s_pix = tid / WPP, s_wi = tid % WPP;
@@ -249,6 +297,9 @@ conv3x3_bits_kernel(ConvMfmaArgs a) {
                                            (s_hy * F6_PITCH + s_hx) * 32 +
                                            ((((I8 ? 0 : s_wi) & 1) ^ (s_hy & 1)) * 16));
   const uint32_t tabl = lds0 + TAB_OFF + (uint32_t)(lane & 31) * 4;   // this lane's table copy
+  // fp6, 16-channel last group: its 8 bytes (channels 0 .. 15: bytes 0, 1 of the word) twice; the
+  // upper half of the word is not looked at
+  const uint32_t s_sh2 = K16 && s_wi == GW ? 0u : 16u, s_sh3 = K16 && s_wi == GW ? 8u : 24u;
   const uint32_t *xb = (const uint32_t *)a.x;
 
   const int ob = out_pix<POOL>(0, lane) * 4 + cg;
@@ -302,8 +353,13 @@ conv3x3_bits_kernel(ConvMfmaArgs a) {
         // the bytes of the 32 lanes are
         s_exp.x = (int)*(lds_cu32_t *)(uintptr_t)(((sw & 0xFFu) << 7) + tabl);
         s_exp.y = (int)*(lds_cu32_t *)(uintptr_t)((((sw >> 8) & 0xFFu) << 7) + tabl);
-        s_exp.z = (int)*(lds_cu32_t *)(uintptr_t)((((sw >> 16) & 0xFFu) << 7) + tabl);
-        s_exp.w = (int)*(lds_cu32_t *)(uintptr_t)(((sw >> 24) << 7) + tabl);
+        if constexpr (K16 > 0) {
+          s_exp.z = (int)*(lds_cu32_t *)(uintptr_t)((((sw >> s_sh2) & 0xFFu) << 7) + tabl);
+          s_exp.w = (int)*(lds_cu32_t *)(uintptr_t)((((sw >> s_sh3) & 0xFFu) << 7) + tabl);
+        } else {
+          s_exp.z = (int)*(lds_cu32_t *)(uintptr_t)((((sw >> 16) & 0xFFu) << 7) + tabl);
+          s_exp.w = (int)*(lds_cu32_t *)(uintptr_t)(((sw >> 24) << 7) + tabl);
+        }
       }
     };
     auto stage_write = [&](uint32_t bufoff) {
@@ -320,6 +376,14 @@ conv3x3_bits_kernel(ConvMfmaArgs a) {
     };
     // A fragment of k-step ks from the halo image whose lane bases are ib
     auto a_read = [&](const Bases &ib, int ks) -> v4i {
+      if (ks >= 9 * NPL + PAIRS) {                // k16 k-step: two 8-byte pieces
+        typedef __attribute__((address_space(3))) const v2i lds_cv2i_t;
+        const int q = ks - 9 * NPL - PAIRS;
+        const uint32_t off = (uint32_t)((GW >> 1) * F6_PLANE + q * 32);
+        const v2i p0 = *(lds_cv2i_t *)(uintptr_t)(ib.ka + off);
+        const v2i p1 = *(lds_cv2i_t *)(uintptr_t)(ib.kb + off + 2 * F6_PITCH * 32);
+        return v4i{p0.x, p0.y, p1.x, p1.y};
+      }
       if (ks >= 9 * NPL) {                        // pair k-step: the padding half ("tap 9")
         const int p = ks - 9 * NPL;               // reads pixel (2, 3), inside the image
         const uint32_t off = (uint32_t)(NPL * F6_PLANE + (p < 3 ? p : 2 * F6_PITCH + 2 * (p - 3)) * 32);
@@ -457,10 +521,13 @@ conv3x3_bits_kernel(ConvMfmaArgs a) {
     };
 
     // ---- A-fragment ring: PF fragments in flight, across step boundaries ----------------
-    // the ring divides KS (5, 9, 14, 18, 27, 36): static indices
-    constexpr int RING = KS % 6 == 0 && !TABLE ? 6 : KS % 3 == 0 ? 3 : KS % 7 == 0 ? 7 : KS;
-    constexpr int PF = RING == 6 || (RING == 7 && !TABLE) ? F6_PF : 2;
-    static_assert(KS % RING == 0 && PF < RING, "ring indices must repeat every step");
+    // the fragment of k-step ks sits in entry ks % RING: static indices.  The ring divides KS
+    // where it can (5, 9, 12, 14, 18, 27, 36); for the other walks of a 16-channel last group (8,
+    // 17, 23, 32; 3 has one fragment in flight) ring_ok checks the wrap into the next timestep
+    constexpr int RING_DIV = KS % 6 == 0 && !TABLE ? 6 : KS % 3 == 0 ? 3 : KS % 7 == 0 ? 7 : KS;
+    constexpr int RING = RING_DIV < KS || KS <= 5 ? RING_DIV : TABLE ? 3 : ring_ok(KS, 6, F6_PF) ? 6 : 8;
+    constexpr int PF = KS == 3 ? 1 : RING == 6 || RING == 8 || (RING == 7 && !TABLE) ? F6_PF : 2;
+    static_assert(ring_ok(KS, RING, PF), "a request must not overwrite a fragment still to be used");
     v4i A[RING];
 
     // One pipelined step s: MFMA(s + 1) from the image rd while the epilogue of timestep s
@@ -475,7 +542,7 @@ conv3x3_bits_kernel(ConvMfmaArgs a) {
     constexpr bool LATE = TABLE || I8;
     constexpr int BAR_LATE = KS * 5 / 6 < KS - PF ? KS * 5 / 6 : KS - PF - 1;
     constexpr int WR_LATE = KS * 5 / 9 < BAR_LATE ? KS * 5 / 9 : BAR_LATE - 1;
-    constexpr int WR_SLOT = LATE ? WR_LATE : F6_WR_SLOT < KS - PF - 2 ? F6_WR_SLOT : 1;
+    constexpr int WR_SLOT = LATE ? WR_LATE : F6_WR_SLOT < KS - PF - 2 ? F6_WR_SLOT : KS - PF > 2 ? 1 : 0;
     constexpr int BAR_SLOT = LATE ? BAR_LATE : F6_BAR_SLOT < KS - PF ? F6_BAR_SLOT : WR_SLOT + 1;
     static_assert(WR_SLOT < BAR_SLOT && BAR_SLOT < KS - PF,
                   "the halo is written before the barrier, the next step's fragments read after it");
@@ -503,7 +570,7 @@ conv3x3_bits_kernel(ConvMfmaArgs a) {
         __builtin_amdgcn_sched_barrier(0);
         // the slot's A read: PF slots ahead, wrapping into the next step's image
         if (ks + PF < KS) A[(ks + PF) % RING] = a_read(rd, ks + PF);
-        else if (more) A[(ks + PF) % RING] = a_read(rn, ks + PF - KS);
+        else if (more) A[(ks + PF - KS) % RING] = a_read(rn, ks + PF - KS);
         // an even share of the epilogue stages
         {
           const int lo = ks * NSTAGES / KS, hi = (ks + 1) * NSTAGES / KS;
@@ -553,7 +620,7 @@ conv3x3_bits_kernel(ConvMfmaArgs a) {
     // lane bases of the halo images: halo(t) lives in image t % 3 of the ring
     auto img = [&](int k) {
       const uint32_t d = (uint32_t)(k * HALO_B);
-      return Bases{abase_even + d, abase_odd + d, abase_pv + d, abase_ph + d};
+      return Bases{abase_even + d, abase_odd + d, abase_pv + d, abase_ph + d, abase_ka + d, abase_kb + d};
     };
 
     // pipeline prologue: halo(0), halo(1) staged; MFMA(0) alone
@@ -580,7 +647,7 @@ conv3x3_bits_kernel(ConvMfmaArgs a) {
         if (ks == 0) accA = mfma_acc(0, A[0], TABLE ? cblk : zero16);
         else accA = mfma_acc(ks, A[ks % RING], accA);
         if (ks + PF < KS) A[(ks + PF) % RING] = a_read(i0, ks + PF);
-        else if (a.T > 1) A[(ks + PF) % RING] = a_read(i1, ks + PF - KS);
+        else if (a.T > 1) A[(ks + PF - KS) % RING] = a_read(i1, ks + PF - KS);
         __builtin_amdgcn_sched_barrier(0);
       }
     }
@@ -631,9 +698,11 @@ static void launch_bits_pool(const ConvMfmaArgs &a, bool pool, unsigned gy, hipS
 template <int FMT, int CIN>
 static void launch_bits_nf(const ConvMfmaArgs &a, int nf, bool pool, int dq, bool fma, bool bnf,
                            unsigned gy, hipStream_t st) {
-  if (nf == NF_MUL) return launch_bits_pool<FMT, CIN, NF_MUL, DQ_ARITH, false, false>(a, pool, gy, st);
-  if (nf == NF_DIV) return launch_bits_pool<FMT, CIN, NF_DIV, DQ_ARITH, false, false>(a, pool, gy, st);
-  if (nf == NF_DECAY) return launch_bits_pool<FMT, CIN, NF_DECAY, DQ_ARITH, false, false>(a, pool, gy, st);
+  if constexpr (CIN % 32 == 0) {
+    if (nf == NF_MUL) return launch_bits_pool<FMT, CIN, NF_MUL, DQ_ARITH, false, false>(a, pool, gy, st);
+    if (nf == NF_DIV) return launch_bits_pool<FMT, CIN, NF_DIV, DQ_ARITH, false, false>(a, pool, gy, st);
+    if (nf == NF_DECAY) return launch_bits_pool<FMT, CIN, NF_DECAY, DQ_ARITH, false, false>(a, pool, gy, st);
+  }
   if constexpr (FMT == FMT_FP6) {
     if (dq == DQ_TABLE) {
       // (the multiplier every channel shares folded into the table: the headline's form)
@@ -660,24 +729,32 @@ static void launch_bits_nf(const ConvMfmaArgs &a, int nf, bool pool, int dq, boo
 // i8: codes wider than fp6 holds (|code| > 7) -> the int8 instruction
 // dq: DQ_ARITH / DQ_ONE (conv_tile.h; ONE is a shortcut, ARITH with L = 1 computes the same);
 // fma: NF_MUL0 with the fused membrane update; bnf: BatchNorm means and biases all zero
-// cin_pad: the input channels the codes `wt` are padded to (32, 64, 96 or 128): the template
+// cin_walk: the input channels the K walk covers, the template: what the codes `wt` are padded to
+// (32, 64, 96 or 128), or 16 less when the upper half of the last group cannot spike.  Those walks
+// exist for the neuron form every shipped config runs (NF_MUL0); the general instances of the
+// other forms walk the whole last group (zero spikes against the codes there: the same sums)
 template <int FMT>
-static void launch_bits_cin(const ConvMfmaArgs &a, int cin_pad, int nf, bool pool, int dq, bool fma,
+static void launch_bits_cin(const ConvMfmaArgs &a, int cin_walk, int nf, bool pool, int dq, bool fma,
                             bool bnf, unsigned gy, hipStream_t st) {
-  if (cin_pad == 32) launch_bits_nf<FMT, 32>(a, nf, pool, dq, fma, bnf, gy, st);
-  else if (cin_pad == 64) launch_bits_nf<FMT, 64>(a, nf, pool, dq, fma, bnf, gy, st);
-  else if (cin_pad == 96) launch_bits_nf<FMT, 96>(a, nf, pool, dq, fma, bnf, gy, st);
+  if (nf != NF_MUL0) cin_walk = (cin_walk + 31) / 32 * 32;
+  if (cin_walk == 16) launch_bits_nf<FMT, 16>(a, nf, pool, dq, fma, bnf, gy, st);
+  else if (cin_walk == 32) launch_bits_nf<FMT, 32>(a, nf, pool, dq, fma, bnf, gy, st);
+  else if (cin_walk == 48) launch_bits_nf<FMT, 48>(a, nf, pool, dq, fma, bnf, gy, st);
+  else if (cin_walk == 64) launch_bits_nf<FMT, 64>(a, nf, pool, dq, fma, bnf, gy, st);
+  else if (cin_walk == 80) launch_bits_nf<FMT, 80>(a, nf, pool, dq, fma, bnf, gy, st);
+  else if (cin_walk == 96) launch_bits_nf<FMT, 96>(a, nf, pool, dq, fma, bnf, gy, st);
+  else if (cin_walk == 112) launch_bits_nf<FMT, 112>(a, nf, pool, dq, fma, bnf, gy, st);
   else launch_bits_nf<FMT, 128>(a, nf, pool, dq, fma, bnf, gy, st);
 }
 
-void launch_conv3x3_bits(const ConvMfmaArgs &a0, int cin_pad, bool i8, int nf, bool pool, int dq,
+void launch_conv3x3_bits(const ConvMfmaArgs &a0, int cin_walk, bool i8, int nf, bool pool, int dq,
                          bool fma, bool bnf, unsigned gy, hipStream_t st) {
   ConvMfmaArgs a = a0;                       // this kernel's patch: one tile of 4x8 pixels
   a.patch_h = 4;
   a.tiles_y = (a.H + 3) / 4;
   a.npatch = (int64_t)a.B * a.tiles_y * a.tiles_x;
-  if (i8) launch_bits_cin<FMT_I8>(a, cin_pad, nf, pool, dq, fma, bnf, gy, st);
-  else launch_bits_cin<FMT_FP6>(a, cin_pad, nf, pool, dq, fma, bnf, gy, st);
+  if (i8) launch_bits_cin<FMT_I8>(a, cin_walk, nf, pool, dq, fma, bnf, gy, st);
+  else launch_bits_cin<FMT_FP6>(a, cin_walk, nf, pool, dq, fma, bnf, gy, st);
 }
 
 }  // namespace snnqp

@@ -906,7 +906,12 @@ int run_conv3x3_mfma(const void *x, int in_type, int64_t xs_t, int64_t xs_b,
     a.lut_bound = tab ? (int32_t)w->abs_sum_max : 0;
     if (tab) check_code_bound_once(stream_device(st), (const int8_t *)w->w, (int64_t)9 * g->Cin, g->Cout,
                                    w->abs_sum_max, st);
-    launch_conv3x3_bits(a, cin_pad, i8, nf, pl, dq, fma, bnf, gy, st);
+    // no input channel in the upper half of the last 32-channel group (Cin mod 32 in 1 .. 16:
+    // a narrow layer, or a compacted producer whose consumer counts the live channels only):
+    // the walk that leaves that half out (snnqp_set_conv_k16(0): the walk over whole groups)
+    const int cin16 = (g->Cin + 15) / 16 * 16;
+    const int cin_walk = conv_k16_enabled() && cin16 + 16 == cin_pad ? cin16 : cin_pad;
+    launch_conv3x3_bits(a, cin_walk, i8, nf, pl, dq, fma, bnf, gy, st);
   } else {
     const int lm = lutc ? LUT_CHANNEL : lut ? LUT_SHARED : LUT_NONE;
     if (lut) check_code_bound_once(stream_device(st), (const int8_t *)w->w, (int64_t)9 * g->Cin, g->Cout,

@@ -649,10 +649,15 @@ static inline void launch_persistent(K kernel, ConvMfmaArgs a, unsigned gy, hipS
 // fma: the membrane update as one fused multiply-add (NF_MUL0, proven exact for this launch
 // by the caller: snnqp_weight_t.min_current_bits + lif_fma_is_exact)
 // bnf: every BatchNorm mean and bias is zero (snnqp_bn_t.flags): x = y * mul
-// cin_pad: the input channels `wt` is padded to, 32 / 64 / 96 / 128 (snnqp_weight_t.wt_cin)
+// cin_walk: the input channels the K walk covers: what `wt` is padded to, 32 / 64 / 96 / 128
+// (snnqp_weight_t.wt_cin), or 16 less (16 / 48 / 80 / 112) when no input channel lies in the upper
+// half of the last group -- the upper 16 rows of that group's tiles and the upper half of a
+// pixel's last spike word are then not read
 enum { DQ_ARITH = 1, DQ_ONE = 2, DQ_TABLE = 3 };
 constexpr int DQT_MAXA = 2047;
-void launch_conv3x3_bits(const ConvMfmaArgs &a, int cin_pad, bool i8, int nf, bool pool, int dq,
+void launch_conv3x3_bits(const ConvMfmaArgs &a, int cin_walk, bool i8, int nf, bool pool, int dq,
                          bool fma, bool bnf, unsigned gy, hipStream_t st);
+// snnqp_set_conv_k16 (api.hip): whether run_conv3x3_mfma picks the 16-less walks
+bool conv_k16_enabled();
 
 }  // namespace snnqp

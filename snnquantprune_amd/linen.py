@@ -161,6 +161,22 @@ def conv_kpack() -> bool:
   return _CONV_KPACK
 
 
+# The 16-channel walk of those convs: a last 32-channel group whose upper half
+# holds no input channel (Cin mod 32 in 1 .. 16) costs half a group of K.  A compacted producer
+# hands its consumer the live channels rounded up to 16, not 32, to get there.  On by default.
+def set_conv_k16(enabled: bool):
+  """True (default): the bit-input 3x3 conv kernel leaves the empty upper half of the last channel
+  group out of its K walk.  False: it walks whole 32-channel groups (the A side of an A/B on one
+  build; the results are the same).  A switch of the library: applies to the launches after it."""
+  from . import _lib
+  _lib.lib().snnqp_set_conv_k16(1 if enabled else 0)
+
+
+def conv_k16() -> bool:
+  from . import _lib
+  return bool(_lib.lib().snnqp_set_conv_k16(-1))
+
+
 def check_compute_dtype(dtype, who: str):
   global _dtype_warned
   if dtype in (torch.float32, None, "float32"):

@@ -210,6 +210,23 @@ def scatter_spike_channels(s: "PackedSpikes", channel_map: torch.Tensor, cout: i
   return PackedSpikes(out, int(cout))
 
 
+def truncate_silent_channels(x: "PackedSpikes"):
+  """A compacted raster for a conv consumer: its channel count cut to the live channels rounded up
+  to 16 (the K walk of the bit-input conv counts in 16s).  The map lists live
+  channels first, so this drops silent padding only; the words per pixel stay as they are and the
+  dropped bits are never set.  Returns (raster, its ChannelMap)."""
+  cm = x.chan_map
+  n = max(16, (int(cm.live.sum()) + 15) // 16 * 16)
+  if n >= cm.index.size or (n + 31) // 32 != x.bits.shape[-1] or cm.live[n:].any():
+    return x, cm
+  cut = getattr(cm, "_cut16", None)
+  if cut is None:
+    cut = cm._cut16 = ChannelMap(cm.index[:n], cm.live[:n], cm.full)
+  out = PackedSpikes(x.bits, n)
+  out.chan_map = cut
+  return out, cut
+
+
 def expand_channels(x):
   """A compacted raster (PackedSpikes with a chan_map) at its logical width, channels in their
   original order, the ones not computed zero; anything else is returned as it is.  A flattened

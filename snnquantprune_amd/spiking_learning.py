@@ -383,6 +383,8 @@ class SpikingBlock(nn.Module):
         x = ops.expand_channels(x)
         flat = x.flat_perm
         cmap_in = None
+      elif not is_dense:
+        x, cmap_in = ops.truncate_silent_channels(x)
     cin = x.shape[-1]
     pk = conn.packed_kernel(cin if cmap_in is None else full_cin)
     packed_out = bool(integer) if self.packed is None else bool(self.packed)

@@ -1,9 +1,11 @@
 """Conv K packing A/B: the same model, weights and batch with nn.set_conv_kpack off
 (codes of the bit-input convs padded to 64 / 128 input channels) and on (to a multiple of 32), in
 one process, alternating; per-kernel device time from the HIP-event profile and the whole apply.
-Checks that logits are bit-equal.
+Checks that logits are bit-equal.  --ab k16: the same A/B of nn.set_conv_k16 (off =
+the kernel walks whole 32-channel groups, on = it leaves the empty upper half of the last group
+out), K packing on in both.
 
-  python tools/kpack_ab.py [--B 1024] [--T 20] [--reps 5] [--out FILE.json]
+  python tools/kpack_ab.py [--ab kpack|k16] [--B 1024] [--T 20] [--reps 5] [--out FILE.json]
 """
 import argparse
 import json
@@ -24,7 +26,7 @@ LEGS = [  # name, bits, prune, layer_bits, input
 ]
 
 
-def leg(name, bits, prune, lb, inp, B, T, reps, dev):
+def leg(name, bits, prune, lb, inp, B, T, reps, dev, switch=nn.set_conv_kpack):
   cfg = syn.make_config(bits=bits, prune_percentage=prune)
   if lb:
     cfg.quant.layer_bits = tuple(lb)
@@ -37,7 +39,7 @@ def leg(name, bits, prune, lb, inp, B, T, reps, dev):
     x = ops.pack_frames(x, L.EV1)
 
   def run(kpack):
-    nn.set_conv_kpack(kpack)
+    switch(kpack)
     return model.apply(variables, x, trgt=None, train=False, rng=None)[0]
 
   out = {}
@@ -71,7 +73,7 @@ def leg(name, bits, prune, lb, inp, B, T, reps, dev):
                          for t in out["on"]["kernel_ms_median"] if t in out["off"]["kernel_ms_median"]}
   out["step_ratio_on_off"] = out["on"]["step_ms_median"] / out["off"]["step_ms_median"]
   out["logits_bit_equal"] = bool(np.array_equal(ref[False], ref[True]))
-  nn.set_conv_kpack(True)
+  switch(True)
   return out
 
 
@@ -81,11 +83,13 @@ def main():
   ap.add_argument("--T", type=int, default=20)
   ap.add_argument("--reps", type=int, default=5)
   ap.add_argument("--out", default=None)
+  ap.add_argument("--ab", choices=["kpack", "k16"], default="kpack")
   args = ap.parse_args()
   dev = torch.device("cuda:0")
-  res = {"B": args.B, "T": args.T, "reps": args.reps, "device": torch.cuda.get_device_name(0), "legs": {}}
+  switch = nn.set_conv_k16 if args.ab == "k16" else nn.set_conv_kpack
+  res = {"ab": args.ab, "B": args.B, "T": args.T, "reps": args.reps, "device": torch.cuda.get_device_name(0), "legs": {}}
   for name, bits, prune, lb, inp in LEGS:
-    r = leg(name, bits, prune, lb, inp, args.B, args.T, args.reps, dev)
+    r = leg(name, bits, prune, lb, inp, args.B, args.T, args.reps, dev, switch)
     res["legs"]["%s_%s" % (name, inp)] = r
     print("%-8s %-4s step %.2f -> %.2f ms (x%.3f)  %s  bit-equal %s" % (
         name, inp, r["off"]["step_ms_median"], r["on"]["step_ms_median"], r["step_ratio_on_off"],
@@ -94,6 +98,7 @@ def main():
         r["logits_bit_equal"]), flush=True)
     torch.cuda.empty_cache()
   res["fallback_counts"] = ops.fallback_counts()
+  res["device_status"] = ops.device_status()
   if args.out:
     with open(args.out, "w") as f:
       json.dump(res, f, indent=1, sort_keys=True)
