@@ -1501,6 +1501,9 @@ def lif_backward(h: torch.Tensor, neuron: Neuron, surrogate: int, gs: Optional[t
   T, C = h.shape[0], h.shape[-1]
   R = (h.numel() // (T * C)) if T * C else 0
   gI = torch.empty_like(h)
+  if h.numel() == 0 and (gs is None) != (glogits is None) and (
+      glogits is None or (group > 0 and C % group == 0)):
+    return gI       # an empty upstream has no pointer for the library to tell gs from glogits by
   L.check(L.lib().snnqp_lif_backward(_ptr(h), _ptr(gs), _ptr(glogits), int(group), T, R, C,
                                      ctypes.byref(neuron.struct()), int(surrogate), _ptr(gI),
                                      _stream()))

@@ -1,6 +1,7 @@
 """DenseSNN training on the GPU: the training forward against the eval forward and the oracle,
-and the HIP backward against a float64 statement of the reference's VJP rules applied to the
-saved float32 forward values (h, s, masks, kernel_fwd)."""
+and the HIP backward against two float64 yardsticks fed the saved float32 forward values (h, s,
+masks): the reference's VJP rules written out by hand, and torch.autograd on the literal forward
+(tests/train_reference.py; tests/test_train_reference_cpu.py holds the two to each other)."""
 from functools import partial
 
 import numpy as np
@@ -8,7 +9,9 @@ import pytest
 import torch
 
 from tests import cases
+from tests import train_reference as tr
 from tests.helpers import qweight_of
+from tests.train_reference import duq_vjp as _duq_vjp, scan_vjp as _scan_vjp  # noqa: F401
 
 pytestmark = pytest.mark.gpu
 
@@ -26,7 +29,7 @@ def _np(t):
 
 
 def _setup(dev, quantized=True, T=6, B=4, K=256, hidden=96, out=110, tau=2.0, v_reset=0.0,
-           surrogate="atan", counts=False, dropout=1.0, seed=941):
+           surrogate="atan", counts=False, dropout=1.0, seed=941, v_threshold=1.0):
   from snnquantprune_amd import linen as nn
   from snnquantprune_amd import models, spiking_learning as sl, synthetic as syn
   v = syn.dense_net_variables(K, hidden, out, quantized, 0.5 if quantized else -1.0)
@@ -37,7 +40,7 @@ def _setup(dev, quantized=True, T=6, B=4, K=256, hidden=96, out=110, tau=2.0, v_
   cfg = syn.make_config(bits=8, prune_percentage=0.5 if quantized else -1.0, hidden=hidden,
                         dropout=dropout)
   cfg.neuron_dynamics = partial(sl.multi_step_LIF, spike_fn=getattr(sl, surrogate), tau=tau,
-                                v_reset=v_reset)
+                                v_reset=v_reset, v_threshold=v_threshold)
   model = models.DenseSNN(num_classes=out // 10, config=cfg)
   return model, v, nn.tree_from_numpy(v, dev), torch.from_numpy(x).to(dev)
 
@@ -62,73 +65,28 @@ def _dense(s):
 
 # ---- float64 yardstick -------------------------------------------------------------------------
 
-def _sg(name, x):                               # spiking_learning.py:139-241
-  if name == "fast_sigmoid":
-    return 1.0 / (10.0 * np.abs(x) + 1.0) ** 2
-  if name == "atan":
-    return 1.0 / (1.0 + (np.pi * x) ** 2)
-  if name == "slayer":
-    return np.exp(-5.0 * np.abs(x))
-  if name == "smooth_step":
-    return ((x < 0.5) & (x >= -0.5)).astype(F64)
-  return np.maximum(1.0 - 2.0 * np.abs(x), 0.0)
-
-
-def _scan_vjp(h, s, gs, tau, vth, name):
-  """spiking_learning.py:410-414 differentiated: no gradient through the reset condition."""
-  T = h.shape[0]
-  gI = np.zeros_like(gs)
-  gu = np.zeros_like(gs[0])
-  for t in range(T - 1, -1, -1):
-    gh = gs[t] * _sg(name, h[t].astype(F64) - vth) + gu * (1.0 - s[t])
-    gI[t] = gh / tau
-    gu = gh * (1.0 - 1.0 / tau)
-  return gI
-
-
-def _duq_vjp(g, leaf, bits, quantized):
-  """quant.py:428-491: prune's grad_zero, DuQ with a straight-through round."""
-  w = leaf["kernel"].astype(F64)
-  a, c = float(leaf["DuQ_0"]["a"][0]), float(leaf["DuQ_0"]["c"][0])
-  mask = leaf.get("prune_0", {}).get("mask")
-  if mask is not None:
-    g = g * mask
-  if not quantized or a == -1.0:
-    return g, 0.0, 0.0
-  L = 2 ** (bits - 1) - 1
-  x = leaf["kernel"] / np.float32(a)
-  inside = np.abs(x.astype(F64)) <= 1
-  r = np.round(np.clip(x, -1, 1) * np.float32(L)).astype(F64) / L
-  gc = float((g * r).sum())
-  gw = np.where(inside, g * c / a, 0.0)
-  ga = float(-np.where(inside, g * c * w / (a * a), 0.0).sum())
-  return gw, ga, gc
+def _saved(x_bt, inter):
+  """The forward's saved values as tr.hand_gradients / tr.TorchDenseSNN64.forward take them."""
+  return (x_bt, _np(inter["dropout_0"]), _np(inter["dropout_1"]), _np(inter["dense1_h"]),
+          _np(inter["dense1_out"]), _np(inter["dense2_h"]), _np(_dense(inter["dense2_out"])))
 
 
 def _yardstick(v, x_bt, inter, logits, labels, loss, tau, vth, name, quantized, o):
   p = v["params"]
   lg = torch.from_numpy(_np(logits).astype(F64)).requires_grad_(True)
-  from snnquantprune_amd import train_utils as tu
   loss(lg, torch.from_numpy(labels)).backward()
-  gL = lg.grad.numpy()
-  m0, m1 = _np(inter["dropout_0"]).astype(F64), _np(inter["dropout_1"]).astype(F64)
-  h1, h2 = _np(inter["dense1_h"]), _np(inter["dense2_h"])
-  s1, s2 = _np(inter["dense1_out"]).astype(F64), _np(_dense(inter["dense2_out"])).astype(F64)
-  T, B, N = s2.shape
-  gs2 = np.repeat(gL, 10, axis=1)[None].repeat(T, 0) / (10 * T)       # models.py:253-255
-  gI2 = _scan_vjp(h2, s2, gs2, tau, vth, name)
-  x1 = s1 * m1
-  gwq2 = np.einsum("tbk,tbn->kn", x1, gI2)
   wq2 = qweight_of(o, p["QuantDense_1"], 8, quantized).w_fq.astype(F64)
-  gs1 = np.einsum("tbn,kn->tbk", gI2, wq2) * m1
-  gI1 = _scan_vjp(h1, s1, gs1, tau, vth, name)
-  x0 = np.swapaxes(x_bt.astype(F64) * m0, 0, 1)
-  gwq1 = np.einsum("tbk,tbn->kn", x0, gI1)
-  out = {}
-  for i, g in ((0, gwq1), (1, gwq2)):
-    gw, ga, gc = _duq_vjp(g, p["QuantDense_%d" % i], 8, quantized)
-    out[i] = (gw, ga, gc)
-  return out
+  return tr.hand_gradients(p, *_saved(x_bt, inter), lg.grad.numpy(), wq2, tau, vth, name,
+                           quantized)
+
+
+def _autograd_yardstick(v, x_bt, inter, logits, labels, loss, tau, vth, vr, name):
+  """The same gradients by torch.autograd on the literal float64 forward."""
+  m = tr.TorchDenseSNN64(v["params"], tau, vth, vr, name)
+  lg = m.forward(*_saved(x_bt, inter))
+  np.testing.assert_allclose(lg.detach().numpy(), _np(logits).astype(F64), rtol=1e-6, atol=1e-7)
+  loss(lg, torch.from_numpy(labels)).backward()
+  return m.grads()
 
 
 def _close(got, ref, what):
@@ -192,6 +150,9 @@ GRID = [
     dict(counts=True, loss="ce"),
     dict(K=100, hidden=96, out=110, B=7, T=5, surrogate="fast_sigmoid"),
     dict(K=2048, hidden=512, out=110, B=64, T=20, loss="ce", counts=True),
+    dict(v_threshold=0.7), dict(v_threshold=0.7, tau=3.0, surrogate="smooth_step"),
+    dict(dropout=1.0), dict(T=1), dict(T=1, surrogate="piecewise_linear", loss="ce"),
+    dict(hidden=100, out=30, B=3, T=7), dict(quantized=False, v_reset=0.1),
 ]
 
 
@@ -216,8 +177,10 @@ def test_gradients_match_yardstick(dev, oracle, case):
   loss_name = case.pop("loss", "mse")
   quantized = case.pop("quantized", True)
   tau, vr = case.get("tau", 2.0), case.get("v_reset", 0.0)
+  vth = case.get("v_threshold", 1.0)
   name = case.get("surrogate", "atan")
-  model, v, variables, x = _setup(dev, quantized, dropout=0.8, **case)
+  case.setdefault("dropout", 0.8)
+  model, v, variables, x = _setup(dev, quantized, **case)
   loss = tu.mse_loss if loss_name == "mse" else tu.cross_entropy_loss
   B = x.shape[0]
   labels = (np.arange(B) * 7 % (model.num_classes)).astype(np.int64)
@@ -225,11 +188,16 @@ def test_gradients_match_yardstick(dev, oracle, case):
   loss(logits, torch.from_numpy(labels).to(dev)).backward()
   torch.cuda.synchronize()
   got = _grads(params)
-  ref = _yardstick(v, _np(x), inter, logits, labels, loss, tau, 1.0, name, quantized, oracle)
+  if case["dropout"] == 1.0:
+    assert float(_np(inter["dropout_1"]).min()) == 1.0
+  assert 0.01 < float(_np(inter["dense1_out"]).mean()) < 0.99            # a layer that spikes
+  ref = _yardstick(v, _np(x), inter, logits, labels, loss, tau, vth, name, quantized, oracle)
+  auto = _autograd_yardstick(v, _np(x), inter, logits, labels, loss, tau, vth, vr, name)
   for i in (0, 1):
-    _close(got[i][0], ref[i][0], "kernel %d" % i)
-    _close(got[i][1], ref[i][1], "a %d" % i)
-    _close(got[i][2], ref[i][2], "c %d" % i)
+    for what, yard in (("hand", ref), ("autograd", auto)):
+      _close(got[i][0], yard[i][0], "kernel %d (%s)" % (i, what))
+      _close(got[i][1], yard[i][1], "a %d (%s)" % (i, what))
+      _close(got[i][2], yard[i][2], "c %d (%s)" % (i, what))
     if got[i][3] is not None:
       assert float(got[i][3].abs().max()) == 0.0
 
