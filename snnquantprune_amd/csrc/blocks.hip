@@ -29,6 +29,21 @@ void note_fallback(bool dense, const char *why) {
     std::fprintf(stderr, "libsnnqp: %s block on the direct-form kernel: %s\n",
                  dense ? "dense" : "conv", why ? why : "");
 }
+
+// a dense layer as the direct-form kernel sees it: a 1x1 convolution on a 1x1 image
+snnqp_conv_geom_t dense_geom(int32_t K, int32_t N) {
+  snnqp_conv_geom_t g;
+  g.H = 1; g.W = 1; g.Cin = K; g.Cout = N; g.KH = 1; g.KW = 1;
+  g.stride_h = g.stride_w = 1;
+  g.pad_h_lo = g.pad_h_hi = g.pad_w_lo = g.pad_w_hi = 0;
+  g.in_dil_h = g.in_dil_w = g.k_dil_h = g.k_dil_w = 1;
+  g.groups = 1;
+  return g;
+}
+
+#define SNNQP_CHECK_NEURON_KIND(nrn, who)                                                      \
+  SNNQP_REQUIRE((nrn)->kind >= SNNQP_NEURON_MULTI_STEP_LIF && (nrn)->kind <= SNNQP_NEURON_LIF, \
+                SNNQP_EINVAL, who ": unknown neuron kind %d", (nrn)->kind)
 }  // namespace
 
 extern "C" {
@@ -69,9 +84,7 @@ int snnqp_conv_lif_forward(const void *x, int in_type, int64_t x_stride_t,
     SNNQP_REQUIRE(x_flags != nullptr, SNNQP_EINVAL,
                   "conv_lif_forward: float32 input into integer codes needs x_flags (snnqp.h)");
   if (int rc = refuse_after_device_report((hipStream_t)stream, "conv_lif_forward")) return rc;
-  SNNQP_REQUIRE(nrn->kind >= SNNQP_NEURON_MULTI_STEP_LIF &&
-                    nrn->kind <= SNNQP_NEURON_LIF,
-                SNNQP_EINVAL, "conv_lif_forward: unknown neuron kind %d", nrn->kind);
+  SNNQP_CHECK_NEURON_KIND(nrn, "conv_lif_forward");
   SNNQP_REQUIRE(pool == 1 || pool == 2, SNNQP_EINVAL,
                 "conv_lif_forward: pool must be 1 or 2");
   SNNQP_REQUIRE(impl >= SNNQP_IMPL_AUTO && impl <= SNNQP_IMPL_MFMA, SNNQP_EINVAL,
@@ -112,8 +125,7 @@ int snnqp_conv_lif_forward_pred(const int32_t *pred, const void *x, int in_type,
     SNNQP_REQUIRE(x_flags != nullptr, SNNQP_EINVAL,
                   "conv_lif_forward_pred: float32 input into integer codes needs x_flags (snnqp.h)");
   if (int rc = refuse_after_device_report((hipStream_t)stream, "conv_lif_forward_pred")) return rc;
-  SNNQP_REQUIRE(nrn->kind >= SNNQP_NEURON_MULTI_STEP_LIF && nrn->kind <= SNNQP_NEURON_LIF, SNNQP_EINVAL,
-                "conv_lif_forward_pred: unknown neuron kind %d", nrn->kind);
+  SNNQP_CHECK_NEURON_KIND(nrn, "conv_lif_forward_pred");
   SNNQP_REQUIRE(pool == 1 || pool == 2, SNNQP_EINVAL, "conv_lif_forward_pred: pool must be 1 or 2");
   SNNQP_REQUIRE(in_type == SNNQP_U8 || in_type == SNNQP_F32 || in_type == SNNQP_EV4, SNNQP_EUNSUPPORTED,
                 "conv_lif_forward_pred: byte, nibble or float32 frames (the event layer's own formats)");
@@ -131,8 +143,7 @@ int snnqp_conv_lif_forward_if(const int32_t *pred, const void *x, int in_type, i
                               snnqp_stream_t stream) {
   SNNQP_REQUIRE(pred && g && w && nrn, SNNQP_EINVAL, "conv_lif_forward_if: null argument");
   if (int rc = refuse_after_device_report((hipStream_t)stream, "conv_lif_forward_if")) return rc;
-  SNNQP_REQUIRE(nrn->kind >= SNNQP_NEURON_MULTI_STEP_LIF && nrn->kind <= SNNQP_NEURON_LIF,
-                SNNQP_EINVAL, "conv_lif_forward_if: unknown neuron kind %d", nrn->kind);
+  SNNQP_CHECK_NEURON_KIND(nrn, "conv_lif_forward_if");
   SNNQP_REQUIRE(pool == 1 || pool == 2, SNNQP_EINVAL, "conv_lif_forward_if: pool must be 1 or 2");
   return run_generic(x, in_type, x_stride_t, x_stride_b, T, B, g, w, bn, nrn, u0, u_out, s_out, s_type,
                      nullptr, (hipStream_t)stream, pool, pred);
@@ -145,14 +156,8 @@ int snnqp_dense_lif_forward_if(const int32_t *pred, const void *x, int in_type, 
                                void *s_out, int s_type, snnqp_stream_t stream) {
   SNNQP_REQUIRE(pred && w && nrn && K > 0 && N > 0, SNNQP_EINVAL, "dense_lif_forward_if: bad argument");
   if (int rc = refuse_after_device_report((hipStream_t)stream, "dense_lif_forward_if")) return rc;
-  SNNQP_REQUIRE(nrn->kind >= SNNQP_NEURON_MULTI_STEP_LIF && nrn->kind <= SNNQP_NEURON_LIF,
-                SNNQP_EINVAL, "dense_lif_forward_if: unknown neuron kind %d", nrn->kind);
-  snnqp_conv_geom_t g;
-  g.H = 1; g.W = 1; g.Cin = K; g.Cout = N; g.KH = 1; g.KW = 1;
-  g.stride_h = g.stride_w = 1;
-  g.pad_h_lo = g.pad_h_hi = g.pad_w_lo = g.pad_w_hi = 0;
-  g.in_dil_h = g.in_dil_w = g.k_dil_h = g.k_dil_w = 1;
-  g.groups = 1;
+  SNNQP_CHECK_NEURON_KIND(nrn, "dense_lif_forward_if");
+  const snnqp_conv_geom_t g = dense_geom(K, N);
   return run_generic(x, in_type, x_stride_t, x_stride_b, T, B, &g, w, bn, nrn, u0, u_out, s_out, s_type,
                      nullptr, (hipStream_t)stream, 1, pred);
 }
@@ -195,9 +200,7 @@ int snnqp_dense_lif_forward_ws(const void *x, int in_type, int64_t x_stride_t,
                   "dense_lif_forward: float32 rows into integer codes need x_flags (snnqp.h)");
   if (int rc = refuse_after_device_report((hipStream_t)stream, "dense_lif_forward")) return rc;
   SNNQP_REQUIRE(K > 0 && N > 0, SNNQP_EINVAL, "dense_lif_forward: bad K/N");
-  SNNQP_REQUIRE(nrn->kind >= SNNQP_NEURON_MULTI_STEP_LIF &&
-                    nrn->kind <= SNNQP_NEURON_LIF,
-                SNNQP_EINVAL, "dense_lif_forward: unknown neuron kind %d", nrn->kind);
+  SNNQP_CHECK_NEURON_KIND(nrn, "dense_lif_forward");
   SNNQP_REQUIRE(impl >= SNNQP_IMPL_AUTO && impl <= SNNQP_IMPL_MFMA, SNNQP_EINVAL,
                 "dense_lif_forward: unknown impl %d", impl);
   // codes that fit fp6, packed as fp6 tiles, over bit-packed rows: the f8f6f4 kernel
@@ -234,12 +237,7 @@ int snnqp_dense_lif_forward_ws(const void *x, int in_type, int64_t x_stride_t,
     return run_dense_mfma(x, in_type, x_stride_t, x_stride_b, T, B, K, N, w, wt, bn, nrn,
                           u0, u_out, (uint32_t *)s_out, (hipStream_t)stream);
   if (impl == SNNQP_IMPL_AUTO) note_fallback(true, why);
-  snnqp_conv_geom_t g;
-  g.H = 1; g.W = 1; g.Cin = K; g.Cout = N; g.KH = 1; g.KW = 1;
-  g.stride_h = g.stride_w = 1;
-  g.pad_h_lo = g.pad_h_hi = g.pad_w_lo = g.pad_w_hi = 0;
-  g.in_dil_h = g.in_dil_w = g.k_dil_h = g.k_dil_w = 1;
-  g.groups = 1;
+  const snnqp_conv_geom_t g = dense_geom(K, N);
   return run_generic(x, in_type, x_stride_t, x_stride_b, T, B, &g, w, bn, nrn, u0,
                      u_out, s_out, s_type, nullptr, (hipStream_t)stream);
 }

@@ -67,10 +67,6 @@ __device__ __forceinline__ float div_exact(float a, const Dequant &d) {
   return __builtin_fmaf(a, d.rL, a * d.rLlo);
 }
 
-__device__ __forceinline__ float dequant_acc_nb(int acc, const Dequant &d) {
-  return div_exact((float)acc, d) * d.m;
-}
-
 __device__ __forceinline__ float dequant_acc(int acc, const Dequant &d) {
   return div_exact((float)acc, d) * d.m;
 }

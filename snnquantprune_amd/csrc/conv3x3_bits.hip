@@ -47,36 +47,16 @@
 
 namespace snnqp {
 
-typedef int v2i __attribute__((ext_vector_type(2)));
-typedef int v8i __attribute__((ext_vector_type(8)));
-typedef float v16f __attribute__((ext_vector_type(16)));
 typedef __attribute__((address_space(3))) const v4i lds_cv4i_t;
-typedef __attribute__((address_space(3))) const uint32_t lds_cu32_t;
 
 constexpr int F6_PITCH = HPITCH;             // pixels per LDS halo row (10 used)
 constexpr int F6_ROWS = 6;                   // halo rows of a 4x8 patch
 constexpr int F6_NT = 256;                   // threads of a workgroup: 4 waves
 constexpr int F6_PLANE = F6_ROWS * HPITCH * 32;   // one k-step plane of a halo image
 constexpr int F6_NBUF = 3;                   // halo images in the ring
-// byte -> 8 fp4 nibbles, 32 interleaved copies: entry e of copy c at dword 32 e + c, so lane
-// l of a 32-lane group reads bank l whatever its byte is (ds_read_b32 banks: (a / 4) % 32)
-constexpr int F6_TAB = 256 * 32 * 4;
+constexpr int F6_TAB = FP4_TAB_BYTES;        // byte -> 8 fp4 nibbles (tile_util.h)
 // (DQT_MAXA = 2047, conv_tile.h: the |acc| bound DQ_TABLE's table is sized for)
 constexpr int DQT_BYTES = 16384;             // 4095 entries
-
-// 4 int8 codes (|c| <= 7) -> 4 e2m3 codes, one per byte
-__device__ __forceinline__ uint32_t fp6_codes4(uint32_t x) {
-  const uint32_t m1 = (x >> 7) & 0x01010101u;       // 1 where negative
-  const uint32_t mag = (x ^ (m1 * 0xFFu)) + m1;     // |c| per byte (no carries)
-  // magnitude 0..7 -> 0x00 0x08 0x10 0x14 0x18 0x1A 0x1C 0x1E (v_perm byte select)
-  const uint32_t code = __builtin_amdgcn_perm(0x1E1C1A18u, 0x14100800u, mag);
-  return code | (m1 << 5);
-}
-
-// four 6-bit codes in the bytes of c -> 24 contiguous bits
-__device__ __forceinline__ uint32_t squeeze6(uint32_t c) {
-  return (c & 0x3Fu) | ((c >> 2) & 0xFC0u) | ((c >> 4) & 0x3F000u) | ((c >> 6) & 0xFC0000u);
-}
 
 // 32 int8 codes in k order (lo = k 0..15, hi = k 16..31) -> 32 fp6 values, value j
 // at bits [6j, 6j + 6) of 6 dwords (the B fragment of one lane for one k-step)
@@ -190,16 +170,8 @@ conv3x3_bits_kernel(ConvMfmaArgs a) {
   const int cpar = cout < a.Cout ? cout : a.Cout - 1;      // parameter loads
   const uint32_t cmask = chan_mask(cout_base, a.Cout);
 
-  // table: byte -> 8 nibbles (bit i set -> 1.0 = 0x2 in nibble i), 32 copies
-  if (!I8) {                                     // (int8: bits -> bytes by arithmetic)
-    for (int i = tid; i < 256 * 32; i += F6_NT) {
-      const int e = i >> 5;
-      uint32_t v = 0;
-#pragma unroll
-      for (int bit = 0; bit < 8; ++bit) v |= ((e >> bit) & 1) ? (0x2u << (4 * bit)) : 0u;
-      ((uint32_t *)(lds + TAB_OFF))[i] = v;
-    }
-  }
+  // the byte -> 8 nibbles table (int8: bits -> bytes by arithmetic)
+  if (!I8) fp4_table_fill((uint32_t *)(lds + TAB_OFF), tid, F6_NT);
   // B operand: k-step ks = NPL tap + kk (< 9 NPL) covers channels 64 kk .. +63 of the tap; lane
   // (n, h) holds k = 32 h + j, i.e. both 16-byte halves of int8 tile WPP tap + 2 kk + h; pair
   // k-step 9 NPL + p: lane half h holds group WPP - 1 of tap pair_tap(p, h)
@@ -296,7 +268,7 @@ conv3x3_bits_kernel(ConvMfmaArgs a) {
   const uint32_t s_dst = lds0 + (uint32_t)((I8 ? s_wi : s_wi >> 1) * F6_PLANE +
                                            (s_hy * F6_PITCH + s_hx) * 32 +
                                            ((((I8 ? 0 : s_wi) & 1) ^ (s_hy & 1)) * 16));
-  const uint32_t tabl = lds0 + TAB_OFF + (uint32_t)(lane & 31) * 4;   // this lane's table copy
+  const uint32_t tabl = fp4_table_lane(lds0 + TAB_OFF, lane);
   // fp6, 16-channel last group: its 8 bytes (channels 0 .. 15: bytes 0, 1 of the word) twice; the
   // upper half of the word is not looked at
   const uint32_t s_sh2 = K16 && s_wi == GW ? 0u : 16u, s_sh3 = K16 && s_wi == GW ? 8u : 24u;
@@ -367,8 +339,8 @@ conv3x3_bits_kernel(ConvMfmaArgs a) {
       if (I8) {
         if (s_task) {
           const uint32_t d = s_dst + bufoff;
-          *(lds_v4i_t *)(uintptr_t)d = expand16<false>(stg_cur & 0xFFFFu);        // channels 0..15
-          *(lds_v4i_t *)(uintptr_t)(s_hy & 1 ? d - 16 : d + 16) = expand16<false>(stg_cur >> 16);
+          *(lds_v4i_t *)(uintptr_t)d = expand16(stg_cur & 0xFFFFu);        // channels 0..15
+          *(lds_v4i_t *)(uintptr_t)(s_hy & 1 ? d - 16 : d + 16) = expand16(stg_cur >> 16);
         }
       } else if (s_task) {
         *(lds_v4i_t *)(uintptr_t)(s_dst + bufoff) = s_exp;

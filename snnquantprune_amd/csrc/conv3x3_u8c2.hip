@@ -561,7 +561,7 @@ current_min_kernel(Dequant dq, BnP bn, int bound, int Cout, uint32_t *out) {
     float mean = 0.f, mul = 1.f, bias = 0.f;
     if (bn.mean) { mean = bn.mean[c]; mul = bn.mul[c]; bias = bn.bias[c]; }
     for (int i = (int)(threadIdx.x >> 6) + 4 * (int)blockIdx.y - bound; i <= bound; i += 4 * (int)gridDim.y) {
-      float x = dequant_acc_nb(i, dq) - mean;       // the epilogue's operation order
+      float x = dequant_acc(i, dq) - mean;       // the epilogue's operation order
       x = x * mul;
       x = x + bias;
       const uint32_t b = __float_as_uint(x) & 0x7FFFFFFFu;

@@ -28,10 +28,6 @@ namespace snnqp {
 
 namespace {
 
-typedef int v8i __attribute__((ext_vector_type(8)));
-typedef int v2i __attribute__((ext_vector_type(2)));
-typedef float v16f __attribute__((ext_vector_type(16)));
-
 constexpr int CG_WAVES = 4;
 constexpr int CG_CMAX = 128;          // input channels (the LDS table is CMAX x 32 dwords per wave)
 

@@ -6,9 +6,6 @@
 
 namespace snnqp {
 
-
-typedef int v4i __attribute__((ext_vector_type(4)));
-typedef int v16i __attribute__((ext_vector_type(16)));
 // Two neurons (two pixels of one channel) travel through the epilogue side by side.
 // As SCALAR float32 instructions: on gfx950 the packed forms (v_pk_fma/mul/add_f32) take
 // two passes anyway and, unlike scalar VALU ops, do not overlap with an MFMA in flight
@@ -94,19 +91,6 @@ constexpr int SCHED_WORDS = SCHED_Y * 16;   // words of one slot
 constexpr int SCHED_SLOTS = 64;             // launches in flight per device
 constexpr int SCHED_CAPTURE_SLOTS = 960;    // launches captured into graphs per device (never reused)
 
-// 16 spike bits -> 16 bytes {0, 1} (or {0, 4} when the accumulator indexes a table)
-template <bool X4>
-__device__ __forceinline__ v4i expand16(uint32_t b) {
-  constexpr uint32_t MUL = X4 ? 0x00810204u : 0x00204081u;
-  constexpr uint32_t AND = X4 ? 0x04040404u : 0x01010101u;
-  v4i o;
-  o.x = (int)((((b >> 0) & 0xFu) * MUL) & AND);
-  o.y = (int)((((b >> 4) & 0xFu) * MUL) & AND);
-  o.z = (int)((((b >> 8) & 0xFu) * MUL) & AND);
-  o.w = (int)((((b >> 12) & 0xFu) * MUL) & AND);
-  return o;
-}
-
 // Patch schedule of a persistent workgroup.  With xcd_split the workgroups that
 // share an XCD (blockIdx.x % 8 under the observed round-robin placement -- a speed
 // assumption only) walk the samples b = xcd (mod 8), neighbouring patches at the
@@ -178,15 +162,6 @@ struct PatchWalk {
   }
 };
 
-// Workgroup barrier that orders LDS traffic only.  __syncthreads() also fences
-// global memory, i.e. waits (vmcnt(0)) for the spike stores of the previous step
-// and the prefetched halo loads -- a full memory round trip per timestep.
-__device__ __forceinline__ void lds_barrier() {
-  __builtin_amdgcn_fence(__ATOMIC_RELEASE, "workgroup", "local");
-  __builtin_amdgcn_s_barrier();
-  __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "workgroup", "local");
-}
-
 // old with lane `lane` replaced by the wave-uniform `val` (v_writelane_b32).
 // This hipcc has no __builtin_amdgcn_writelane; binding the LLVM intrinsic by its
 // name keeps the instruction visible to the compiler, which then inserts the wait
@@ -236,13 +211,7 @@ __host__ inline int neuron_form(const NeuronP &n) {
   return n.vr == 0.0f ? NF_MUL0 : NF_MUL;
 }
 
-// LDS accesses by absolute 32-bit LDS address (address space 3): the table reads
-// take the MFMA result itself as the address, with no per-read base add.
-typedef __attribute__((address_space(3))) const float lds_cfloat_t;
-typedef __attribute__((address_space(3))) const uint8_t lds_cu8_t;
-__device__ __forceinline__ uint32_t lds_addr(const void *p) {
-  return (uint32_t)(uintptr_t)(lds_cu8_t *)p;
-}
+// (LDS by absolute address, tile_util.h: a table read takes the MFMA result itself as the address)
 __device__ __forceinline__ float lds_read_f32(uint32_t addr) {
   return *(lds_cfloat_t *)(uintptr_t)addr;
 }
@@ -251,12 +220,12 @@ __device__ __forceinline__ float lds_read_f32(uint32_t addr) {
 // value i - bound, built once per workgroup (same exact division, common.h).
 __device__ __forceinline__ void build_lut(float *lut, int bound, const Dequant &dq,
                                           int tid, int nthreads = 256) {
-  for (int i = tid; i <= 2 * bound; i += nthreads) lut[i] = dequant_acc_nb(i - bound, dq);
+  for (int i = tid; i <= 2 * bound; i += nthreads) lut[i] = dequant_acc(i - bound, dq);
 }
 
 // Per-channel tables of the workgroup's 128 output channels: one block per wave,
 // [acc + bound][32 channels] (rows of 128 B), entry = BatchNorm_c(dequant(acc)), the
-// same op sequence the epilogue would run (bn_apply on dequant_acc_nb), so folding
+// same op sequence the epilogue would run (bn_apply on dequant_acc), so folding
 // changes no bit.  With this order lane (channel c) reads LDS bank c whatever its
 // accumulator is: the table reads of a wave never conflict (the channel-major order
 // [channel][acc] lost half of its LDS cycles to conflicts of the lanes with acc != 0).
@@ -290,7 +259,7 @@ __device__ __forceinline__ uint32_t build_lut_channel(float *lut, const uint32_t
   float bm = 0.f, bmul = 1.f, bb = 0.f;
   if (bn.mean) { bm = bn.mean[co]; bmul = bn.mul[co]; bb = bn.bias[co]; }
   for (int i = hf; i < rows; i += 2) {
-    const float y = bn_apply(dequant_acc_nb(i - negx, dq), bm, bmul, bb);
+    const float y = bn_apply(dequant_acc(i - negx, dq), bm, bmul, bb);
     lut[(st + i) * 32 + col] = y;
     const uint32_t mag = __float_as_uint(y) & 0x7FFFFFFFu;
     if (mag != 0u && mag < minbits) minbits = mag;

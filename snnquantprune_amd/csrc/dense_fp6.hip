@@ -25,22 +25,16 @@
 // MFMAs with its share of the loads and of the expansion, slot by slot.
 #include <cstdlib>
 
-#include "kernels.h"
+#include "dense_tile.h"
 
 namespace snnqp {
-
-typedef int v2i __attribute__((ext_vector_type(2)));
-typedef int v4i __attribute__((ext_vector_type(4)));
-typedef int v8i __attribute__((ext_vector_type(8)));
-typedef float v16f __attribute__((ext_vector_type(16)));
-typedef __attribute__((address_space(3))) const uint32_t lds_cu32_t;
 
 namespace {
 
 constexpr int F6_BK = 256;            // k per chunk
 constexpr int F6_KSC = F6_BK / 64;    // MFMA k-steps per chunk
 constexpr int F6_ROWB = F6_BK / 2;    // LDS bytes of a row per chunk (fp4)
-constexpr int F6_TAB = 256 * 32 * 4;  // byte -> 8 nibbles, 32 interleaved copies (conv3x3_bits.hip)
+constexpr int F6_TAB = FP4_TAB_BYTES;  // byte -> 8 fp4 nibbles (tile_util.h)
 constexpr int F6_KGROUPS = 2;
 constexpr int F6_TILE = 1536;         // bytes of one B tile: 64 lanes x (16 + 8)
 
@@ -62,28 +56,11 @@ struct DenseFp6Args {
   uint32_t *status;              // the device's status word (runtime.hip), or null
 };
 
-__device__ __forceinline__ void lds_barrier6() {
-  __builtin_amdgcn_fence(__ATOMIC_RELEASE, "workgroup", "local");
-  __builtin_amdgcn_s_barrier();
-  __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "workgroup", "local");
-}
-
 // 16-byte piece c (of 8) of row `row`: pieces swizzled by (row >> 1) & 7, so that the 16 lanes
 // a ds_read_b128 serves per cycle ({0-3, 12-15, 20-27}, ...) hit 16 different bank quads
 // (quad = 8 (row & 1) + (c ^ (row >> 1) & 7))
 __device__ __forceinline__ int a6_addr(int row, int c) {
   return row * F6_ROWB + ((c ^ ((row >> 1) & 7)) << 4);
-}
-
-// 4 int8 codes (|c| <= 7) -> 4 e2m3 codes, one per byte (conv3x3_bits.hip)
-__device__ __forceinline__ uint32_t fp6_codes4(uint32_t x) {
-  const uint32_t m1 = (x >> 7) & 0x01010101u;
-  const uint32_t mag = (x ^ (m1 * 0xFFu)) + m1;
-  const uint32_t code = __builtin_amdgcn_perm(0x1E1C1A18u, 0x14100800u, mag);
-  return code | (m1 << 5);
-}
-__device__ __forceinline__ uint32_t squeeze6(uint32_t c) {
-  return (c & 0x3Fu) | ((c >> 2) & 0xFC0u) | ((c >> 4) & 0x3F000u) | ((c >> 6) & 0xFC0000u);
 }
 
 }  // namespace
@@ -174,17 +151,9 @@ dense_fp6_kernel(DenseFp6Args a) {
     return lc < ngc ? gc0 + pc : nchunks;
   };
 
-  // table: byte -> 8 nibbles (bit i set -> 1.0 = 0x2 in nibble i), 32 copies: entry e of copy c
-  // at dword 32 e + c, so lane l of a 32-lane group reads bank l whatever its byte is
-  for (int i = threadIdx.x; i < 256 * 32; i += 256 * F6_KGROUPS) {
-    const int e = i >> 5;
-    uint32_t v = 0;
-#pragma unroll
-    for (int bit = 0; bit < 8; ++bit) v |= ((e >> bit) & 1) ? (0x2u << (4 * bit)) : 0u;
-    ((uint32_t *)lds)[i] = v;
-  }
-  typedef __attribute__((address_space(3))) const uint8_t lds_cu8_t;
-  const uint32_t tabl = (uint32_t)(uintptr_t)(lds_cu8_t *)lds + (uint32_t)(lane & 31) * 4;
+  // the byte -> 8 nibbles table, at the start of LDS
+  fp4_table_fill((uint32_t *)lds, threadIdx.x, 256 * F6_KGROUPS);
+  const uint32_t tabl = fp4_table_lane(lds_addr(lds), lane);
 
   v16f acc[RT];
 #pragma unroll
@@ -296,7 +265,7 @@ dense_fp6_kernel(DenseFp6Args a) {
     asm volatile("s_waitcnt lgkmcnt(%0)\n\ts_barrier" : : "n"(PF) : "memory");
   };
 
-  lds_barrier6();                                  // the table is visible
+  lds_barrier();                                  // the table is visible
   // prologue: words of chunks 0..3, B fragments of chunks 0..1 requested; chunks 0 and 1 expanded
 #pragma unroll
   for (int d = 0; d < D; ++d) {
@@ -319,7 +288,7 @@ dense_fp6_kernel(DenseFp6Args a) {
   // (ring slots 0 and 1 are free again: chunk 3 goes to slot 0 now, chunk 4 to slot 1 in step 0)
 #pragma unroll
   for (int k = 0; k < TPT; ++k) stgr[0][k] = stage_load1(phys(3), k);
-  lds_barrier6();
+  lds_barrier();
 #pragma unroll
   for (int s = 0; s < PF; ++s) av[s] = frag(0, s);
   for (int c = 0; c < ngc; c += D) {
@@ -332,25 +301,11 @@ dense_fp6_kernel(DenseFp6Args a) {
                   stgr[(i + 2) % D], phys(c + i + 2));
     }
   }
-  lds_barrier6();                                  // every wave is done with the A buffers
+  lds_barrier();                                  // every wave is done with the A buffers
 
-  // partial tiles -> LDS [row][128] as float (exact integers; group 1 stores, group 0 adds);
-  // C/D layout: col = lane & 31, row = (i & 3) + 8 * (i >> 2) + 4 * (lane >> 5)
+  // partial tiles -> LDS [row][128] as float (exact integers; dense_tile.h)
   float *et = (float *)work;
-#pragma unroll
-  for (int g = F6_KGROUPS - 1; g >= 0; --g) {
-    if (wave_on && grp == g) {
-#pragma unroll
-      for (int r = 0; r < RT; ++r)
-#pragma unroll
-        for (int i = 0; i < 16; ++i) {
-          const int row = r * 32 + (i & 3) + 8 * (i >> 2) + 4 * h;
-          float *e = et + row * 128 + wave * 32 + n;
-          *e = (g == F6_KGROUPS - 1) ? acc[r][i] : *e + acc[r][i];
-        }
-    }
-    lds_barrier6();
-  }
+  dense_tile_merge<RT, F6_KGROUPS>(et, acc, grp, wave, n, h, wave_on);
 
   // K split over workgroups: every workgroup of a tile leaves its partial tile (exact integers
   // in float32) in its slab and draws a ticket; the one that draws the last adds the others'
@@ -389,34 +344,8 @@ dense_fp6_kernel(DenseFp6Args a) {
     __syncthreads();
   }
 
-  const int CW = (a.N + 31) >> 5;
-  for (int p = threadIdx.x; p < a.SB * 128; p += 256 * F6_KGROUPS) {
-    const int bl = p >> 7, col = p & 127;
-    const int feat = blockIdx.y * 128 + col;
-    const bool live = bl < nsamp && feat < a.N;
-    float bmean = 0.f, bmul = 1.f, bbias = 0.f, dec = 0.f, u = 0.0f;
-    if (live) {
-      if (a.bn.mean) { bmean = a.bn.mean[feat]; bmul = a.bn.mul[feat]; bbias = a.bn.bias[feat]; }
-      if (a.nrn.kind == SNNQP_NEURON_LIF) dec = a.nrn.decay[feat];
-      if (a.u0) u = a.u0[(int64_t)(b0 + bl) * a.N + feat];
-    }
-    for (int t = 0; t < a.T; ++t) {
-      bool s = false;
-      if (live) {
-        float cur = div_exact(et[(bl * a.T + t) * 128 + col], a.dq) * a.dq.m;
-        if (a.bn.mean) cur = bn_apply(cur, bmean, bmul, bbias);
-        s = neuron_step(u, cur, a.nrn, dec);
-      }
-      const unsigned long long m = __ballot(s);
-      const int word = (blockIdx.y * 128 + (col & 64)) >> 5;     // wave-uniform
-      if (bl < nsamp) {
-        uint32_t *o = a.s_out + ((int64_t)t * a.B + (b0 + bl)) * CW;
-        if (lane == 0 && word < CW) o[word] = (uint32_t)m;
-        if (lane == 32 && word + 1 < CW) o[word + 1] = (uint32_t)(m >> 32);
-      }
-    }
-    if (live && a.u_out) a.u_out[(int64_t)(b0 + bl) * a.N + feat] = u;
-  }
+  dense_tile_neurons<false>(et, nullptr, a.dq, a.bn, a.nrn, a.T, a.B, a.N, a.SB, b0, nsamp, a.u0, a.u_out,
+                            a.s_out, 256 * F6_KGROUPS);
 }
 
 template <int RT>

@@ -25,9 +25,6 @@ namespace snnqp {
 
 namespace {
 
-typedef int v8i __attribute__((ext_vector_type(8)));
-typedef int v4i __attribute__((ext_vector_type(4)));
-typedef float v16f __attribute__((ext_vector_type(16)));
 typedef uint32_t u2 __attribute__((ext_vector_type(2)));
 
 constexpr int DG_CMAX = 128;          // input channels

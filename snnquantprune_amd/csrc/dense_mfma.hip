@@ -27,12 +27,9 @@
 //    neuron with u in a register and ballots the spikes into 32-bit words.
 #include <type_traits>
 
-#include "kernels.h"
+#include "dense_tile.h"
 
 namespace snnqp {
-
-typedef int v4i __attribute__((ext_vector_type(4)));
-typedef int v16i __attribute__((ext_vector_type(16)));
 
 constexpr int BK = 256;          // k per chunk (bytes per LDS row)
 constexpr int KSC = BK / 32;     // MFMA k-steps per chunk
@@ -51,23 +48,8 @@ struct DenseMfmaArgs {
   uint32_t *s_out;
 };
 
-__device__ __forceinline__ v4i expand16b(uint32_t b) {
-  v4i o;
-  o.x = (int)((((b >> 0) & 0xFu) * 0x00204081u) & 0x01010101u);
-  o.y = (int)((((b >> 4) & 0xFu) * 0x00204081u) & 0x01010101u);
-  o.z = (int)((((b >> 8) & 0xFu) * 0x00204081u) & 0x01010101u);
-  o.w = (int)((((b >> 12) & 0xFu) * 0x00204081u) & 0x01010101u);
-  return o;
-}
-
-// Workgroup barrier ordering LDS traffic only (see conv_tile.h): the K loop
-// keeps the next chunk's global loads in flight across it.
-__device__ __forceinline__ void lds_barrier() {
-  __builtin_amdgcn_fence(__ATOMIC_RELEASE, "workgroup", "local");
-  __builtin_amdgcn_s_barrier();
-  __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "workgroup", "local");
-}
-
+// (the barriers order LDS traffic only, lds_barrier: the K loop keeps the next chunk's global
+// loads in flight across them)
 __device__ __forceinline__ int a_addr(int row, int c16) {
   return row * BK + ((c16 ^ (row & 15)) << 4);
 }
@@ -170,8 +152,8 @@ dense_mfma_kernel(DenseMfmaArgs a) {
                   (v.z ^ (int)0x80808080) & m, (v.w ^ (int)0x80808080) & m};
         } else {
           const uint32_t wv = stg[k] & rmask[k] & (uint32_t)((chunk_word(chunk, k) - a.KS) >> 31);
-          *(v4i *)(base + a_addr(row, wi * 2)) = expand16b(wv & 0xFFFFu);
-          *(v4i *)(base + a_addr(row, wi * 2 + 1)) = expand16b(wv >> 16);
+          *(v4i *)(base + a_addr(row, wi * 2)) = expand16(wv & 0xFFFFu);
+          *(v4i *)(base + a_addr(row, wi * 2 + 1)) = expand16(wv >> 16);
         }
       }
     }
@@ -270,7 +252,7 @@ dense_mfma_kernel(DenseMfmaArgs a) {
           } else {
             const int hf = (p / 4) & 1;
             asm volatile("" : "+v"(wv[k]));
-            ex[d] = (int)((((wv[k] >> (16 * hf + 4 * d)) & 0xFu) * 0x00204081u) & 0x01010101u);
+            ex[d] = (int)expand4(wv[k] >> (16 * hf + 4 * d));
             if (d == 3 && tid + k * 256 < NTASK)
               *(v4i *)(abuf + (rbuf ^ 1) * ABYTES + wr_off[k][hf]) = ex;
           }
@@ -299,57 +281,12 @@ dense_mfma_kernel(DenseMfmaArgs a) {
     }
   }
 
-  // int32 tile -> LDS [row][128]; C/D layout: col = lane & 31,
-  // row = (i & 3) + 8 * (i >> 2) + 4 * (lane >> 5)
-  // (group 1 stores its partial sums, group 0 adds its own on top: exact int32)
+  // int32 tile -> LDS [row][128], then one (sample, feature) pair per thread (dense_tile.h);
+  // uint8 input: 128 * sum_k w[k][feat] is added back (the x - 128 operand)
   int *et = (int *)lds;
-#pragma unroll
-  for (int g = KGROUPS - 1; g >= 0; --g) {
-    if (wave_on && grp == g) {
-#pragma unroll
-      for (int r = 0; r < RT; ++r)
-#pragma unroll
-        for (int i = 0; i < 16; ++i) {
-          const int row = r * 32 + (i & 3) + 8 * (i >> 2) + 4 * h;
-          int *e = et + row * 128 + wave * 32 + n;
-          *e = (g == KGROUPS - 1) ? acc[r][i] : *e + acc[r][i];
-        }
-    }
-    lds_barrier();
-  }
-
-  // one (sample, feature) pair per thread and pass; 64 consecutive features of
-  // one sample per wave, so a ballot is two output words
-  const int CW = (a.N + 31) >> 5;
-  for (int p = threadIdx.x; p < a.SB * 128; p += 256 * KGROUPS) {
-    const int bl = p >> 7, col = p & 127;
-    const int feat = blockIdx.y * 128 + col;
-    const bool live = bl < nsamp && feat < a.N;
-    float bmean = 0.f, bmul = 1.f, bbias = 0.f, dec = 0.f, u = 0.0f;
-    int off = 0;                       // uint8 input: 128 * sum_k w[k][feat] (the x - 128 operand)
-    if (live) {
-      if (U8) off = 128 * a.col_sum[feat];
-      if (a.bn.mean) { bmean = a.bn.mean[feat]; bmul = a.bn.mul[feat]; bbias = a.bn.bias[feat]; }
-      if (a.nrn.kind == SNNQP_NEURON_LIF) dec = a.nrn.decay[feat];
-      if (a.u0) u = a.u0[(int64_t)(b0 + bl) * a.N + feat];
-    }
-    for (int t = 0; t < a.T; ++t) {
-      bool s = false;
-      if (live) {
-        float cur = dequant_acc(et[(bl * a.T + t) * 128 + col] + off, a.dq);
-        if (a.bn.mean) cur = bn_apply(cur, bmean, bmul, bbias);
-        s = neuron_step(u, cur, a.nrn, dec);
-      }
-      const unsigned long long m = __ballot(s);
-      const int word = (blockIdx.y * 128 + (col & 64)) >> 5;     // wave-uniform
-      if (bl < nsamp) {
-        uint32_t *o = a.s_out + ((int64_t)t * a.B + (b0 + bl)) * CW;
-        if (lane == 0 && word < CW) o[word] = (uint32_t)m;
-        if (lane == 32 && word + 1 < CW) o[word + 1] = (uint32_t)(m >> 32);
-      }
-    }
-    if (live && a.u_out) a.u_out[(int64_t)(b0 + bl) * a.N + feat] = u;
-  }
+  dense_tile_merge<RT, KGROUPS>(et, acc, grp, wave, n, h, wave_on);
+  dense_tile_neurons<U8>(et, a.col_sum, a.dq, a.bn, a.nrn, a.T, a.B, a.N, a.SB, b0, nsamp, a.u0, a.u_out,
+                         a.s_out, 256 * KGROUPS);
 }
 
 const char *dense_mfma_unsupported(int in_type, int32_t K, int32_t N,

@@ -50,8 +50,6 @@ extern "C" __device__ uint32_t snnqp_writelane_i32(uint32_t, uint32_t, uint32_t)
 
 namespace {
 
-typedef int v4i __attribute__((ext_vector_type(4)));
-typedef int v16i __attribute__((ext_vector_type(16)));
 typedef __attribute__((address_space(3))) const uint16_t lds_cu16_t;
 
 constexpr int W_BK = 128;         // bytes of a row per chunk (int8: 128 k)
@@ -91,8 +89,6 @@ struct DenseWideArgs {
   int32_t *x_flags;               // float32 rows: OR-ed with SNNQP_FLAG_NOT_INTEGER (zeroed by the launcher)
 };
 
-typedef float v4f __attribute__((ext_vector_type(4)));
-
 // four float32 values -> the four bytes x - 128 of the int8 operand; `bad` collects what is not
 // an integer in [0, 255]: fl(cvt(x)) - x is +0.0 exactly for the integers v_cvt_u32_f32 can hold
 // (-0.0 counts as 0), a NaN for a NaN, non-zero otherwise; the range is checked on the integers
@@ -107,12 +103,6 @@ __device__ __forceinline__ uint32_t f32x4_to_i8x4(const v4f &f, uint32_t &bad) {
   return (u0 | (u1 << 8) | (u2 << 16) | (u3 << 24)) ^ 0x80808080u;
 }
 
-__device__ __forceinline__ void wide_barrier() {
-  __builtin_amdgcn_fence(__ATOMIC_RELEASE, "workgroup", "local");
-  __builtin_amdgcn_s_barrier();
-  __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "workgroup", "local");
-}
-
 // 16-byte piece c (of 8) of row `row` (dense_fp6.hip: the ds_read_b128 of an A fragment and
 // the ds_write_b128 of the staging are conflict-free)
 __device__ __forceinline__ int wa_addr(int row, int c) {
@@ -122,15 +112,6 @@ __device__ __forceinline__ int wa_addr(int row, int c) {
 // row of the MFMA tile set <-> (lane half h, the half's row k)
 __device__ __forceinline__ int rho_of(int k, int h) {
   return (k >> 4) * 32 + ((k >> 2) & 3) * 8 + h * 4 + (k & 3);
-}
-
-__device__ __forceinline__ v4i expand16w(uint32_t b) {
-  v4i o;
-  o.x = (int)((((b >> 0) & 0xFu) * 0x00204081u) & 0x01010101u);
-  o.y = (int)((((b >> 4) & 0xFu) * 0x00204081u) & 0x01010101u);
-  o.z = (int)((((b >> 8) & 0xFu) * 0x00204081u) & 0x01010101u);
-  o.w = (int)((((b >> 12) & 0xFu) * 0x00204081u) & 0x01010101u);
-  return o;
 }
 
 // u += (x - (u - v_reset)) * m ; s = (u - v_th) >= 0 ; hard reset  (spiking_learning.py:410-414,
@@ -428,8 +409,8 @@ dense_wide_kernel(DenseWideArgs a) {
                                        (v.z ^ (int)0x80808080) & m, (v.w ^ (int)0x80808080) & m};
     } else {
       const uint32_t w = v & rmask[q] & (uint32_t)((chunk_word(chunk, q) - a.KW) >> 31);
-      *(v4i *)(base + wr_off[q]) = expand16w(w & 0xFFFFu);
-      *(v4i *)(base + (wr_off[q] ^ 16)) = expand16w(w >> 16);     // piece 2 wi + 1: the swizzle flips bit 4 only
+      *(v4i *)(base + wr_off[q]) = expand16(w & 0xFFFFu);
+      *(v4i *)(base + (wr_off[q] ^ 16)) = expand16(w >> 16);     // piece 2 wi + 1: the swizzle flips bit 4 only
     }
   };
 
@@ -557,7 +538,7 @@ dense_wide_kernel(DenseWideArgs a) {
 #pragma unroll
   for (int q = 0; q < TPT; ++q) stgr[0][q] = stage_load1(phys(3), q);
   }
-  wide_barrier();
+  lds_barrier();
 #pragma unroll
   for (int f = 0; f < W_PF; ++f) av[f] = frag(0, f);
   for (int c = 0; c < nsteps; c += W_NBUF) {
@@ -565,7 +546,7 @@ dense_wide_kernel(DenseWideArgs a) {
     for (int i = 0; i < W_NBUF; ++i)
       if (c + i < nchunks) fused_chunk(i, c + i);   // (the chunks beyond K are the last ones)
   }
-  wide_barrier();                                   // every wave is done with the A images
+  lds_barrier();                                   // every wave is done with the A images
   if constexpr (F32IN) {
     if (__ballot(bad != 0u) != 0ull && lane == 0 && a.x_flags) atomicOr(a.x_flags, SNNQP_FLAG_NOT_INTEGER);
   }
@@ -617,7 +598,7 @@ dense_wide_kernel(DenseWideArgs a) {
       }
     }
   }
-  wide_barrier();
+  lds_barrier();
   if (a.s_out) {
     const int CW = (a.N + 31) >> 5;
     for (int q = tid; q < ROWS * 16; q += W_THREADS) {
@@ -656,7 +637,7 @@ dense_wide_kernel(DenseWideArgs a) {
       for (int q = tid; q < ROWS * 8; q += W_THREADS)
         s1[(q >> 3) * W_S1P + (8 - wofs) + (q & 7)] =
             __hip_atomic_load(other + q, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-      wide_barrier();
+      lds_barrier();
     }
   }
   // ---- second block + vote --------------------------------------------------------------------
@@ -674,12 +655,12 @@ dense_wide_kernel(DenseWideArgs a) {
           for (int r = 0; r < RT; ++r) {
             // the lane's 16 k of row 32 r + n: halfword 2 ks + h of the raster row
             const uint32_t bits = *(lds_cu16_t *)(uintptr_t)(s1h + (uint32_t)(r * 32 * W_S1P * 4 + ks * 4));
-            acc2[r][0] = __builtin_amdgcn_mfma_i32_32x32x32_i8(expand16w(bits), b2[ks], acc2[r][0], 0, 0, 0);
+            acc2[r][0] = __builtin_amdgcn_mfma_i32_32x32x32_i8(expand16(bits), b2[ks], acc2[r][0], 0, 0, 0);
           }
         }
       }
     }
-    wide_barrier();
+    lds_barrier();
     if (wave < NB2) {
       int off[1] = {0}, col2[1] = {wave * 32 + n};
       bool col2_live[1] = {col2[0] < a.N2};
@@ -724,7 +705,7 @@ dense_wide_kernel(DenseWideArgs a) {
         }
       }
     }
-    wide_barrier();
+    lds_barrier();
     // mean over each class's `group` neurons, in order (ops.vote / snnqp_vote)
     const int NC = a.N2 / a.group;
     for (int q = tid; q < nsamp * NC; q += W_THREADS) {

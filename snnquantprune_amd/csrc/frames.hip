@@ -60,7 +60,6 @@ pack_ev1_kernel(const uint8_t *__restrict__ x, int64_t frames, int64_t fbytes, i
 __global__ void __launch_bounds__(256)
 pack_ev1_f32_kernel(const float *__restrict__ x, int64_t frames, int64_t fvals, int64_t fwords,
                     uint32_t *__restrict__ y, int32_t *__restrict__ flags) {
-  typedef float v4f __attribute__((ext_vector_type(4)));
   const int64_t n = frames * fwords;
   uint32_t notbin = 0, notint = 0;
   const bool vec = ((uintptr_t)x & 15) == 0 && (fvals & 31) == 0;
@@ -128,7 +127,7 @@ unpack_ev1_kernel(const uint32_t *__restrict__ x, int64_t frames, int64_t fbytes
       v4u o[2];
 #pragma unroll
       for (int j = 0; j < 8; ++j)
-        o[j >> 2][j & 3] = (((w >> (4 * j)) & 0xFu) * 0x00204081u) & 0x01010101u;
+        o[j >> 2][j & 3] = expand4(w >> (4 * j));
       ((v4u *)dst)[0] = o[0];
       ((v4u *)dst)[1] = o[1];
     } else {

@@ -23,9 +23,6 @@
 
 namespace snnqp {
 
-typedef float v16f __attribute__((ext_vector_type(16)));
-typedef float v4f __attribute__((ext_vector_type(4)));
-
 constexpr int FG_KC = 16;
 // TM: 32 x 32 MFMA tiles per wave and direction.  2: a workgroup owns 128 x 128 outputs (the
 // throughput shape: every operand read from LDS feeds two MFMAs); 1: 64 x 64 -- for problems of a
@@ -126,7 +123,7 @@ fseq_gemm_kernel(FseqGemmArgs a) {
         } else {
           const uint32_t w = ((const uint32_t *)a.x)[pix * ((a.Cin + 31) >> 5) + (kk >> 5)] >> (kk & 31);
 #pragma unroll
-          for (int j = 0; j < TM; ++j) q[j] = (((w >> (4 * j)) & 0xFu) * 0x00204081u) & 0x01010101u;
+          for (int j = 0; j < TM; ++j) q[j] = expand4(w >> (4 * j));
         }
       }
 #pragma unroll

@@ -1,6 +1,7 @@
 // Internal declarations shared by the .hip translation units of libsnnqp.
 #pragma once
 #include "common.h"
+#include "tile_util.h"
 
 namespace snnqp {
 

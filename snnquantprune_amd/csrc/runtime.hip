@@ -27,9 +27,6 @@ namespace snnqp {
 
 namespace {
 
-typedef int v8i __attribute__((ext_vector_type(8)));
-typedef float v16f __attribute__((ext_vector_type(16)));
-
 constexpr int PROBE_CHAIN = 18;      // MFMAs per chain, as conv1 / conv2 issue them
 
 struct DeviceState {

@@ -72,7 +72,6 @@ inspect_u8_kernel(const uint8_t *__restrict__ x, int64_t n, int32_t *__restrict_
 __global__ void __launch_bounds__(256)
 narrow_f32_kernel(const float *__restrict__ x, uint8_t *__restrict__ y, int64_t n,
                   int32_t *__restrict__ flags) {
-  typedef float v4f __attribute__((ext_vector_type(4)));
   const int64_t tid = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
   const int64_t nthreads = (int64_t)gridDim.x * blockDim.x;
   const bool vec = (((uintptr_t)x & 15) == 0) && (((uintptr_t)y & 3) == 0);
