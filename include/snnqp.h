@@ -219,10 +219,12 @@ typedef struct {
  * snnqp_conv3d_*; 501: snnqp_weight_t.ch_stack_max / ch_slots, the *_gated_*_ex pack calls; 502:
  * snnqp_pack_frames_checked, snnqp_conv_lif_forward_pred, SNNQP_BN_MUL_UNIFORM; 503:
  * snnqp_scatter_spike_channels; 505: training of the dense blocks -- SNNQP_SURR_*,
- * snnqp_lif_forward_save, snnqp_lif_backward, snnqp_dense_weight_grad, snnqp_dense_input_grad).
+ * snnqp_lif_forward_save, snnqp_lif_backward, snnqp_dense_weight_grad, snnqp_dense_input_grad;
+ * 506: training of the conv blocks -- snnqp_conv_weight_grad, snnqp_conv_input_grad,
+ * snnqp_conv_grad_splits, snnqp_conv_weight_grad_workspace_bytes, snnqp_maxpool2x2_backward).
  * A binding compares snnqp_version()
  * with the SNNQP_VERSION it was written against and refuses a library of another version (_lib.py does). */
-#define SNNQP_VERSION 505
+#define SNNQP_VERSION 506
 int snnqp_version(void);
 const char *snnqp_last_error(void);
 /* Extra compiler flags the library was built with: "" for the product build
@@ -747,6 +749,43 @@ int snnqp_dense_weight_grad(const float *x, const float *gI, int64_t M, int32_t 
  * optional (the dropout mask of the block's input). */
 int snnqp_dense_input_grad(const float *gI, const float *w, const float *mask, int64_t M,
                            int32_t K, int32_t N, float *gx, snnqp_stream_t stream);
+
+/* ---- training of the conv blocks (csrc/train_conv.hip) ---------------------------------------
+ * The two gradient products of a 2-D convolution (flax_qconv.py:158-168 differentiated) and the
+ * pool's gradient routing.  All tensors float32: x [NB][H][W][Cin], gI [NB][OH][OW][Cout], w and
+ * gw HWIO [KH][KW][Cin][Cout].  Geometry served: groups == 1, every dilation 1, non-negative
+ * explicit padding, any kernel size and stride; anything else is SNNQP_EUNSUPPORTED, decided on
+ * the host before any launch.  Each product is the r-ascending fmaf chain from +0 (the contract
+ * of snnqp_dense_weight_grad) over the explicitly gathered matrices, a tap outside the image
+ * reading as the literal 0.0.  Index arithmetic is 64-bit; grids beyond the launch limits are
+ * SNNQP_EINVAL.
+ *
+ * gw[(kh KW + kw) Cin + ci][co] = sum_r x[n, oh sh + kh - pt, ow sw + kw - pl, ci] gI[r][co],
+ * r = (n OH + oh) OW + ow ascending over Rn = NB OH OW rows.  r is cut into `splits` (1..64)
+ * contiguous ranges of L = 16 ceil(ceil(Rn / 16) / splits) rows (trailing ranges may be empty),
+ * each its own chain from +0 into workspace[s] ([KH KW Cin][Cout] each); a second kernel forms
+ * ((p0 + p1) + p2) + ... in float32 in s order.  No atomics: bitwise reproducible for a given
+ * `splits`.  With splits == 1 gw is written directly and `workspace` is not read (may be null).
+ * NB == 0 writes zeros to gw and touches nothing else. */
+int snnqp_conv_weight_grad(const float *x, const float *gI, int64_t NB,
+                           const snnqp_conv_geom_t *g, int32_t splits, float *workspace,
+                           float *gw, snnqp_stream_t stream);
+/* Host only.  Bytes of `workspace` for `splits` ranges (0 for one), or a negative SNNQP_E*. */
+int64_t snnqp_conv_weight_grad_workspace_bytes(const snnqp_conv_geom_t *g, int32_t splits);
+/* Host only.  The default `splits` for NB images: a function of the shapes alone (the device is
+ * not asked, so a gradient does not depend on the machine), in 1..64: tiles x splits near 1024
+ * workgroups, no range shorter than 256 rows.  A negative SNNQP_E* on a geometry not served. */
+int snnqp_conv_grad_splits(const snnqp_conv_geom_t *g, int64_t NB);
+/* gx[n, ih, iw, ci] = sum_r gI[n, oh, ow, co] w[kh, kw, ci, co], r = (kh KW + kw) Cout + co
+ * ascending, oh = (ih + pt - kh) / sh and likewise ow; the tap reads 0.0 where that is not an
+ * integer in range. */
+int snnqp_conv_input_grad(const float *gI, const float *w, int64_t NB,
+                          const snnqp_conv_geom_t *g, float *gx, snnqp_stream_t stream);
+/* The gradient of snnqp_maxpool2x2 on float32 s [NB][H][W][C]: each gp [NB][H/2][W/2][C] element
+ * goes to the first position, in row-major window order, that holds the window's maximum; every
+ * other position, and a trailing odd row or column, gets 0.  gs [NB][H][W][C]. */
+int snnqp_maxpool2x2_backward(const float *s, const float *gp, int64_t NB, int32_t H, int32_t W,
+                              int32_t C, float *gs, snnqp_stream_t stream);
 
 #ifdef __cplusplus
 }

@@ -16,7 +16,7 @@ _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.path.join(_HERE, "csrc", "libsnnqp.so")
 
 # include/snnqp.h SNNQP_VERSION the prototypes below were written against
-ABI_VERSION = 505
+ABI_VERSION = 506
 
 # enums of include/snnqp.h
 F32, U8, BITS, EV1, EV4 = 0, 1, 2, 3, 4
@@ -180,6 +180,14 @@ _PROTOTYPES = {
                                         c_void_p]),
     "snnqp_dense_input_grad": (c_int, [c_void_p, c_void_p, c_void_p, c_int64, c_int32, c_int32,
                                        c_void_p, c_void_p]),
+    "snnqp_conv_weight_grad": (c_int, [c_void_p, c_void_p, c_int64, POINTER(ConvGeomT), c_int32,
+                                       c_void_p, c_void_p, c_void_p]),
+    "snnqp_conv_weight_grad_workspace_bytes": (c_int64, [POINTER(ConvGeomT), c_int32]),
+    "snnqp_conv_grad_splits": (c_int, [POINTER(ConvGeomT), c_int64]),
+    "snnqp_conv_input_grad": (c_int, [c_void_p, c_void_p, c_int64, POINTER(ConvGeomT), c_void_p,
+                                      c_void_p]),
+    "snnqp_maxpool2x2_backward": (c_int, [c_void_p, c_void_p, c_int64, c_int32, c_int32, c_int32,
+                                          c_void_p, c_void_p]),
 }
 
 EXPORTED_SYMBOLS = tuple(_PROTOTYPES)

@@ -1,0 +1,153 @@
+"""Training forward and surrogate-gradient backward of the conv blocks of ConvDenseSNN (config C3).
+
+jax.grad of examples/tcja/models.py:101-147 in train mode, offline, stated as one
+torch.autograd.Function per block:
+
+  x -> QuantConv 3x3 -> BatchNorm (batch statistics) -> multi_step_LIF -> 2x2 max pool
+
+Forward: the currents come from the eval connection kernels (ops.conv_forward; from block 1 on
+the input is the bit-packed raster of the block before, so the integer path stays exact), the
+batch-statistics BatchNorm runs as torch tensor ops, one scan writes the spikes and the pre-reset
+potential h (ops.lif_forward_save), and ops.maxpool2x2 pools.  Backward (csrc/train_conv.hip,
+csrc/train_dense.hip): the pool's routing, the BPTT scan, BatchNorm's backward in torch ops, then
+the two conv gradient products.
+
+BatchNorm in train mode, per scan step t and per channel over (B, H, W) -- the reference's
+SpikingBlock scans over time, so each step normalises with its own statistics:
+  mean = mean(x),  var = mean(x^2) - mean^2  (the flax 0.4.0 form, biased)
+  y = (x - mean) * (rsqrt(var + eps) * scale) + bias
+The two means are accumulated in float64 and rounded to float32 once; given those float32
+statistics, y is the arithmetic of the eval BatchNorm (each op rounded in float32).  The running
+statistics move once per step, in t order: ra = momentum * ra + (1 - momentum) * new.
+"""
+
+from __future__ import annotations
+
+import torch
+
+from . import ops
+from . import packing
+
+
+def batch_stats(x: torch.Tensor):
+  """x [T, N, C] float32 -> (mean, var) float32 [T, C]: float64 accumulation, one rounding."""
+  x64 = x.to(torch.float64)
+  mean = x64.mean(1)
+  var = (x64 * x64).mean(1) - mean * mean
+  return mean.to(torch.float32), var.to(torch.float32)
+
+
+def bn_multiplier(var: torch.Tensor, scale: torch.Tensor, eps: float) -> torch.Tensor:
+  """fl(fl(1 / sqrt(fl(var + eps))) * scale), the fold of the eval BatchNorm."""
+  return (1.0 / torch.sqrt(var + torch.tensor(eps, dtype=torch.float32, device=var.device))) * scale
+
+
+def bn_normalise(x, mean, mul, bias):
+  """x [T, N, C], per-step coefficients [T, C] -> fl(fl(fl(x - mean) * mul) + bias)."""
+  y = x - mean[:, None, :]
+  y *= mul[:, None, :]
+  y += bias if bias.ndim == 1 else bias[:, None, :]
+  return y
+
+
+def bn_backward(g, x, mean, var, scale, eps):
+  """The VJP of y = (x - mean) * (r * scale) + bias with r = (var + eps)^-1/2 and the batch
+  statistics functions of x.  g, x [T, N, C]; -> (gx [T, N, C], gscale [C], gbias [C]).
+  The channel-sized reductions and coefficients are float64, the image-sized result float32."""
+  N = x.shape[1]
+  g64 = g.to(torch.float64)
+  mean64, var64, scale64 = mean.to(torch.float64), var.to(torch.float64), scale.to(torch.float64)
+  r = torch.rsqrt(var64 + eps)                                   # [T, C]
+  sg = g64.sum(1)                                                # sum g
+  sgx = (g64 * x).sum(1) - mean64 * sg                           # sum g (x - mean)
+  gbias = sg.sum(0)
+  gscale = (sgx * r).sum(0)
+  gvar = sgx * scale64 * (-0.5) * r * r * r
+  gmean = -(r * scale64) * sg - 2.0 * mean64 * gvar
+  # gx = g m + (gmean + 2 gvar x) / N
+  m = (r * scale64).to(torch.float32)
+  c0 = (gmean / N).to(torch.float32)
+  c1 = (2.0 * gvar / N).to(torch.float32)
+  gx = g * m[:, None, :]
+  gx += c0[:, None, :]
+  gx.addcmul_(x, c1[:, None, :])
+  return gx, gscale.to(scale.dtype), gbias.to(scale.dtype)
+
+
+def running_update(old: torch.Tensor, new_t: torch.Tensor, momentum: float) -> torch.Tensor:
+  """T steps of ra = momentum * ra + (1 - momentum) * new_t, float32, in t order."""
+  m = torch.tensor(momentum, dtype=torch.float32, device=old.device)
+  k = 1.0 - m
+  ra = old.to(torch.float32)
+  for t in range(new_t.shape[0]):
+    ra = m * ra + k * new_t[t]
+  return ra
+
+
+def conv_currents(x, pk: packing.PackedKernel, geom: ops.ConvGeom) -> torch.Tensor:
+  """x [NB, H, W, Cin] (uint8, float32 or PackedSpikes) -> float32 [NB, OH, OW, Cout] on the eval
+  connection kernels: integer codes for integer-valued inputs, the float32 kernel otherwise."""
+  w = pk.int_weight()
+  if w is not None and isinstance(x, torch.Tensor) and x.dtype == torch.float32:
+    if bool(((x == torch.round(x)) & (x >= 0) & (x <= 255)).all()):
+      x = x.to(torch.uint8)
+    else:
+      w = None
+  if w is None:
+    w = pk.float_weight()
+    if isinstance(x, ops.PackedSpikes):
+      x = x.to_dense().to(torch.float32)
+    elif x.dtype != torch.float32:
+      x = x.to(torch.float32)
+  return ops.conv_forward(x, geom, w)
+
+
+class ConvBlock(torch.autograd.Function):
+  """x [T, B, H, W, Cin] -> pooled spikes float32 [T, B, OH/2, OW/2, C], and without gradient the
+  unpooled h, s [T, B, OH, OW, C] and the per-step statistics mean, var [T, C].  Gradients to x
+  (not for the first block: the frames need none), the transformed kernel wq (HWIO) and
+  BatchNorm's scale and bias."""
+
+  @staticmethod
+  def forward(ctx, x, wq, scale, bias, pk, geom, nrn, surrogate, eps, first):
+    T, B = x.shape[0], x.shape[1]
+    C = geom.Cout
+    if first or pk.int_weight() is None:
+      xin = x.reshape(T * B, geom.H, geom.W, geom.Cin)
+    else:
+      xin = ops.pack_bits(x.reshape(T * B, geom.H, geom.W, geom.Cin).contiguous())
+    cur = conv_currents(xin, pk, geom)
+    OH, OW = cur.shape[1], cur.shape[2]
+    cur = cur.reshape(T, B * OH * OW, C)
+    mean, var = batch_stats(cur)
+    y = bn_normalise(cur.clone(), mean, bn_multiplier(var, scale, eps), bias)
+    h, s = ops.lif_forward_save(y, nrn)
+    del y
+    h = h.reshape(T, B, OH, OW, C)
+    s = s.reshape(T, B, OH, OW, C)
+    pooled = ops.maxpool2x2(s)
+    ctx.save_for_backward(x, wq, scale, cur, mean, var, h)
+    ctx.geom, ctx.nrn, ctx.surrogate, ctx.eps, ctx.first = geom, nrn, surrogate, eps, first
+    ctx.mark_non_differentiable(h, s, mean, var)
+    return pooled, h, s, mean, var
+
+  @staticmethod
+  def backward(ctx, gp, _gh, _gs, _gmean, _gvar):
+    x, wq, scale, cur, mean, var, h = ctx.saved_tensors
+    geom, nrn = ctx.geom, ctx.nrn
+    T, B, OH, OW, C = h.shape
+    s = ((h - nrn.v_threshold) >= 0).to(torch.float32)          # the forward's spikes
+    gs = ops.maxpool2x2_backward(s, gp.contiguous())
+    del s
+    gy = ops.lif_backward(h.reshape(T, B * OH * OW, C), nrn, ctx.surrogate,
+                          gs=gs.reshape(T, B * OH * OW, C))
+    del gs
+    gcur, gscale, gbias = bn_backward(gy, cur, mean, var, scale, ctx.eps)
+    del gy
+    gcur = gcur.reshape(T * B, OH, OW, C)
+    x4 = x.reshape(T * B, geom.H, geom.W, geom.Cin).to(torch.float32)
+    gw = ops.conv_weight_grad(x4, gcur, geom)
+    gx = None
+    if not ctx.first and ctx.needs_input_grad[0]:
+      gx = ops.conv_input_grad(gcur, wq.detach(), geom).reshape(x.shape)
+    return gx, gw, gscale, gbias, None, None, None, None, None, None

@@ -12,6 +12,7 @@
 // output element is reduced by one wave in one fixed order (no atomics), so gradients are
 // bitwise reproducible run to run.
 #include "common.h"
+#include "grad_gemm.h"
 
 namespace snnqp {
 namespace {
@@ -98,116 +99,28 @@ int launch_backward(const float *h, const float *gs, const float *glogits, int32
 
 // ---- C[i][j] = sum_r A(r, i) B(r, j) (* mask[i][j]) -----------------------------------------
 // A(r, i) = a[r * a_sr + i * a_si], B(r, j) = b[r * b_sr + j * b_sj]; C row-major [I][J].
-// 256 threads, a 64 x 64 tile of C per workgroup, 32 x 32 per wave (2 x 2 16x16x4 MFMAs);
-// r walks in chunks of 16 through LDS, the next chunk held in registers while this one computes.
-constexpr int GT = 64;     // tile edge
-constexpr int GR = 16;     // r per chunk
-constexpr int GLD = GT + 4;
-
-using f32x4 = __attribute__((ext_vector_type(4))) float;
-
-// Element q (0..3) of this thread's share of one GR x GT operand chunk: (rr, ii) in the chunk.
-// When the r axis is the contiguous one, neighbouring threads walk r; else they walk i.
-__device__ __forceinline__ void chunk_coord(int tid, int q, bool r_contig, int &rr, int &ii) {
-  const int idx = tid + 256 * q;
-  if (r_contig) {
-    rr = idx % GR;
-    ii = idx / GR;
-  } else {
-    rr = idx / GT;
-    ii = idx % GT;
-  }
-}
-
-__device__ __forceinline__ void load_chunk(const float *__restrict__ a, int64_t sr, int64_t si,
-                                           int64_t r0, int64_t Rn, int64_t i0, int64_t I,
-                                           bool r_contig, int tid, float (&reg)[4]) {
-#pragma unroll
-  for (int q = 0; q < 4; ++q) {
-    int rr, ii;
-    chunk_coord(tid, q, r_contig, rr, ii);
-    const int64_t r = r0 + rr, i = i0 + ii;
-    reg[q] = (r < Rn && i < I) ? a[r * sr + i * si] : 0.0f;
-  }
-}
-
-__device__ __forceinline__ void store_chunk(float (*lds)[GLD], bool r_contig, int tid,
-                                            const float (&reg)[4]) {
-#pragma unroll
-  for (int q = 0; q < 4; ++q) {
-    int rr, ii;
-    chunk_coord(tid, q, r_contig, rr, ii);
-    lds[rr][ii] = reg[q];
-  }
-}
-
-__global__ __launch_bounds__(256) void grad_gemm_kernel(
-    const float *__restrict__ a, int64_t a_sr, int64_t a_si,
-    const float *__restrict__ b, int64_t b_sr, int64_t b_sj,
-    int64_t I, int64_t J, int64_t Rn, const float *__restrict__ mask, float *__restrict__ c) {
-  __shared__ float As[GR][GLD];
-  __shared__ float Bs[GR][GLD];
-  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-  const int64_t i0 = (int64_t)blockIdx.y * GT, j0 = (int64_t)blockIdx.x * GT;
-  const int wi = (wave & 1) * 32, wj = (wave >> 1) * 32;
-  const bool a_rc = a_sr == 1 && a_si != 1, b_rc = b_sr == 1 && b_sj != 1;
-  f32x4 acc[2][2];
-#pragma unroll
-  for (int x = 0; x < 2; ++x)
-#pragma unroll
-    for (int y = 0; y < 2; ++y) acc[x][y] = f32x4{0.0f, 0.0f, 0.0f, 0.0f};
-  float ra[4], rb[4];
-  load_chunk(a, a_sr, a_si, 0, Rn, i0, I, a_rc, tid, ra);
-  load_chunk(b, b_sr, b_sj, 0, Rn, j0, J, b_rc, tid, rb);
-  const int kl = lane >> 4, il = lane & 15;
-  for (int64_t r0 = 0; r0 < Rn; r0 += GR) {
-    __syncthreads();                       // the previous chunk's reads are done
-    store_chunk(As, a_rc, tid, ra);
-    store_chunk(Bs, b_rc, tid, rb);
-    __syncthreads();
-    if (r0 + GR < Rn) {
-      load_chunk(a, a_sr, a_si, r0 + GR, Rn, i0, I, a_rc, tid, ra);
-      load_chunk(b, b_sr, b_sj, r0 + GR, Rn, j0, J, b_rc, tid, rb);
-    }
-#pragma unroll
-    for (int kk = 0; kk < GR; kk += 4) {
-      // 16x16x4: lane l holds A[i = l & 15][k = l >> 4] and B[k = l >> 4][j = l & 15]
-      float av[2], bv[2];
-#pragma unroll
-      for (int x = 0; x < 2; ++x) av[x] = As[kk + kl][wi + 16 * x + il];
-#pragma unroll
-      for (int y = 0; y < 2; ++y) bv[y] = Bs[kk + kl][wj + 16 * y + il];
-#pragma unroll
-      for (int x = 0; x < 2; ++x)
-#pragma unroll
-        for (int y = 0; y < 2; ++y)
-          acc[x][y] = __builtin_amdgcn_mfma_f32_16x16x4f32(av[x], bv[y], acc[x][y], 0, 0, 0);
-    }
-  }
-  // C/D: col = lane & 15, row = (lane >> 4) * 4 + reg
-#pragma unroll
-  for (int x = 0; x < 2; ++x)
-#pragma unroll
-    for (int y = 0; y < 2; ++y)
-#pragma unroll
-      for (int g = 0; g < 4; ++g) {
-        const int64_t i = i0 + wi + 16 * x + kl * 4 + g;
-        const int64_t j = j0 + wj + 16 * y + il;
-        if (i < I && j < J) {
-          float v = acc[x][y][g];
-          if (mask) v = v * mask[i * J + j];
-          c[i * J + j] = v;
-        }
-      }
+// The tile is grad_gemm.h's.
+__global__ __launch_bounds__(256) void grad_gemm_kernel(gg::Strided a, gg::Strided b, int64_t Rn,
+                                                        const float *__restrict__ mask,
+                                                        float *__restrict__ c) {
+  const int64_t i0 = (int64_t)blockIdx.y * gg::GT, j0 = (int64_t)blockIdx.x * gg::GT;
+  const int64_t J = b.n;
+  gg::f32x4 acc[2][2];
+  gg::tile_chain(a, b, i0, j0, 0, Rn, acc);
+  gg::tile_store(acc, i0, j0, a.n, J, [&](int64_t i, int64_t j, float v) {
+    if (mask) v = v * mask[i * J + j];
+    c[i * J + j] = v;
+  });
 }
 
 int launch_gemm(const float *a, int64_t a_sr, int64_t a_si, const float *b, int64_t b_sr,
                 int64_t b_sj, int64_t I, int64_t J, int64_t Rn, const float *mask, float *c,
                 hipStream_t st, const char *name) {
-  const int64_t gx = ceil_div64(J, GT), gy = ceil_div64(I, GT);
+  const int64_t gx = ceil_div64(J, gg::GT), gy = ceil_div64(I, gg::GT);
   SNNQP_REQUIRE(gx < 65536 && gy < 65536, SNNQP_EINVAL, "%s: grid too large", name);
   hipLaunchKernelGGL(grad_gemm_kernel, dim3((unsigned)gx, (unsigned)gy), dim3(256), 0, st,
-                     a, a_sr, a_si, b, b_sr, b_sj, I, J, Rn, mask, c);
+                     gg::make_strided(a, a_sr, a_si, I), gg::make_strided(b, b_sr, b_sj, J), Rn,
+                     mask, c);
   SNNQP_CHECK_LAUNCH(name);
   return SNNQP_OK;
 }

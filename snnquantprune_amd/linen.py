@@ -486,8 +486,8 @@ _bn_cache = TensorCache(256)
 class BatchNorm(Module):
   """Eval-mode batch normalisation over the last axis with running statistics:
   y = (x - mean) * (rsqrt(var + eps) * scale) + bias, each op rounded in
-  float32.  params: scale, bias; batch_stats: mean, var.  Training-mode
-  statistics are out of scope (forward / eval only)."""
+  float32.  params: scale, bias; batch_stats: mean, var.  In training the
+  batch statistics are the owning block's (conv_train.py); `update_running` moves the running ones."""
   use_running_average: Optional[bool] = None
   axis: int = -1
   momentum: float = 0.99
@@ -532,6 +532,30 @@ class BatchNorm(Module):
                        torch.from_numpy(b).to(dev), flags)
     return _bn_cache.put((mean, var, scale, bias), float(self.epsilon), out)
 
+  # Batch statistics (use_running_average=False) are computed by the training block that owns the
+  # module (conv_train.ConvBlock: they belong to its backward); the module holds the parameters
+  # and moves the running statistics.
+  @compact_method
+  def scale_param(self, features: int):
+    return self.param("scale", ones, (int(features),))
+
+  @compact_method
+  def bias_param(self, features: int):
+    return self.param("bias", zeros, (int(features),))
+
+  @compact_method
+  def update_running(self, mean_t, var_t):
+    """One update per scan step, in t order, of the running statistics with the per-step batch
+    statistics [T, C] (the biased variance): ra = momentum * ra + (1 - momentum) * new.  Nothing
+    when 'batch_stats' is not mutable."""
+    if not self.is_mutable_collection("batch_stats"):
+      return
+    from .conv_train import running_update
+    feat = (int(mean_t.shape[-1]),)
+    for name, new, init in (("mean", mean_t, zeros), ("var", var_t, ones)):
+      v = self.variable("batch_stats", name, lambda i=init: i(None, feat))
+      v.value = running_update(v.value.to(new.device), new.detach(), float(self.momentum))
+
   def __call__(self, x, use_running_average: Optional[bool] = None):
     from . import ops
     ura = self.use_running_average if use_running_average is None else use_running_average
@@ -539,8 +563,8 @@ class BatchNorm(Module):
       raise ValueError("BatchNorm needs use_running_average")
     if not ura:
       raise NotImplementedError(
-          "BatchNorm batch statistics (training mode) are out of scope: this "
-          "package implements the eval forward pass")
+          "BatchNorm on batch statistics runs inside the training blocks (conv_train.ConvBlock); "
+          "as a stand-alone call it is not supported")
     if self.axis not in (-1, x.ndim - 1):
       raise NotImplementedError("BatchNorm over a non-last axis")
     return ops.batchnorm_forward(x, self.coeffs(x.shape[-1]))

@@ -68,8 +68,8 @@ def _layer_bits(cfg, i):
 def _require_eval(train):
   if train:
     raise NotImplementedError(
-        "training (dropout, batch statistics, gradients) is out of scope: this "
-        "package implements the eval forward pass (train=False)")
+        "training is implemented for DenseSNN and ConvDenseSNN only (DESIGN.md 10, 11); this "
+        "model implements the eval forward pass (train=False)")
 
 
 def _probing(mod, cfg):
@@ -279,7 +279,8 @@ class ConvDenseSNN(nn.Module):
 
   def __call__(self, inputs, trgt=None, train: bool = False, rng: Any = None,
                u_state=None, online=False):
-    _require_eval(train)
+    if train:
+      return self._train_forward(inputs, rng, u_state, online)
     cfg = self.config
     x = _as_input(inputs)
     nblocks = cfg.num_conv_blocks if "num_conv_blocks" in cfg else 3
@@ -321,6 +322,72 @@ class ConvDenseSNN(nn.Module):
     if probe:
       _sow_density(self, "dense1_out", x)
     return ops.vote(x, 10), None
+
+  def _train_forward(self, inputs, rng, u_state, online):
+    """The training forward of models.py:101-147, :189-190, :219-255 (BatchNorm on batch
+    statistics, one dropout mask with keep probability config.dropout, not rescaled, in front of
+    the read-out), attached to torch autograd through the parameter leaves (conv_train.py,
+    dense_train.py).  Channel compaction and the fused kernels are not used."""
+    from . import conv_train as ct
+    from . import dense_train as dt
+    if isinstance(inputs, (ops.PackedSpikes, ops.PackedFrames, ops.GatedSpikes)) or not (
+        isinstance(inputs, torch.Tensor) and inputs.ndim == 5
+        and inputs.dtype in (torch.uint8, torch.float32)):
+      raise NotImplementedError("training takes uint8 or float32 [B, T, H, W, C] tensors")
+    cfg = self.config
+    if rng is None:
+      raise NotImplementedError("train=True needs an rng (an int seed or a torch.Generator) for "
+                                "the dropout mask; the reference splits it unconditionally")
+    if u_state is not None or online:
+      raise NotImplementedError("training: the online mode and a carried state are not supported")
+    if _probing(self, cfg):
+      raise NotImplementedError("training: density probes are not supported")
+    if "dropout" not in cfg:
+      raise ValueError("train=True needs config.dropout (the keep probability of the dropout "
+                       "mask, models.py:219-224)")
+    qw = cfg.quant.get("weight")
+    if qw is not None and getattr(qw, "func", qw) is not DuQ:
+      raise NotImplementedError("training supports the DuQ weight quantiser or none, not %r" % (qw,))
+    x = inputs.transpose(0, 1).contiguous()               # models.py:109, [T, B, H, W, C]
+    nblocks = cfg.num_conv_blocks if "num_conv_blocks" in cfg else 3
+    params = self._root.variables["params"]
+    sowing = self.is_mutable_collection("intermediates")
+    for i in range(nblocks):
+      conv = QuantConv(features=cfg.channels, kernel_size=(3, 3), padding=((1, 1), (1, 1)),
+                       use_bias=False, dtype=self.dtype, config=cfg.quant,
+                       bits=_layer_bits(cfg, i), g_scale=cfg.quant.g_scale)
+      dyn = cfg.neuron_dynamics(dtype=self.dtype)
+      norm = nn.BatchNorm(use_running_average=False, momentum=0.9, epsilon=1e-5, use_bias=True,
+                          use_scale=True, dtype=self.dtype)
+      surr = dt.surrogate_of(dyn)
+      H, W, cin = x.shape[2], x.shape[3], x.shape[4]
+      geom = conv.geometry((H, W), cin)
+      pk = conv.packed_kernel(cin)
+      wq = dt.transformed_kernel(params["QuantConv_%d" % i], pk)
+      x, h, s, mean, var = ct.ConvBlock.apply(
+          x, wq, norm.scale_param(cfg.channels), norm.bias_param(cfg.channels), pk, geom,
+          dyn.neuron(cfg.channels), surr, float(norm.epsilon), i == 0)
+      norm.update_running(mean, var)
+      if sowing:
+        self.sow("intermediates", "conv%d_h" % i, h)
+        self.sow("intermediates", "conv%d_out" % i, s)
+        self.sow("intermediates", "bn%d_mean" % i, mean)
+        self.sow("intermediates", "bn%d_var" % i, var)
+    x = flatten_channel_major(x)
+    dense = QuantDense(self.num_classes * 10, use_bias=False, dtype=self.dtype, config=cfg.quant,
+                       bits=_layer_bits(cfg, nblocks), g_scale=cfg.quant.g_scale)
+    dyn = cfg.neuron_dynamics(dtype=self.dtype)
+    surr = dt.surrogate_of(dyn)
+    pk = dense.packed_kernel(x.shape[-1])
+    gen = dt.generator_of(rng, x.device)
+    m = dt.dropout_mask(x.shape, cfg.dropout, gen, x.device)             # models.py:219-224
+    wq = dt.transformed_kernel(params["QuantDense_0"], pk)
+    logits, s, h = dt.DenseBlock2.apply(x, wq, m, pk, dyn.neuron(self.num_classes * 10), surr, 10)
+    if sowing:
+      self.sow("intermediates", "dropout_0", m)
+      self.sow("intermediates", "dense_out", s)
+      self.sow("intermediates", "dense_h", h)
+    return logits, None
 
 
 class CextNet(nn.Module):

@@ -1534,3 +1534,75 @@ def dense_input_grad(gI: torch.Tensor, w: torch.Tensor, mask: Optional[torch.Ten
   L.check(L.lib().snnqp_dense_input_grad(_ptr(gI), _ptr(w), _ptr(mask), M, K, N, _ptr(gx),
                                          _stream()))
   return gx
+
+
+# ---------------------------------------------------------------------------
+# training of the conv blocks (csrc/train_conv.hip)
+# ---------------------------------------------------------------------------
+
+
+def conv_grad_splits(geom: ConvGeom, NB: int) -> int:
+  """The default number of r ranges of conv_weight_grad for NB images: shapes only, 1..64."""
+  g = geom.struct()
+  rc = L.lib().snnqp_conv_grad_splits(ctypes.byref(g), int(NB))
+  if rc < 0:
+    L.check(rc)
+  return rc
+
+
+def conv_weight_grad_workspace_bytes(geom: ConvGeom, splits: int) -> int:
+  g = geom.struct()
+  rc = L.lib().snnqp_conv_weight_grad_workspace_bytes(ctypes.byref(g), int(splits))
+  if rc < 0:
+    L.check(rc)
+  return rc
+
+
+def conv_weight_grad(x: torch.Tensor, gI: torch.Tensor, geom: ConvGeom,
+                     splits: Optional[int] = None) -> torch.Tensor:
+  """x [NB, H, W, Cin], gI [NB, OH, OW, Cout] -> gw HWIO [KH, KW, Cin, Cout]: the r-ascending
+  chain over r = (n, oh, ow), cut into `splits` ranges summed in order (None: conv_grad_splits)."""
+  x, gI = _f32c(x), _f32c(gI)
+  _require_gpu(x, gI)
+  NB = x.shape[0]
+  g = geom.struct()
+  if splits is None:
+    splits = conv_grad_splits(geom, NB)
+  nbytes = conv_weight_grad_workspace_bytes(geom, splits)
+  OH, OW = geom.out_hw()
+  assert tuple(x.shape) == (NB, geom.H, geom.W, geom.Cin), (tuple(x.shape), geom)
+  assert tuple(gI.shape) == (NB, OH, OW, geom.Cout), (tuple(gI.shape), geom)
+  ws = torch.empty(nbytes // 4, dtype=torch.float32, device=x.device) if nbytes else None
+  gw = torch.empty((geom.KH, geom.KW, geom.Cin, geom.Cout), dtype=torch.float32, device=x.device)
+  L.check(L.lib().snnqp_conv_weight_grad(_ptr(x), _ptr(gI), NB, ctypes.byref(g), int(splits),
+                                         _ptr(ws), _ptr(gw), _stream()))
+  return gw
+
+
+def conv_input_grad(gI: torch.Tensor, w: torch.Tensor, geom: ConvGeom) -> torch.Tensor:
+  """gI [NB, OH, OW, Cout], w HWIO -> gx [NB, H, W, Cin], the chain over r = (kh, kw, co)."""
+  gI, w = _f32c(gI), _f32c(w)
+  _require_gpu(gI, w)
+  NB = gI.shape[0]
+  g = geom.struct()
+  conv_grad_splits(geom, 0)                    # refuses the geometry before any shape is used
+  OH, OW = geom.out_hw()
+  assert tuple(gI.shape) == (NB, OH, OW, geom.Cout), (tuple(gI.shape), geom)
+  assert tuple(w.shape) == (geom.KH, geom.KW, geom.Cin, geom.Cout), (tuple(w.shape), geom)
+  gx = torch.empty((NB, geom.H, geom.W, geom.Cin), dtype=torch.float32, device=gI.device)
+  L.check(L.lib().snnqp_conv_input_grad(_ptr(gI), _ptr(w), NB, ctypes.byref(g), _ptr(gx),
+                                        _stream()))
+  return gx
+
+
+def maxpool2x2_backward(s: torch.Tensor, gp: torch.Tensor) -> torch.Tensor:
+  """s [..., H, W, C] the pool's float32 input, gp [..., H/2, W/2, C] -> gs like s: gp to the
+  first maximum of each window in row-major order, 0 elsewhere."""
+  s, gp = _f32c(s), _f32c(gp)
+  _require_gpu(s, gp)
+  H, W, C = s.shape[-3:]
+  assert tuple(gp.shape) == tuple(s.shape[:-3]) + (H // 2, W // 2, C), (s.shape, gp.shape)
+  NB = s.numel() // (H * W * C) if H * W * C else 0
+  gs = torch.empty_like(s)
+  L.check(L.lib().snnqp_maxpool2x2_backward(_ptr(s), _ptr(gp), NB, H, W, C, _ptr(gs), _stream()))
+  return gs

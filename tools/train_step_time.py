@@ -5,6 +5,13 @@ kernel, against a plain PyTorch-eager float32 autograd statement of the same ste
 Prints one JSON line.
 
   python tools/train_step_time.py [--steps 20] [--warmup 5] [--batch 256] [--frames 20]
+
+--conv times one ConvDenseSNN train_step at the C3 topology instead (three 3x3 conv blocks of 128
+channels on 128 x 128 x 2 frames, 4-bit DuQ, 90 % pruned, default B = 2, T = 20: the reference's
+per-device batch), against the same step in PyTorch eager float32 autograd, and conv1's weight
+gradient with one range of r against the default split.
+
+  python tools/train_step_time.py --conv [--steps 5] [--warmup 2] [--batch 2] [--frames 20] [--hw 128]
 """
 import argparse
 import json
@@ -69,13 +76,115 @@ def _eager_loss(params, x, labels, tau=2.0, L=127.0):
   return torch.mean(torch.square(logits - oh))
 
 
+def _eager_conv_loss(params, x, labels, nblocks, keep_mask, tau=2.0, L=7.0, eps=1e-5):
+  """The ConvDenseSNN step as float32 torch autograd: DuQ + prune, conv + batch-statistics
+  BatchNorm per time step + LIF + max pool, flatten, dropout, dense + LIF, vote, MSE."""
+  def wq(leaf):
+    w, a, c, m = leaf["kernel"], leaf["DuQ_0"]["a"], leaf["DuQ_0"]["c"], leaf["prune_0"]["mask"]
+    y = torch.nn.functional.hardtanh(w / a)
+    y = y + (torch.round(y * L) / L - y).detach()
+    return y * c * m
+
+  def scan(cur):
+    u = torch.zeros_like(cur[0])
+    out = []
+    for t in range(cur.shape[0]):
+      u = u + (cur[t] - u) / tau
+      s = _Spike.apply(u - 1.0)
+      u = u * (1 - s.detach())
+      out.append(s)
+    return torch.stack(out)
+
+  xs = x.transpose(0, 1).to(torch.float32).permute(0, 1, 4, 2, 3)            # [T, B, C, H, W]
+  for i in range(nblocks):
+    T, B = xs.shape[:2]
+    w = wq(params["QuantConv_%d" % i]).permute(3, 2, 0, 1)
+    cur = torch.nn.functional.conv2d(xs.reshape((T * B,) + tuple(xs.shape[2:])), w, padding=1)
+    cur = cur.reshape((T, B) + tuple(cur.shape[1:]))
+    mean = cur.mean((1, 3, 4), keepdim=True)
+    var = (cur * cur).mean((1, 3, 4), keepdim=True) - mean * mean
+    bn = params["BatchNorm_%d" % i]
+    cur = (cur - mean) * (torch.rsqrt(var + eps) * bn["scale"][None, None, :, None, None]) \
+        + bn["bias"][None, None, :, None, None]
+    s = scan(cur)
+    xs = torch.nn.functional.max_pool2d(s.reshape((T * B,) + tuple(s.shape[2:])), 2)
+    xs = xs.reshape((T, B) + tuple(xs.shape[1:]))
+  flat = xs.reshape(xs.shape[0], xs.shape[1], -1) * keep_mask
+  s2 = scan(torch.einsum("tbk,kn->tbn", flat, wq(params["QuantDense_0"])))
+  logits = s2.mean(0).reshape(s2.shape[1], -1, 10).mean(-1)
+  oh = torch.nn.functional.one_hot(labels, logits.shape[1]).to(torch.float32)
+  return torch.mean(torch.square(logits - oh))
+
+
+def conv_main(args):
+  from snnquantprune_amd import linen as nn
+  from snnquantprune_amd import models, ops, synthetic as syn, train_utils as tu
+  dev = torch.device("cuda:0")
+  B, T, HW, C, NB = args.batch, args.frames, args.hw, 128, 3
+  cfg = syn.make_config(bits=4, prune_percentage=0.9, channels=C, dropout=0.9)
+  cfg.optimizer = "adam"
+  model = models.ConvDenseSNN(num_classes=11, config=cfg)
+  v = syn.conv_net_variables(C, 2, NB, HW, 110, True, 0.9)
+  variables = nn.tree_from_numpy(v, dev)
+  x = torch.from_numpy(syn.poisson_counts((B, T, HW, HW, 2), 0.3, seed=941)).to(dev)
+  labels = torch.arange(B, device=dev) % 11
+  batch = {"dvs_matrix": x, "label": labels}
+  box = [tu.create_train_state(variables, cfg, model)]
+
+  def hip_step():
+    box[0], _ = tu.train_step(box[0], batch, 0, lambda s: 1e-4, 0.0, 0.0, tu.mse_loss)
+
+  hip_ms = _time(hip_step, args.steps, args.warmup)
+
+  # conv1's two gradient products alone, on the step's shapes
+  geom = ops.ConvGeom(HW // 2, HW // 2, C, C, 3, 3, (1, 1), ((1, 1), (1, 1)))
+  x1 = (torch.rand((T * B, HW // 2, HW // 2, C), device=dev) < 0.1).to(torch.float32)
+  g1 = torch.randn((T * B, HW // 2, HW // 2, C), device=dev)
+  w1 = torch.randn((3, 3, C, C), device=dev)
+  splits = ops.conv_grad_splits(geom, T * B)
+  kern = {
+      "conv1_weight_grad_splits": splits,
+      "conv1_weight_grad_1_ms": _time(lambda: ops.conv_weight_grad(x1, g1, geom, splits=1), args.steps, 2),
+      "conv1_weight_grad_default_ms": _time(lambda: ops.conv_weight_grad(x1, g1, geom), args.steps, 2),
+      "conv1_input_grad_ms": _time(lambda: ops.conv_input_grad(g1, w1, geom), args.steps, 2),
+  }
+  del x1, g1, w1
+
+  eparams = {k: {kk: ({kkk: t.detach().clone().requires_grad_(True) for kkk, t in vv.items()}
+                      if isinstance(vv, dict) else vv.detach().clone().requires_grad_(True))
+                 for kk, vv in leaf.items()} for k, leaf in nn.tree_from_numpy(v, dev)["params"].items()}
+  opt = torch.optim.Adam([t for _, t in tu._flatten(eparams)], lr=1e-4, eps=1e-8)
+  K = (HW >> NB) ** 2 * C
+  keep = (torch.rand((T, B, K), device=dev) < 0.9).to(torch.float32)
+
+  def eager_step():
+    opt.zero_grad(set_to_none=True)
+    _eager_conv_loss(eparams, x, labels, NB, keep).backward()
+    opt.step()
+
+  eager_ms = _time(eager_step, args.steps, args.warmup)
+  print(json.dumps({"workload": "conv_dense_snn_c3_train_step", "batch": B, "frames": T, "hw": HW,
+                    "hip_train_step_ms": round(hip_ms, 3), "eager_torch_train_step_ms": round(eager_ms, 3),
+                    "speedup_vs_eager": round(eager_ms / hip_ms, 2),
+                    "samples_per_s": round(B / hip_ms * 1e3, 1),
+                    **{k: round(val, 4) for k, val in kern.items()}}))
+
+
 def main():
   ap = argparse.ArgumentParser()
-  ap.add_argument("--steps", type=int, default=20)
-  ap.add_argument("--warmup", type=int, default=5)
-  ap.add_argument("--batch", type=int, default=256)
+  ap.add_argument("--conv", action="store_true")
+  ap.add_argument("--steps", type=int, default=None)
+  ap.add_argument("--warmup", type=int, default=None)
+  ap.add_argument("--batch", type=int, default=None)
   ap.add_argument("--frames", type=int, default=20)
+  ap.add_argument("--hw", type=int, default=128)
   args = ap.parse_args()
+  dflt = (5, 2, 2) if args.conv else (20, 5, 256)
+  args.steps = dflt[0] if args.steps is None else args.steps
+  args.warmup = dflt[1] if args.warmup is None else args.warmup
+  args.batch = dflt[2] if args.batch is None else args.batch
+  if args.conv:
+    return conv_main(args)
   from snnquantprune_amd import linen as nn
   from snnquantprune_amd import models, ops, synthetic as syn, train_utils as tu
   dev = torch.device("cuda:0")
