@@ -822,15 +822,18 @@ def dense_block(inputs, qw: QWeight, neuron_cfg=None, mode="int", u0=None):
 
 
 def conv_block(inputs, qw: QWeight, bn: Optional[dict], neuron_cfg=None,
-               mode="int", padding=((1, 1), (1, 1)), strides=None, u0=None):
-  """SpikingBlock(QuantConv, neuron, BatchNorm) on [T, B, H, W, C]."""
+               mode="int", padding=((1, 1), (1, 1)), strides=None, u0=None,
+               input_dilation=None, kernel_dilation=None, feature_group_count=1):
+  """SpikingBlock(QuantConv, neuron, BatchNorm) on [T, B, *spatial, C]."""
   norm = None
   if bn is not None:
     norm = lambda x: batchnorm_eval(x, bn["mean"], bn["var"], bn.get("scale"),
                                     bn.get("bias"), bn.get("eps", 1e-5))
   return spiking_block(
       u0, inputs,
-      lambda x: quant_conv(x, qw, strides=strides, padding=padding, mode=mode),
+      lambda x: quant_conv(x, qw, strides=strides, padding=padding,
+                           input_dilation=input_dilation, kernel_dilation=kernel_dilation,
+                           feature_group_count=feature_group_count, mode=mode),
       _neuron(neuron_cfg or {}), norm)
 
 

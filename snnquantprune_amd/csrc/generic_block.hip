@@ -248,14 +248,8 @@ int run_generic(const void *x, int in_type, int64_t xs_t, int64_t xs_b, int32_t 
   if (a.nrn.kind != SNNQP_NEURON_NONE) {
     SNNQP_REQUIRE(s_type == SNNQP_F32 || s_type == SNNQP_BITS, SNNQP_EINVAL,
                   "spike output type must be F32 or BITS");
-    if (s_type == SNNQP_BITS && (g->Cout & 31) != 0) {
-      const int64_t words = (int64_t)T * B * a.OD * a.OH * a.OW * ((g->Cout + 31) / 32);
-      const int64_t zb = (words + 255) / 256;
-      hipLaunchKernelGGL(zero_words_if_kernel, dim3((unsigned)(zb < 4096 ? zb : 4096)), dim3(256), 0, st,
-                         pred, (uint32_t *)s_out, words);
-      SNNQP_CHECK_LAUNCH("zero_words_if_kernel");
-    }
   }
+  // (every refusal comes before the first launch: a refused call leaves its outputs as they were)
   const bool intpath = (w->wtype == SNNQP_W_I8);
   if (intpath) {
     SNNQP_REQUIRE(in_type == SNNQP_U8 || in_type == SNNQP_BITS, SNNQP_EUNSUPPORTED,
@@ -266,10 +260,21 @@ int run_generic(const void *x, int in_type, int64_t xs_t, int64_t xs_b, int32_t 
     const int64_t kk = (int64_t)a.KD * g->KH * g->KW * a.CinG;
     SNNQP_REQUIRE(kk * 255 * 127 < (1ll << 31), SNNQP_EUNSUPPORTED,
                   "contraction length %lld overflows int32", (long long)kk);
+  } else {
+    SNNQP_REQUIRE(w->wtype == SNNQP_W_F32, SNNQP_EINVAL, "unknown weight type");
+    SNNQP_REQUIRE(in_type == SNNQP_F32 || in_type == SNNQP_U8 || in_type == SNNQP_BITS, SNNQP_EINVAL,
+                  "unknown input type %d", in_type);
+  }
+  if (a.nrn.kind != SNNQP_NEURON_NONE && s_type == SNNQP_BITS && (g->Cout & 31) != 0) {
+    const int64_t words = (int64_t)T * B * a.OD * a.OH * a.OW * ((g->Cout + 31) / 32);
+    const int64_t zb = (words + 255) / 256;
+    hipLaunchKernelGGL(zero_words_if_kernel, dim3((unsigned)(zb < 4096 ? zb : 4096)), dim3(256), 0, st,
+                       pred, (uint32_t *)s_out, words);
+    SNNQP_CHECK_LAUNCH("zero_words_if_kernel");
+  }
+  if (intpath)
     return in_type == SNNQP_U8 ? launch_generic<SNNQP_U8, true>(a, pool, st)
                                : launch_generic<SNNQP_BITS, true>(a, pool, st);
-  }
-  SNNQP_REQUIRE(w->wtype == SNNQP_W_F32, SNNQP_EINVAL, "unknown weight type");
   switch (in_type) {
     case SNNQP_F32: return launch_generic<SNNQP_F32, false>(a, pool, st);
     case SNNQP_U8: return launch_generic<SNNQP_U8, false>(a, pool, st);

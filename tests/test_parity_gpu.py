@@ -3886,21 +3886,21 @@ def test_quant_conv_3d(dev, oracle, case):
                                   "batch_stats": {"norm_fn": {"mean": bn["mean"], "var": bn["var"]}}}, dev)
   xs = rng.integers(0, 2, size=(T, B, D, H, W, C)).astype(np.uint8)
   u0 = (rng.standard_normal(e_int.shape) * 0.3).astype(F32)
-  ckw = dict(padding=kw["padding"], strides=kw.get("strides"))
-  if G == 1 and "input_dilation" not in kw:
-    eu, es = oracle.conv_block(xs.astype(F32), qw, bn, None, "int", u0=u0, **ckw)
-    for xin in (_t(xs, dev), _t(xs.astype(F32), dev), ops.pack_bits(_t(xs, dev))):
-      u, sp = blk.apply(variables, _t(u0, dev), xin)
-      got = _np(sp) if not isinstance(sp, ops.PackedSpikes) else _np(sp.to_dense())
-      np.testing.assert_array_equal(got.astype(np.uint8), es.astype(np.uint8))
-      np.testing.assert_array_equal(_np(u), eu)
-    xf = xs.astype(F32)
-    xf[2, 1, 0, 1, 1, 0] = 1.5
-    eu, es = oracle.conv_block(xf, qw, bn, None, "fseq", u0=u0, **ckw)
-    u, sp = blk.apply(variables, _t(u0, dev), _t(xf, dev))
+  ckw = dict(padding=kw["padding"], strides=kw.get("strides"), input_dilation=kw.get("input_dilation"),
+             kernel_dilation=kw.get("kernel_dilation"), feature_group_count=G)
+  eu, es = oracle.conv_block(xs.astype(F32), qw, bn, None, "int", u0=u0, **ckw)
+  for xin in (_t(xs, dev), _t(xs.astype(F32), dev), ops.pack_bits(_t(xs, dev))):
+    u, sp = blk.apply(variables, _t(u0, dev), xin)
     got = _np(sp) if not isinstance(sp, ops.PackedSpikes) else _np(sp.to_dense())
     np.testing.assert_array_equal(got.astype(np.uint8), es.astype(np.uint8))
     np.testing.assert_array_equal(_np(u), eu)
+  xf = xs.astype(F32)
+  xf[2, 1, 0, 1, 1, 0] = 1.5
+  eu, es = oracle.conv_block(xf, qw, bn, None, "fseq", u0=u0, **ckw)
+  u, sp = blk.apply(variables, _t(u0, dev), _t(xf, dev))
+  got = _np(sp) if not isinstance(sp, ops.PackedSpikes) else _np(sp.to_dense())
+  np.testing.assert_array_equal(got.astype(np.uint8), es.astype(np.uint8))
+  np.testing.assert_array_equal(_np(u), eu)
   assert ops.device_status() == 0
 
 
