@@ -221,10 +221,11 @@ typedef struct {
  * snnqp_scatter_spike_channels; 505: training of the dense blocks -- SNNQP_SURR_*,
  * snnqp_lif_forward_save, snnqp_lif_backward, snnqp_dense_weight_grad, snnqp_dense_input_grad;
  * 506: training of the conv blocks -- snnqp_conv_weight_grad, snnqp_conv_input_grad,
- * snnqp_conv_grad_splits, snnqp_conv_weight_grad_workspace_bytes, snnqp_maxpool2x2_backward).
+ * snnqp_conv_grad_splits, snnqp_conv_weight_grad_workspace_bytes, snnqp_maxpool2x2_backward;
+ * 507: snnqp_conv_forward_ex -- currents from the bit-input MFMA conv).
  * A binding compares snnqp_version()
  * with the SNNQP_VERSION it was written against and refuses a library of another version (_lib.py does). */
-#define SNNQP_VERSION 506
+#define SNNQP_VERSION 507
 int snnqp_version(void);
 const char *snnqp_last_error(void);
 /* Extra compiler flags the library was built with: "" for the product build
@@ -337,6 +338,29 @@ int snnqp_unpack_bits(const uint32_t *bits, int64_t rows, int32_t C, float *y,
 int snnqp_conv_forward(const void *x, int in_type, int64_t NB,
                        const snnqp_conv_geom_t *g, const snnqp_weight_t *w,
                        float *y, int32_t *acc, snnqp_stream_t stream);
+/* The same call site with a choice of kernel.  On integer codes and a spike raster
+ * snnqp_conv_forward runs the direct-form kernel, one thread per output; here the 3x3 / stride 1
+ * / pad 1 connection over SNNQP_BITS input with 1 <= Cin <= 128 (any H, W, Cout) runs as an MFMA
+ * implicit GEMM that hands back currents: v_mfma_scale_f32_32x32x64_f8f6f4 (fp4 spikes x fp6
+ * codes) for code_max in 1..7, v_mfma_i32_32x32x32_i8 for wider or unknown codes.  The
+ * accumulator is the same exact integer and y = fl(fl(acc / L) * m) is computed with the same
+ * instructions, so y and acc hold the bits snnqp_conv_forward writes.
+ * wt    the codes tiled by snnqp_pack_codes_mfma exactly as snnqp_conv_lif_forward documents
+ *       (HWIO kernel zero-padded along Cin to 32 ceil(Cin / 32), or to w->wt_cin, flattened to
+ *       [9 * that][Cout]); bits of a pixel's last spike word beyond Cin must be zero.
+ * acc   nullable int32, the shape of y: the accumulators.
+ * impl  SNNQP_IMPL_GENERIC: exactly snnqp_conv_forward (its float32 MFMA route for W_F32
+ *       included; wt is not read).  SNNQP_IMPL_MFMA: the kernel above, or SNNQP_EUNSUPPORTED with
+ *       the reason (weights not int8 codes; not 3x3 / stride 1 / pad 1 / undilated / ungrouped;
+ *       input not SNNQP_BITS; Cin > 128; wt NULL; wt_cin not a multiple of 32 in [Cin, 128]; 2^30
+ *       patches of 4x8 pixels or more).  SNNQP_IMPL_AUTO: that kernel when it can, otherwise
+ *       snnqp_conv_forward.  A refused call has launched nothing and leaves y and acc untouched;
+ *       NB == 0 enqueues nothing.  snnqp_fallback_counts is not touched: it counts fused blocks.
+ * x, y and acc need 4-byte alignment only. */
+int snnqp_conv_forward_ex(const void *x, int in_type, int64_t NB,
+                          const snnqp_conv_geom_t *g, const snnqp_weight_t *w,
+                          const int8_t *wt, float *y, int32_t *acc, int impl,
+                          snnqp_stream_t stream);
 /* The same, executed only if *pred != 0 when the stream reaches it: the float32 connection behind
  * a speculative integer one (a float32 tensor narrowed by snnqp_narrow_f32, whose flag word is
  * `pred`) -- QuantDense / QuantConv called on their own with float32 inputs

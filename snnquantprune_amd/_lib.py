@@ -16,7 +16,7 @@ _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.path.join(_HERE, "csrc", "libsnnqp.so")
 
 # include/snnqp.h SNNQP_VERSION the prototypes below were written against
-ABI_VERSION = 506
+ABI_VERSION = 507
 
 # enums of include/snnqp.h
 F32, U8, BITS, EV1, EV4 = 0, 1, 2, 3, 4
@@ -92,6 +92,8 @@ _PROTOTYPES = {
     "snnqp_unpack_bits": (c_int, [c_void_p, c_int64, c_int32, c_void_p, c_void_p]),
     "snnqp_conv_forward": (c_int, [c_void_p, c_int, c_int64, POINTER(ConvGeomT),
                                    POINTER(WeightT), c_void_p, c_void_p, c_void_p]),
+    "snnqp_conv_forward_ex": (c_int, [c_void_p, c_int, c_int64, POINTER(ConvGeomT),
+                                      POINTER(WeightT), c_void_p, c_void_p, c_void_p, c_int, c_void_p]),
     "snnqp_conv_forward_if": (c_int, [c_void_p, c_void_p, c_int, c_int64, POINTER(ConvGeomT),
                                       POINTER(WeightT), c_void_p, c_void_p]),
     "snnqp_conv3d_out_shape": (c_int, [POINTER(Conv3dGeomT), POINTER(c_int32), POINTER(c_int32),

@@ -6,7 +6,8 @@ torch.autograd.Function per block:
   x -> QuantConv 3x3 -> BatchNorm (batch statistics) -> multi_step_LIF -> 2x2 max pool
 
 Forward: the currents come from the eval connection kernels (ops.conv_forward; from block 1 on
-the input is the bit-packed raster of the block before, so the integer path stays exact), the
+the input is the bit-packed raster of the block before, so the integer path stays exact, and
+the connection runs on the currents form of the bit-input MFMA conv, nn.set_train_conv_mfma), the
 batch-statistics BatchNorm runs as torch tensor ops, one scan writes the spikes and the pre-reset
 potential h (ops.lif_forward_save), and ops.maxpool2x2 pools.  Backward (csrc/train_conv.hip,
 csrc/train_dense.hip): the pool's routing, the BPTT scan, BatchNorm's backward in torch ops, then
@@ -25,6 +26,7 @@ from __future__ import annotations
 
 import torch
 
+from . import linen as _nn
 from . import ops
 from . import packing
 
@@ -88,6 +90,10 @@ def conv_currents(x, pk: packing.PackedKernel, geom: ops.ConvGeom) -> torch.Tens
   """x [NB, H, W, Cin] (uint8, float32 or PackedSpikes) -> float32 [NB, OH, OW, Cout] on the eval
   connection kernels: integer codes for integer-valued inputs, the float32 kernel otherwise."""
   w = pk.int_weight()
+  if w is not None and isinstance(x, ops.PackedSpikes) and _nn.train_conv_mfma():
+    # the bit-packed raster of the block before: the codes tiled for the MFMA currents kernel
+    # (ops.conv_forward takes it where the shape allows, the direct-form launch otherwise)
+    w = pk.int_weight_mfma((geom.Cout + 31) // 32 * 32) or w
   if w is not None and isinstance(x, torch.Tensor) and x.dtype == torch.float32:
     if bool(((x == torch.round(x)) & (x >= 0) & (x <= 255)).all()):
       x = x.to(torch.uint8)

@@ -47,33 +47,11 @@
 
 namespace snnqp {
 
-typedef __attribute__((address_space(3))) const v4i lds_cv4i_t;
-
-constexpr int F6_PITCH = HPITCH;             // pixels per LDS halo row (10 used)
-constexpr int F6_ROWS = 6;                   // halo rows of a 4x8 patch
-constexpr int F6_NT = 256;                   // threads of a workgroup: 4 waves
-constexpr int F6_PLANE = F6_ROWS * HPITCH * 32;   // one k-step plane of a halo image
+// (halo image geometry F6_*, fp6_pack32, FMT_*, pair_tap: conv_tile.h, shared with the currents
+// form of this conv, conv3x3_currents.hip)
 constexpr int F6_NBUF = 3;                   // halo images in the ring
-constexpr int F6_TAB = FP4_TAB_BYTES;        // byte -> 8 fp4 nibbles (tile_util.h)
 // (DQT_MAXA = 2047, conv_tile.h: the |acc| bound DQ_TABLE's table is sized for)
 constexpr int DQT_BYTES = 16384;             // 4095 entries
-
-// 32 int8 codes in k order (lo = k 0..15, hi = k 16..31) -> 32 fp6 values, value j
-// at bits [6j, 6j + 6) of 6 dwords (the B fragment of one lane for one k-step)
-__device__ __forceinline__ void fp6_pack32(const v4i &lo, const v4i &hi, int (&d)[6]) {
-  uint32_t t[8];
-#pragma unroll
-  for (int i = 0; i < 4; ++i) {
-    t[i] = squeeze6(fp6_codes4((uint32_t)lo[i]));
-    t[4 + i] = squeeze6(fp6_codes4((uint32_t)hi[i]));
-  }
-#pragma unroll
-  for (int g = 0; g < 2; ++g) {
-    d[3 * g + 0] = (int)(t[4 * g] | (t[4 * g + 1] << 24));
-    d[3 * g + 1] = (int)((t[4 * g + 1] >> 8) | (t[4 * g + 2] << 16));
-    d[3 * g + 2] = (int)((t[4 * g + 2] >> 16) | (t[4 * g + 3] << 8));
-  }
-}
 
 // FMT: the matrix instruction the contraction runs on
 //   FMT_FP6: v_mfma_scale_f32_32x32x64_f8f6f4, fp4 spikes x fp6 codes (|code| <= 7), K = 64
@@ -101,15 +79,10 @@ __device__ __forceinline__ void fp6_pack32(const v4i &lo, const v4i &hi, int (&d
 // BNU: ... and every channel has the same multiplier (SNNQP_BN_MUL_UNIFORM; DQ_TABLE only): the
 //      table entry is fl(current * mul) -- the same float32 product, once per entry instead of once
 //      per neuron update -- and the epilogue has no BatchNorm instruction left
-enum { FMT_FP6 = 0, FMT_I8 = 1 };
-
 constexpr int F6_WR_SLOT = 2;    // slot of a step after which the staged halo is written
 constexpr int F6_BAR_SLOT = 4;   // slot of a step after which the step's barrier sits
 constexpr int F6_PF = 4;         // A fragments in flight (ring of 6 or 7); 2 with a ring of 3 or 5
 
-// fp6, odd G: the tap lane half h reads in pair k-step p of the last group -- (0, 3), (1, 4),
-// (2, 5) one halo row apart, (6, 7), (8, -) one pixel apart; "tap 9" has zero codes
-__host__ __device__ constexpr int pair_tap(int p, int h) { return p < 3 ? p + 3 * h : 2 * p + h; }
 // fp6, 16-channel last group: the tap of piece i (k rows 32 h + 16 i .. + 15) of lane half h in
 // k-step q = 0 .. 2 of that group -- h = 0: taps q and 6 + q (two halo rows apart), h = 1: tap
 // 3 + q and nothing ("tap 9": zero codes; the piece re-reads tap 6 + q)

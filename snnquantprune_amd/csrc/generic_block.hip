@@ -307,6 +307,27 @@ extern "C" int snnqp_conv_forward(const void *x, int in_type, int64_t NB,
                      nullptr, nullptr, y, SNNQP_F32, acc, (hipStream_t)stream);
 }
 
+// snnqp_conv_forward with a choice of kernel (snnqp.h): the currents form of the bit-input MFMA
+// conv where it can serve the request, else (or on demand) the routes above.  Every refusal
+// comes before a launch; the fallback counters are for fused blocks and stay as they are.
+extern "C" int snnqp_conv_forward_ex(const void *x, int in_type, int64_t NB,
+                                     const snnqp_conv_geom_t *g, const snnqp_weight_t *w,
+                                     const int8_t *wt, float *y, int32_t *acc, int impl,
+                                     snnqp_stream_t stream) {
+  using namespace snnqp;
+  SNNQP_REQUIRE(g, SNNQP_EINVAL, "conv_forward_ex: null geometry");
+  SNNQP_REQUIRE(impl >= SNNQP_IMPL_AUTO && impl <= SNNQP_IMPL_MFMA, SNNQP_EINVAL,
+                "conv_forward_ex: unknown impl %d", impl);
+  SNNQP_REQUIRE(NB >= 0 && NB < (1ll << 31), SNNQP_EINVAL, "conv_forward_ex: bad NB");
+  if (impl == SNNQP_IMPL_GENERIC) return snnqp_conv_forward(x, in_type, NB, g, w, y, acc, stream);
+  const char *why = w ? conv3x3_currents_unsupported(in_type, NB, g, w, wt) : "null weight descriptor";
+  if (impl == SNNQP_IMPL_MFMA)
+    SNNQP_REQUIRE(!why, SNNQP_EUNSUPPORTED, "conv_forward_ex: MFMA kernel: %s", why);
+  if (why) return snnqp_conv_forward(x, in_type, NB, g, w, y, acc, stream);
+  if (int rc = refuse_after_device_report((hipStream_t)stream, "conv_forward_ex")) return rc;
+  return run_conv3x3_currents(x, NB, g, w, wt, y, acc, (hipStream_t)stream);
+}
+
 // The predicated form of snnqp_conv_forward (snnqp.h): the float32 re-evaluation of a connection
 // whose integer launch met a value that is not an integer in [0, 255].  Direct form (the same fmaf
 // chain as the f32-MFMA kernel, which is not predicated): the rare path.

@@ -20,6 +20,13 @@ int run_generic(const void *x, int in_type, int64_t xs_t, int64_t xs_b, int32_t 
 const char *conv3x3_mfma_unsupported(int in_type, const snnqp_conv_geom_t *g,
                                      const snnqp_weight_t *w, const int8_t *wt,
                                      const snnqp_neuron_t *nrn, int s_type);
+// The same for the currents form of the bit-input 3x3 conv (conv3x3_currents.hip): the connection
+// alone, NB images, float32 currents (and nullable int32 accumulators) out.
+const char *conv3x3_currents_unsupported(int in_type, int64_t NB, const snnqp_conv_geom_t *g,
+                                         const snnqp_weight_t *w, const int8_t *wt);
+int run_conv3x3_currents(const void *x, int64_t NB, const snnqp_conv_geom_t *g,
+                         const snnqp_weight_t *w, const int8_t *wt, float *y, int32_t *acc,
+                         hipStream_t st);
 int run_current_min(const snnqp_weight_t *w, const snnqp_bn_t *bn, int32_t bound, int32_t Cout,
                     uint32_t *out_bits, hipStream_t st);
 int conv3x3_bits_dequant_form(const snnqp_weight_t *w, const snnqp_neuron_t *nrn);

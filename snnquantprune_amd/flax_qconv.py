@@ -135,6 +135,10 @@ class QuantConv(nn.Module):
       return y
     if isinstance(x, ops.PackedSpikes):
       x4 = x.reshape_leading(nb, g.H, g.W)
+      if nsp == 2 and w.is_int and nn.train_conv_mfma():
+        # a spike raster: the codes tiled for the MFMA currents kernel (ops.conv_forward takes it
+        # for 3x3 / stride 1 / pad 1 and Cin <= 128, the direct-form launch otherwise)
+        w = pk.int_weight_mfma((self.features + 31) // 32 * 32) or w
     else:
       x4 = x.reshape(nb, g.H, g.W, cin)
     if integer is packing.SPECULATE and w.is_int:     # float32 that may hold integers: decided on the device

@@ -177,6 +177,27 @@ def conv_k16() -> bool:
   return bool(_lib.lib().snnqp_set_conv_k16(-1))
 
 
+# The connection alone over a bit-packed raster: the training forward of a conv
+# block (conv_train.conv_currents) and QuantConv called on its own hand ops.conv_forward the
+# MFMA-tiled codes, so a 3x3 / stride 1 / pad 1 connection with Cin <= 128 runs on the currents
+# form of the bit-input MFMA conv.  On by default.
+_TRAIN_CONV_MFMA = True
+
+
+def set_train_conv_mfma(enabled: bool) -> bool:
+  """True (default): those two callers take the MFMA currents kernel where it serves the shape.
+  False: the direct-form launch of earlier versions (the A side of an A/B; the results hold the
+  same bits).  Process-wide, for the calls after it; returns the previous setting."""
+  global _TRAIN_CONV_MFMA
+  old = _TRAIN_CONV_MFMA
+  _TRAIN_CONV_MFMA = bool(enabled)
+  return old
+
+
+def train_conv_mfma() -> bool:
+  return _TRAIN_CONV_MFMA
+
+
 def check_compute_dtype(dtype, who: str):
   global _dtype_warned
   if dtype in (torch.float32, None, "float32"):

@@ -781,18 +781,37 @@ def fseq_gemm_supported(geom: ConvGeom) -> bool:
           and pt + pb == geom.KH - 1 and pl + pr == geom.KW - 1)
 
 
-def conv_forward(x, geom: ConvGeom, weight: Weight, want_acc: bool = False):
-  """x [NB, H, W, Cin] -> float32 [NB, OH, OW, Cout] (+ int32 accumulators)."""
+_IMPLS = {"auto": L.IMPL_AUTO, "generic": L.IMPL_GENERIC, "mfma": L.IMPL_MFMA}
+
+
+def conv_forward(x, geom: ConvGeom, weight: Weight, want_acc: bool = False, impl: str = "auto"):
+  """x [NB, H, W, Cin] -> float32 [NB, OH, OW, Cout] (+ int32 accumulators).
+
+  impl "auto": a 3x3 / stride 1 / pad 1 connection over PackedSpikes whose `weight` carries the
+  MFMA-tiled codes `wt` runs on the currents form of the bit-input MFMA conv
+  (snnqp_conv_forward_ex), where that kernel can serve it; everything else, and every Weight
+  without `wt`, takes the launch of snnqp_conv_forward.  "generic": always that launch.  "mfma":
+  the MFMA kernel or an error with the reason.  The results hold the same bits either way."""
+  if impl not in _IMPLS:
+    raise ValueError("impl must be 'auto', 'generic' or 'mfma', not %r" % (impl,))
+  mfma = impl != "generic" and weight.wt is not None and isinstance(x, PackedSpikes)
+  if impl == "mfma" and not mfma:
+    raise L.SnnqpError(L.EUNSUPPORTED, "conv_forward: MFMA kernel: %s" % (
+        "MFMA-tiled codes `wt` not given" if weight.wt is None else "input must be bit-packed spikes"))
   xt, in_type = _in_desc(x)
   xt = xt.contiguous()
-  _require_gpu(xt, weight.w)
+  _require_gpu(xt, weight.w, weight.wt if mfma else None)
   NB = xt.shape[0]
   OH, OW = geom.out_hw()
   y = torch.empty((NB, OH, OW, geom.Cout), dtype=torch.float32, device=xt.device)
   acc = torch.empty(y.shape, dtype=torch.int32, device=xt.device) if want_acc else None
   g, w = geom.struct(), weight.struct()
-  L.check(L.lib().snnqp_conv_forward(_ptr(xt), in_type, NB, ctypes.byref(g),
-                                     ctypes.byref(w), _ptr(y), _ptr(acc), _stream()))
+  if mfma:
+    L.check(L.lib().snnqp_conv_forward_ex(_ptr(xt), in_type, NB, ctypes.byref(g), ctypes.byref(w),
+                                          _ptr(weight.wt), _ptr(y), _ptr(acc), _IMPLS[impl], _stream()))
+  else:
+    L.check(L.lib().snnqp_conv_forward(_ptr(xt), in_type, NB, ctypes.byref(g),
+                                       ctypes.byref(w), _ptr(y), _ptr(acc), _stream()))
   return (y, acc) if want_acc else y
 
 

@@ -9,9 +9,11 @@ Prints one JSON line.
 --conv times one ConvDenseSNN train_step at the C3 topology instead (three 3x3 conv blocks of 128
 channels on 128 x 128 x 2 frames, 4-bit DuQ, 90 % pruned, default B = 2, T = 20: the reference's
 per-device batch), against the same step in PyTorch eager float32 autograd, and conv1's weight
-gradient with one range of r against the default split.
+gradient with one range of r against the default split.  It also prints the step and the
+connection launch of conv1 and conv2 with nn.set_train_conv_mfma on and off (alternating, --reps
+timings each), and conv0's direct-form connection.
 
-  python tools/train_step_time.py --conv [--steps 5] [--warmup 2] [--batch 2] [--frames 20] [--hw 128]
+  python tools/train_step_time.py --conv [--steps 5] [--warmup 2] [--batch 2] [--frames 20] [--hw 128] [--reps 3]
 """
 import argparse
 import json
@@ -136,6 +138,43 @@ def conv_main(args):
 
   hip_ms = _time(hip_step, args.steps, args.warmup)
 
+  # the A/B of nn.set_train_conv_mfma in one process: the whole step with the connection of conv1
+  # and conv2 on the MFMA currents kernel (on) and on the direct-form kernel (off, the launch of
+  # earlier versions), alternating, `reps` timings each after the warm-up above
+  ab = {True: [], False: []}
+  for _ in range(args.reps):
+    for on in (True, False):
+      nn.set_train_conv_mfma(on)
+      ab[on].append(_time(hip_step, args.steps, 1))
+  nn.set_train_conv_mfma(True)
+
+  # the connection launch of every conv block alone, on the step's shapes: conv0 on the uint8
+  # frames (direct form either way), conv1 and conv2 on a bit-packed raster both ways
+  from snnquantprune_amd import _lib as L
+  from snnquantprune_amd import packing
+  from snnquantprune_amd.quant import QuantDesc
+  conn = {}
+  hw, cin = HW, 2
+  for i in range(NB):
+    leaf = variables["params"]["QuantConv_%d" % i]
+    a, c = float(leaf["DuQ_0"]["a"][0]), float(leaf["DuQ_0"]["c"][0])
+    pk = packing.PackedKernel(leaf["kernel"], QuantDesc(L.Q_DUQ, 4, a, c, 7.0, c), leaf["prune_0"]["mask"])
+    g = ops.ConvGeom(hw, hw, cin, C, 3, 3, (1, 1), ((1, 1), (1, 1)))
+    if i == 0:
+      xi = x.transpose(0, 1).reshape(T * B, hw, hw, cin).contiguous()
+      wi = pk.int_weight()
+      conn["conv0_direct_ms"] = [_time(lambda: ops.conv_forward(xi, g, wi), args.steps, 2) for _ in range(args.reps)]
+    else:
+      xi = ops.pack_bits((torch.rand((T * B, hw, hw, cin), device=dev) < 0.1).to(torch.uint8))
+      wi = pk.int_weight_mfma(C)
+      on_ms, off_ms = [], []
+      for _ in range(args.reps):
+        on_ms.append(_time(lambda: ops.conv_forward(xi, g, wi, impl="mfma"), args.steps, 2))
+        off_ms.append(_time(lambda: ops.conv_forward(xi, g, wi, impl="generic"), args.steps, 2))
+      conn["conv%d_mfma_ms" % i], conn["conv%d_direct_ms" % i] = on_ms, off_ms
+    hw, cin = hw // 2, C
+  del xi
+
   # conv1's two gradient products alone, on the step's shapes
   geom = ops.ConvGeom(HW // 2, HW // 2, C, C, 3, 3, (1, 1), ((1, 1), (1, 1)))
   x1 = (torch.rand((T * B, HW // 2, HW // 2, C), device=dev) < 0.1).to(torch.float32)
@@ -167,6 +206,9 @@ def conv_main(args):
                     "hip_train_step_ms": round(hip_ms, 3), "eager_torch_train_step_ms": round(eager_ms, 3),
                     "speedup_vs_eager": round(eager_ms / hip_ms, 2),
                     "samples_per_s": round(B / hip_ms * 1e3, 1),
+                    "step_conv_mfma_on_ms": [round(t, 3) for t in ab[True]],
+                    "step_conv_mfma_off_ms": [round(t, 3) for t in ab[False]],
+                    **{k: [round(t, 4) for t in val] for k, val in conn.items()},
                     **{k: round(val, 4) for k, val in kern.items()}}))
 
 
@@ -178,6 +220,7 @@ def main():
   ap.add_argument("--batch", type=int, default=None)
   ap.add_argument("--frames", type=int, default=20)
   ap.add_argument("--hw", type=int, default=128)
+  ap.add_argument("--reps", type=int, default=3, help="--conv: timings of each side of the A/B")
   args = ap.parse_args()
   dflt = (5, 2, 2) if args.conv else (20, 5, 256)
   args.steps = dflt[0] if args.steps is None else args.steps
