@@ -148,6 +148,24 @@ typedef struct {
                           upper 16 channels of the last 32-channel group empty (16 ceil(Cin / 16)
                           + 16 equals the padding), the upper 16 rows of that group's tiles are
                           not read (snnqp_set_conv_k16) */
+  int32_t cout_fire;   /* W_I8, the 2-channel event layer (snnqp_conv_lif_forward[_pred] on U8 / EV1 /
+                          EV4 / F32 frames, IMPL_MFMA route): the caller's assertion that the output
+                          channels cout_fire .. Cout - 1 never fire -- silent padding of a compacted
+                          block.  0 = every channel may fire; otherwise a multiple of 16 in (0, Cout],
+                          anything else is refused before a launch.  Like the BatchNorm flags it is
+                          not checked against the codes: the spike bits from cout_fire on are stored
+                          as zeros, so a wrong value loses spikes without an error.  With cout_fire
+                          + 16 == Cout and Cout a multiple of 32, a launch on bit-packed frames
+                          (EV1), pool 1 or 2, no state carried in or out, every timestep in one
+                          staging chunk, per-channel tables and the v_reset = 0 neuron with a
+                          multiplied time constant computes the last 32-channel group in a
+                          16-channel half: half the neuron updates of that group
+                          (snnqp_set_event_half_group, snnqp_conv_event_half_group).  For such a
+                          weight ch_stack_max / ch_slots must size the slot of channel cout_fire + j
+                          for max(range(cout_fire + j), range(cout_fire - 16 + j)): on the half path
+                          the slot holds the table of that twin.  The field takes the four bytes
+                          that were tail padding: the struct's size and every other offset are as
+                          before, and a caller that zeroes the struct says 0. */
 } snnqp_weight_t;
 
 /* Eval-mode BatchNorm folded on the host: y = fl(fl(fl(x - mean) * mul) + bias),
@@ -222,7 +240,9 @@ typedef struct {
  * snnqp_lif_forward_save, snnqp_lif_backward, snnqp_dense_weight_grad, snnqp_dense_input_grad;
  * 506: training of the conv blocks -- snnqp_conv_weight_grad, snnqp_conv_input_grad,
  * snnqp_conv_grad_splits, snnqp_conv_weight_grad_workspace_bytes, snnqp_maxpool2x2_backward;
- * 507: snnqp_conv_forward_ex -- currents from the bit-input MFMA conv).
+ * 507: snnqp_conv_forward_ex -- currents from the bit-input MFMA conv; within 507, layout-
+ * compatible: snnqp_weight_t.cout_fire in the struct's former tail padding,
+ * snnqp_set_event_half_group, snnqp_conv_event_half_group).
  * A binding compares snnqp_version()
  * with the SNNQP_VERSION it was written against and refuses a library of another version (_lib.py does). */
 #define SNNQP_VERSION 507
@@ -243,6 +263,17 @@ const char *snnqp_build_flags(void);
  * launches enqueued after the call; returns the previous setting.  A negative argument only
  * queries. */
 int snnqp_set_conv_k16(int enabled);
+/* The half group of the event layer (snnqp_weight_t.cout_fire).  1 (the default): a launch that
+ * meets the conditions stated there computes the last channel group in a 16-channel half.  0: it
+ * computes the whole group and cout_fire only masks the stored bits (the same results).
+ * Process-wide, for the launches enqueued after the call; returns the previous setting.  A negative
+ * argument only queries. */
+int snnqp_set_event_half_group(int enabled);
+/* 1 when snnqp_conv_lif_forward(x of `in_type`, T, g, w, nrn, pool, x_max; IMPL_AUTO / IMPL_MFMA)
+ * would run on the half-group path under the current setting, 0 when not (has_state: u0 or u_out
+ * given), a negative error for a null or malformed descriptor.  Launches nothing. */
+int snnqp_conv_event_half_group(int in_type, int32_t T, const snnqp_conv_geom_t *g, const snnqp_weight_t *w,
+                                const snnqp_neuron_t *nrn, int has_state, int pool, int x_max);
 
 int snnqp_conv_out_shape(const snnqp_conv_geom_t *g, int32_t *OH, int32_t *OW);
 

@@ -35,7 +35,7 @@ class WeightT(Structure):
   _fields_ = [("wtype", c_int32), ("w", c_void_p), ("L", c_float), ("m", c_float),
               ("abs_sum_max", c_int32), ("code_max", c_int32), ("col_sum", c_void_p),
               ("wt_fp6", c_void_p), ("min_current_bits", c_uint32), ("ch_stack_max", c_int32),
-              ("ch_slots", c_void_p), ("wt_cin", c_int32)]
+              ("ch_slots", c_void_p), ("wt_cin", c_int32), ("cout_fire", c_int32)]
 
 
 BN_MEAN_ZERO, BN_BIAS_ZERO, BN_MUL_UNIFORM = 1, 2, 4
@@ -68,6 +68,9 @@ _PROTOTYPES = {
     "snnqp_last_error": (c_char_p, []),
     "snnqp_build_flags": (c_char_p, []),
     "snnqp_set_conv_k16": (c_int, [c_int]),
+    "snnqp_set_event_half_group": (c_int, [c_int]),
+    "snnqp_conv_event_half_group": (c_int, [c_int, c_int32, POINTER(ConvGeomT), POINTER(WeightT),
+                                            POINTER(NeuronT), c_int, c_int, c_int]),
     "snnqp_conv_out_shape": (c_int, [POINTER(ConvGeomT), POINTER(c_int32),
                                      POINTER(c_int32)]),
     "snnqp_quantize": (c_int, [c_int, c_void_p, c_void_p, c_int64, c_int, c_float,

@@ -102,11 +102,23 @@ constexpr int u8c2_waves() {
   if (IN == SNNQP_EV1) return SNNQP_U8C2_EV1_WPS;
   return ONE ? SNNQP_U8C2_ONE_WPS : U8C2_WPS;
 }
-template <int NF, bool POOL, int LUTM, int IN = SNNQP_U8, bool ONE = false>
+// HALF (the half group): a launch whose weight says that the last 16 of its output
+// channels never fire (snnqp_weight_t.cout_fire + 16 == Cout, Cout a multiple of 32).  The wave of
+// the last 32 channels then computes 16 channels, and spends the lanes of the other 16 on a second
+// pixel: lane n >= 16 holds the SAME channel as lane n - 16 with its taps one halo row lower (B: zeros
+// in k 0..7, rows dy 0, 1, 2 in k 8..31), the A fragment is four halo rows Y .. Y + 3 of the patch's
+// even image rows Y = 2 ty, and column n >= 16 of the product is the channel's accumulator at the pixel
+// one image row below.  One MFMA and 16 potentials per lane cover the whole 8x8 patch: half the neuron
+// updates.  All 32 k rows carry taps, so the table address comes in as the C operand; lane n >= 16 builds
+// its twin's table (codes, BatchNorm) in its own slot.  The other waves, the staging, the barriers, the
+// flush and the queue are the full path's.
+template <int NF, bool POOL, int LUTM, int IN = SNNQP_U8, bool ONE = false, bool HALF = false>
 __global__ void __launch_bounds__(256, (u8c2_waves<NF, POOL, LUTM, IN, ONE>()))
 conv3x3_u8c2_kernel(ConvMfmaArgs a) {
   constexpr int FL = OutStage<POOL>::FL;
   constexpr bool EV1 = IN == SNNQP_EV1;
+  static_assert(!HALF || (EV1 && ONE && LUTM == LUT_CHANNEL && NF == NF_MUL0),
+                "the half group: bit-packed frames, one chunk, per-channel tables, NF_MUL0");
   constexpr bool EV4 = IN == SNNQP_EV4;     // one byte per pixel: polarity 0 low nibble, 1 high
   // float32 frames as the reference hands them over (flax_qconv.py:101): eight bytes per pixel,
   // converted to the two count bytes and checked while they wait in registers (snnqp.h, x_flags)
@@ -129,7 +141,11 @@ conv3x3_u8c2_kernel(ConvMfmaArgs a) {
   const bool wave_on = cout_base < a.Cout;
   const int cout = wave_on ? cout_base + n : n;
   const int cpar = cout < a.Cout ? cout : a.Cout - 1;      // parameter loads
-  const uint32_t cmask = chan_mask(cout_base, a.Cout);
+  // (the channels from cout_fire on are the caller's silent ones: their bits are stored as zeros)
+  const uint32_t cmask = chan_mask(cout_base, a.cout_fire);
+  // the wave of the half group (a scalar), and the channel whose codes and table this lane holds
+  const bool half_wave = HALF && cout_base + 32 == a.Cout;
+  const int ctab = half_wave && n >= 16 ? cout - 16 : cout;
   // workgroup words behind the spike-word ring:
   //   [0] smallest non-zero |input current| of this workgroup's channels (table kernels):
   //       decides whether the membrane update may be one fused multiply-add
@@ -167,7 +183,7 @@ conv3x3_u8c2_kernel(ConvMfmaArgs a) {
     for (int j = 0; j < 16; ++j) {
       const int k = 16 * h + j, dy = k >> 3, b = k & 7;
       if (k < 24 && b < 6 && wave_on && cout < a.Cout) {      // (a wave beyond Cout: one row per lane)
-        const int code = a.w[(int64_t)(6 * dy + b) * a.Cout + cout];
+        const int code = a.w[(int64_t)(6 * dy + b) * a.Cout + ctab];
         pos += code > 0 ? code : 0;
         neg += code < 0 ? -code : 0;
       }
@@ -194,8 +210,8 @@ conv3x3_u8c2_kernel(ConvMfmaArgs a) {
     // came with.  Its entries are not written (reads beyond the allocation return zeros): wrong
     // currents, reported -- the next call fails until the status is reset (snnqp.h).
     if (total > a.lut_rows && a.status) *(volatile uint32_t *)a.status = SNNQP_STATUS_BOUND;
-    const uint32_t mb = build_lut_channel((float *)(lds + lut_off), scr, a.lut_rows, a.dq, a.bn,
-                                          blockIdx.y * 128, a.Cout, tid);
+    const uint32_t mb = build_lut_channel<HALF>((float *)(lds + lut_off), scr, a.lut_rows, a.dq, a.bn,
+                                                blockIdx.y * 128, a.Cout, tid);
     atomicMin(wgw, mb);
     lds_barrier();                   // the scratch becomes the spike-word ring again
   }
@@ -210,13 +226,17 @@ conv3x3_u8c2_kernel(ConvMfmaArgs a) {
   // plain codes; the input is taken as x - 128 (a signed int8 for every count up to 255;
   // padding pixels are x = 0 like any other) and 128 * sum_k w[k] is added back to the
   // accumulator in the epilogue (an integer below 2^24: exact in float32).
+  // The half-group wave: all 32 k rows are taps (lanes n >= 16: the twin's, one halo row lower) and the
+  // address goes in as C (tab0).
   float acc_off = 0.0f;
+  int tab0 = 0;
   v4i bf, bfg;
   {
     int bias = 0;
     if (LUTM == LUT_SHARED) bias = (int)lds_addr(lds) + lut_off + 4 * a.lut_bound;
     if (LUTM == LUT_CHANNEL)     // row of acc = 0 of this lane's channel, its column
       bias = (int)lds_addr(lds) + lut_off + 4 * (ch_row0 * 32 + ch_col);
+    if (HALF) tab0 = bias;
     int q = bias / 127;
     const int r = bias - 127 * q;
     int wsum = 0;
@@ -228,7 +248,11 @@ conv3x3_u8c2_kernel(ConvMfmaArgs a) {
       for (int j = 0; j < 4; ++j) {
         const int k = 16 * h + 4 * d + j;
         uint32_t bv = 0, bg = 0;
-        if (k < 24) {
+        if (HALF && half_wave) {
+          const int kk = n >= 16 ? k - 8 : k;
+          if (kk >= 0 && kk < 24 && (kk & 7) < 6)
+            bv = (uint8_t)(a.w[(int64_t)(6 * (kk >> 3) + (kk & 7)) * a.Cout + ctab] * 8);
+        } else if (k < 24) {
           const int dy = k >> 3, b = k & 7;
           if (b < 6 && cout < a.Cout) {   // HWIO with Cin = 2: row (3 dy + dx) * 2 + cin = 6 dy + b
             const int code = a.w[(int64_t)(6 * dy + b) * a.Cout + cout];
@@ -264,16 +288,21 @@ conv3x3_u8c2_kernel(ConvMfmaArgs a) {
   // the two 8-byte reads of this lane's fragment (tile 1 is 4 halo rows further)
   const int cpy = tx & 1;
   const int px0 = (int)lds_addr(lds) + cpy * HCOPY2 + 2 * tx + 2 * cpy;
+  // (the half-group wave: halo rows Y + 2 h and, at an immediate offset, Y + 2 h + 1 of image row Y = 2 ty)
+  const int tyh = half_wave ? 2 * ty : ty;
   int offA[2], offB[2];
 #pragma unroll
   for (int tl = 0; tl < 2; ++tl) {
-    offA[tl] = px0 + (ty + 4 * tl + (h ? 2 : 0)) * HROW2;
+    offA[tl] = px0 + (tyh + 4 * tl + (h ? 2 : 0)) * HROW2;
     offB[tl] = h ? (int)lds_addr(lds) + HCONST2 : px0 + (ty + 4 * tl + 1) * HROW2;
   }
+  // (the half-group wave reads no second fragment: the register carries its table address, the C operand)
+  if (HALF && half_wave) offB[1] = tab0;
   const uint8_t *xb = (const uint8_t *)a.x;
-  const int ob0 = out_pix<POOL>(0, lane) * 4 + wave;
+  // (the half-group wave: lane = (pooled) pixel of the patch, sixteen or all sixty-four of them)
+  const int ob0 = (half_wave ? lane : out_pix<POOL>(0, lane)) * 4 + wave;
   const int ob1 = out_pix<POOL>(1, lane) * 4 + wave;
-  const bool store_lane = POOL ? lane < 8 : lane < 32;
+  const bool store_lane = POOL ? lane < (half_wave ? 16 : 8) : (half_wave || lane < 32);
   uint32_t seen = 0;                       // largest input value this thread's waves met
   // staged chunks by their largest value: <= 1, <= 2, <= 7, <= 31, above (workgroup-uniform
   // counters; they reach x_seen[1..5] once, at the end of the launch)
@@ -479,6 +508,38 @@ conv3x3_u8c2_kernel(ConvMfmaArgs a) {
       constexpr bool FMA = decltype(fma_tag)::value;
       constexpr bool OFFS = MODE == LUT_NONE;
       const v4i bw = OFFS ? bfg : bf;
+      if constexpr (HALF) {
+        // the wave of the half group, on a scalar branch: one MFMA from C = the table address, 16
+        // potentials, one word per (pooled) pixel of the patch; the barriers and the flush are the
+        // other waves'
+        if (half_wave) {
+          // (sixteen registers, made per patch: as a loop invariant they would live through the staging code)
+          int ctab0 = offB[1];
+          asm volatile("" : "+v"(ctab0));
+          const v16i c0 = splat16(ctab0);
+          for (int tf = 0; tf < nt; tf += FL) {
+            const int nf = min(FL, nt - tf);
+#pragma unroll 1
+            for (int tt = tf; tt < tf + nf; ++tt) {
+              const uint32_t img = (uint32_t)(tt * HIMG2);
+              const v2i_a4 lo = *(lds_cv2i_t *)(uintptr_t)(img + (uint32_t)offA[0]);
+              const v2i_a4 hi = *(lds_cv2i_t *)(uintptr_t)(img + (uint32_t)offA[0] + (uint32_t)HROW2);
+              const v16i acc = __builtin_amdgcn_mfma_i32_32x32x32_i8(v4i{lo.x, lo.y, hi.x, hi.y}, bw, c0,
+                                                                     0, 0, 0);
+              const uint32_t word = tile_epilogue_halves<NF, POOL, MODE, FMA, OFFS, true>(
+                  acc, u[0], a.dq, lc, a.nrn, lane, acc_off);
+              if (store_lane) {
+                uint32_t *o = obuf + ((t0 + tt) % FL) * (OutStage<POOL>::NPIX * 4);
+                o[ob0] = word & cmask;
+              }
+            }
+            lds_barrier();
+            flush_out<POOL>(obuf, a, t0 + tf, nf, b, y0, x0, tid);
+            lds_barrier();
+          }
+          return;
+        }
+      }
       for (int tf = 0; tf < nt; tf += FL) {          // FL steps, then flush
         const int nf = min(FL, nt - tf);
         // a wave beyond Cout (a launch of 32, 64 or 96 channels: a compacted block)
@@ -791,6 +852,87 @@ int conv3x3_bits_dequant_form(const snnqp_weight_t *w, const snnqp_neuron_t *nrn
   return tab ? DQ_TABLE : DQ_ARITH;
 }
 
+// What an event-layer launch is made of -- table mode, staging chunk, LDS bytes, the ONE and HALF
+// variants -- decided in one place for the launch and for snnqp_conv_event_half_group.
+namespace {
+struct U8c2Plan {
+  int32_t x_limit, lut_bound, lut_rows, tchunk;
+  bool lut, lutc, one, half;
+  size_t ldsb;
+};
+U8c2Plan u8c2_plan(int in_type, int32_t T, const snnqp_conv_geom_t *g, const snnqp_weight_t *w, int nf,
+                   bool has_state, bool pl, int x_max) {
+  U8c2Plan p;
+  // |acc| <= abs_sum_max * x_max; small enough -> dequantise through an LDS table
+  // (the A operand then carries 4 * x, which must stay an int8).  For U8 input x_max is the
+  // value the caller EXPECTS not to be exceeded (0 / unknown: binary events); the kernel
+  // checks every chunk it stages and runs the general path where the hint does not hold
+  const bool ev1 = in_type == SNNQP_EV1;
+  const int64_t xm = (in_type == SNNQP_BITS || ev1) ? 1 : (x_max > 0 ? x_max : 1);
+  p.x_limit = (int32_t)(xm > 255 ? 255 : xm);
+  const int64_t bound = (int64_t)w->abs_sum_max * xm;
+  p.lut = w->abs_sum_max > 0 && xm > 0 && xm <= LUT_XMAX && bound <= LUT_CAP;
+  p.lut_bound = p.lut ? (int32_t)bound : 0;
+  p.tchunk = T >= TCHUNK ? TCHUNK : T;
+  // images | table | spike-word ring | 4 workgroup words | EV1: byte -> 8-byte table
+  const size_t lds_fixed = (size_t)p.tchunk * HIMG2 + 16 + (ev1 ? 2048 : 0) +
+                           (pl ? OutStage<true>::BYTES : OutStage<false>::BYTES);
+  // per-channel tables (BatchNorm folded in; the accumulator counts table rows of 128 B: A = 16 x
+  // input, B = 8 x code), every channel over its own accumulator range, stacked per LDS bank
+  // (conv_tile.h build_lut_channel): ch_stack_max x the largest input + 4 rows -- 8 x abs_sum_max
+  // bounds it when the caller does not know
+  const int64_t stack = w->ch_stack_max > 0 ? (int64_t)w->ch_stack_max : 8 * (int64_t)w->abs_sum_max;
+  const int64_t crows = stack * xm + 4;
+  p.lutc = p.lut && in_type != SNNQP_BITS && crows <= LUT2_ROWS && xm <= 7 &&
+           w->code_max > 0 && w->code_max <= 15;
+  p.lut_rows = p.lutc ? (int32_t)crows : 0;
+  p.one = false;
+  p.half = false;
+  p.ldsb = 0;
+  if (in_type == SNNQP_BITS) return p;
+  const int lm = p.lutc ? LUT_CHANNEL : p.lut ? LUT_SHARED : LUT_NONE;
+  // LDS decides how many workgroups share a CU (every variant needs < 128 VGPRs: up to four
+  // waves per SIMD): stage fewer timesteps per pass rather than lose a workgroup to LDS --
+  // four per CU measured 7.1 ms on the headline shape, three 7.8, two 11.2.  Any chunk length
+  // works (the staging loops test every timestep against it), so the chunk is the largest
+  // that fits: at T = 20 all of it in ONE pass (5.35 ms against 5.57 for 16 + 4: a staging
+  // phase, a flush and three barriers fewer per patch), at T = 50 20 + 20 + 10.
+  const size_t lds_rest = lds_fixed - (size_t)p.tchunk * HIMG2 + u8c2_table_bytes(lm, p.lut_bound, p.lut_rows);
+  for (int wgs = 4; wgs >= 2; --wgs) {
+    const size_t per_wg = (size_t)(160 * 1024) / wgs - 512;
+    int tc = p.tchunk;
+    while (tc > 16 && (size_t)tc * HIMG2 + lds_rest > per_wg) tc -= 1;
+    if ((size_t)tc * HIMG2 + lds_rest <= per_wg) {
+      p.tchunk = tc;
+      break;
+    }
+  }
+  p.ldsb = (size_t)p.tchunk * HIMG2 + lds_rest;
+  // nothing carried in or out and every timestep in one chunk: the variant whose potentials start
+  // their life behind the staging code (template parameter ONE)
+  p.one = !has_state && T <= p.tchunk;
+  // ... and of those, the launch whose last 16 channels are silent by the caller's word: the last
+  // 32-channel group in a 16-channel half (template parameter HALF; snnqp_set_event_half_group)
+  p.half = event_half_group_enabled() && ev1 && p.one && p.lutc && nf == NF_MUL0 && w->cout_fire > 0 &&
+           w->cout_fire % 16 == 0 && w->cout_fire + 16 == g->Cout && g->Cout % 32 == 0;
+  return p;
+}
+}  // namespace
+
+int conv3x3_event_half_group(int in_type, int32_t T, const snnqp_conv_geom_t *g, const snnqp_weight_t *w,
+                             const snnqp_neuron_t *nrn, bool has_state, int pool, int x_max) {
+  SNNQP_REQUIRE(g && w && nrn, SNNQP_EINVAL, "conv_event_half_group: null descriptor");
+  SNNQP_REQUIRE(pool == 1 || pool == 2, SNNQP_EINVAL, "conv_event_half_group: pool must be 1 or 2");
+  SNNQP_REQUIRE(T >= 0, SNNQP_EINVAL, "conv_event_half_group: negative T");
+  if (in_type != SNNQP_EV1 || T == 0) return 0;
+  if (conv3x3_mfma_unsupported(in_type, g, w, nullptr, nrn, SNNQP_BITS)) return 0;
+  SNNQP_REQUIRE(w->L >= 1.0f, SNNQP_EINVAL, "dequant L must be >= 1");
+  SNNQP_REQUIRE(w->cout_fire == 0 || (w->cout_fire > 0 && w->cout_fire % 16 == 0 && w->cout_fire <= g->Cout),
+                SNNQP_EINVAL, "conv_event_half_group: cout_fire %d is not a multiple of 16 in (0, Cout = %d]",
+                w->cout_fire, g->Cout);
+  return u8c2_plan(in_type, T, g, w, neuron_form(make_neuron(nrn)), has_state, pool == 2, x_max).half ? 1 : 0;
+}
+
 int run_conv3x3_mfma(const void *x, int in_type, int64_t xs_t, int64_t xs_b,
                      int32_t T, int32_t B, const snnqp_conv_geom_t *g,
                      const snnqp_weight_t *w, const int8_t *wt,
@@ -809,6 +951,10 @@ int run_conv3x3_mfma(const void *x, int in_type, int64_t xs_t, int64_t xs_b,
   SNNQP_REQUIRE(T >= 0 && B >= 0, SNNQP_EINVAL, "conv3x3 mfma: negative T/B");
   SNNQP_REQUIRE(w->L >= 1.0f, SNNQP_EINVAL, "dequant L must be >= 1");
   SNNQP_CHECK_BN(bn);
+  // the caller's silent channels (snnqp.h): a malformed value is refused before anything runs
+  SNNQP_REQUIRE(w->cout_fire == 0 || (w->cout_fire > 0 && w->cout_fire % 16 == 0 && w->cout_fire <= g->Cout),
+                SNNQP_EINVAL, "conv3x3 mfma: cout_fire %d is not a multiple of 16 in (0, Cout = %d]",
+                w->cout_fire, g->Cout);
   if (T == 0 || B == 0) return SNNQP_OK;
   // the kernels keep a patch index (+ one grid stride) in a 32-bit scalar register; the
   // smallest patch is the bits kernel's 4 x 8 pixels
@@ -826,6 +972,7 @@ int run_conv3x3_mfma(const void *x, int in_type, int64_t xs_t, int64_t xs_b,
   a.x_seen = x_seen;
   a.x_flags = nullptr;
   a.pred = pred;
+  a.cout_fire = w->cout_fire > 0 ? w->cout_fire : g->Cout;
   if (in_type == SNNQP_F32) {
     SNNQP_REQUIRE(x_flags != nullptr && (((uintptr_t)x) & 7) == 0 && xs_t % 2 == 0 && xs_b % 2 == 0,
                   SNNQP_EINVAL, "conv3x3 mfma: float32 frames need x_flags and 8-byte aligned pixels");
@@ -838,29 +985,13 @@ int run_conv3x3_mfma(const void *x, int in_type, int64_t xs_t, int64_t xs_b,
   const int nf = neuron_form(a.nrn);          // which straight-line epilogue (conv_tile.h)
   const bool pl = pool == 2;
   const unsigned gy = (unsigned)((g->Cout + 127) / 128);
-  // |acc| <= abs_sum_max * x_max; small enough -> dequantise through an LDS table
-  // (the A operand then carries 4 * x, which must stay an int8).  For U8 input x_max is the
-  // value the caller EXPECTS not to be exceeded (0 / unknown: binary events); the kernel
-  // checks every chunk it stages and runs the general path where the hint does not hold
   const bool ev1 = in_type == SNNQP_EV1;
-  const int64_t xm = (in_type == SNNQP_BITS || ev1) ? 1 : (x_max > 0 ? x_max : 1);
-  a.x_limit = (int32_t)(xm > 255 ? 255 : xm);
-  const int64_t bound = (int64_t)w->abs_sum_max * xm;
-  const bool lut = w->abs_sum_max > 0 && xm > 0 && xm <= LUT_XMAX && bound <= LUT_CAP;
-  a.lut_bound = lut ? (int32_t)bound : 0;
-  a.tchunk = T >= TCHUNK ? TCHUNK : T;
-  // images | table | spike-word ring | 4 workgroup words | EV1: byte -> 8-byte table
-  const size_t lds_fixed = (size_t)a.tchunk * HIMG2 + 16 + (ev1 ? 2048 : 0) +
-                           (pl ? OutStage<true>::BYTES : OutStage<false>::BYTES);
-  // per-channel tables (BatchNorm folded in; the accumulator counts table rows of 128 B: A = 16 x
-  // input, B = 8 x code), every channel over its own accumulator range, stacked per LDS bank
-  // (conv_tile.h build_lut_channel): ch_stack_max x the largest input + 4 rows -- 8 x abs_sum_max
-  // bounds it when the caller does not know
-  const int64_t stack = w->ch_stack_max > 0 ? (int64_t)w->ch_stack_max : 8 * (int64_t)w->abs_sum_max;
-  const int64_t crows = stack * xm + 4;
-  const bool lutc = lut && in_type != SNNQP_BITS && crows <= LUT2_ROWS && xm <= 7 &&
-                    w->code_max > 0 && w->code_max <= 15;
-  a.lut_rows = lutc ? (int32_t)crows : 0;
+  const U8c2Plan plan = u8c2_plan(in_type, T, g, w, nf, u0 || u_out, pl, x_max);
+  const bool lut = plan.lut, lutc = plan.lutc;
+  a.x_limit = plan.x_limit;
+  a.lut_bound = plan.lut_bound;
+  a.tchunk = plan.tchunk;
+  a.lut_rows = plan.lut_rows;
   a.ch_slots = lutc && w->ch_stack_max > 0 ? w->ch_slots : nullptr;
 #define SNNQP_CONV_LAUNCH_IN(KERN, NFV, PL, LM, LDS)                               \
   do {                                                                             \
@@ -913,30 +1044,15 @@ int run_conv3x3_mfma(const void *x, int in_type, int64_t xs_t, int64_t xs_b,
     const int cin_walk = conv_k16_enabled() && cin16 + 16 == cin_pad ? cin16 : cin_pad;
     launch_conv3x3_bits(a, cin_walk, i8, nf, pl, dq, fma, bnf, gy, st);
   } else {
-    const int lm = lutc ? LUT_CHANNEL : lut ? LUT_SHARED : LUT_NONE;
     if (lut) check_code_bound_once(stream_device(st), (const int8_t *)w->w, (int64_t)9 * g->Cin, g->Cout,
                                    w->abs_sum_max, st);
-    // LDS decides how many workgroups share a CU (every variant needs < 128 VGPRs: up to four
-    // waves per SIMD): stage fewer timesteps per pass rather than lose a workgroup to LDS --
-    // four per CU measured 7.1 ms on the headline shape, three 7.8, two 11.2.  Any chunk length
-    // works (the staging loops test every timestep against it), so the chunk is the largest
-    // that fits: at T = 20 all of it in ONE pass (5.35 ms against 5.57 for 16 + 4: a staging
-    // phase, a flush and three barriers fewer per patch), at T = 50 20 + 20 + 10.
-    const size_t lds_rest = lds_fixed - (size_t)a.tchunk * HIMG2 + u8c2_table_bytes(lm, a.lut_bound, a.lut_rows);
-    for (int wgs = 4; wgs >= 2; --wgs) {
-      const size_t per_wg = (size_t)(160 * 1024) / wgs - 512;
-      int tc = a.tchunk;
-      while (tc > 16 && (size_t)tc * HIMG2 + lds_rest > per_wg) tc -= 1;
-      if ((size_t)tc * HIMG2 + lds_rest <= per_wg) {
-        a.tchunk = tc;
-        break;
-      }
-    }
-    const size_t ldsb = (size_t)a.tchunk * HIMG2 + lds_rest;
-    // nothing carried in or out and every timestep in one chunk: the variant whose potentials start
-    // their life behind the staging code (template parameter ONE)
-    const bool one = !a.u0 && !a.u_out && a.T <= a.tchunk;
-    if (lutc) SNNQP_CONV_LAUNCH(conv3x3_u8c2_kernel, LUT_CHANNEL, ldsb);
+    const size_t ldsb = plan.ldsb;
+    const bool one = plan.one;
+    if (plan.half && pl)
+      launch_persistent(conv3x3_u8c2_kernel<NF_MUL0, true, LUT_CHANNEL, SNNQP_EV1, true, true>, a, gy, st, ldsb);
+    else if (plan.half)
+      launch_persistent(conv3x3_u8c2_kernel<NF_MUL0, false, LUT_CHANNEL, SNNQP_EV1, true, true>, a, gy, st, ldsb);
+    else if (lutc) SNNQP_CONV_LAUNCH(conv3x3_u8c2_kernel, LUT_CHANNEL, ldsb);
     else if (lut) SNNQP_CONV_LAUNCH(conv3x3_u8c2_kernel, LUT_SHARED, ldsb);
     else SNNQP_CONV_LAUNCH(conv3x3_u8c2_kernel, LUT_NONE, ldsb);
   }

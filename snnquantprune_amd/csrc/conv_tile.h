@@ -116,6 +116,7 @@ struct ConvMfmaArgs {
   uint32_t *status;   // the device's status word (runtime.hip), or null
   int32_t patch_h;    // rows of a patch: 8 (two 4x8 tiles), or 4 (conv3x3_bits.hip, one tile)
   const int32_t *pred;  // u8c2 kernel on byte / float32 frames: (nullable) the launch runs only if *pred != 0
+  int32_t cout_fire;  // u8c2 kernel: the stored spike bits from this channel on are zeros (snnqp_weight_t; Cout: all may fire)
 };
 
 // Work queues of one launch: per blockIdx.y, one patch counter per XCD queue and one count
@@ -280,6 +281,10 @@ __device__ __forceinline__ int lut_column_start(const uint32_t *scr, int slot) {
   for (int k = 0; k < (slot & 3); ++k) st += (int)scr[(slot & ~3) + k];
   return st;
 }
+// TWIN (the half-group launch, conv3x3_u8c2.hip): the slots of the last 16 channels hold the tables
+// of the 16 channels before them -- their rows and neg_c came from the twin's codes, and so do
+// the BatchNorm constants here.
+template <bool TWIN = false>
 __device__ __forceinline__ uint32_t build_lut_channel(float *lut, const uint32_t *scr, int max_rows,
                                                       const Dequant &dq, const BnP &bn, int cout0,
                                                       int Cout, int tid) {
@@ -289,7 +294,8 @@ __device__ __forceinline__ uint32_t build_lut_channel(float *lut, const uint32_t
   const int st = lut_column_start(scr, slot);
   const int rows = (int)scr[slot], negx = (int)scr[128 + c];
   if (st + rows > max_rows) return minbits;                    // (reported by the caller)
-  const int co = cout0 + c < Cout ? cout0 + c : Cout - 1;
+  int co = cout0 + c < Cout ? cout0 + c : Cout - 1;
+  if (TWIN && cout0 + c >= Cout - 16 && cout0 + c < Cout) co -= 16;
   float bm = 0.f, bmul = 1.f, bb = 0.f;
   if (bn.mean) { bm = bn.mean[co]; bmul = bn.mul[co]; bb = bn.bias[co]; }
   for (int i = hf; i < rows; i += 2) {
@@ -458,7 +464,14 @@ __device__ __forceinline__ uint32_t tile_epilogue(const v16i &acc, float (&u)[16
 
 // The same in two halves of four pairs: eight table reads in flight instead of sixteen -- fewer
 // registers alive, for the build that buys a sixth wave per SIMD with them (conv3x3_u8c2.hip)
-template <int NF, bool POOL, int LUTM, bool FMA = false, bool OFFS = false>
+// HALFW (the half-group wave, conv3x3_u8c2.hip): lanes n and n + 16 hold ONE channel at the pixels
+// (Y, tx) and (Y + 1, tx), Y = 2 ty the even image rows of the 8x8 patch, so the 64-bit mask of
+// register i (tx = i & 7, g = i >> 3) is four 16-channel fields: image rows 4 g .. 4 g + 3.  The
+// 2x2 pool's row pair lies inside a lane half.  Returns
+//   POOL : lanes 0..15 = pooled pixel `lane` of the patch (4 x 4)
+//   !POOL: lanes 0..63 = pixel `lane` of the patch (8 x 8)
+// in bits 0..15; bits 16..31 are zero.
+template <int NF, bool POOL, int LUTM, bool FMA = false, bool OFFS = false, bool HALFW = false>
 __device__ __forceinline__ uint32_t tile_epilogue_halves(const v16i &acc, float (&u)[16],
                                                          const Dequant &dq, const LaneConsts &lc,
                                                          const NeuronP &nrn, int lane, float off = 0.0f) {
@@ -473,7 +486,18 @@ __device__ __forceinline__ uint32_t tile_epilogue_halves(const v16i &acc, float 
       const int i = 8 * g + 2 * j;
       unsigned long long m0, m1;
       neuron_pair<NF, LUTM == LUT_CHANNEL, FMA>(y[j], u[i], u[i + 1], lc, nrn, m0, m1);
-      if (POOL) {
+      if (HALFW && POOL) {
+        const unsigned long long o = m0 | m1;
+        const uint32_t lo = (uint32_t)o, hi = (uint32_t)(o >> 32);
+        myw = writelane_u32((lo | (lo >> 16)) & 0xFFFFu, 8 * g + j, myw);          // pooled row 2 g
+        myw = writelane_u32((hi | (hi >> 16)) & 0xFFFFu, 8 * g + 4 + j, myw);      // pooled row 2 g + 1
+      } else if (HALFW) {
+#pragma unroll
+        for (int r = 0; r < 4; ++r) {
+          myw = writelane_u32((uint32_t)(m0 >> (16 * r)) & 0xFFFFu, (4 * g + r) * 8 + 2 * j, myw);
+          myw = writelane_u32((uint32_t)(m1 >> (16 * r)) & 0xFFFFu, (4 * g + r) * 8 + 2 * j + 1, myw);
+        }
+      } else if (POOL) {
         const unsigned long long o = m0 | m1;
         const uint32_t pw = (uint32_t)o | (uint32_t)(o >> 32);
         myw = writelane_u32(pw, i >> 1, myw);
@@ -662,5 +686,7 @@ void launch_conv3x3_bits(const ConvMfmaArgs &a, int cin_walk, bool i8, int nf, b
                          bool fma, bool bnf, unsigned gy, hipStream_t st);
 // snnqp_set_conv_k16 (api.hip): whether run_conv3x3_mfma picks the 16-less walks
 bool conv_k16_enabled();
+// snnqp_set_event_half_group (api.hip): whether run_conv3x3_mfma picks the half-group instances
+bool event_half_group_enabled();
 
 }  // namespace snnqp

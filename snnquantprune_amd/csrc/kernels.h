@@ -30,6 +30,9 @@ int run_conv3x3_currents(const void *x, int64_t NB, const snnqp_conv_geom_t *g,
 int run_current_min(const snnqp_weight_t *w, const snnqp_bn_t *bn, int32_t bound, int32_t Cout,
                     uint32_t *out_bits, hipStream_t st);
 int conv3x3_bits_dequant_form(const snnqp_weight_t *w, const snnqp_neuron_t *nrn);
+// snnqp_conv_event_half_group: 1 / 0, or a negative error (conv3x3_u8c2.hip)
+int conv3x3_event_half_group(int in_type, int32_t T, const snnqp_conv_geom_t *g, const snnqp_weight_t *w,
+                             const snnqp_neuron_t *nrn, bool has_state, int pool, int x_max);
 int run_conv3x3_mfma(const void *x, int in_type, int64_t xs_t, int64_t xs_b,
                      int32_t T, int32_t B, const snnqp_conv_geom_t *g,
                      const snnqp_weight_t *w, const int8_t *wt,

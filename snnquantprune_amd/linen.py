@@ -177,6 +177,23 @@ def conv_k16() -> bool:
   return bool(_lib.lib().snnqp_set_conv_k16(-1))
 
 
+# The half group of the event layer: a compacted event layer whose last
+# 32-channel group holds at most 16 live channels (C3: 79 live of 96 computed) runs that group's wave
+# on 16 channels at two pixels per lane pair, half the neuron updates.  On by default.
+def set_event_half_group(enabled: bool):
+  """True (default): the event-layer kernel computes a last channel group whose upper 16 channels
+  never fire (snnqp_weight_t.cout_fire) in a 16-channel half.  False: the whole group, the silent
+  bits masked (the A side of an A/B on one build; the results are the same).  A switch of the
+  library: applies to the launches after it."""
+  from . import _lib
+  _lib.lib().snnqp_set_event_half_group(1 if enabled else 0)
+
+
+def event_half_group() -> bool:
+  from . import _lib
+  return bool(_lib.lib().snnqp_set_event_half_group(-1))
+
+
 # The connection alone over a bit-packed raster (DESIGN.md 4.3.2): the training forward of a conv
 # block (conv_train.conv_currents) and QuantConv called on its own hand ops.conv_forward the
 # MFMA-tiled codes, so a 3x3 / stride 1 / pad 1 connection with Cin <= 128 runs on the currents

@@ -383,6 +383,7 @@ class Weight:
   ch_stack_max: int = 0     # event layer: largest stacked per-channel code range (snnqp.h), 0 = unknown
   ch_slots: Optional[torch.Tensor] = None  # event layer: int32 [padded Cout] table slots (packing.table_slots)
   wt_cin: int = 0           # 3x3 conv over bits: the Cin `wt` is padded to (snnqp.h), 0 = 32 ceil(Cin / 32)
+  cout_fire: int = 0        # event layer: output channels from here on never fire (snnqp.h), 0 = all may
 
   def struct(self) -> L.WeightT:
     # (built once per object: a Weight is not modified after the pack step made it --
@@ -394,7 +395,8 @@ class Weight:
                      None if self.col_sum is None else self.col_sum.data_ptr(),
                      None if self.wt6 is None else self.wt6.data_ptr(),
                      int(self.min_current_bits), int(self.ch_stack_max),
-                     None if self.ch_slots is None else self.ch_slots.data_ptr(), int(self.wt_cin))
+                     None if self.ch_slots is None else self.ch_slots.data_ptr(), int(self.wt_cin),
+                     int(self.cout_fire))
       self.__dict__["_cstruct"] = st
     return st
 
@@ -1080,6 +1082,11 @@ def conv_lif_forward(x, geom: ConvGeom, weight: Weight, neuron: Neuron,
   if _PROFILE is not None and logical is not None:
     PROFILE_NOTES.setdefault(tag, {})["channels"] = {
         "cin": geom.Cin, "cout": geom.Cout, "live_out": int(logical[2])}
+    if weight.cout_fire and packed_out:
+      # (the bit-packed launch of binary-first byte frames is the one that can take the half path)
+      ev1 = L.EV1 if (in_type == L.EV1 or (binary_first and in_type in (L.U8, L.F32))) else in_type
+      PROFILE_NOTES[tag]["channels"]["half_group"] = conv_event_half_group(
+          ev1, T, geom, weight, neuron, state=u0 is not None or want_u, pool=pool, x_max=1 if ev1 == L.EV1 else x_max)
   # (the bit-packed variant writes bit-packed spikes only: float32 spikes take the frames as they are)
   speculate = (binary_first and packed_out and not isinstance(x, (PackedFrames, PackedSpikes))
                and in_type in (L.U8, L.F32) and geom.Cin == 2 and weight.is_int and impl != L.IMPL_GENERIC
@@ -1306,6 +1313,21 @@ def workqueue_capture_release(device, begin: int, end: int):
 
 
 DQ_FORMS = {1: "arith", 2: "one", 3: "table"}
+
+
+def conv_event_half_group(in_type: int, T: int, geom: ConvGeom, w: Weight, nrn: Neuron, state: bool = False,
+                          pool: int = 1, x_max: int = 0) -> bool:
+  """Whether snnqp_conv_lif_forward runs this event-layer launch (frame format, T, geometry, weight,
+  neuron, membrane state carried in or out, pool, input hint) on the half-group path
+  (snnqp_conv_event_half_group): the weight's cout_fire leaves the upper 16 channels of the last
+  32-channel group silent, the launch is the bit-packed single-chunk table variant, and
+  nn.set_event_half_group is on."""
+  gs, ws, ns = geom.struct(), w.struct(), nrn.struct()
+  rc = L.lib().snnqp_conv_event_half_group(int(in_type), int(T), ctypes.byref(gs), ctypes.byref(ws),
+                                           ctypes.byref(ns), 1 if state else 0, int(pool), int(x_max))
+  if rc < 0:
+    L.check(rc)
+  return rc == 1
 
 
 def conv_dequant_form(w: Weight, nrn: Neuron) -> str:

@@ -85,9 +85,23 @@ def table_slots(ranges):
   return slots, worst
 
 
-def _int_weight_of(codes: torch.Tensor, Lq: float, m: float) -> ops.Weight:
+def half_group_ranges(ranges, cout_fire: int):
+  """The table ranges of an event-layer weight whose channels from `cout_fire` on never fire
+  (snnqp.h cout_fire, cout_fire + 16 == Cout): on the half-group path the slot of padding channel
+  cout_fire + j holds the table of its twin cout_fire - 16 + j, so the slot must be tall enough for
+  either -- max(own, twin) -- and one slot table serves the launch with the path on and off."""
+  import numpy as np
+  r = np.array(ranges, np.int64)
+  cf = int(cout_fire)
+  if cf >= 16 and cf + 16 == r.size:
+    r[cf:] = np.maximum(r[cf:], r[cf - 16:cf])
+  return r
+
+
+def _int_weight_of(codes: torch.Tensor, Lq: float, m: float, cout_fire: int = 0) -> ops.Weight:
   """ops.Weight of integer codes in the kernel's layout, with the per-channel statistics the
-  kernels want."""
+  kernels want.  cout_fire: the caller's proof that the output channels from there on never fire
+  (the event layer only; 0: none)."""
   c2 = codes.reshape(-1, codes.shape[-1]).to(torch.int32)
   # inputs of the integer kernels are never negative (spikes, event counts), so an
   # accumulator lies in [-sum of |negative codes|, +sum of positive codes] * x_max: the
@@ -98,10 +112,13 @@ def _int_weight_of(codes: torch.Tensor, Lq: float, m: float) -> ops.Weight:
   col = c2.sum(0).to(torch.int32).contiguous() if codes.ndim == 2 else None
   slots, stack = None, 0
   if codes.ndim == 4 and codes.shape[2] == 2:
-    slots, stack = table_slots(c2.abs().sum(0).cpu().numpy())
+    slots, stack = table_slots(half_group_ranges(c2.abs().sum(0).cpu().numpy(), cout_fire))
     slots = torch.from_numpy(slots).to(codes.device)
+  else:
+    cout_fire = 0
   return ops.Weight(L.W_I8, codes, Lq, m, abs_sum_max=int(stats[0]),
-                    code_max=int(stats[1]), col_sum=col, ch_stack_max=stack, ch_slots=slots)
+                    code_max=int(stats[1]), col_sum=col, ch_stack_max=stack, ch_slots=slots,
+                    cout_fire=int(cout_fire))
 
 
 def conv_cin_pad(cin: int, kpack: bool = True) -> int:
@@ -141,16 +158,17 @@ class PackedKernel:
     self._int = _int_weight_of(codes, d.L, d.m)
     return self._int
 
-  def sliced(self, rows, cols) -> "PackedKernel":
+  def sliced(self, rows, cols, cout_fire: int = 0) -> "PackedKernel":
     """The integer codes restricted to input rows `rows` (conv: channels of the Cin axis; dense:
     rows of K) and output channels `cols` (int64 numpy indices, None = all), as a PackedKernel of
     their own (cached): what a compacted block launches with.  Codes are
-    elementwise in the per-tensor a, c: slicing after quantisation is exact."""
+    elementwise in the per-tensor a, c: slicing after quantisation is exact.  cout_fire: the sliced
+    channels from there on are silent padding (prune_utils.half_group_fire), 0: nothing known."""
     base = self.int_weight()
     assert base is not None, "only integer codes are sliced"
     import numpy as np
     key = ("_sliced", None if rows is None else np.asarray(rows).tobytes(),
-           None if cols is None else np.asarray(cols).tobytes())
+           None if cols is None else np.asarray(cols).tobytes(), int(cout_fire))
     pk = self._wt.get(key)
     if pk is None:
       codes = base.w
@@ -159,7 +177,7 @@ class PackedKernel:
         codes = codes.index_select(codes.ndim - 2, torch.as_tensor(np.asarray(rows), device=dev))
       if cols is not None:
         codes = codes.index_select(codes.ndim - 1, torch.as_tensor(np.asarray(cols), device=dev))
-      pk = self._wt[key] = _SlicedKernel(codes.contiguous(), self.desc, base)
+      pk = self._wt[key] = _SlicedKernel(codes.contiguous(), self.desc, base, cout_fire)
     return pk
 
   def host_codes(self):
@@ -249,7 +267,7 @@ class PackedKernel:
         wt6 = ops.pack_codes_fp6(codes, n_pad)
       w = ops.Weight(L.W_I8, codes, base.L, base.m, wt=wt, abs_sum_max=base.abs_sum_max,
                      code_max=base.code_max, col_sum=base.col_sum, wt6=wt6, ch_stack_max=base.ch_stack_max,
-                     ch_slots=base.ch_slots, wt_cin=wt_cin)
+                     ch_slots=base.ch_slots, wt_cin=wt_cin, cout_fire=base.cout_fire)
       self._wt[key] = w
     return w
 
@@ -258,9 +276,9 @@ class _SlicedKernel(PackedKernel):
   """Integer codes sliced out of another PackedKernel (PackedKernel.sliced): `kernel` holds the
   codes themselves (only its layout is read), there is no float32 form."""
 
-  def __init__(self, codes: torch.Tensor, desc, base: ops.Weight):
+  def __init__(self, codes: torch.Tensor, desc, base: ops.Weight, cout_fire: int = 0):
     super().__init__(codes, desc, None)
-    self._int = _int_weight_of(codes, base.L, base.m)
+    self._int = _int_weight_of(codes, base.L, base.m, cout_fire)
     self._int_done = True
 
   def float_weight(self):

@@ -224,6 +224,15 @@ def computed_channels(live, multiple: int = 32):
   return np.concatenate([idx, pad]).astype(np.int64)
 
 
+def half_group_fire(n_live: int, n_computed: int) -> int:
+  """snnqp_weight_t.cout_fire of a compacted event layer: computed_channels puts the
+  live channels first, so the computed channels from 16 ceil(live / 16) on are silent padding.
+  Where that leaves the upper 16 channels of the last 32-channel group silent (live mod 32 in
+  1 .. 16) the kernel computes that group in a 16-channel half; otherwise 0: nothing to say."""
+  fire = -(-int(n_live) // 16) * 16
+  return fire if 0 < fire < int(n_computed) else 0
+
+
 def _host_codes(leaf, bits):
   """DuQ codes * mask of a layer leaf on the host (round half to even of hard_tanh(w / a) * L,
   float32), and (L, m); None when the layer is not integer-coded (a == -1, bits > 8)."""

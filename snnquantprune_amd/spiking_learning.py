@@ -403,7 +403,12 @@ class SpikingBlock(nn.Module):
                                     self.norm_fn.coeffs(conn.features) if self.norm_fn is not None else None,
                                     x_bound, cmap_in)
     if rows is not None or cmap_out is not None:
-      pk = pk.sliced(rows, None if cmap_out is None else cmap_out.index)
+      fire = 0
+      if cmap_out is not None and cin == 2:
+        # the event layer: the padding channels of the last half group never fire (snnqp.h cout_fire)
+        from . import prune_utils
+        fire = prune_utils.half_group_fire(int(cmap_out.live.sum()), int(cmap_out.index.size))
+      pk = pk.sliced(rows, None if cmap_out is None else cmap_out.index, fire)
     w = None
     if integer:
       if is_dense:
