@@ -692,14 +692,47 @@ static void launch_bits_cin(const ConvMfmaArgs &a, int cin_walk, int nf, bool po
   else launch_bits_nf<FMT, 128>(a, nf, pool, dq, fma, bnf, gy, st);
 }
 
-void launch_conv3x3_bits(const ConvMfmaArgs &a0, int cin_walk, bool i8, int nf, bool pool, int dq,
-                         bool fma, bool bnf, unsigned gy, hipStream_t st) {
-  ConvMfmaArgs a = a0;                       // this kernel's patch: one tile of 4x8 pixels
-  a.patch_h = 4;
+int conv3x3_bits_dequant_form(const snnqp_weight_t *w, const snnqp_neuron_t *nrn) {
+  if (w->L == 1.0f) return DQ_ONE;
+  const bool fp6 = w->code_max > 0 && w->code_max <= 7;
+  const bool tab = fp6 && neuron_form(make_neuron(nrn)) == NF_MUL0 && w->abs_sum_max > 0 &&
+                   w->abs_sum_max <= DQT_MAXA;
+  return tab ? DQ_TABLE : DQ_ARITH;
+}
+
+// codes exact in fp6 -> f8f6f4 MFMA, wider codes -> int8 MFMA
+void launch_conv3x3_bits(ConvMfmaArgs a, const snnqp_weight_t *w, const snnqp_neuron_t *nrn, hipStream_t st) {
+  a.patch_h = 4;                             // this kernel's patch: one tile of 4x8 pixels
   a.tiles_y = (a.H + 3) / 4;
   a.npatch = (int64_t)a.B * a.tiles_y * a.tiles_x;
-  if (i8) launch_bits_cin<FMT_I8>(a, cin_walk, nf, pool, dq, fma, bnf, gy, st);
-  else launch_bits_cin<FMT_FP6>(a, cin_walk, nf, pool, dq, fma, bnf, gy, st);
+  const int nf = neuron_form(a.nrn);          // which straight-line epilogue (conv_tile.h)
+  const unsigned gy = (unsigned)((a.Cout + 127) / 128);
+  // (min_current_bits covers |acc| <= abs_sum_max, table or not)
+  const bool fma = nf == NF_MUL0 && w->min_current_bits != 0 && w->abs_sum_max > 0 &&
+                   lif_fma_is_exact(w->min_current_bits, a.nrn.k_log2, a.T, a.u0 != nullptr);
+  // dequantisation: one multiply when L == 1 (2-bit DuQ, the step quantisers), else the current
+  // is read from an LDS table at the address the accumulator spells (fp6 instruction, |acc| <=
+  // abs_sum_max <= DQT_MAXA), else the three-instruction form; BatchNorm is the multiply alone
+  // when the caller knows every mean and bias is zero
+  const bool i8 = !(w->code_max > 0 && w->code_max <= 7);
+  // (the table form rests on the matrix pipe adding float32 denormals exactly: probed once
+  // per device, runtime.hip; a device that does not gets the arithmetic form, same results)
+  const int dev = stream_device(st);
+  int dq = conv3x3_bits_dequant_form(w, nrn);
+  if (dq == DQ_TABLE && !dq_table_trusted(dev, st)) dq = DQ_ARITH;
+  const bool bnf = (a.bn.flags & (SNNQP_BN_MEAN_ZERO | SNNQP_BN_BIAS_ZERO)) ==
+                   (SNNQP_BN_MEAN_ZERO | SNNQP_BN_BIAS_ZERO);
+  if (dq == DQ_TABLE) {
+    a.lut_bound = (int32_t)w->abs_sum_max;
+    check_code_bound_once(dev, a.w, (int64_t)9 * a.Cin, a.Cout, w->abs_sum_max, st);
+  }
+  // no input channel in the upper half of the last 32-channel group (Cin mod 32 in 1 .. 16:
+  // a narrow layer, or a compacted producer whose consumer counts the live channels only):
+  // the walk that leaves that half out (snnqp_set_conv_k16(0): the walk over whole groups)
+  const int cin_pad = wt_cin_pad(w, a.Cin), cin16 = (a.Cin + 15) / 16 * 16;
+  const int cin_walk = conv_k16_enabled() && cin16 + 16 == cin_pad ? cin16 : cin_pad;
+  if (i8) launch_bits_cin<FMT_I8>(a, cin_walk, nf, a.pool == 2, dq, fma, bnf, gy, st);
+  else launch_bits_cin<FMT_FP6>(a, cin_walk, nf, a.pool == 2, dq, fma, bnf, gy, st);
 }
 
 }  // namespace snnqp

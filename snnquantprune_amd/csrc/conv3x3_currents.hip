@@ -195,15 +195,7 @@ conv3x3_currents_kernel(ConvMfmaArgs a, int32_t *acc_out) {
 template <int FMT, int WPP>
 static void launch_currents(ConvMfmaArgs a, int32_t *acc, unsigned gy, hipStream_t st) {
   const auto kernel = conv3x3_currents_kernel<FMT, WPP>;
-  int cus = 256, occ = 2;
-  persistent_limits((const void *)kernel, F6_NT, 0, stream_device(st), &cus, &occ);
-  const int64_t gmax = (int64_t)cus * occ;
-  unsigned gx = (unsigned)(a.npatch < gmax ? a.npatch : gmax);
-  a.xcd_split = 0;
-  if (gx >= 64 && a.B >= 8) {                    // whole images per XCD (launch_persistent)
-    gx &= ~7u;
-    a.xcd_split = 1;
-  }
+  const unsigned gx = persistent_grid((const void *)kernel, F6_NT, 0, stream_device(st), a.npatch, a.B, &a.xcd_split);
   hipLaunchKernelGGL(kernel, dim3(gx, gy), dim3(F6_NT), 0, st, a, acc);
 }
 
@@ -213,11 +205,6 @@ static void launch_currents_wpp(const ConvMfmaArgs &a, int wpp, int32_t *acc, un
   else if (wpp == 2) launch_currents<FMT, 2>(a, acc, gy, st);
   else if (wpp == 3) launch_currents<FMT, 3>(a, acc, gy, st);
   else launch_currents<FMT, 4>(a, acc, gy, st);
-}
-
-// the input channels `wt` is padded to: one 32-channel group per int8 tile of a tap
-static int currents_cin_pad(const snnqp_conv_geom_t *g, const snnqp_weight_t *w) {
-  return w->wt_cin ? w->wt_cin : (g->Cin + 31) / 32 * 32;
 }
 
 const char *conv3x3_currents_unsupported(int in_type, int64_t NB, const snnqp_conv_geom_t *g,
@@ -235,7 +222,7 @@ const char *conv3x3_currents_unsupported(int in_type, int64_t NB, const snnqp_co
   if (in_type != SNNQP_BITS) return "input must be bit-packed spikes";
   if (g->Cin < 1 || g->Cin > 128) return "bit input needs Cin <= 128";
   if (!wt) return "MFMA-tiled codes `wt` not given";
-  const int cin_pad = currents_cin_pad(g, w);
+  const int cin_pad = wt_cin_pad(w, g->Cin);
   if (cin_pad % 32 != 0 || cin_pad < g->Cin || cin_pad > 128)
     return "wt_cin must be a multiple of 32 in [Cin, 128]";
   // the kernel keeps a patch index (+ one grid stride) in 32 bits
@@ -268,7 +255,7 @@ int run_conv3x3_currents(const void *x, int64_t NB, const snnqp_conv_geom_t *g,
   a.tiles_y = (g->H + 3) / 4; a.tiles_x = (g->W + 7) / 8;
   a.npatch = NB * a.tiles_y * a.tiles_x;
   const unsigned gy = (unsigned)((g->Cout + 127) / 128);
-  const int wpp = currents_cin_pad(g, w) / 32;
+  const int wpp = wt_cin_pad(w, g->Cin) / 32;
   // codes exact in fp6 -> the f8f6f4 instruction; wider or unknown -> int8
   if (w->code_max > 0 && w->code_max <= 7) launch_currents_wpp<FMT_FP6>(a, wpp, acc, gy, st);
   else launch_currents_wpp<FMT_I8>(a, wpp, acc, gy, st);

@@ -1,23 +1,15 @@
 // Fused SpikingBlock for the first 3x3 / stride 1 / pad 1 QuantConv layer of the DVS128
 // topology (examples/tcja/models.py:111-147, Cin = 2 event-count frames): implicit-GEMM
 // int8 MFMA (v_mfma_i32_32x32x32_i8) + dequantisation + eval BatchNorm + neuron update +
-// optional 2x2 max-pool, with the T loop inside the kernel (conv3x3_u8c2_kernel), and
-// the host side of both fused conv kernels: what they support
-// (conv3x3_mfma_unsupported) and the dispatch (run_conv3x3_mfma) -- bit-packed inputs
-// go to conv3x3_bits.hip.
+// optional 2x2 max-pool, with the T loop inside the kernel (conv3x3_u8c2_kernel), the plan of
+// a launch (u8c2_plan) and its launcher (launch_conv3x3_u8c2).  The checks and the dispatch both
+// fused conv kernels share are in conv3x3_mfma.hip, the work queues in workqueue.hip.
 //
 // C/D layout of the MFMA: lane = output channel, register = pixel, so the per-channel
 // dequant / BatchNorm constants are per-lane registers, the membrane potentials of a
 // tile stay in 16 VGPRs for all T, and the v_cmp that thresholds a register *is* the
 // packed spike word of two pixels (64-bit lane mask); pooling is an OR of those masks.
-#include <atomic>
-#include <map>
-#include <mutex>
-#include <tuple>
 #include <type_traits>
-#include <utility>
-
-#include <vector>
 
 #include "conv_tile.h"
 
@@ -610,247 +602,8 @@ conv3x3_u8c2_kernel(ConvMfmaArgs a) {
 }
 
 // ---------------------------------------------------------------------------
-// host side
+// host side: the plan of a launch and the launcher run_conv3x3_mfma (conv3x3_mfma.hip) hands over to
 // ---------------------------------------------------------------------------
-
-// snnqp_current_min: one thread per (channel, table slice)
-__global__ void __launch_bounds__(256)
-current_min_kernel(Dequant dq, BnP bn, int bound, int Cout, uint32_t *out) {
-  const int c = blockIdx.x * 64 + (threadIdx.x & 63);
-  uint32_t mb = 0x7F800000u;
-  if (c < Cout) {
-    float mean = 0.f, mul = 1.f, bias = 0.f;
-    if (bn.mean) { mean = bn.mean[c]; mul = bn.mul[c]; bias = bn.bias[c]; }
-    for (int i = (int)(threadIdx.x >> 6) + 4 * (int)blockIdx.y - bound; i <= bound; i += 4 * (int)gridDim.y) {
-      float x = dequant_acc(i, dq) - mean;       // the epilogue's operation order
-      x = x * mul;
-      x = x + bias;
-      const uint32_t b = __float_as_uint(x) & 0x7FFFFFFFu;
-      if (b != 0 && b < mb) mb = b;
-    }
-  }
-  for (int off = 32; off > 0; off >>= 1) {
-    const uint32_t o = (uint32_t)__shfl_xor((int)mb, off);
-    mb = o < mb ? o : mb;
-  }
-  if ((threadIdx.x & 63) == 0 && mb != 0x7F800000u) atomicMin(out, mb);
-}
-
-namespace {
-struct SchedPool {
-  uint32_t *words = nullptr;
-  hipEvent_t busy[SCHED_SLOTS] = {};
-  bool has_event[SCHED_SLOTS] = {};
-  bool retired[SCHED_SLOTS] = {};      // no event could be made: never handed out again
-  unsigned next = 0;
-  unsigned next_capture = 0;           // slots SCHED_SLOTS + i: one per captured launch
-  std::vector<int> capture_log;        // capture slots in the order they were handed out
-  std::vector<int> capture_free;       // ... and the ones handed back (snnqp_workqueue_capture_release)
-};
-std::atomic<int64_t> g_static_captured{0}, g_static_busy{0};
-std::mutex g_sched_mu;
-SchedPool g_sched[64];
-
-// The pool's words and events belong to the device of the launch stream, which need not be
-// the calling thread's current device: allocate and create them with that device current.
-struct DeviceGuard {
-  int prev = -1;
-  bool ok = true;
-  explicit DeviceGuard(int dev) {
-    int cur = -1;
-    if (hipGetDevice(&cur) != hipSuccess) { (void)hipGetLastError(); ok = false; return; }
-    if (cur == dev) return;
-    if (hipSetDevice(dev) != hipSuccess) { (void)hipGetLastError(); ok = false; return; }
-    prev = cur;
-  }
-  ~DeviceGuard() {
-    if (prev >= 0 && hipSetDevice(prev) != hipSuccess) (void)hipGetLastError();
-  }
-};
-}  // namespace
-
-uint32_t *sched_acquire(hipStream_t st, int *dev_out, int *slot_out) {
-  int dev = 0;
-  hipStreamCaptureStatus cap = hipStreamCaptureStatusNone;
-  if (hipStreamIsCapturing(st, &cap) != hipSuccess) { (void)hipGetLastError(); return nullptr; }
-  const bool capturing = cap != hipStreamCaptureStatusNone;
-  hipDevice_t sdev;
-  if (hipStreamGetDevice(st, &sdev) == hipSuccess) dev = (int)sdev;
-  else if (hipGetDevice(&dev) != hipSuccess) return nullptr;
-  if (dev < 0 || dev >= 64) return nullptr;
-  std::lock_guard<std::mutex> lock(g_sched_mu);
-  SchedPool &p = g_sched[dev];
-  if (capturing) {
-    // a slot of its own, zero since the pool was allocated and zero again after every launch
-    // that walked it (conv_tile.h)
-    if (!p.words) { g_static_captured.fetch_add(1, std::memory_order_relaxed); return nullptr; }
-    int slot;
-    if (!p.capture_free.empty()) {
-      slot = p.capture_free.back();
-      p.capture_free.pop_back();
-    } else if (p.next_capture < (unsigned)SCHED_CAPTURE_SLOTS) {
-      slot = SCHED_SLOTS + (int)p.next_capture++;
-    } else {
-      g_static_captured.fetch_add(1, std::memory_order_relaxed);     // every capture slot is taken
-      return nullptr;
-    }
-    p.capture_log.push_back(slot);
-    *dev_out = dev;
-    *slot_out = slot;
-    return p.words + (size_t)slot * SCHED_WORDS;
-  }
-  if (!p.words) {
-    DeviceGuard on(dev);
-    if (!on.ok) return nullptr;
-    uint32_t *w = nullptr;
-    if (hipMalloc((void **)&w, (size_t)(SCHED_SLOTS + SCHED_CAPTURE_SLOTS) * SCHED_WORDS *
-                                   sizeof(uint32_t)) != hipSuccess) {
-      (void)hipGetLastError();
-      return nullptr;
-    }
-    // (synchronous, once per device: the capture slots rely on it)
-    if (hipMemset(w, 0, (size_t)(SCHED_SLOTS + SCHED_CAPTURE_SLOTS) * SCHED_WORDS * sizeof(uint32_t)) !=
-        hipSuccess) {
-      (void)hipGetLastError();
-      (void)hipFree(w);
-      return nullptr;
-    }
-    p.words = w;
-  }
-  const int slot = (int)(p.next++ % SCHED_SLOTS);
-  if (p.retired[slot]) return nullptr;
-  if (!p.has_event[slot]) {
-    // the event that will guard the slot exists BEFORE the slot is handed out: a slot whose
-    // launches could not be tracked would look free while one is still walking it
-    DeviceGuard on(dev);
-    if (!on.ok || hipEventCreateWithFlags(&p.busy[slot], hipEventDisableTiming) != hipSuccess) {
-      (void)hipGetLastError();
-      p.retired[slot] = true;
-      return nullptr;
-    }
-    p.has_event[slot] = true;
-  } else if (hipEventQuery(p.busy[slot]) != hipSuccess) {
-    (void)hipGetLastError();            // hipErrorNotReady: the slot's last launch is in flight
-    g_static_busy.fetch_add(1, std::memory_order_relaxed);
-    return nullptr;
-  }
-  uint32_t *words = p.words + (size_t)slot * SCHED_WORDS;
-  if (hipMemsetAsync(words, 0, SCHED_WORDS * sizeof(uint32_t), st) != hipSuccess) {
-    (void)hipGetLastError();
-    return nullptr;
-  }
-  *dev_out = dev;
-  *slot_out = slot;
-  return words;
-}
-
-void sched_release(int dev, int slot, hipStream_t st) {
-  if (slot >= SCHED_SLOTS) return;      // a captured launch's slot: never reused, nothing to track
-  std::lock_guard<std::mutex> lock(g_sched_mu);
-  SchedPool &p = g_sched[dev];
-  // (the event was created in sched_acquire).  A failed record leaves the event at its
-  // previous state -- "complete" -- while the launch runs: the slot can no longer be
-  // proven free, so it leaves the rotation.
-  if (hipEventRecord(p.busy[slot], st) != hipSuccess) {
-    (void)hipGetLastError();
-    p.retired[slot] = true;
-  }
-}
-
-int stream_device(hipStream_t st) {
-  int dev = 0;
-  hipDevice_t sdev;
-  if (hipStreamGetDevice(st, &sdev) == hipSuccess) return (int)sdev;
-  (void)hipGetLastError();
-  if (hipGetDevice(&dev) != hipSuccess) { (void)hipGetLastError(); dev = 0; }
-  return dev;
-}
-
-void persistent_limits(const void *kernel, int threads, size_t dyn_lds, int dev, int *cus_out,
-                       int *occ_out) {
-  typedef std::tuple<const void *, int, size_t, int> Key;
-  static std::mutex mu;
-  static std::map<Key, std::pair<int, int>> cache;
-  const Key key(kernel, threads, dyn_lds, dev);
-  std::lock_guard<std::mutex> lock(mu);
-  auto it = cache.find(key);
-  if (it == cache.end()) {
-    int cus = 256, occ = 1;
-    DeviceGuard on(dev);               // the occupancy query answers for the current device
-    if (hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess) {
-      (void)hipGetLastError();
-      cus = 256;
-    }
-    if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&occ, kernel, threads, dyn_lds) != hipSuccess) {
-      (void)hipGetLastError();
-      occ = 1;
-    }
-    if (occ < 1) occ = 1;
-    if (occ > 8) occ = 8;
-    it = cache.emplace(key, std::make_pair(cus, occ)).first;
-  }
-  *cus_out = it->second.first;
-  *occ_out = it->second.second;
-}
-
-int run_current_min(const snnqp_weight_t *w, const snnqp_bn_t *bn, int32_t bound, int32_t Cout,
-                    uint32_t *out_bits, hipStream_t st) {
-  SNNQP_REQUIRE(w && out_bits && Cout > 0 && bound >= 0, SNNQP_EINVAL, "current_min: bad argument");
-  SNNQP_REQUIRE(w->L >= 1.0f, SNNQP_EINVAL, "dequant L must be >= 1");
-  SNNQP_CHECK_BN(bn);
-  const int slices = bound >= 256 ? 16 : 1;
-  hipLaunchKernelGGL(current_min_kernel, dim3((Cout + 63) / 64, slices), dim3(256), 0, st,
-                     make_dequant(w->L, w->m), make_bn(bn), bound, Cout, out_bits);
-  SNNQP_CHECK_LAUNCH("current_min_kernel");
-  return SNNQP_OK;
-}
-
-const char *conv3x3_mfma_unsupported(int in_type, const snnqp_conv_geom_t *g,
-                                     const snnqp_weight_t *w, const int8_t *wt,
-                                     const snnqp_neuron_t *nrn, int s_type) {
-  if (w->wtype != SNNQP_W_I8) return "weights are not int8 codes";
-  if (g->KH != 3 || g->KW != 3) return "kernel is not 3x3";
-  if (g->stride_h != 1 || g->stride_w != 1) return "stride is not 1";
-  if (g->pad_h_lo != 1 || g->pad_h_hi != 1 || g->pad_w_lo != 1 || g->pad_w_hi != 1)
-    return "padding is not ((1,1),(1,1))";
-  if (g->in_dil_h != 1 || g->in_dil_w != 1 || g->k_dil_h != 1 || g->k_dil_w != 1)
-    return "dilated convolution";
-  if (g->groups != 1) return "grouped convolution";
-  if (g->H <= 0 || g->W <= 0) return "empty image";    // any size: edge patches are clipped
-  if (g->Cout <= 0) return "no output channels";    // any count: the last word is masked
-  if (s_type != SNNQP_BITS) return "spike output must be bit-packed";
-  if (in_type == SNNQP_BITS) {
-    // any width up to 128: `wt` is tiled from the kernel zero-padded along Cin to
-    // 32 ceil(Cin / 32) (or wt_cin); the spike words beyond ceil(Cin / 32) are not read
-    if (g->Cin < 1 || g->Cin > 128) return "bit input needs Cin <= 128";
-  } else if (in_type == SNNQP_U8) {     // any count 0..255 (taken as x - 128 without a table)
-    if (g->Cin != 2) return "u8 input needs Cin == 2";
-    if ((int64_t)g->H * g->W * 2 >= (int64_t)1 << 31) return "u8 frame of 2 GiB or more";
-  } else if (in_type == SNNQP_EV1) {    // bit-packed binary event frames, staged directly
-    if (g->Cin != 2) return "EV1 frames have Cin == 2";
-    if ((int64_t)g->H * g->W * 2 >= (int64_t)1 << 31) return "EV1 frame of 2^31 bits or more";
-  } else if (in_type == SNNQP_EV4) {    // nibble-packed count frames (<= 15), staged directly
-    if (g->Cin != 2) return "EV4 frames have Cin == 2";
-    if ((int64_t)g->H * g->W >= (int64_t)1 << 31) return "EV4 frame of 2 GiB or more";
-  } else if (in_type == SNNQP_F32) {    // integer-valued float32 frames, staged in place and checked
-    if (g->Cin != 2) return "float32 input into integer codes needs Cin == 2";
-    if ((int64_t)g->H * g->W * 8 >= (int64_t)1 << 31) return "float32 frame of 2 GiB or more";
-  } else {
-    return "input must be BITS, U8, EV1, EV4 or (Cin == 2) F32";
-  }
-  if (nrn->kind == SNNQP_NEURON_LIF && !nrn->decay) return "LIF without decay";
-  if (in_type == SNNQP_BITS && !wt) return "MFMA-tiled codes `wt` not given";
-  return nullptr;
-}
-
-// DQ_ONE / DQ_TABLE / DQ_ARITH (conv_tile.h) for a bit-input block on these weights
-int conv3x3_bits_dequant_form(const snnqp_weight_t *w, const snnqp_neuron_t *nrn) {
-  if (w->L == 1.0f) return DQ_ONE;
-  const bool fp6 = w->code_max > 0 && w->code_max <= 7;
-  const bool tab = fp6 && neuron_form(make_neuron(nrn)) == NF_MUL0 && w->abs_sum_max > 0 &&
-                   w->abs_sum_max <= DQT_MAXA;
-  return tab ? DQ_TABLE : DQ_ARITH;
-}
 
 // What an event-layer launch is made of -- table mode, staging chunk, LDS bytes, the ONE and HALF
 // variants -- decided in one place for the launch and for snnqp_conv_event_half_group.
@@ -860,15 +613,15 @@ struct U8c2Plan {
   bool lut, lutc, one, half;
   size_t ldsb;
 };
-U8c2Plan u8c2_plan(int in_type, int32_t T, const snnqp_conv_geom_t *g, const snnqp_weight_t *w, int nf,
-                   bool has_state, bool pl, int x_max) {
+U8c2Plan u8c2_plan(int in_type, int32_t T, int32_t Cout, const snnqp_weight_t *w, int nf, bool has_state,
+                   bool pl, int x_max) {
   U8c2Plan p;
   // |acc| <= abs_sum_max * x_max; small enough -> dequantise through an LDS table
   // (the A operand then carries 4 * x, which must stay an int8).  For U8 input x_max is the
   // value the caller EXPECTS not to be exceeded (0 / unknown: binary events); the kernel
   // checks every chunk it stages and runs the general path where the hint does not hold
   const bool ev1 = in_type == SNNQP_EV1;
-  const int64_t xm = (in_type == SNNQP_BITS || ev1) ? 1 : (x_max > 0 ? x_max : 1);
+  const int64_t xm = ev1 ? 1 : (x_max > 0 ? x_max : 1);
   p.x_limit = (int32_t)(xm > 255 ? 255 : xm);
   const int64_t bound = (int64_t)w->abs_sum_max * xm;
   p.lut = w->abs_sum_max > 0 && xm > 0 && xm <= LUT_XMAX && bound <= LUT_CAP;
@@ -883,13 +636,8 @@ U8c2Plan u8c2_plan(int in_type, int32_t T, const snnqp_conv_geom_t *g, const snn
   // bounds it when the caller does not know
   const int64_t stack = w->ch_stack_max > 0 ? (int64_t)w->ch_stack_max : 8 * (int64_t)w->abs_sum_max;
   const int64_t crows = stack * xm + 4;
-  p.lutc = p.lut && in_type != SNNQP_BITS && crows <= LUT2_ROWS && xm <= 7 &&
-           w->code_max > 0 && w->code_max <= 15;
+  p.lutc = p.lut && crows <= LUT2_ROWS && xm <= 7 && w->code_max > 0 && w->code_max <= 15;
   p.lut_rows = p.lutc ? (int32_t)crows : 0;
-  p.one = false;
-  p.half = false;
-  p.ldsb = 0;
-  if (in_type == SNNQP_BITS) return p;
   const int lm = p.lutc ? LUT_CHANNEL : p.lut ? LUT_SHARED : LUT_NONE;
   // LDS decides how many workgroups share a CU (every variant needs < 128 VGPRs: up to four
   // waves per SIMD): stage fewer timesteps per pass rather than lose a workgroup to LDS --
@@ -914,7 +662,7 @@ U8c2Plan u8c2_plan(int in_type, int32_t T, const snnqp_conv_geom_t *g, const snn
   // ... and of those, the launch whose last 16 channels are silent by the caller's word: the last
   // 32-channel group in a 16-channel half (template parameter HALF; snnqp_set_event_half_group)
   p.half = event_half_group_enabled() && ev1 && p.one && p.lutc && nf == NF_MUL0 && w->cout_fire > 0 &&
-           w->cout_fire % 16 == 0 && w->cout_fire + 16 == g->Cout && g->Cout % 32 == 0;
+           w->cout_fire % 16 == 0 && w->cout_fire + 16 == Cout && Cout % 32 == 0;
   return p;
 }
 }  // namespace
@@ -926,189 +674,69 @@ int conv3x3_event_half_group(int in_type, int32_t T, const snnqp_conv_geom_t *g,
   SNNQP_REQUIRE(T >= 0, SNNQP_EINVAL, "conv_event_half_group: negative T");
   if (in_type != SNNQP_EV1 || T == 0) return 0;
   if (conv3x3_mfma_unsupported(in_type, g, w, nullptr, nrn, SNNQP_BITS)) return 0;
-  SNNQP_REQUIRE(w->L >= 1.0f, SNNQP_EINVAL, "dequant L must be >= 1");
-  SNNQP_REQUIRE(w->cout_fire == 0 || (w->cout_fire > 0 && w->cout_fire % 16 == 0 && w->cout_fire <= g->Cout),
-                SNNQP_EINVAL, "conv_event_half_group: cout_fire %d is not a multiple of 16 in (0, Cout = %d]",
-                w->cout_fire, g->Cout);
-  return u8c2_plan(in_type, T, g, w, neuron_form(make_neuron(nrn)), has_state, pool == 2, x_max).half ? 1 : 0;
+  if (int rc = conv3x3_check_weight("conv_event_half_group", w, nullptr, g->Cout)) return rc;
+  return u8c2_plan(in_type, T, g->Cout, w, neuron_form(make_neuron(nrn)), has_state, pool == 2, x_max).half ? 1 : 0;
 }
 
-int run_conv3x3_mfma(const void *x, int in_type, int64_t xs_t, int64_t xs_b,
-                     int32_t T, int32_t B, const snnqp_conv_geom_t *g,
-                     const snnqp_weight_t *w, const int8_t *wt,
-                     const snnqp_bn_t *bn, const snnqp_neuron_t *nrn,
-                     const float *u0, float *u_out, uint32_t *s_out, int pool,
-                     int x_max, int32_t *x_seen, int32_t *x_flags, hipStream_t st, const int32_t *pred) {
-  SNNQP_REQUIRE(w->w && ((x && s_out) || T == 0 || B == 0), SNNQP_EINVAL, "conv3x3 mfma: null pointer");
-  SNNQP_REQUIRE(!pred || in_type == SNNQP_U8 || in_type == SNNQP_F32 || in_type == SNNQP_EV4, SNNQP_EUNSUPPORTED,
-                "conv3x3 mfma: only the event layer on byte / nibble / float32 frames takes a predicate");   // (an empty batch has no buffers)
-  SNNQP_REQUIRE(in_type != SNNQP_BITS || wt, SNNQP_EINVAL,
-                "conv3x3 mfma: bit input needs the MFMA-tiled codes `wt`");
-  // the input channels `wt` is padded to: one 32-channel group per int8 tile of a tap
-  const int cin_pad = w->wt_cin ? w->wt_cin : (g->Cin + 31) / 32 * 32;
-  SNNQP_REQUIRE(in_type != SNNQP_BITS || (cin_pad % 32 == 0 && cin_pad >= g->Cin && cin_pad <= 128),
-                SNNQP_EINVAL, "conv3x3 mfma: wt_cin must be a multiple of 32 in [Cin, 128]");
-  SNNQP_REQUIRE(T >= 0 && B >= 0, SNNQP_EINVAL, "conv3x3 mfma: negative T/B");
-  SNNQP_REQUIRE(w->L >= 1.0f, SNNQP_EINVAL, "dequant L must be >= 1");
-  SNNQP_CHECK_BN(bn);
-  // the caller's silent channels (snnqp.h): a malformed value is refused before anything runs
-  SNNQP_REQUIRE(w->cout_fire == 0 || (w->cout_fire > 0 && w->cout_fire % 16 == 0 && w->cout_fire <= g->Cout),
-                SNNQP_EINVAL, "conv3x3 mfma: cout_fire %d is not a multiple of 16 in (0, Cout = %d]",
-                w->cout_fire, g->Cout);
-  if (T == 0 || B == 0) return SNNQP_OK;
-  // the kernels keep a patch index (+ one grid stride) in a 32-bit scalar register; the
-  // smallest patch is the bits kernel's 4 x 8 pixels
-  SNNQP_REQUIRE((int64_t)B * ((g->H + 3) / 4) * ((g->W + 7) / 8) < ((int64_t)1 << 30),
-                SNNQP_EUNSUPPORTED, "conv3x3 mfma: more than 2^30 patches in one launch");
-  ConvMfmaArgs a;
-  a.x = x; a.xs_t = xs_t; a.xs_b = xs_b; a.T = T; a.B = B;
-  a.H = g->H; a.W = g->W; a.Cin = g->Cin; a.Cout = g->Cout;
-  a.w = (const int8_t *)w->w;
-  a.wt = wt;
-  a.dq = make_dequant(w->L, w->m);
-  a.bn = make_bn(bn);
-  a.nrn = make_neuron(nrn);
-  a.u0 = u0; a.u_out = u_out; a.s_out = s_out; a.pool = pool;
-  a.x_seen = x_seen;
-  a.x_flags = nullptr;
-  a.pred = pred;
-  a.cout_fire = w->cout_fire > 0 ? w->cout_fire : g->Cout;
-  if (in_type == SNNQP_F32) {
-    SNNQP_REQUIRE(x_flags != nullptr && (((uintptr_t)x) & 7) == 0 && xs_t % 2 == 0 && xs_b % 2 == 0,
-                  SNNQP_EINVAL, "conv3x3 mfma: float32 frames need x_flags and 8-byte aligned pixels");
-    if (int rc = zero_words_async((uint32_t *)x_flags, 1, st)) return rc;
-    a.x_flags = x_flags;
-  }
-  a.patch_h = 8;
-  a.tiles_y = (g->H + 7) / 8; a.tiles_x = (g->W + 7) / 8;
-  a.npatch = (int64_t)B * a.tiles_y * a.tiles_x;
+// The instance of a launch, one template parameter per step: table mode (launch_conv3x3_u8c2), neuron
+// form, input format, then pool and ONE.
+template <int NF, int LUTM, int IN>
+static void launch_u8c2_pool(const ConvMfmaArgs &a, bool pool, bool one, unsigned gy, hipStream_t st, size_t lds) {
+  if (pool && one) launch_persistent(conv3x3_u8c2_kernel<NF, true, LUTM, IN, true>, a, gy, st, lds);
+  else if (pool) launch_persistent(conv3x3_u8c2_kernel<NF, true, LUTM, IN>, a, gy, st, lds);
+  else if (one) launch_persistent(conv3x3_u8c2_kernel<NF, false, LUTM, IN, true>, a, gy, st, lds);
+  else launch_persistent(conv3x3_u8c2_kernel<NF, false, LUTM, IN>, a, gy, st, lds);
+}
+
+template <int NF, int LUTM>
+static void launch_u8c2_in(const ConvMfmaArgs &a, int in_type, bool pool, bool one, unsigned gy, hipStream_t st,
+                           size_t lds) {
+  if (in_type == SNNQP_EV1) launch_u8c2_pool<NF, LUTM, SNNQP_EV1>(a, pool, one, gy, st, lds);
+  else if (in_type == SNNQP_EV4) launch_u8c2_pool<NF, LUTM, SNNQP_EV4>(a, pool, one, gy, st, lds);
+  else if (in_type == SNNQP_F32) launch_u8c2_pool<NF, LUTM, SNNQP_F32>(a, pool, one, gy, st, lds);
+  else launch_u8c2_pool<NF, LUTM, SNNQP_U8>(a, pool, one, gy, st, lds);
+}
+
+template <int LUTM>
+static void launch_u8c2_nf(const ConvMfmaArgs &a, int nf, int in_type, bool pool, bool one, unsigned gy,
+                           hipStream_t st, size_t lds) {
+  if (nf == NF_MUL0) launch_u8c2_in<NF_MUL0, LUTM>(a, in_type, pool, one, gy, st, lds);
+  else if (nf == NF_MUL) launch_u8c2_in<NF_MUL, LUTM>(a, in_type, pool, one, gy, st, lds);
+  else if (nf == NF_DIV) launch_u8c2_in<NF_DIV, LUTM>(a, in_type, pool, one, gy, st, lds);
+  else launch_u8c2_in<NF_DECAY, LUTM>(a, in_type, pool, one, gy, st, lds);
+}
+
+int launch_conv3x3_u8c2(ConvMfmaArgs a, int in_type, const snnqp_weight_t *w, int x_max, int32_t *x_flags,
+                        hipStream_t st) {
+  a.patch_h = 8;                             // this kernel's patch: two tiles of 4x8 pixels
+  a.tiles_y = (a.H + 7) / 8;
+  a.npatch = (int64_t)a.B * a.tiles_y * a.tiles_x;
   const int nf = neuron_form(a.nrn);          // which straight-line epilogue (conv_tile.h)
-  const bool pl = pool == 2;
-  const unsigned gy = (unsigned)((g->Cout + 127) / 128);
-  const bool ev1 = in_type == SNNQP_EV1;
-  const U8c2Plan plan = u8c2_plan(in_type, T, g, w, nf, u0 || u_out, pl, x_max);
-  const bool lut = plan.lut, lutc = plan.lutc;
+  const bool pl = a.pool == 2;
+  const unsigned gy = (unsigned)((a.Cout + 127) / 128);
+  const U8c2Plan plan = u8c2_plan(in_type, a.T, a.Cout, w, nf, a.u0 || a.u_out, pl, x_max);
   a.x_limit = plan.x_limit;
   a.lut_bound = plan.lut_bound;
   a.tchunk = plan.tchunk;
   a.lut_rows = plan.lut_rows;
-  a.ch_slots = lutc && w->ch_stack_max > 0 ? w->ch_slots : nullptr;
-#define SNNQP_CONV_LAUNCH_IN(KERN, NFV, PL, LM, LDS)                               \
-  do {                                                                             \
-    if (ev1 && one) launch_persistent(KERN<NFV, PL, LM, SNNQP_EV1, true>, a, gy, st, LDS); \
-    else if (ev1) launch_persistent(KERN<NFV, PL, LM, SNNQP_EV1>, a, gy, st, LDS);       \
-    else if (in_type == SNNQP_EV4 && one) launch_persistent(KERN<NFV, PL, LM, SNNQP_EV4, true>, a, gy, st, LDS); \
-    else if (in_type == SNNQP_EV4) launch_persistent(KERN<NFV, PL, LM, SNNQP_EV4>, a, gy, st, LDS); \
-    else if (in_type == SNNQP_F32 && one) launch_persistent(KERN<NFV, PL, LM, SNNQP_F32, true>, a, gy, st, LDS); \
-    else if (in_type == SNNQP_F32) launch_persistent(KERN<NFV, PL, LM, SNNQP_F32>, a, gy, st, LDS); \
-    else if (one) launch_persistent(KERN<NFV, PL, LM, SNNQP_U8, true>, a, gy, st, LDS);            \
-    else launch_persistent(KERN<NFV, PL, LM, SNNQP_U8>, a, gy, st, LDS);            \
-  } while (0)
-#define SNNQP_CONV_LAUNCH_NF(KERN, NFV, LM, LDS)                                   \
-  do {                                                                             \
-    if (pl) SNNQP_CONV_LAUNCH_IN(KERN, NFV, true, LM, LDS);                         \
-    else SNNQP_CONV_LAUNCH_IN(KERN, NFV, false, LM, LDS);                           \
-  } while (0)
-#define SNNQP_CONV_LAUNCH(KERN, LM, LDS)                                           \
-  do {                                                                             \
-    if (nf == NF_MUL0) SNNQP_CONV_LAUNCH_NF(KERN, NF_MUL0, LM, LDS);                \
-    else if (nf == NF_MUL) SNNQP_CONV_LAUNCH_NF(KERN, NF_MUL, LM, LDS);             \
-    else if (nf == NF_DIV) SNNQP_CONV_LAUNCH_NF(KERN, NF_DIV, LM, LDS);             \
-    else SNNQP_CONV_LAUNCH_NF(KERN, NF_DECAY, LM, LDS);                             \
-  } while (0)
-  if (in_type == SNNQP_BITS) {
-    // conv3x3_bits.hip: codes exact in fp6 -> f8f6f4 MFMA, wider codes -> int8 MFMA
-    // (min_current_bits covers |acc| <= abs_sum_max, table or not)
-    const bool fma = nf == NF_MUL0 && w->min_current_bits != 0 && w->abs_sum_max > 0 &&
-                     lif_fma_is_exact(w->min_current_bits, a.nrn.k_log2, T, u0 != nullptr);
-    // dequantisation of the bits kernel: one multiply when L == 1 (2-bit DuQ, the step
-    // quantisers), else the current is read from an LDS table at the address the accumulator
-    // spells (fp6 instruction, |acc| <= abs_sum_max <= DQT_MAXA; conv3x3_bits.hip), else the
-    // three-instruction form; BatchNorm is the multiply alone when the caller knows every mean
-    // and bias is zero
-    const bool i8 = !(w->code_max > 0 && w->code_max <= 7);
-    // (the table form rests on the matrix pipe adding float32 denormals exactly: probed once
-    // per device, runtime.hip; a device that does not gets the arithmetic form, same results)
-    int dq = conv3x3_bits_dequant_form(w, nrn);
-    if (dq == DQ_TABLE && !dq_table_trusted(stream_device(st), st)) dq = DQ_ARITH;
-    const bool tab = dq == DQ_TABLE;
-    const bool bnf = (a.bn.flags & (SNNQP_BN_MEAN_ZERO | SNNQP_BN_BIAS_ZERO)) ==
-                     (SNNQP_BN_MEAN_ZERO | SNNQP_BN_BIAS_ZERO);
-    a.lut_bound = tab ? (int32_t)w->abs_sum_max : 0;
-    if (tab) check_code_bound_once(stream_device(st), (const int8_t *)w->w, (int64_t)9 * g->Cin, g->Cout,
-                                   w->abs_sum_max, st);
-    // no input channel in the upper half of the last 32-channel group (Cin mod 32 in 1 .. 16:
-    // a narrow layer, or a compacted producer whose consumer counts the live channels only):
-    // the walk that leaves that half out (snnqp_set_conv_k16(0): the walk over whole groups)
-    const int cin16 = (g->Cin + 15) / 16 * 16;
-    const int cin_walk = conv_k16_enabled() && cin16 + 16 == cin_pad ? cin16 : cin_pad;
-    launch_conv3x3_bits(a, cin_walk, i8, nf, pl, dq, fma, bnf, gy, st);
-  } else {
-    if (lut) check_code_bound_once(stream_device(st), (const int8_t *)w->w, (int64_t)9 * g->Cin, g->Cout,
-                                   w->abs_sum_max, st);
-    const size_t ldsb = plan.ldsb;
-    const bool one = plan.one;
-    if (plan.half && pl)
-      launch_persistent(conv3x3_u8c2_kernel<NF_MUL0, true, LUT_CHANNEL, SNNQP_EV1, true, true>, a, gy, st, ldsb);
-    else if (plan.half)
-      launch_persistent(conv3x3_u8c2_kernel<NF_MUL0, false, LUT_CHANNEL, SNNQP_EV1, true, true>, a, gy, st, ldsb);
-    else if (lutc) SNNQP_CONV_LAUNCH(conv3x3_u8c2_kernel, LUT_CHANNEL, ldsb);
-    else if (lut) SNNQP_CONV_LAUNCH(conv3x3_u8c2_kernel, LUT_SHARED, ldsb);
-    else SNNQP_CONV_LAUNCH(conv3x3_u8c2_kernel, LUT_NONE, ldsb);
+  a.ch_slots = plan.lutc && w->ch_stack_max > 0 ? w->ch_slots : nullptr;
+  a.cout_fire = w->cout_fire > 0 ? w->cout_fire : a.Cout;
+  // (the last check: nothing may be launched before a launch that is refused)
+  if (in_type == SNNQP_F32) {
+    SNNQP_REQUIRE(x_flags != nullptr && (((uintptr_t)a.x) & 7) == 0 && a.xs_t % 2 == 0 && a.xs_b % 2 == 0,
+                  SNNQP_EINVAL, "conv3x3 mfma: float32 frames need x_flags and 8-byte aligned pixels");
+    if (int rc = zero_words_async((uint32_t *)x_flags, 1, st)) return rc;
+    a.x_flags = x_flags;
   }
-#undef SNNQP_CONV_LAUNCH
-#undef SNNQP_CONV_LAUNCH_NF
-#undef SNNQP_CONV_LAUNCH_IN
-  SNNQP_CHECK_LAUNCH("conv3x3 mfma kernel");
+  if (plan.lut) check_code_bound_once(stream_device(st), a.w, (int64_t)9 * a.Cin, a.Cout, w->abs_sum_max, st);
+  if (plan.half && pl)
+    launch_persistent(conv3x3_u8c2_kernel<NF_MUL0, true, LUT_CHANNEL, SNNQP_EV1, true, true>, a, gy, st, plan.ldsb);
+  else if (plan.half)
+    launch_persistent(conv3x3_u8c2_kernel<NF_MUL0, false, LUT_CHANNEL, SNNQP_EV1, true, true>, a, gy, st, plan.ldsb);
+  else if (plan.lutc) launch_u8c2_nf<LUT_CHANNEL>(a, nf, in_type, pl, plan.one, gy, st, plan.ldsb);
+  else if (plan.lut) launch_u8c2_nf<LUT_SHARED>(a, nf, in_type, pl, plan.one, gy, st, plan.ldsb);
+  else launch_u8c2_nf<LUT_NONE>(a, nf, in_type, pl, plan.one, gy, st, plan.ldsb);
   return SNNQP_OK;
 }
 
 }  // namespace snnqp
-
-// ---- work-queue bookkeeping visible to the binding -----------------------------------------
-extern "C" int snnqp_workqueue_capture_mark(int device, int64_t *mark) {
-  using namespace snnqp;
-  SNNQP_REQUIRE(device >= 0 && device < 64 && mark, SNNQP_EINVAL, "workqueue_capture_mark: bad argument");
-  std::lock_guard<std::mutex> lock(g_sched_mu);
-  *mark = (int64_t)g_sched[device].capture_log.size();
-  return SNNQP_OK;
-}
-
-extern "C" int snnqp_workqueue_capture_release(int device, int64_t mark_begin, int64_t mark_end) {
-  using namespace snnqp;
-  SNNQP_REQUIRE(device >= 0 && device < 64, SNNQP_EINVAL, "workqueue_capture_release: bad device");
-  std::lock_guard<std::mutex> lock(g_sched_mu);
-  SchedPool &p = g_sched[device];
-  SNNQP_REQUIRE(0 <= mark_begin && mark_begin <= mark_end && mark_end <= (int64_t)p.capture_log.size(),
-                SNNQP_EINVAL, "workqueue_capture_release: marks out of range");
-  for (int64_t i = mark_begin; i < mark_end; ++i) {
-    const int slot = p.capture_log[(size_t)i];
-    if (slot < 0) continue;                        // handed back already
-    p.capture_free.push_back(slot);
-    p.capture_log[(size_t)i] = -1;
-  }
-  return SNNQP_OK;
-}
-
-extern "C" int snnqp_workqueue_stats(int64_t *captured_static, int64_t *busy_static,
-                                     int64_t *dequant_fallbacks, int reset) {
-  using namespace snnqp;
-  if (captured_static) *captured_static = g_static_captured.load(std::memory_order_relaxed);
-  if (busy_static) *busy_static = g_static_busy.load(std::memory_order_relaxed);
-  if (dequant_fallbacks) *dequant_fallbacks = dq_table_fallbacks(reset != 0);
-  if (reset) { g_static_captured = 0; g_static_busy = 0; }
-  return SNNQP_OK;
-}
-
-extern "C" int snnqp_debug_workqueue_poke(int device, int64_t mark, int word, uint32_t value) {
-  using namespace snnqp;
-  SNNQP_REQUIRE(device >= 0 && device < 64 && word >= 0 && word < SCHED_WORDS, SNNQP_EINVAL,
-                "debug_workqueue_poke: bad argument");
-  std::lock_guard<std::mutex> lock(g_sched_mu);
-  SchedPool &p = g_sched[device];
-  SNNQP_REQUIRE(p.words && mark >= 0 && mark < (int64_t)p.capture_log.size() && p.capture_log[(size_t)mark] >= 0,
-                SNNQP_EINVAL, "debug_workqueue_poke: no live capture slot at mark %lld", (long long)mark);
-  SNNQP_HIP(hipMemcpy(p.words + (size_t)p.capture_log[(size_t)mark] * SCHED_WORDS + word, &value, 4,
-                      hipMemcpyHostToDevice));
-  return SNNQP_OK;
-}

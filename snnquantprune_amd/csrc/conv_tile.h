@@ -612,81 +612,47 @@ __device__ __forceinline__ v16i splat16(int v) {
   return v16i{v, v, v, v, v, v, v, v, v, v, v, v, v, v, v, v};
 }
 
-// Work-queue words for a launch: a per-device pool of SCHED_SLOTS slots handed out round-robin,
-// allocated once per device and kept for the life of the process.  A slot is self-validating:
-//  * it is zeroed on the launch's stream right before the launch (so whatever an earlier,
-//    possibly aborted, launch left in it cannot be walked), and
-//  * an event recorded after the launch marks it busy: when the round-robin pointer comes
-//    back to a slot whose last launch has not completed (more than SCHED_SLOTS launches in
-//    flight across streams / threads), the launch takes the static walk instead (sched =
-//    nullptr), which is always correct, only less well balanced (C3 under a graph without
-//    queues: 13.6 ms against 12.3).
-// A launch that is being CAPTURED into a graph (events cannot be queried there) gets a slot of
-// its own out of SCHED_CAPTURE_SLOTS further ones, handed back when the caller says the graph is
-// gone (snnqp_workqueue_capture_release; linen.CapturedApply does).  Nothing is added to
-// the graph for it: the pool is zeroed when it is allocated, the last workgroup of every launch
-// leaves the slot's words zero again (PatchWalk::finish), and a graph does not run concurrently
-// with itself -- every replay finds zeroed words.  (A memset node in front of the kernel node,
-// the obvious way, aborted on the replay of the second graph captured in a process in round 3,
-// and in round 5 a memset node in front of the dense hand-over never reached its target in the
-// second graph a framework captured -- profiles/r05_capture_memset.txt; round 6 walked the nodes
-// (profiles/r06_capture_memset_nodes.txt): the node is there and correctly addressed, the runtime's
-// replay of it writes another memset node's fill-kernel arguments instead of zeros.  The library
-// records no memset node: kernels zero.)  A word that is NOT zero at a replay makes workgroups skip
-// patches: finish() tallies the patches and reports a mismatch through the device's status word
-// (runtime.hip).  The pool must
-// exist by then -- nothing may be allocated during a capture: one eager launch on the device,
-// the usual warm-up.  With all 960 capture slots taken, or without the pool, a captured launch
-// takes the static walk (counted: snnqp_workqueue_stats).
-// sched_acquire returns the slot's words (or nullptr) and its index; sched_release records
-// the event.  The device comes from the stream, not from the calling thread's current device.
-uint32_t *sched_acquire(hipStream_t st, int *dev, int *slot);
+// Work-queue words of one launch on `dev`, the device of `st` (the pool: workqueue.hip): the slot's
+// words and its index, or nullptr -- the launch then takes the static walk.  sched_release records
+// the event that marks the slot busy until the launch is done.
+uint32_t *sched_acquire(hipStream_t st, int dev, int *slot);
 void sched_release(int dev, int slot, hipStream_t st);
-uint32_t *device_status_word(int dev);            // runtime.hip
-
-// CUs of device `dev` and the workgroups of `kernel` one CU holds (threads, dynamic LDS):
-// asked from the runtime once per (kernel, threads, LDS bytes, device) and remembered -- the
-// two queries cost tens of microseconds, as much as a small layer's kernel.
-void persistent_limits(const void *kernel, int threads, size_t dyn_lds, int dev, int *cus, int *occ);
-int stream_device(hipStream_t st);
 
 template <typename K>
 static inline void launch_persistent(K kernel, ConvMfmaArgs a, unsigned gy, hipStream_t st,
                                      size_t dyn_lds = 0, int threads = 256) {
-  int dev = 0, cus = 256, occ = 2, slot = -1;
-  a.sched = gy <= (unsigned)SCHED_Y ? sched_acquire(st, &dev, &slot) : nullptr;   // npatch < 2^30: run_conv3x3_mfma
-  if (!a.sched) dev = stream_device(st);
+  const int dev = stream_device(st);
+  int slot = -1;
+  a.sched = gy <= (unsigned)SCHED_Y ? sched_acquire(st, dev, &slot) : nullptr;   // npatch < 2^30: run_conv3x3_mfma
   a.status = a.sched ? device_status_word(dev) : nullptr;
-  persistent_limits((const void *)kernel, threads, dyn_lds, dev, &cus, &occ);
-  const int64_t gmax = (int64_t)cus * occ;
-  unsigned gx = (unsigned)(a.npatch < gmax ? a.npatch : gmax);
-  a.xcd_split = 0;
-  if (gx >= 64 && a.B >= 8) {     // whole samples per XCD
-    gx &= ~7u;
-    a.xcd_split = 1;
-  }
+  const unsigned gx = persistent_grid((const void *)kernel, threads, dyn_lds, dev, a.npatch, a.B, &a.xcd_split);
   hipLaunchKernelGGL(kernel, dim3(gx, gy), dim3(threads), dyn_lds, st, a);
   if (a.sched) sched_release(dev, slot, st);
 }
 
-// conv3x3_bits.hip: bit-packed input, Cin <= 128; i8 = codes wider than fp6 holds
-// dq: how the accumulator becomes the current -- DQ_ARITH (three float32 instructions),
-// DQ_ONE (L == 1: one multiply), DQ_TABLE (fp6 instruction, NF_MUL0, 0 < a.lut_bound =
-// abs_sum_max <= DQT_MAXA: an LDS table addressed by the accumulator's bit pattern)
-// fma: the membrane update as one fused multiply-add (NF_MUL0, proven exact for this launch
-// by the caller: snnqp_weight_t.min_current_bits + lif_fma_is_exact)
-// bnf: every BatchNorm mean and bias is zero (snnqp_bn_t.flags): x = y * mul
-// cin_walk: the input channels the K walk covers: what `wt` is padded to, 32 / 64 / 96 / 128
-// (snnqp_weight_t.wt_cin), or 16 less (16 / 48 / 80 / 112) when no input channel lies in the upper
-// half of the last group -- the upper 16 rows of that group's tiles and the upper half of a
-// pixel's last spike word are then not read
+// The checks run_conv3x3_mfma and snnqp_conv_event_half_group share: the dequantisation step, the
+// BatchNorm descriptor (nullable) and the caller's silent channels (snnqp.h) -- a malformed value is
+// refused before anything runs.  `who` opens the message.  (conv3x3_mfma.hip)
+int conv3x3_check_weight(const char *who, const snnqp_weight_t *w, const snnqp_bn_t *bn, int32_t Cout);
+// the input channels `wt` is padded to: one 32-channel group per int8 tile of a tap
+inline int wt_cin_pad(const snnqp_weight_t *w, int32_t Cin) { return w->wt_cin ? w->wt_cin : (Cin + 31) / 32 * 32; }
+
+// The two launchers run_conv3x3_mfma hands a checked launch to; `a` holds the fields both kernels
+// read, each launcher adds what only its kernel consumes and picks the instance.
+// conv3x3_bits.hip: bit-packed input, Cin <= 128.  How the accumulator becomes the current --
+// DQ_ARITH (three float32 instructions), DQ_ONE (L == 1: one multiply), DQ_TABLE (fp6 instruction,
+// NF_MUL0, 0 < a.lut_bound = abs_sum_max <= DQT_MAXA: an LDS table addressed by the accumulator's
+// bit pattern)
 enum { DQ_ARITH = 1, DQ_ONE = 2, DQ_TABLE = 3 };
 constexpr int DQT_MAXA = 2047;
-void launch_conv3x3_bits(const ConvMfmaArgs &a, int cin_walk, bool i8, int nf, bool pool, int dq,
-                         bool fma, bool bnf, unsigned gy, hipStream_t st);
-// snnqp_set_conv_k16 (api.hip): whether run_conv3x3_mfma picks the 16-less walks
+void launch_conv3x3_bits(ConvMfmaArgs a, const snnqp_weight_t *w, const snnqp_neuron_t *nrn, hipStream_t st);
+// conv3x3_u8c2.hip: the event layer (Cin = 2) on U8 / EV1 / EV4 / F32 frames; SNNQP_OK or the error
+// of its own checks
+int launch_conv3x3_u8c2(ConvMfmaArgs a, int in_type, const snnqp_weight_t *w, int x_max, int32_t *x_flags,
+                        hipStream_t st);
+// snnqp_set_conv_k16 (api.hip): whether launch_conv3x3_bits picks the 16-less walks
 bool conv_k16_enabled();
-// snnqp_set_event_half_group (api.hip): whether run_conv3x3_mfma picks the half-group instances
+// snnqp_set_event_half_group (api.hip): whether launch_conv3x3_u8c2 picks the half-group instances
 bool event_half_group_enabled();
 
 }  // namespace snnqp

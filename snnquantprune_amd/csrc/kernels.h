@@ -16,7 +16,8 @@ int run_generic(const void *x, int in_type, int64_t xs_t, int64_t xs_b, int32_t 
                 hipStream_t st, int pool = 1, const int32_t *pred = nullptr,
                 const GenericDepth *dz = nullptr);
 
-// nullptr when the MFMA kernel can serve the request, else the reason.
+// nullptr when a fused 3x3 MFMA kernel can serve the request, else the reason; run_conv3x3_mfma
+// below checks the launch and hands it to the kernel of its input format (conv3x3_mfma.hip).
 const char *conv3x3_mfma_unsupported(int in_type, const snnqp_conv_geom_t *g,
                                      const snnqp_weight_t *w, const int8_t *wt,
                                      const snnqp_neuron_t *nrn, int s_type);
@@ -27,8 +28,10 @@ const char *conv3x3_currents_unsupported(int in_type, int64_t NB, const snnqp_co
 int run_conv3x3_currents(const void *x, int64_t NB, const snnqp_conv_geom_t *g,
                          const snnqp_weight_t *w, const int8_t *wt, float *y, int32_t *acc,
                          hipStream_t st);
+// snnqp_current_min (runtime.hip)
 int run_current_min(const snnqp_weight_t *w, const snnqp_bn_t *bn, int32_t bound, int32_t Cout,
                     uint32_t *out_bits, hipStream_t st);
+// DQ_ONE / DQ_TABLE / DQ_ARITH (conv_tile.h) for a bit-input block on these weights (conv3x3_bits.hip)
 int conv3x3_bits_dequant_form(const snnqp_weight_t *w, const snnqp_neuron_t *nrn);
 // snnqp_conv_event_half_group: 1 / 0, or a negative error (conv3x3_u8c2.hip)
 int conv3x3_event_half_group(int in_type, int32_t T, const snnqp_conv_geom_t *g, const snnqp_weight_t *w,
@@ -41,8 +44,36 @@ int run_conv3x3_mfma(const void *x, int in_type, int64_t xs_t, int64_t xs_b,
                      int x_max, int32_t *x_seen, int32_t *x_flags, hipStream_t st,
                      const int32_t *pred = nullptr);
 
-// per-device state (runtime.hip): the status word kernels report broken invariants into, the
-// probe of the matrix pipe's denormal arithmetic behind DQ_TABLE
+// per-device state and helpers (runtime.hip): the status word kernels report broken invariants
+// into, the probe of the matrix pipe's denormal arithmetic behind DQ_TABLE
+constexpr int MAX_DEVICES = 64;      // devices the per-device tables of the library hold
+// Makes `dev` the calling thread's current device for a scope: per-device resources belong to the
+// device of the launch stream, which need not be the thread's current one.
+struct DeviceGuard {
+  int prev = -1;
+  bool ok = true;
+  explicit DeviceGuard(int dev) {
+    int cur = -1;
+    if (hipGetDevice(&cur) != hipSuccess) { (void)hipGetLastError(); ok = false; return; }
+    if (cur == dev) return;
+    if (hipSetDevice(dev) != hipSuccess) { (void)hipGetLastError(); ok = false; return; }
+    prev = cur;
+  }
+  ~DeviceGuard() {
+    if (prev >= 0 && hipSetDevice(prev) != hipSuccess) (void)hipGetLastError();
+  }
+};
+// the device of `st`; the thread's current device, then 0, when the runtime does not say
+int stream_device(hipStream_t st);
+// 1: `st` is being captured into a graph, 0: it is not, -1: the query failed (error cleared)
+int stream_capturing(hipStream_t st);
+// Grid of a persistent launch over `npatch` patches of `B` samples: min(npatch, CUs x the workgroups
+// of `kernel` a CU holds), and with 64 workgroups or more and B >= 8 a multiple of 8 with
+// *xcd_split = 1 (whole samples per XCD, PatchWalk in conv_tile.h).  The two runtime queries
+// behind it are made once per (kernel, threads, LDS bytes, device) and remembered -- they cost
+// tens of microseconds, as much as a small layer's kernel.
+unsigned persistent_grid(const void *kernel, int threads, size_t dyn_lds, int dev, int64_t npatch,
+                         int32_t B, int32_t *xcd_split);
 uint32_t *device_status_word(int dev);
 // `nwords` 32-bit words at `p` := 0 on `st`, by a kernel of the library (a kernel node when the
 // stream is being captured).  Not hipMemsetAsync: on replay the runtime (ROCm 7.2.0) executed a
@@ -59,7 +90,6 @@ const char *device_status_text(uint32_t code);
 bool dq_table_trusted(int dev, hipStream_t st);
 void check_code_bound_once(int dev, const int8_t *w, int64_t K, int32_t N, int32_t bound, hipStream_t st);
 int64_t dq_table_fallbacks(bool reset);
-int stream_device(hipStream_t st);
 
 // float32 x float32 connection on the f32 MFMA (fseq_gemm.hip)
 const char *fseq_gemm_unsupported(int in_type, const snnqp_conv_geom_t *g,

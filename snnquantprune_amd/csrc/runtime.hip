@@ -14,11 +14,16 @@
 //    firmware, or runtime) on which they differ gets the arithmetic form (DQ_ARITH: the same
 //    results from three float32 instructions per value) and the fallback is counted
 //    (snnqp_workqueue_stats).  Reference semantics at stake: quant.py:443,467 (the dequantised
-//    current) feeding spiking_learning.py:410-414.
+//    current) feeding spiking_learning.py:410-414;
+//  * the helpers every per-device resource goes through: the device of a stream, whether it is
+//    being captured, the grid of a persistent launch (DeviceGuard, MAX_DEVICES: kernels.h);
+//  * snnqp_current_min: it needs nothing but common.h, as the bound check below.
 #include <atomic>
 #include <cstdlib>
 #include <cstring>
+#include <map>
 #include <mutex>
+#include <tuple>
 #include <vector>
 
 #include "kernels.h"
@@ -36,23 +41,8 @@ struct DeviceState {
   int denorm = 0;                    // 0 not probed yet, 1 exact, -1 not exact / probe failed
 };
 std::mutex g_rt_mu;
-DeviceState g_rt[64];
+DeviceState g_rt[MAX_DEVICES];
 std::atomic<int64_t> g_dq_fallbacks{0};
-
-struct RtDeviceGuard {
-  int prev = -1;
-  bool ok = true;
-  explicit RtDeviceGuard(int dev) {
-    int cur = -1;
-    if (hipGetDevice(&cur) != hipSuccess) { (void)hipGetLastError(); ok = false; return; }
-    if (cur == dev) return;
-    if (hipSetDevice(dev) != hipSuccess) { (void)hipGetLastError(); ok = false; return; }
-    prev = cur;
-  }
-  ~RtDeviceGuard() {
-    if (prev >= 0 && hipSetDevice(prev) != hipSuccess) (void)hipGetLastError();
-  }
-};
 
 }  // namespace
 
@@ -65,6 +55,90 @@ int zero_words_async(uint32_t *p, int64_t nwords, hipStream_t st) {
   const int64_t blocks = (nwords + 255) / 256;
   hipLaunchKernelGGL(zero_words_kernel, dim3((unsigned)(blocks < 1024 ? blocks : 1024)), dim3(256), 0, st, p, nwords);
   SNNQP_CHECK_LAUNCH("zero_words_kernel");
+  return SNNQP_OK;
+}
+
+int stream_device(hipStream_t st) {
+  int dev = 0;
+  hipDevice_t sdev;
+  if (hipStreamGetDevice(st, &sdev) == hipSuccess) return (int)sdev;
+  (void)hipGetLastError();
+  if (hipGetDevice(&dev) != hipSuccess) { (void)hipGetLastError(); dev = 0; }
+  return dev;
+}
+
+int stream_capturing(hipStream_t st) {
+  hipStreamCaptureStatus cap = hipStreamCaptureStatusNone;
+  if (hipStreamIsCapturing(st, &cap) != hipSuccess) { (void)hipGetLastError(); return -1; }
+  return cap != hipStreamCaptureStatusNone ? 1 : 0;
+}
+
+unsigned persistent_grid(const void *kernel, int threads, size_t dyn_lds, int dev, int64_t npatch,
+                         int32_t B, int32_t *xcd_split) {
+  typedef std::tuple<const void *, int, size_t, int> Key;
+  static std::mutex mu;
+  static std::map<Key, int64_t> cache;       // CUs of `dev` x the workgroups of `kernel` one CU holds
+  int64_t gmax;
+  {
+    std::lock_guard<std::mutex> lock(mu);
+    auto it = cache.find(Key(kernel, threads, dyn_lds, dev));
+    if (it == cache.end()) {
+      int cus = 256, occ = 1;
+      DeviceGuard on(dev);               // the occupancy query answers for the current device
+      if (hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess) {
+        (void)hipGetLastError();
+        cus = 256;
+      }
+      if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&occ, kernel, threads, dyn_lds) != hipSuccess) {
+        (void)hipGetLastError();
+        occ = 1;
+      }
+      occ = occ < 1 ? 1 : occ > 8 ? 8 : occ;
+      it = cache.emplace(Key(kernel, threads, dyn_lds, dev), (int64_t)cus * occ).first;
+    }
+    gmax = it->second;
+  }
+  unsigned gx = (unsigned)(npatch < gmax ? npatch : gmax);
+  *xcd_split = 0;
+  if (gx >= 64 && B >= 8) {     // whole samples per XCD
+    gx &= ~7u;
+    *xcd_split = 1;
+  }
+  return gx;
+}
+
+// snnqp_current_min: one thread per (channel, table slice)
+__global__ void __launch_bounds__(256)
+current_min_kernel(Dequant dq, BnP bn, int bound, int Cout, uint32_t *out) {
+  const int c = blockIdx.x * 64 + (threadIdx.x & 63);
+  uint32_t mb = 0x7F800000u;
+  if (c < Cout) {
+    float mean = 0.f, mul = 1.f, bias = 0.f;
+    if (bn.mean) { mean = bn.mean[c]; mul = bn.mul[c]; bias = bn.bias[c]; }
+    for (int i = (int)(threadIdx.x >> 6) + 4 * (int)blockIdx.y - bound; i <= bound; i += 4 * (int)gridDim.y) {
+      float x = dequant_acc(i, dq) - mean;       // the epilogue's operation order
+      x = x * mul;
+      x = x + bias;
+      const uint32_t b = __float_as_uint(x) & 0x7FFFFFFFu;
+      if (b != 0 && b < mb) mb = b;
+    }
+  }
+  for (int off = 32; off > 0; off >>= 1) {
+    const uint32_t o = (uint32_t)__shfl_xor((int)mb, off);
+    mb = o < mb ? o : mb;
+  }
+  if ((threadIdx.x & 63) == 0 && mb != 0x7F800000u) atomicMin(out, mb);
+}
+
+int run_current_min(const snnqp_weight_t *w, const snnqp_bn_t *bn, int32_t bound, int32_t Cout,
+                    uint32_t *out_bits, hipStream_t st) {
+  SNNQP_REQUIRE(w && out_bits && Cout > 0 && bound >= 0, SNNQP_EINVAL, "current_min: bad argument");
+  SNNQP_REQUIRE(w->L >= 1.0f, SNNQP_EINVAL, "dequant L must be >= 1");
+  SNNQP_CHECK_BN(bn);
+  const int slices = bound >= 256 ? 16 : 1;
+  hipLaunchKernelGGL(current_min_kernel, dim3((Cout + 63) / 64, slices), dim3(256), 0, st,
+                     make_dequant(w->L, w->m), make_bn(bn), bound, Cout, out_bits);
+  SNNQP_CHECK_LAUNCH("current_min_kernel");
   return SNNQP_OK;
 }
 
@@ -139,7 +213,7 @@ bool run_denorm_probe() {
   return ok;
 }
 
-DeviceState *state_of(int dev) { return dev >= 0 && dev < 64 ? &g_rt[dev] : nullptr; }
+DeviceState *state_of(int dev) { return dev >= 0 && dev < MAX_DEVICES ? &g_rt[dev] : nullptr; }
 
 // one thread per output column: the two one-sided code sums against the caller's bound
 __global__ void __launch_bounds__(256)
@@ -158,8 +232,8 @@ check_code_bound_kernel(const int8_t *__restrict__ w, int64_t K, int32_t N, int3
 
 // (codes pointer, K, N, bound) tuples already checked on a device: a small ring
 struct Checked { const void *w; int64_t K; int32_t N, bound; };
-Checked g_checked[64][32];
-unsigned g_checked_next[64];
+Checked g_checked[MAX_DEVICES][32];
+unsigned g_checked_next[MAX_DEVICES];
 
 }  // namespace
 
@@ -171,7 +245,7 @@ uint32_t *device_status_word(int dev) {
   if (!s) return nullptr;
   std::lock_guard<std::mutex> lock(g_rt_mu);
   if (s->status_dev || s->status_failed) return s->status_dev;
-  RtDeviceGuard on(dev);
+  DeviceGuard on(dev);
   void *h = nullptr, *d = nullptr;
   if (!on.ok || hipHostMalloc(&h, 64, hipHostMallocMapped | hipHostMallocCoherent) != hipSuccess) {
     (void)hipGetLastError();
@@ -226,13 +300,13 @@ bool dq_table_trusted(int dev, hipStream_t st) {
       return s->denorm > 0;
     }
   }
-  hipStreamCaptureStatus cap = hipStreamCaptureStatusNone;
-  if (hipStreamIsCapturing(st, &cap) != hipSuccess) { (void)hipGetLastError(); return false; }
-  if (cap != hipStreamCaptureStatusNone) {
+  const int capturing = stream_capturing(st);
+  if (capturing < 0) return false;
+  if (capturing) {
     g_dq_fallbacks.fetch_add(1, std::memory_order_relaxed);
     return false;
   }
-  RtDeviceGuard on(dev);
+  DeviceGuard on(dev);
   bool ok = on.ok && run_denorm_probe();
   static const bool force_fail = std::getenv("SNNQP_FORCE_DENORM_PROBE_FAIL") != nullptr;   // test hook
   if (force_fail) ok = false;
@@ -249,7 +323,7 @@ bool dq_table_trusted(int dev, hipStream_t st) {
 // goes to the status word, i.e. the NEXT call fails.  The tuple is remembered (a ring of 32 per
 // device): codes rewritten in place under an unchanged bound are not checked again.
 void check_code_bound_once(int dev, const int8_t *w, int64_t K, int32_t N, int32_t bound, hipStream_t st) {
-  if (dev < 0 || dev >= 64 || !w || bound <= 0) return;
+  if (dev < 0 || dev >= MAX_DEVICES || !w || bound <= 0) return;
   {
     std::lock_guard<std::mutex> lock(g_rt_mu);
     for (const Checked &c : g_checked[dev])
@@ -257,9 +331,7 @@ void check_code_bound_once(int dev, const int8_t *w, int64_t K, int32_t N, int32
   }
   uint32_t *status = device_status_word(dev);
   if (!status) return;
-  hipStreamCaptureStatus cap = hipStreamCaptureStatusNone;
-  if (hipStreamIsCapturing(st, &cap) != hipSuccess) { (void)hipGetLastError(); return; }
-  if (cap != hipStreamCaptureStatusNone) return;      // not into a graph: the next eager launch checks
+  if (stream_capturing(st) != 0) return;      // not into a graph: the next eager launch checks
   hipLaunchKernelGGL(check_code_bound_kernel, dim3((unsigned)((N + 255) / 256)), dim3(256), 0, st, w, K, N,
                      bound, status);
   if (hipGetLastError() != hipSuccess) return;
@@ -286,7 +358,7 @@ int refuse_after_device_report(hipStream_t st, const char *who) {
 
 extern "C" int snnqp_device_status(int device, uint32_t *codes, int reset) {
   using namespace snnqp;
-  SNNQP_REQUIRE(device >= 0 && device < 64, SNNQP_EINVAL, "device_status: device %d out of range", device);
+  SNNQP_REQUIRE(device >= 0 && device < MAX_DEVICES, SNNQP_EINVAL, "device_status: device %d out of range", device);
   const uint32_t c = device_status_read(device);
   if (codes) *codes = c;
   if (reset) {

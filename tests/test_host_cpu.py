@@ -72,6 +72,47 @@ def test_argument_errors_are_reported_without_a_gpu():
                                   ctypes.byref(wi), None, None, ctypes.byref(nrn),
                                   None, None, ctypes.c_void_p(8), L.BITS, 2, L.IMPL_MFMA, 1, None, None, None)
   assert rc == L.EINVAL and b"x_flags" in lib.snnqp_last_error()
+  # the work-queue bookkeeping (workqueue.hip) needs no device.  In a process of its own: one that
+  # has launched conv kernels holds a pool and capture marks, and a poke would then land in it.
+  p = subprocess.run([sys.executable, "-c", _WORKQUEUE_CALLS % ROOT], stdout=subprocess.PIPE,
+                     stderr=subprocess.PIPE, timeout=120)
+  assert p.returncode == 0, p.stderr.decode()
+  got = json.loads(p.stdout.decode().strip().splitlines()[-1])
+  bad = [L.EINVAL, "bad argument"]
+  assert got == {
+      "mark": [0, 0], "mark_device_64": bad, "mark_null": bad,
+      "release_0_0": [0], "release_0_1": [L.EINVAL, "marks out of range"],
+      "release_1_0": [L.EINVAL, "marks out of range"], "release_device_-1": [L.EINVAL, "bad device"],
+      "stats": [0, 0, 0, 0], "poke": [L.EINVAL, "no live capture slot"], "poke_word_128": bad}, got
+
+
+_WORKQUEUE_CALLS = """
+import ctypes, json, sys
+sys.path.insert(0, %r)
+from snnquantprune_amd import _lib as L
+lib = ctypes.CDLL(L.LIB_PATH)
+for name in ("snnqp_last_error", "snnqp_workqueue_capture_mark", "snnqp_workqueue_capture_release",
+             "snnqp_workqueue_stats", "snnqp_debug_workqueue_poke"):
+  getattr(lib, name).restype, getattr(lib, name).argtypes = L._PROTOTYPES[name]
+def err(rc, text):
+  msg = lib.snnqp_last_error().decode()
+  return [rc, text if rc != 0 and text in msg else msg]
+i64 = ctypes.c_int64
+m, a, b, c = i64(-1), i64(-1), i64(-1), i64(-1)
+out = {}
+out["mark"] = [lib.snnqp_workqueue_capture_mark(0, ctypes.byref(m)), m.value]
+out["mark_device_64"] = err(lib.snnqp_workqueue_capture_mark(64, ctypes.byref(m)), "bad argument")
+out["mark_null"] = err(lib.snnqp_workqueue_capture_mark(0, None), "bad argument")
+out["release_0_0"] = [lib.snnqp_workqueue_capture_release(0, 0, 0)]
+out["release_0_1"] = err(lib.snnqp_workqueue_capture_release(0, 0, 1), "marks out of range")
+out["release_1_0"] = err(lib.snnqp_workqueue_capture_release(0, 1, 0), "marks out of range")
+out["release_device_-1"] = err(lib.snnqp_workqueue_capture_release(-1, 0, 0), "bad device")
+out["stats"] = [lib.snnqp_workqueue_stats(ctypes.byref(a), ctypes.byref(b), ctypes.byref(c), 0),
+                a.value, b.value, c.value]
+out["poke"] = err(lib.snnqp_debug_workqueue_poke(0, 0, 0, 5), "no live capture slot")
+out["poke_word_128"] = err(lib.snnqp_debug_workqueue_poke(0, 0, 128, 5), "bad argument")
+print(json.dumps(out))
+"""
 
 
 def test_conv_out_shape_matches_reference_table():
