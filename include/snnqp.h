@@ -242,7 +242,9 @@ typedef struct {
  * snnqp_conv_grad_splits, snnqp_conv_weight_grad_workspace_bytes, snnqp_maxpool2x2_backward;
  * 507: snnqp_conv_forward_ex -- currents from the bit-input MFMA conv; within 507, layout-
  * compatible: snnqp_weight_t.cout_fire in the struct's former tail padding,
- * snnqp_set_event_half_group, snnqp_conv_event_half_group).
+ * snnqp_set_event_half_group, snnqp_conv_event_half_group; training of CextNet's gated stages --
+ * snnqp_gate_pool_grad_gate, snnqp_gate_pool_grad_input, snnqp_conv_weight_grad_f64,
+ * snnqp_conv_weight_grad_f64_workspace_bytes: new entry points, nothing else moves).
  * A binding compares snnqp_version()
  * with the SNNQP_VERSION it was written against and refuses a library of another version (_lib.py does). */
 #define SNNQP_VERSION 507
@@ -831,6 +833,20 @@ int64_t snnqp_conv_weight_grad_workspace_bytes(const snnqp_conv_geom_t *g, int32
  * not asked, so a gradient does not depend on the machine), in 1..64: tiles x splits near 1024
  * workgroups, no range shorter than 256 rows.  A negative SNNQP_E* on a geometry not served. */
 int snnqp_conv_grad_splits(const snnqp_conv_geom_t *g, int64_t NB);
+/* snnqp_conv_weight_grad's sum with the chain in float64, for a layer whose gradient cancels too
+ * far for a float32 chain (CextNet's first block: the most rows, count frames with a large mean
+ * against a gI that sums to zero).  Same tensors and geometry.  r is cut into
+ * S = min(1024, max(1, ceil(Rn / 1024))) contiguous ranges of ceil(Rn / S) rows; each range is the
+ * r-ascending chain acc = acc + (double)x (double)gI from +0 (the product is exact, the addition
+ * rounds once) into workspace[s] ([KH KW Cin][Cout] doubles); a second kernel forms
+ * ((p0 + p1) + p2) + ... in float64 in s order and rounds to float32 once.  No atomics: bitwise
+ * reproducible.  `workspace` holds snnqp_conv_weight_grad_f64_workspace_bytes(g, NB) bytes (host
+ * only; a negative SNNQP_E* on a geometry not served).  NB == 0 writes zeros to gw.  One lane per
+ * element of gw: meant for a small KH KW Cin. */
+int snnqp_conv_weight_grad_f64(const float *x, const float *gI, int64_t NB,
+                               const snnqp_conv_geom_t *g, double *workspace, float *gw,
+                               snnqp_stream_t stream);
+int64_t snnqp_conv_weight_grad_f64_workspace_bytes(const snnqp_conv_geom_t *g, int64_t NB);
 /* gx[n, ih, iw, ci] = sum_r gI[n, oh, ow, co] w[kh, kw, ci, co], r = (kh KW + kw) Cout + co
  * ascending, oh = (ih + pt - kh) / sh and likewise ow; the tap reads 0.0 where that is not an
  * integer in range. */
@@ -841,6 +857,33 @@ int snnqp_conv_input_grad(const float *gI, const float *w, int64_t NB,
  * other position, and a trailing odd row or column, gets 0.  gs [NB][H][W][C]. */
 int snnqp_maxpool2x2_backward(const float *s, const float *gp, int64_t NB, int32_t H, int32_t W,
                               int32_t C, float *gs, snnqp_stream_t stream);
+
+/* ---- training of CextNet's gated stages (csrc/train_gate.hip) --------------------------------
+ * The backward of p = maxpool2x2(y), y[n, h, w, c] = x[n, h, w, c] gate[n, c], with the spatial
+ * mean m = snnqp_spatial_mean(x) the gate is a function of (examples/tcja/models.py:41-99,
+ * :184-187).  All tensors float32: x, gx [NB][H][W][C] (general values, not only 0 / 1), gate,
+ * ggate, gm [NB][C], gp [NB][H/2][W/2][C].  p*(window) is the first position, in the row-major
+ * window order (0,0), (0,1), (1,0), (1,1), at which y_i = fl(x_i gate) attains the window's
+ * maximum, by the compare rule of snnqp_maxpool2x2_backward applied to y (a later position wins
+ * only when strictly greater; with gate == 0 every y_i is equal and the first position wins).
+ * Index arithmetic is 64-bit, every access is predicated; H, W, C > 0; a grid beyond the launch
+ * limits is SNNQP_EINVAL; shapes and null pointers are refused on the host before any launch.
+ * NB == 0 returns SNNQP_OK and writes nothing (no pointer is looked at).
+ *
+ * ggate[n, c] = sum over windows of gp[n, ph, pw, c] x[n, p*, c]: one fmaf chain from +0,
+ * acc = fmaf(gp, x, acc), over (ph, pw) ascending, ph the slow index -- never cut into ranges, so
+ * the order is a function of (H, W) alone.  No atomics: bitwise reproducible.  With H < 2 or
+ * W < 2 there is no window: ggate = +0 and gp is not read (may be null). */
+int snnqp_gate_pool_grad_gate(const float *x, const float *gate, const float *gp, int64_t NB,
+                              int32_t H, int32_t W, int32_t C, float *ggate,
+                              snnqp_stream_t stream);
+/* gx[n, h, w, c] = fl(route + fl(gm[n, c] / (float)(H W))): route = fl(gp[n, h/2, w/2, c]
+ * gate[n, c]) where (h, w) is p* of its window and +0 elsewhere (a trailing odd row or column
+ * belongs to no window); the second term is the VJP of snnqp_spatial_mean, which divides its
+ * sum by (float)(H W) -- the same division, not a multiplication by a reciprocal. */
+int snnqp_gate_pool_grad_input(const float *x, const float *gate, const float *gp, const float *gm,
+                               int64_t NB, int32_t H, int32_t W, int32_t C, float *gx,
+                               snnqp_stream_t stream);
 
 #ifdef __cplusplus
 }

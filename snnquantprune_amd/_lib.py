@@ -193,6 +193,13 @@ _PROTOTYPES = {
                                       c_void_p]),
     "snnqp_maxpool2x2_backward": (c_int, [c_void_p, c_void_p, c_int64, c_int32, c_int32, c_int32,
                                           c_void_p, c_void_p]),
+    "snnqp_conv_weight_grad_f64": (c_int, [c_void_p, c_void_p, c_int64, POINTER(ConvGeomT), c_void_p,
+                                           c_void_p, c_void_p]),
+    "snnqp_conv_weight_grad_f64_workspace_bytes": (c_int64, [POINTER(ConvGeomT), c_int64]),
+    "snnqp_gate_pool_grad_gate": (c_int, [c_void_p, c_void_p, c_void_p, c_int64, c_int32, c_int32,
+                                          c_int32, c_void_p, c_void_p]),
+    "snnqp_gate_pool_grad_input": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_int64, c_int32,
+                                           c_int32, c_int32, c_void_p, c_void_p]),
 }
 
 EXPORTED_SYMBOLS = tuple(_PROTOTYPES)

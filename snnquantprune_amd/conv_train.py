@@ -1,4 +1,5 @@
-"""Training forward and surrogate-gradient backward of the conv blocks of ConvDenseSNN (config C3).
+"""Training forward and surrogate-gradient backward of the conv blocks of ConvDenseSNN (config C3)
+and CextNet.
 
 jax.grad of examples/tcja/models.py:101-147 in train mode, offline, stated as one
 torch.autograd.Function per block:
@@ -86,10 +87,12 @@ def running_update(old: torch.Tensor, new_t: torch.Tensor, momentum: float) -> t
   return ra
 
 
-def conv_currents(x, pk: packing.PackedKernel, geom: ops.ConvGeom) -> torch.Tensor:
+def conv_currents(x, pk: packing.PackedKernel, geom: ops.ConvGeom, real: bool = False) -> torch.Tensor:
   """x [NB, H, W, Cin] (uint8, float32 or PackedSpikes) -> float32 [NB, OH, OW, Cout] on the eval
-  connection kernels: integer codes for integer-valued inputs, the float32 kernel otherwise."""
-  w = pk.int_weight()
+  connection kernels: integer codes for integer-valued inputs, the float32 kernel otherwise.
+  `real`: the input is real-valued by construction (a gated raster) -- the float32 connection
+  without looking at the values, as eval runs it under packing.integer_inputs(False)."""
+  w = None if real else pk.int_weight()
   if w is not None and isinstance(x, ops.PackedSpikes) and _nn.train_conv_mfma():
     # the bit-packed raster of the block before: the codes tiled for the MFMA currents kernel
     # (ops.conv_forward takes it where the shape allows, the direct-form launch otherwise)
@@ -112,17 +115,33 @@ class ConvBlock(torch.autograd.Function):
   """x [T, B, H, W, Cin] -> pooled spikes float32 [T, B, OH/2, OW/2, C], and without gradient the
   unpooled h, s [T, B, OH, OW, C] and the per-step statistics mean, var [T, C].  Gradients to x
   (not for the first block: the frames need none), the transformed kernel wq (HWIO) and
-  BatchNorm's scale and bias."""
+  BatchNorm's scale and bias.
+
+  pool = 1: no pool, the first output is the spike raster itself and its gradient arrives
+  directly (the blocks in front of CextNet's TCJA gates).  real_input: x is a real-valued raster
+  (what a gate leaves), not spikes: it is not bit-packed and the currents come from the float32
+  connection on it.  wgrad_f64: the weight gradient's chain runs in float64
+  (ops.conv_weight_grad_f64) -- CextNet's first block, whose 64 x 64 and larger count frames make
+  the sum cancel further than a float32 chain resolves."""
+
+  @classmethod
+  def apply(cls, x, wq, scale, bias, pk, geom, nrn, surrogate, eps, first, pool=2,
+            real_input=False, wgrad_f64=False):
+    if pool not in (1, 2):
+      raise ValueError("ConvBlock: pool must be 1 or 2, got %r" % (pool,))
+    return super().apply(x, wq, scale, bias, pk, geom, nrn, surrogate, eps, first, pool,
+                         real_input, wgrad_f64)
 
   @staticmethod
-  def forward(ctx, x, wq, scale, bias, pk, geom, nrn, surrogate, eps, first):
+  def forward(ctx, x, wq, scale, bias, pk, geom, nrn, surrogate, eps, first, pool, real_input,
+              wgrad_f64):
     T, B = x.shape[0], x.shape[1]
     C = geom.Cout
-    if first or pk.int_weight() is None:
+    if first or real_input or pk.int_weight() is None:
       xin = x.reshape(T * B, geom.H, geom.W, geom.Cin)
     else:
       xin = ops.pack_bits(x.reshape(T * B, geom.H, geom.W, geom.Cin).contiguous())
-    cur = conv_currents(xin, pk, geom)
+    cur = conv_currents(xin, pk, geom, real=real_input)
     OH, OW = cur.shape[1], cur.shape[2]
     cur = cur.reshape(T, B * OH * OW, C)
     mean, var = batch_stats(cur)
@@ -131,9 +150,10 @@ class ConvBlock(torch.autograd.Function):
     del y
     h = h.reshape(T, B, OH, OW, C)
     s = s.reshape(T, B, OH, OW, C)
-    pooled = ops.maxpool2x2(s)
+    pooled = ops.maxpool2x2(s) if pool == 2 else s.clone()
     ctx.save_for_backward(x, wq, scale, cur, mean, var, h)
     ctx.geom, ctx.nrn, ctx.surrogate, ctx.eps, ctx.first = geom, nrn, surrogate, eps, first
+    ctx.pool, ctx.wgrad_f64 = pool, wgrad_f64
     ctx.mark_non_differentiable(h, s, mean, var)
     return pooled, h, s, mean, var
 
@@ -142,9 +162,12 @@ class ConvBlock(torch.autograd.Function):
     x, wq, scale, cur, mean, var, h = ctx.saved_tensors
     geom, nrn = ctx.geom, ctx.nrn
     T, B, OH, OW, C = h.shape
-    s = ((h - nrn.v_threshold) >= 0).to(torch.float32)          # the forward's spikes
-    gs = ops.maxpool2x2_backward(s, gp.contiguous())
-    del s
+    if ctx.pool == 2:
+      s = ((h - nrn.v_threshold) >= 0).to(torch.float32)        # the forward's spikes
+      gs = ops.maxpool2x2_backward(s, gp.contiguous())
+      del s
+    else:
+      gs = gp.contiguous()
     gy = ops.lif_backward(h.reshape(T, B * OH * OW, C), nrn, ctx.surrogate,
                           gs=gs.reshape(T, B * OH * OW, C))
     del gs
@@ -152,8 +175,8 @@ class ConvBlock(torch.autograd.Function):
     del gy
     gcur = gcur.reshape(T * B, OH, OW, C)
     x4 = x.reshape(T * B, geom.H, geom.W, geom.Cin).to(torch.float32)
-    gw = ops.conv_weight_grad(x4, gcur, geom)
+    gw = ops.conv_weight_grad_f64(x4, gcur, geom) if ctx.wgrad_f64 else ops.conv_weight_grad(x4, gcur, geom)
     gx = None
     if not ctx.first and ctx.needs_input_grad[0]:
       gx = ops.conv_input_grad(gcur, wq.detach(), geom).reshape(x.shape)
-    return gx, gw, gscale, gbias, None, None, None, None, None, None
+    return gx, gw, gscale, gbias, None, None, None, None, None, None, None, None, None

@@ -135,6 +135,55 @@ __global__ void split_sum_kernel(const float *__restrict__ ws, int32_t splits, i
   gw[e] = v;
 }
 
+// The weight gradient accumulated in float64: one lane per element (i, co) of gw and range
+// blockIdx.y of r, consecutive lanes on consecutive co (rows of gI coalesce, the gathered x is one
+// address per i).  The product of two float32 values is exact in float64, so each step of the
+// r-ascending chain rounds once, in the addition.
+__global__ __launch_bounds__(256) void conv_wgrad_f64_kernel(XGather a, const float *__restrict__ gI,
+                                                             int64_t J, int64_t Rn, int64_t L,
+                                                             double *__restrict__ out) {
+  const int64_t n = a.n * J;
+  const int64_t e = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (e >= n) return;
+  const int64_t i = e / J, j = e - i * J;
+  const int64_t r_begin = (int64_t)blockIdx.y * L;
+  const int64_t r_end = r_begin + L < Rn ? r_begin + L : Rn;
+  double acc = 0.0;
+  if (r_begin < r_end) {
+    // the tap of this lane is fixed; (img, oh, ow) of r is split once and walked from there
+    const ConvP &g = a.g;
+    int32_t kh, kw, ci, oh, ow;
+    int64_t img;
+    split_tap(i, g.Cin, g.KW, kh, kw, ci);
+    split_pixel(r_begin, (int64_t)g.OH * g.OW, g.OW, img, oh, ow);
+    for (int64_t r = r_begin; r < r_end; ++r) {
+      const int64_t ih = (int64_t)oh * g.sh + kh - g.pt, iw = (int64_t)ow * g.sw + kw - g.pl;
+      const float xv = (ih < 0 || ih >= g.H || iw < 0 || iw >= g.W)
+                           ? 0.0f
+                           : a.x[((img * g.H + ih) * g.W + iw) * g.Cin + ci];
+      acc = acc + (double)xv * (double)gI[r * J + j];
+      if (++ow == g.OW) {
+        ow = 0;
+        if (++oh == g.OH) {
+          oh = 0;
+          ++img;
+        }
+      }
+    }
+  }
+  out[(int64_t)blockIdx.y * n + e] = acc;
+}
+
+// gw = fl32(((p0 + p1) + p2) + ...) over the ranges' float64 partial sums ws [splits][n].
+__global__ void split_sum_f64_kernel(const double *__restrict__ ws, int32_t splits, int64_t n,
+                                     float *__restrict__ gw) {
+  const int64_t e = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (e >= n) return;
+  double v = ws[e];
+  for (int32_t s = 1; s < splits; ++s) v = v + ws[(int64_t)s * n + e];
+  gw[e] = (float)v;
+}
+
 // blockIdx.x walks the pixels (the long axis), blockIdx.y the input channels.
 __global__ __launch_bounds__(256) void conv_igrad_kernel(GIGather a, WGather b, int64_t Rn,
                                                          float *__restrict__ gx) {
@@ -220,6 +269,15 @@ int default_splits(const ConvP &p, int64_t NB) {
   return s < 1 ? 1 : (int)s;
 }
 
+// The ranges of the float64 weight gradient: about F64_ROWS rows each, at most F64_MAX_SPLITS (a
+// lane walks its range row by row, so the ranges are what fills the machine).  Shapes only.
+constexpr int64_t F64_ROWS = 1024, F64_MAX_SPLITS = 1024;
+
+int f64_splits(int64_t Rn) {
+  const int64_t s = ceil_div64(Rn, F64_ROWS);
+  return s < 1 ? 1 : s > F64_MAX_SPLITS ? (int)F64_MAX_SPLITS : (int)s;
+}
+
 }  // namespace
 }  // namespace snnqp
 
@@ -271,6 +329,38 @@ int snnqp_conv_weight_grad(const float *x, const float *gI, int64_t NB,
                        workspace, splits, I * J, gw);
     SNNQP_CHECK_LAUNCH("split_sum_kernel");
   }
+  return SNNQP_OK;
+}
+
+int64_t snnqp_conv_weight_grad_f64_workspace_bytes(const snnqp_conv_geom_t *g, int64_t NB) {
+  ConvP p;
+  if (int rc = check_geom(g, "conv_weight_grad_f64_workspace_bytes", &p)) return rc;
+  SNNQP_REQUIRE(images_fit(p, NB), SNNQP_EINVAL, "conv_weight_grad_f64_workspace_bytes: bad NB");
+  return (int64_t)f64_splits(NB * p.OH * p.OW) * p.KH * p.KW * p.Cin * p.Cout *
+         (int64_t)sizeof(double);
+}
+
+int snnqp_conv_weight_grad_f64(const float *x, const float *gI, int64_t NB,
+                               const snnqp_conv_geom_t *g, double *workspace, float *gw,
+                               snnqp_stream_t stream) {
+  ConvP p;
+  if (int rc = check_geom(g, "conv_weight_grad_f64", &p)) return rc;
+  SNNQP_REQUIRE(images_fit(p, NB), SNNQP_EINVAL, "conv_weight_grad_f64: bad NB");
+  const int64_t Rn = NB * p.OH * p.OW;
+  SNNQP_REQUIRE(gw && workspace && ((x && gI) || Rn == 0), SNNQP_EINVAL,
+                "conv_weight_grad_f64: null argument");
+  const int64_t I = (int64_t)p.KH * p.KW * p.Cin, J = p.Cout;
+  const int64_t blocks = ceil_div64(I * J, 256);
+  SNNQP_REQUIRE(blocks < (1ll << 31), SNNQP_EINVAL, "conv_weight_grad_f64: grid too large");
+  const int splits = f64_splits(Rn);
+  const int64_t L = ceil_div64(Rn, splits);
+  hipStream_t st = (hipStream_t)stream;
+  hipLaunchKernelGGL(conv_wgrad_f64_kernel, dim3((unsigned)blocks, (unsigned)splits), dim3(256), 0,
+                     st, XGather{x, p, I}, gI, J, Rn, L, workspace);
+  SNNQP_CHECK_LAUNCH("conv_wgrad_f64_kernel");
+  hipLaunchKernelGGL(split_sum_f64_kernel, dim3((unsigned)blocks), dim3(256), 0, st, workspace,
+                     splits, I * J, gw);
+  SNNQP_CHECK_LAUNCH("split_sum_f64_kernel");
   return SNNQP_OK;
 }
 

@@ -131,12 +131,13 @@ def transformed_kernel(leaf: dict, pk: packing.PackedKernel):
 # ---------------------------------------------------------------------------
 
 
-def _currents(x_tm: torch.Tensor, pk: packing.PackedKernel, N: int) -> torch.Tensor:
+def _currents(x_tm: torch.Tensor, pk: packing.PackedKernel, N: int, real: bool = False) -> torch.Tensor:
   """x [T, B, K] (uint8, float32 or PackedSpikes) -> float32 currents [T, B, N] on the eval
-  connection kernels: integer codes for integer-valued rows, the float32 kernel otherwise."""
+  connection kernels: integer codes for integer-valued rows, the float32 kernel otherwise
+  (`real`: rows real-valued by construction -- the float32 kernel without looking at them)."""
   T, B = x_tm.shape[0], x_tm.shape[1]
   K = x_tm.shape[-1]
-  w = pk.int_weight()
+  w = None if real else pk.int_weight()
   if w is not None and isinstance(x_tm, torch.Tensor) and x_tm.dtype == torch.float32:
     if bool(((x_tm == torch.round(x_tm)) & (x_tm >= 0) & (x_tm <= 255)).all()):
       x_tm = x_tm.to(torch.uint8)
@@ -181,20 +182,34 @@ class DenseBlock1(torch.autograd.Function):
 
 class DenseBlock2(torch.autograd.Function):
   """s1 [T, B, K], dropout mask M1 [T, B, K] -> (logits [B, N // group], s2, h2).  Gradients to
-  s1 (through * M1, fused into the input-gradient kernel) and to the transformed kernel wq."""
+  s1 (through * M1, fused into the input-gradient kernel) and to the transformed kernel wq.
+
+  group None: a hidden block -- no vote; -> (s2, None, h2), and the spikes' gradient drives the
+  scan.  real_input: s1 holds real-valued rows (CextNet's dense1 behind the second gate): they are
+  not bit-packed and the currents come from the float32 connection."""
+
+  @classmethod
+  def apply(cls, s1, wq, m1, pk, nrn, surrogate, group, real_input=False):
+    return super().apply(s1, wq, m1, pk, nrn, surrogate, group, real_input)
 
   @staticmethod
-  def forward(ctx, s1, wq, m1, pk, nrn, surrogate, group):
+  def forward(ctx, s1, wq, m1, pk, nrn, surrogate, group, real_input):
     T, B, K = s1.shape
     N = wq.shape[1]
     x1 = s1 * m1 if m1 is not None else s1
-    xin = ops.pack_bits(x1.contiguous()) if pk.int_weight() is not None else x1
-    cur = _currents(xin, pk, N)
+    if real_input:
+      cur = _currents(x1.contiguous(), pk, N, real=True)
+    else:
+      xin = ops.pack_bits(x1.contiguous()) if pk.int_weight() is not None else x1
+      cur = _currents(xin, pk, N)
     h, s = ops.lif_forward_save(cur, nrn)
-    logits = ops.vote(s, group)
     ctx.save_for_backward(h, wq, m1)
     ctx.x1 = x1
     ctx.nrn, ctx.surrogate, ctx.group = nrn, surrogate, group
+    if group is None:
+      ctx.mark_non_differentiable(h)
+      return s, None, h
+    logits = ops.vote(s, group)
     ctx.mark_non_differentiable(s, h)
     return logits, s, h
 
@@ -204,14 +219,17 @@ class DenseBlock2(torch.autograd.Function):
     x1 = ctx.x1
     T, B, K = x1.shape
     N = h.shape[-1]
-    gI = ops.lif_backward(h, ctx.nrn, ctx.surrogate, glogits=glogits, group=ctx.group)
+    if ctx.group is None:
+      gI = ops.lif_backward(h, ctx.nrn, ctx.surrogate, gs=glogits.contiguous())
+    else:
+      gI = ops.lif_backward(h, ctx.nrn, ctx.surrogate, glogits=glogits, group=ctx.group)
     gI2 = gI.reshape(T * B, N)
     gw = ops.dense_weight_grad(x1.reshape(T * B, K), gI2)
     gs1 = None
     if ctx.needs_input_grad[0]:
       gs1 = ops.dense_input_grad(gI2, wq.detach(), None if m1 is None else m1.reshape(T * B, K))
       gs1 = gs1.reshape(T, B, K)
-    return gs1, gw, None, None, None, None, None
+    return gs1, gw, None, None, None, None, None, None
 
 
 def dropout_mask(shape, keep: float, generator: torch.Generator, device) -> torch.Tensor:

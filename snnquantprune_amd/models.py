@@ -15,6 +15,9 @@ with the same call signature as the reference's CextNet
 
 Variable names follow Flax auto-naming in construction order (QuantConv_i,
 BatchNorm_i, QuantDense_i; tcja_load_pretrained_weights.py:19-36).
+
+All three train (`apply(..., train=True, rng=...)`): the training forward
+is each model's `_train_forward`, attached to torch autograd through the parameter leaves.
 """
 
 from __future__ import annotations
@@ -63,13 +66,6 @@ def _layer_bits(cfg, i):
   if "layer_bits" in q and q.layer_bits is not None:
     return int(q.layer_bits[i])
   return q.bits
-
-
-def _require_eval(train):
-  if train:
-    raise NotImplementedError(
-        "training is implemented for DenseSNN and ConvDenseSNN only (DESIGN.md 10, 11); this "
-        "model implements the eval forward pass (train=False)")
 
 
 def _probing(mod, cfg):
@@ -391,7 +387,7 @@ class ConvDenseSNN(nn.Module):
 
 
 class CextNet(nn.Module):
-  """TCJA-SNN, examples/tcja/models.py:31-257 (eval forward).
+  """TCJA-SNN, examples/tcja/models.py:31-257 (eval forward; train=True: _train_forward).
 
   inputs [B, T, H, W, 2] -> (logits [B, num_classes], None).  Variables:
   QuantConv_0..8, BatchNorm_0..4, QuantDense_0..1 in the reference's order
@@ -404,7 +400,8 @@ class CextNet(nn.Module):
 
   def __call__(self, inputs, trgt=None, train: bool = False, rng: Any = None,
                u_state=None, online=False):
-    _require_eval(train)
+    if train:
+      return self._train_forward(inputs, rng, u_state, online)
     cfg = self.config
 
     def qconv1d(features, x):
@@ -505,3 +502,111 @@ class CextNet(nn.Module):
     if probe:
       _sow_density(self, "dense2_out", x)
     return ops.vote(x, 10), None
+
+  def _train_forward(self, inputs, rng, u_state, online):
+    """The training forward of models.py:101-257 (BatchNorm on batch statistics in all five conv
+    blocks, the two TCJA gates, dropout masks with keep probability config.dropout, not rescaled,
+    in front of both dense blocks), attached to torch autograd through the parameter leaves
+    (conv_train.py, tcja_train.py, dense_train.py).  Behind the first gate the activations are
+    real-valued: those blocks run the float32 connection on the multiplied-out product, as eval
+    does under config.gated_int = False.  Channel compaction, the gated integer kernels and the
+    fused kernels are not used."""
+    from . import conv_train as ct
+    from . import dense_train as dt
+    from . import tcja_train as tt
+    if isinstance(inputs, (ops.PackedSpikes, ops.PackedFrames, ops.GatedSpikes)) or not (
+        isinstance(inputs, torch.Tensor) and inputs.ndim == 5
+        and inputs.dtype in (torch.uint8, torch.float32)):
+      raise NotImplementedError("training takes uint8 or float32 [B, T, H, W, C] tensors")
+    if inputs.shape[2] < 32 or inputs.shape[3] < 32:
+      raise NotImplementedError("training CextNet needs frames of at least 32 x 32 (five 2x2 pools "
+                                "leave the read-out an empty raster), got %d x %d"
+                                % (inputs.shape[2], inputs.shape[3]))
+    cfg = self.config
+    if rng is None:
+      raise NotImplementedError("train=True needs an rng (an int seed or a torch.Generator) for "
+                                "the dropout mask; the reference splits it unconditionally")
+    if u_state is not None or online:
+      raise NotImplementedError("training: the online mode and a carried state are not supported")
+    if _probing(self, cfg):
+      raise NotImplementedError("training: density probes are not supported")
+    if "dropout" not in cfg:
+      raise ValueError("train=True needs config.dropout (the keep probability of the dropout "
+                       "mask, models.py:219-224)")
+    qw = cfg.quant.get("weight")
+    if qw is not None and getattr(qw, "func", qw) is not DuQ:
+      raise NotImplementedError("training supports the DuQ weight quantiser or none, not %r" % (qw,))
+    ops._require_gpu(inputs)
+    x = inputs.transpose(0, 1).contiguous()               # models.py:109, [T, B, H, W, C]
+    params = self._root.variables["params"]
+    sowing = self.is_mutable_collection("intermediates")
+    nconv = [0]
+
+    def conv_block(x, i, pool, real_input):
+      conv = QuantConv(features=cfg.channels, kernel_size=(3, 3), padding=((1, 1), (1, 1)),
+                       use_bias=False, dtype=self.dtype, config=cfg.quant, bits=cfg.quant.bits,
+                       g_scale=cfg.quant.g_scale)
+      dyn = cfg.neuron_dynamics(dtype=self.dtype)
+      norm = nn.BatchNorm(use_running_average=False, momentum=0.9, epsilon=1e-5, use_bias=True,
+                          use_scale=True, dtype=self.dtype)
+      surr = dt.surrogate_of(dyn)
+      H, W, cin = x.shape[2], x.shape[3], x.shape[4]
+      geom = conv.geometry((H, W), cin)
+      pk = conv.packed_kernel(cin)
+      wq = dt.transformed_kernel(params["QuantConv_%d" % nconv[0]], pk)
+      nconv[0] += 1
+      y, h, s, mean, var = ct.ConvBlock.apply(
+          x, wq, norm.scale_param(cfg.channels), norm.bias_param(cfg.channels), pk, geom,
+          dyn.neuron(cfg.channels), surr, float(norm.epsilon), i == 0, pool, real_input,
+          i == 0)       # block 0's weight gradient in float64: the most rows, count frames (DESIGN.md 12)
+      norm.update_running(mean, var)
+      if sowing:
+        self.sow("intermediates", "conv%d_h" % i, h)
+        self.sow("intermediates", "conv%d_out" % i, s)
+        self.sow("intermediates", "bn%d_mean" % i, mean)
+        self.sow("intermediates", "bn%d_var" % i, var)
+      return y
+
+    def qconv1d(features, spatial, cin):
+      conv = QuantConv(features=features, kernel_size=[4], padding="SAME", use_bias=False,
+                       dtype=self.dtype, config=cfg.quant, bits=cfg.quant.bits,
+                       g_scale=cfg.quant.g_scale)
+      pk = conv.packed_kernel(cin)
+      wq = dt.transformed_kernel(params["QuantConv_%d" % nconv[0]], pk)
+      nconv[0] += 1
+      return wq, pk, conv.geometry((spatial,), cin)
+
+    for i in range(3):                                    # models.py:111-147
+      x = conv_block(x, i, 2, False)
+    for j in range(2):                                    # models.py:149-187
+      i = 3 + j
+      if sowing:                                          # what a test steps the oracle block on
+        self.sow("intermediates", "conv%d_in" % i, x.detach())
+      x = conv_block(x, i, 1, j == 1)
+      T, C = x.shape[0], x.shape[-1]
+      wq_t, pk_t, geom_t = qconv1d(T, C, T)               # over the channel axis, on [B, C, T]
+      wq_c, pk_c, geom_c = qconv1d(C, T, C)               # over the time axis, on [B, T, C]
+      x, gate = tt.TcjaGate.apply(x, wq_t, wq_c, pk_t, pk_c, geom_t, geom_c)
+      if sowing:
+        self.sow("intermediates", "tcja_gate_%d" % j, gate)
+    x = flatten_channel_major(x)                          # models.py:189-190
+    gen = dt.generator_of(rng, x.device)
+
+    def dense_block(x, n, features, group, real_input):
+      dense = QuantDense(features, use_bias=False, dtype=self.dtype, config=cfg.quant,
+                         bits=cfg.quant.bits, g_scale=cfg.quant.g_scale)
+      dyn = cfg.neuron_dynamics(dtype=self.dtype)
+      surr = dt.surrogate_of(dyn)
+      pk = dense.packed_kernel(x.shape[-1])
+      m = dt.dropout_mask(x.shape, cfg.dropout, gen, x.device)
+      wq = dt.transformed_kernel(params["QuantDense_%d" % n], pk)
+      out, s, h = dt.DenseBlock2.apply(x, wq, m, pk, dyn.neuron(features), surr, group, real_input)
+      if sowing:
+        self.sow("intermediates", "dropout_%d" % n, m)
+        self.sow("intermediates", "dense%d_out" % (n + 1), (out if group is None else s).detach())
+        self.sow("intermediates", "dense%d_h" % (n + 1), h)
+      return out
+
+    x = dense_block(x, 0, cfg.channels * 2 * 2, None, True)         # models.py:192-216
+    logits = dense_block(x, 1, self.num_classes * 10, 10, False)    # models.py:223-255
+    return logits, None

@@ -1620,6 +1620,26 @@ def conv_weight_grad(x: torch.Tensor, gI: torch.Tensor, geom: ConvGeom,
   return gw
 
 
+def conv_weight_grad_f64(x: torch.Tensor, gI: torch.Tensor, geom: ConvGeom) -> torch.Tensor:
+  """conv_weight_grad with the chain over r in float64 (ranges of about 1024 rows summed in order,
+  one rounding to float32): for a layer whose gradient cancels too far for a float32 chain."""
+  x, gI = _f32c(x), _f32c(gI)
+  _require_gpu(x, gI)
+  NB = x.shape[0]
+  g = geom.struct()
+  nbytes = L.lib().snnqp_conv_weight_grad_f64_workspace_bytes(ctypes.byref(g), int(NB))
+  if nbytes < 0:
+    L.check(nbytes)
+  OH, OW = geom.out_hw()
+  assert tuple(x.shape) == (NB, geom.H, geom.W, geom.Cin), (tuple(x.shape), geom)
+  assert tuple(gI.shape) == (NB, OH, OW, geom.Cout), (tuple(gI.shape), geom)
+  ws = torch.empty(nbytes // 8, dtype=torch.float64, device=x.device)
+  gw = torch.empty((geom.KH, geom.KW, geom.Cin, geom.Cout), dtype=torch.float32, device=x.device)
+  L.check(L.lib().snnqp_conv_weight_grad_f64(_ptr(x), _ptr(gI), NB, ctypes.byref(g), _ptr(ws),
+                                             _ptr(gw), _stream()))
+  return gw
+
+
 def conv_input_grad(gI: torch.Tensor, w: torch.Tensor, geom: ConvGeom) -> torch.Tensor:
   """gI [NB, OH, OW, Cout], w HWIO -> gx [NB, H, W, Cin], the chain over r = (kh, kw, co)."""
   gI, w = _f32c(gI), _f32c(w)
@@ -1647,3 +1667,44 @@ def maxpool2x2_backward(s: torch.Tensor, gp: torch.Tensor) -> torch.Tensor:
   gs = torch.empty_like(s)
   L.check(L.lib().snnqp_maxpool2x2_backward(_ptr(s), _ptr(gp), NB, H, W, C, _ptr(gs), _stream()))
   return gs
+
+
+# ---------------------------------------------------------------------------
+# training of CextNet's gated stages (csrc/train_gate.hip)
+# ---------------------------------------------------------------------------
+
+
+def _gate_stage_shapes(x, gate, gp):
+  H, W, C = x.shape[-3:]
+  lead = tuple(x.shape[:-3])
+  assert tuple(gate.shape) == lead + (C,), (x.shape, gate.shape)
+  assert tuple(gp.shape) == lead + (H // 2, W // 2, C), (x.shape, gp.shape)
+  NB = x.numel() // (H * W * C) if H * W * C else 0
+  return NB, H, W, C, lead
+
+
+def gate_pool_grad_gate(x: torch.Tensor, gate: torch.Tensor, gp: torch.Tensor) -> torch.Tensor:
+  """x [..., H, W, C], gate [..., C], gp [..., H/2, W/2, C] -> ggate [..., C] of
+  p = maxpool2x2(x * gate): sum over the windows of gp * x at the first maximum of x * gate, one
+  fmaf chain in ascending (ph, pw)."""
+  x, gate, gp = _f32c(x), _f32c(gate), _f32c(gp)
+  _require_gpu(x, gate, gp)
+  NB, H, W, C, lead = _gate_stage_shapes(x, gate, gp)
+  ggate = torch.empty(lead + (C,), dtype=torch.float32, device=x.device)
+  L.check(L.lib().snnqp_gate_pool_grad_gate(_ptr(x), _ptr(gate), _ptr(gp), NB, H, W, C, _ptr(ggate),
+                                            _stream()))
+  return ggate
+
+
+def gate_pool_grad_input(x: torch.Tensor, gate: torch.Tensor, gp: torch.Tensor,
+                         gm: torch.Tensor) -> torch.Tensor:
+  """-> gx like x: gp * gate routed to the first maximum of x * gate in each window, plus
+  gm [..., C] / (H W), the gradient through spatial_mean(x)."""
+  x, gate, gp, gm = _f32c(x), _f32c(gate), _f32c(gp), _f32c(gm)
+  _require_gpu(x, gate, gp, gm)
+  NB, H, W, C, lead = _gate_stage_shapes(x, gate, gp)
+  assert tuple(gm.shape) == lead + (C,), (x.shape, gm.shape)
+  gx = torch.empty_like(x)
+  L.check(L.lib().snnqp_gate_pool_grad_input(_ptr(x), _ptr(gate), _ptr(gp), _ptr(gm), NB, H, W, C,
+                                             _ptr(gx), _stream()))
+  return gx

@@ -1,6 +1,6 @@
 """Step functions -- mirror of examples/train_utils.py (eval_step :370-390, compute_metrics
 :220-225, mse_loss :210-217, cross_entropy_loss :196-207, create_model :133-134, and for the
-models that train here (DenseSNN, ConvDenseSNN) create_train_state :161-195, weight_decay_fn :228-234 and the
+models that train here (DenseSNN, ConvDenseSNN, CextNet) create_train_state :161-195, weight_decay_fn :228-234 and the
 offline branch of train_step :249-368).  Not ported: the optax learning-rate schedules (any
 step -> lr callable is taken), the online branch, checkpoint writing.
 """
@@ -133,7 +133,7 @@ def train_step(state: TrainState, batch, rng, learning_rate_fn, weight_decay, sm
                loss_type, online=False, burnin=0, return_grads=False):
   """One offline step (train_utils.py:249-368): loss = loss_type(logits, labels, smoothing) +
   weight_decay * weight_decay_fn(params); gradients by the model's backward (DenseSNN:
-  dense_train.py; ConvDenseSNN: conv_train.py), averaged over ranks when torch.distributed is initialised; then one update.
+  dense_train.py; ConvDenseSNN: conv_train.py; CextNet: those and tcja_train.py), averaged over ranks when torch.distributed is initialised; then one update.
   Returns (state, metrics) -- metrics with loss, accuracy, learning_rate and logits --, and the
   gradient tree as a third element when return_grads."""
   if online:

@@ -1,0 +1,379 @@
+"""CextNet training on the GPU, on the small model of tests/cextnet_train_reference.py (16 channels,
+64x64x2 frames, T = 4, B = 2; tests/test_cextnet_train_cpu.py checks through the oracle that it fires,
+gates and has gradients): every block of the saved forward against the oracle stepped on that
+block's sown input with the sown statistics, the gates against the eval TCJA arithmetic, and the HIP
+backward against torch.autograd on the float64 forward fed the saved float32 spikes
+(TorchCextNet64)."""
+import numpy as np
+import pytest
+import torch
+
+from tests import cextnet_train_reference as xr
+
+pytestmark = pytest.mark.gpu
+
+F32, F64 = np.float32, np.float64
+U = 2.0 ** -24
+CASES = [(q, d) for q in (True, False) for d in ("uint8", "float32")]
+_ids = ["%s-%s" % ("q4p90" if q else "float", d) for q, d in CASES]
+
+
+@pytest.fixture(scope="module")
+def dev():
+  assert torch.cuda.is_available()
+  return torch.device("cuda:0")
+
+
+def _np(t):
+  return t.detach().cpu().numpy()
+
+
+def _setup(dev, quantized, dtype="uint8", keep=xr.KEEP, **fx):
+  from snnquantprune_amd import linen as nn
+  from snnquantprune_amd import models, synthetic as syn
+  v, x = xr.fixture(quantized, dtype, **fx)
+  cfg = syn.make_config(bits=xr.BITS, prune_percentage=0.9 if quantized else -1.0, channels=xr.CHANNELS,
+                        tau=xr.TAU, quantized=quantized, dropout=keep, gated_int=False)
+  model = models.CextNet(num_classes=xr.CLASSES, config=cfg)
+  return model, v, nn.tree_from_numpy(v, dev), torch.from_numpy(x).to(dev)
+
+
+def _leaves(tree):
+  return {k: (_leaves(t) if isinstance(t, dict) else t.detach().clone().requires_grad_(True))
+          for k, t in tree.items()}
+
+
+def _run_train(model, variables, x, rng=0):
+  params = _leaves(variables["params"])
+  (logits, _), mut = model.apply({"params": params, "batch_stats": variables["batch_stats"]}, x,
+                                 train=True, rng=rng, mutable=["intermediates", "batch_stats"])
+  return params, logits, {k: v[0] for k, v in mut["intermediates"].items()}, mut["batch_stats"]
+
+
+def _grad_tree(params, prefix=()):
+  out = {}
+  for k, t in params.items():
+    if isinstance(t, dict):
+      out.update(_grad_tree(t, prefix + (k,)))
+    else:
+      out[prefix + (k,)] = None if t.grad is None else _np(t.grad)
+  return out
+
+
+_runs = {}
+
+
+def _run(dev, quantized, dtype):
+  """One training forward and backward per case, shared by the checks (nothing modifies it)."""
+  key = (quantized, dtype)
+  if key not in _runs:
+    from snnquantprune_amd import train_utils as tu
+    model, v, variables, x = _setup(dev, quantized, dtype)
+    params, logits, inter, stats = _run_train(model, variables, x, rng=11)
+    labels = torch.arange(x.shape[0], device=dev) % xr.CLASSES
+    tu.mse_loss(logits, labels).backward()
+    torch.cuda.synchronize()
+    _runs[key] = dict(model=model, v=v, variables=variables, x=x, params=params, logits=logits,
+                      inter={k: _np(t) for k, t in inter.items()}, stats=stats, labels=labels,
+                      grads=_grad_tree(params))
+  return _runs[key]
+
+
+def _block_input(r, i):
+  """What conv block i read, [T, B, H, W, Cin] float32: the frames, the pooled spikes of the block
+  before, or what the model sowed for the two gated stages."""
+  inter = r["inter"]
+  if i == 0:
+    return np.swapaxes(_np(r["x"]).astype(F32), 0, 1)
+  if i >= 3:
+    return inter["conv%d_in" % i]
+  from oracle import snn_oracle as oracle
+  return oracle.max_pool_2x2(inter["conv%d_out" % (i - 1)])
+
+
+# ---- 1. the saved forward, block by block ------------------------------------------------------------
+
+@pytest.mark.parametrize("quantized,dtype", CASES, ids=_ids)
+def test_saved_state_bit_equal_oracle(dev, oracle, quantized, dtype):
+  r = _run(dev, quantized, dtype)
+  inter = r["inter"]
+  T, B, C = xr.T_STEPS, xr.BATCH, xr.CHANNELS
+  want = {"dropout_0", "dropout_1", "tcja_gate_0", "tcja_gate_1", "conv3_in", "conv4_in", "dense1_out",
+          "dense1_h", "dense2_out", "dense2_h"}
+  for i in range(xr.NCONV):
+    want |= {"conv%d_h" % i, "conv%d_out" % i, "bn%d_mean" % i, "bn%d_var" % i}
+  assert set(inter) >= want, want - set(inter)
+  assert inter["conv3_out"].shape == (T, B, 8, 8, C) and inter["conv4_h"].shape == (T, B, 4, 4, C)
+  assert inter["tcja_gate_1"].shape == (T, B, C) and inter["bn4_var"].shape == (T, C)
+  params = r["v"]["params"]
+  mode = "int" if quantized else "fseq"
+  for i in range(xr.NCONV):
+    x_in = _block_input(r, i)
+    blk = xr.oracle_conv_block(x_in, params["QuantConv_%d" % xr.CONV_OF_BLOCK[i]], params["BatchNorm_%d" % i],
+                               quantized, "fseq" if i == 4 else mode,
+                               stats=(inter["bn%d_mean" % i], inter["bn%d_var" % i]))
+    rate = float(inter["conv%d_out" % i].mean())
+    print("conv block", i, "rate", rate)
+    assert 0.02 <= rate <= 0.30
+    np.testing.assert_array_equal(inter["conv%d_h" % i], blk["h"])
+    np.testing.assert_array_equal(inter["conv%d_out" % i], blk["s"])
+    if i >= 3:
+      # the gate is the eval TCJA arithmetic on the sown raster; the gated, pooled raster feeds on
+      y, gate = xr.oracle_gate(inter["conv%d_out" % i], params, i - 3, quantized)
+      np.testing.assert_array_equal(inter["tcja_gate_%d" % (i - 3)], gate)
+      assert 0.0 < gate.min() and gate.max() < 1.0
+      if i == 3:
+        np.testing.assert_array_equal(inter["conv4_in"], oracle.max_pool_2x2(y))
+    elif i == 2:
+      np.testing.assert_array_equal(inter["conv3_in"], oracle.max_pool_2x2(blk["s"]))
+  y, _ = xr.oracle_gate(inter["conv4_out"], params, 1, quantized)
+  m0, m1 = inter["dropout_0"], inter["dropout_1"]
+  for m in (m0, m1):
+    assert set(np.unique(m)) <= {0.0, 1.0} and 0.7 < m.mean() < 1.0
+  flat = oracle.flatten_channel_major(oracle.max_pool_2x2(y)) * m0
+  h1, s1 = xr.oracle_dense_block(flat, params["QuantDense_0"], quantized, "fseq")
+  np.testing.assert_array_equal(inter["dense1_h"], h1)
+  np.testing.assert_array_equal(inter["dense1_out"], s1)
+  assert 0.02 <= float(s1.mean()) <= 0.30
+  h2, s2 = xr.oracle_dense_block(s1 * m1, params["QuantDense_1"], quantized, mode)
+  np.testing.assert_array_equal(inter["dense2_h"], h2)
+  np.testing.assert_array_equal(inter["dense2_out"], s2)
+  logits = s2.astype(F64).mean(0).reshape(B, -1, 10).mean(-1)
+  np.testing.assert_allclose(_np(r["logits"]).astype(F64), logits, rtol=1e-6)
+
+
+@pytest.mark.parametrize("quantized", [True, False], ids=["q4p90", "float"])
+def test_gate_bit_equal_eval_closure(dev, quantized):
+  """The gate the training forward sows is the one the eval TCJA closure computes from the same
+  raster with the same kernels (ops.spatial_mean on the bit-packed raster, QuantConv.__call__), at
+  T = 4, so the convolution along the time axis has more than one step to run over."""
+  from snnquantprune_amd import ops, packing
+  from snnquantprune_amd.flax_qconv import QuantConv
+  from snnquantprune_amd import linen as nn
+  r = _run(dev, quantized, "uint8")
+  cfg = r["model"].config
+
+  class Gate(nn.Module):
+    config: dict = None
+
+    def __call__(self, x_seq, skip):
+      mk = lambda f: QuantConv(features=f, kernel_size=[4], padding="SAME", use_bias=False,   # noqa: E731
+                               config=cfg.quant, bits=cfg.quant.bits, g_scale=cfg.quant.g_scale)
+      for _ in range(skip):                     # burn the auto-names of the layers in front
+        mk(1)
+      T, C = x_seq.shape[0], x_seq.shape[-1]
+      x = ops.spatial_mean(x_seq).transpose(0, 1).contiguous()
+      x_c = x.transpose(1, 2).contiguous()
+      with packing.integer_inputs(False):
+        t_out = mk(T)(x_c)
+        c_out = mk(C)(x)
+      return ops.sigmoid_gate(c_out.transpose(0, 1).contiguous(), t_out.permute(2, 0, 1).contiguous())
+
+  for j in range(2):
+    s = ops.pack_bits(torch.from_numpy(r["inter"]["conv%d_out" % (3 + j)]).to(dev))
+    gate = Gate(config=cfg).apply({"params": r["variables"]["params"]}, s, xr.GATE_CONVS[j][0])
+    np.testing.assert_array_equal(_np(gate), r["inter"]["tcja_gate_%d" % j])
+
+
+# ---- 2. the statistics, and the running ones -----------------------------------------------------------
+
+@pytest.mark.parametrize("quantized,dtype", CASES[:1] + CASES[3:], ids=_ids[:1] + _ids[3:])
+def test_batch_statistics_within_bound_of_float64(dev, oracle, quantized, dtype):
+  """mean and var are float64 accumulations rounded once: within u of the float64 value, plus the
+  float64 accumulation's own error (N 2^-53 of the mean magnitude, charged 1e-12)."""
+  r = _run(dev, quantized, dtype)
+  inter = r["inter"]
+  params = r["v"]["params"]
+  for i in range(xr.NCONV):
+    blk = xr.oracle_conv_block(_block_input(r, i), params["QuantConv_%d" % xr.CONV_OF_BLOCK[i]],
+                               params["BatchNorm_%d" % i], quantized,
+                               "fseq" if i == 4 or not quantized else "int")
+    cur = blk["cur"].astype(F64)
+    flat = cur.reshape(cur.shape[0], -1, cur.shape[-1])
+    mean64 = flat.mean(1)
+    ex2 = (flat * flat).mean(1)
+    var64 = ex2 - mean64 * mean64
+    mean, var = inter["bn%d_mean" % i], inter["bn%d_var" % i]
+    assert mean.dtype == F32 and var.dtype == F32
+    assert (np.abs(mean - mean64) <= U * np.abs(mean64) + 1e-12 * np.abs(flat).mean(1) + 2.0 ** -149).all()
+    assert (np.abs(var - var64) <= U * np.abs(var64) + 1e-12 * ex2 + 2.0 ** -149).all()
+    assert (var >= 0).all()
+
+
+def test_running_statistics_are_the_t_fold_recurrence(dev):
+  r = _run(dev, True, "uint8")
+  m, k = F32(0.9), F32(1) - F32(0.9)
+  assert set(r["stats"]) == {"BatchNorm_%d" % i for i in range(xr.NCONV)}
+  for i in range(xr.NCONV):
+    old = r["v"]["batch_stats"]["BatchNorm_%d" % i]
+    new = r["stats"]["BatchNorm_%d" % i]
+    for name in ("mean", "var"):
+      sown = r["inter"]["bn%d_%s" % (i, name)]
+      ra = old[name].astype(F32)
+      for t in range(xr.T_STEPS):
+        ra = (m * ra + k * sown[t]).astype(F32)
+      np.testing.assert_array_equal(_np(new[name]), ra)
+      assert not np.array_equal(ra, old[name])
+      np.testing.assert_array_equal(_np(r["variables"]["batch_stats"]["BatchNorm_%d" % i][name]), old[name])
+
+
+def test_eval_forward_on_the_folded_statistics_gives_the_same_logits(dev):
+  """T = 1, keep probability 1 (both masks all ones): one set of statistics per block, so they can
+  stand in as running statistics -- the eval forward (config.gated_int = False: the multiplied-out
+  product on the float32 connection, as training runs it) then gives the training forward's logits
+  and read-out spikes bit for bit."""
+  model, v, variables, x = _setup(dev, True, "uint8", keep=1.0, T=1)
+  params, logits, inter, _ = _run_train(model, variables, x, rng=3)
+  assert bool((inter["dropout_0"] == 1).all()) and bool((inter["dropout_1"] == 1).all())
+  stats = {"BatchNorm_%d" % i: {"mean": inter["bn%d_mean" % i][0].clone(), "var": inter["bn%d_var" % i][0].clone()}
+           for i in range(xr.NCONV)}
+  (ev, _), mut = model.apply({"params": variables["params"], "batch_stats": stats}, x, train=False, rng=None,
+                             mutable=["intermediates"])
+  s2 = mut["intermediates"]["dense2_out"][0]
+  s2 = s2.to_dense() if hasattr(s2, "to_dense") else s2
+  np.testing.assert_array_equal(_np(s2).astype(F32), _np(inter["dense2_out"]))
+  np.testing.assert_array_equal(_np(ev), _np(logits))
+  assert float(_np(inter["dense2_out"]).mean()) > 0
+
+
+# ---- 3. gradients against the float64 yardstick ----------------------------------------------------------
+
+@pytest.mark.parametrize("quantized,dtype", CASES, ids=_ids)
+def test_gradients_match_float64_autograd(dev, quantized, dtype):
+  """Every parameter gradient within relative L2 1e-5 of TorchCextNet64 -- the four 1-D kernels of the
+  gates and their a and c included --, by the rule DESIGN.md section 11 holds the conv blocks to:
+  DuQ's c of a 3x3 conv layer in front of a batch-statistics BatchNorm has a gradient that is zero
+  but for eps (the block is invariant to the scale of its currents), so where its relative figure
+  is over 1e-5 the element-wise gamma bound of the weight gradient's chain decides
+  (TorchCextNet64.c_gamma_bound), as in tests/test_conv_train_gpu.py.
+
+  The model runs block 0's weight gradient with its chain in float64
+  (snnqp_conv_weight_grad_f64).  With the float32 chain there -- 32768 rows of count frames against a
+  gI that sums to zero per channel, and a's sum -sum g c W / a^2 cancelling 74-fold on top --
+  QuantConv_0/DuQ_0/a measured 1.37e-4 on MI355X and this test failed at 4-bit / 90 % pruned; the
+  same x and gI multiplied in float64 on the CPU gave 1.6e-6."""
+  from snnquantprune_amd import train_utils as tu
+  r = _run(dev, quantized, dtype)
+  inter = r["inter"]
+  saved = {"hd1": inter["dense1_h"], "sd1": inter["dense1_out"], "hd2": inter["dense2_h"],
+           "sd2": inter["dense2_out"]}
+  for i in range(xr.NCONV):
+    saved["h%d" % i], saved["s%d" % i] = inter["conv%d_h" % i], inter["conv%d_out" % i]
+  m = xr.TorchCextNet64(r["v"]["params"])
+  lg = m.forward(_np(r["x"]), (inter["dropout_0"], inter["dropout_1"]), saved)
+  np.testing.assert_allclose(lg.detach().numpy(), _np(r["logits"]).astype(F64), rtol=1e-6, atol=1e-7)
+  assert m.h_gap < 1e-4, m.h_gap
+  for j in range(2):
+    np.testing.assert_allclose(m.gates[j], inter["tcja_gate_%d" % j], rtol=1e-4)
+  tu.mse_loss(lg, _np(r["labels"])).backward()
+  ref = m.grads()
+  got = r["grads"]
+  worst, over = 0.0, []
+  for (layer, name), want in ref.items():
+    path = (layer, name) if layer.startswith("BatchNorm") else (
+        (layer, "kernel") if name == "kernel" else (layer, "DuQ_0", name))
+    g = got[path]
+    if name in ("a", "c") and not quantized:
+      assert g is None or np.abs(g).max() == 0.0             # a == -1: pass-through
+      continue
+    assert g is not None and np.abs(g).max() > 0, path
+    rel = np.linalg.norm(g.astype(F64) - want) / np.linalg.norm(want)
+    print("%-28s relative L2 %.3g" % ("/".join(path), rel))
+    idx = int(layer.split("_")[1])
+    if rel > 1e-5 and name == "c" and layer.startswith("QuantConv") and idx in xr.CONV_OF_BLOCK:
+      bound = m.c_gamma_bound(xr.CONV_OF_BLOCK.index(idx))
+      err = float(np.abs(g.astype(F64) - want).max())
+      print("%-28s |got - ref| %.3g, gamma bound %.3g, |ref| %.3g" % ("/".join(path), err, bound,
+                                                                      float(np.abs(want).max())))
+      assert err <= bound, "%s: |got - ref| %.3g over the gamma bound %.3g" % ("/".join(path), err, bound)
+      continue
+    worst = max(worst, rel)
+    if rel > 1e-5:
+      over.append("%s: relative L2 %.3g" % ("/".join(path), rel))
+  for path, g in got.items():
+    if path[-1] == "mask":
+      assert g is None or np.abs(g).max() == 0.0
+  print("worst relative L2 %.3g" % worst)
+  assert not over, over
+
+
+# ---- 4. reproducible ---------------------------------------------------------------------------------------
+
+def test_backward_bitwise_reproducible(dev):
+  from snnquantprune_amd import train_utils as tu
+  model, v, variables, x = _setup(dev, True, "uint8", B=3)
+  labels = torch.arange(3, device=dev) % xr.CLASSES
+  runs = []
+  for _ in range(2):
+    params, logits, _, _ = _run_train(model, variables, x, rng=7)
+    tu.cross_entropy_loss(logits, labels).backward()
+    runs.append(_grad_tree(params))
+  for path, g in runs[0].items():
+    if g is None:
+      assert runs[1][path] is None
+    else:
+      assert g.tobytes() == runs[1][path].tobytes(), path
+
+
+# ---- 5. one Adam step ----------------------------------------------------------------------------------------
+
+def test_train_step_adam_matches_torch(dev):
+  from snnquantprune_amd import train_utils as tu
+  model, v, variables, x = _setup(dev, True)
+  cfg = model.config
+  cfg.optimizer = "adam"
+  labels = torch.arange(x.shape[0], device=dev) % xr.CLASSES
+  before = tu._flatten(variables["params"])
+  ref_params = [p.detach().clone() for _, p in before]
+  params, logits, inter, stats = _run_train(model, variables, x, rng=21)
+  loss = tu.mse_loss(logits, labels) + 1e-4 * tu.weight_decay_fn(params)
+  loss.backward()
+  ref_grads = [(p.grad if p.grad is not None else torch.zeros_like(p)) for _, p in tu._flatten(params)]
+  state = tu.create_train_state(variables, cfg, model)
+  state, metrics, grads = tu.train_step(state, {"dvs_matrix": x, "label": labels}, 21,
+                                        lambda step: 1e-3, 1e-4, 0.0, tu.mse_loss, return_grads=True)
+  assert state.step == 1 and metrics["learning_rate"] == 1e-3
+  for (path, g), rg in zip(tu._flatten(grads), ref_grads):
+    assert torch.equal(g, rg), path
+  leaves = [p.clone().requires_grad_(False) for p in ref_params]
+  opt = torch.optim.Adam(leaves, lr=1e-3, eps=1e-8)
+  for p, g in zip(leaves, ref_grads):
+    p.grad = g.clone()
+  opt.step()
+  for (path, p), want in zip(tu._flatten(state.params["params"]), leaves):
+    assert not p.requires_grad
+    assert torch.equal(p, want), path
+  for k, s in stats.items():
+    for n in ("mean", "var"):
+      assert torch.equal(state.batch_stats[k][n], s[n]), (k, n)
+  new = tu.eval_step(state, {"dvs_matrix": x, "label": labels}, None, 0.0, tu.mse_loss)
+  assert new["loss"].shape == () and bool(torch.isfinite(new["loss"]))
+
+
+# ---- 6. it learns ----------------------------------------------------------------------------------------------
+
+def test_twenty_steps_lower_the_loss(dev):
+  """Twenty Adam steps on one fixed batch of 8 class-dependent samples (class c lights half c of
+  the frame)."""
+  from snnquantprune_amd import train_utils as tu
+  model, v, variables, _ = _setup(dev, True)
+  cfg = model.config
+  cfg.optimizer = "adam"
+  g = torch.Generator(device=dev)
+  g.manual_seed(1234)
+  B = 8
+  labels = torch.arange(B, device=dev) % xr.CLASSES
+  rates = torch.full((xr.CLASSES, xr.HW, xr.HW, xr.CIN), 0.1, device=dev)
+  rates[0, :, :xr.HW // 2] = 0.8
+  rates[1, :, xr.HW // 2:] = 0.8
+  x = (torch.rand((B, xr.T_STEPS, xr.HW, xr.HW, xr.CIN), generator=g, device=dev)
+       < rates[labels][:, None]).to(torch.uint8)
+  state = tu.create_train_state(variables, cfg, model)
+  losses = []
+  for step in range(20):
+    state, m = tu.train_step(state, {"dvs_matrix": x, "label": labels}, step, lambda s: 1e-2, 0.0, 0.0,
+                             tu.mse_loss)
+    losses.append(float(m["loss"]))
+  print("losses", losses)
+  assert np.isfinite(losses).all()
+  assert np.mean(losses[-5:]) < np.mean(losses[:5]), losses

@@ -14,6 +14,13 @@ connection launch of conv1 and conv2 with nn.set_train_conv_mfma on and off (alt
 timings each), and conv0's direct-form connection.
 
   python tools/train_step_time.py --conv [--steps 5] [--warmup 2] [--batch 2] [--frames 20] [--hw 128] [--reps 3]
+
+--cext times one CextNet train_step on the reference's geometry (128 x 128 x 2 frames, 128 channels,
+4-bit DuQ, 90 % pruned, default B = 2, T = 20, atan, Adam), the two kernels of csrc/train_gate.hip
+alone on both gated stages' shapes, block 0's weight gradient on the float64 and the float32 chain, and the same step in PyTorch eager float32 autograd; --reps
+timings of each.
+
+  python tools/train_step_time.py --cext [--steps 5] [--warmup 2] [--batch 2] [--frames 20] [--hw 128] [--reps 3]
 """
 import argparse
 import json
@@ -118,6 +125,132 @@ def _eager_conv_loss(params, x, labels, nblocks, keep_mask, tau=2.0, L=7.0, eps=
   return torch.mean(torch.square(logits - oh))
 
 
+def _eager_cext_loss(params, x, labels, keep0, keep1, tau=2.0, L=7.0, eps=1e-5):
+  """The CextNet step as float32 torch autograd: five conv blocks (batch-statistics BatchNorm per
+  time step), the two TCJA gates, 2x2 max pools, flatten, two dropout masks, two dense blocks, vote,
+  MSE."""
+  def wq(leaf):
+    w, a, c, m = leaf["kernel"], leaf["DuQ_0"]["a"], leaf["DuQ_0"]["c"], leaf["prune_0"]["mask"]
+    y = torch.nn.functional.hardtanh(w / a)
+    y = y + (torch.round(y * L) / L - y).detach()
+    return y * c * m
+
+  def scan(cur):
+    u = torch.zeros_like(cur[0])
+    out = []
+    for t in range(cur.shape[0]):
+      u = u + (cur[t] - u) / tau
+      s = _Spike.apply(u - 1.0)
+      u = u * (1 - s.detach())
+      out.append(s)
+    return torch.stack(out)
+
+  def conv1d(v, w):                                      # v [B, L, Cin], w [4, Cin, Cout], SAME
+    vp = torch.nn.functional.pad(v.transpose(1, 2), (1, 2))
+    return torch.nn.functional.conv1d(vp, w.permute(2, 1, 0)).transpose(1, 2)
+
+  def pool(v):
+    T, B = v.shape[:2]
+    p = torch.nn.functional.max_pool2d(v.reshape((T * B,) + tuple(v.shape[2:])), 2)
+    return p.reshape((T, B) + tuple(p.shape[1:]))
+
+  xs = x.transpose(0, 1).to(torch.float32).permute(0, 1, 4, 2, 3)            # [T, B, C, H, W]
+  q = 0
+  for i in range(5):
+    T, B = xs.shape[:2]
+    w = wq(params["QuantConv_%d" % q]).permute(3, 2, 0, 1)
+    q += 1
+    cur = torch.nn.functional.conv2d(xs.reshape((T * B,) + tuple(xs.shape[2:])), w, padding=1)
+    cur = cur.reshape((T, B) + tuple(cur.shape[1:]))
+    mean = cur.mean((1, 3, 4), keepdim=True)
+    var = (cur * cur).mean((1, 3, 4), keepdim=True) - mean * mean
+    bn = params["BatchNorm_%d" % i]
+    cur = (cur - mean) * (torch.rsqrt(var + eps) * bn["scale"][None, None, :, None, None]) \
+        + bn["bias"][None, None, :, None, None]
+    s = scan(cur)
+    if i >= 3:
+      m = s.mean((3, 4)).transpose(0, 1)                                     # [B, T, C]
+      a = conv1d(m.transpose(1, 2), wq(params["QuantConv_%d" % q])).permute(2, 0, 1)
+      b = conv1d(m, wq(params["QuantConv_%d" % (q + 1)])).transpose(0, 1)
+      q += 2
+      s = s * torch.sigmoid(b * a)[:, :, :, None, None]
+    xs = pool(s)
+  flat = xs.reshape(xs.shape[0], xs.shape[1], -1) * keep0
+  s1 = scan(torch.einsum("tbk,kn->tbn", flat, wq(params["QuantDense_0"])))
+  s2 = scan(torch.einsum("tbk,kn->tbn", s1 * keep1, wq(params["QuantDense_1"])))
+  logits = s2.mean(0).reshape(s2.shape[1], -1, 10).mean(-1)
+  oh = torch.nn.functional.one_hot(labels, logits.shape[1]).to(torch.float32)
+  return torch.mean(torch.square(logits - oh))
+
+
+def cext_main(args):
+  from snnquantprune_amd import linen as nn
+  from snnquantprune_amd import models, ops, synthetic as syn, train_utils as tu
+  dev = torch.device("cuda:0")
+  B, T, HW, C = args.batch, args.frames, args.hw, 128
+  cfg = syn.make_config(bits=4, prune_percentage=0.9, channels=C, dropout=0.9)
+  cfg.optimizer = "adam"
+  model = models.CextNet(num_classes=11, config=cfg)
+  v = syn.cextnet_variables(C, T, HW, 110, 0.9)
+  variables = nn.tree_from_numpy(v, dev)
+  x = torch.from_numpy(syn.poisson_counts((B, T, HW, HW, 2), 0.3, seed=941)).to(dev)
+  labels = torch.arange(B, device=dev) % 11
+  batch = {"dvs_matrix": x, "label": labels}
+  box = [tu.create_train_state(variables, cfg, model)]
+
+  def hip_step():
+    box[0], _ = tu.train_step(box[0], batch, 0, lambda s: 1e-4, 0.0, 0.0, tu.mse_loss)
+
+  _time(hip_step, 1, args.warmup)
+  hip_ms = [_time(hip_step, args.steps, 0) for _ in range(args.reps)]
+
+  # the two gate kernels alone, on the shapes of both gated stages
+  kern = {}
+  for j, hw in enumerate((HW // 8, HW // 16)):
+    xs = (torch.rand((T, B, hw, hw, C), device=dev) < 0.2).to(torch.float32)
+    gate = torch.rand((T, B, C), device=dev)
+    gp = torch.randn((T, B, hw // 2, hw // 2, C), device=dev)
+    gm = torch.randn((T, B, C), device=dev)
+    kern["gate%d_grad_gate_ms" % j] = [_time(lambda: ops.gate_pool_grad_gate(xs, gate, gp), 50, 5)
+                                       for _ in range(args.reps)]
+    kern["gate%d_grad_input_ms" % j] = [_time(lambda: ops.gate_pool_grad_input(xs, gate, gp, gm), 50, 5)
+                                        for _ in range(args.reps)]
+    del xs, gate, gp, gm
+
+  # block 0's weight gradient on the step's shapes: the float64 chain the model uses, and the
+  # float32 MFMA chain of the other blocks
+  geom0 = ops.ConvGeom(HW, HW, 2, C, 3, 3, (1, 1), ((1, 1), (1, 1)))
+  x0 = x.transpose(0, 1).reshape(T * B, HW, HW, 2).to(torch.float32).contiguous()
+  g0 = torch.randn((T * B, HW, HW, C), device=dev)
+  kern["conv0_weight_grad_f64_ms"] = [_time(lambda: ops.conv_weight_grad_f64(x0, g0, geom0), 10, 2)
+                                      for _ in range(args.reps)]
+  kern["conv0_weight_grad_f32_ms"] = [_time(lambda: ops.conv_weight_grad(x0, g0, geom0), 10, 2)
+                                      for _ in range(args.reps)]
+  del x0, g0
+
+  eparams = {k: {kk: ({kkk: t.detach().clone().requires_grad_(True) for kkk, t in vv.items()}
+                      if isinstance(vv, dict) else vv.detach().clone().requires_grad_(True))
+                 for kk, vv in leaf.items()} for k, leaf in nn.tree_from_numpy(v, dev)["params"].items()}
+  opt = torch.optim.Adam([t for _, t in tu._flatten(eparams)], lr=1e-4, eps=1e-8)
+  K = (HW >> 5) ** 2 * C
+  keep0 = (torch.rand((T, B, K), device=dev) < 0.9).to(torch.float32)
+  keep1 = (torch.rand((T, B, 4 * C), device=dev) < 0.9).to(torch.float32)
+
+  def eager_step():
+    opt.zero_grad(set_to_none=True)
+    _eager_cext_loss(eparams, x, labels, keep0, keep1).backward()
+    opt.step()
+
+  _time(eager_step, 1, args.warmup)
+  eager_ms = [_time(eager_step, args.steps, 0) for _ in range(args.reps)]
+  print(json.dumps({"workload": "cextnet_train_step", "batch": B, "frames": T, "hw": HW,
+                    "hip_train_step_ms": [round(t, 3) for t in hip_ms],
+                    "eager_torch_train_step_ms": [round(t, 3) for t in eager_ms],
+                    "speedup_vs_eager": round(min(eager_ms) / min(hip_ms), 2),
+                    "samples_per_s": round(B / min(hip_ms) * 1e3, 1),
+                    **{k: [round(t, 4) for t in val] for k, val in kern.items()}}))
+
+
 def conv_main(args):
   from snnquantprune_amd import linen as nn
   from snnquantprune_amd import models, ops, synthetic as syn, train_utils as tu
@@ -215,17 +348,20 @@ def conv_main(args):
 def main():
   ap = argparse.ArgumentParser()
   ap.add_argument("--conv", action="store_true")
+  ap.add_argument("--cext", action="store_true")
   ap.add_argument("--steps", type=int, default=None)
   ap.add_argument("--warmup", type=int, default=None)
   ap.add_argument("--batch", type=int, default=None)
   ap.add_argument("--frames", type=int, default=20)
   ap.add_argument("--hw", type=int, default=128)
-  ap.add_argument("--reps", type=int, default=3, help="--conv: timings of each side of the A/B")
+  ap.add_argument("--reps", type=int, default=3, help="--conv: timings of each side of the A/B; --cext: timings of each figure")
   args = ap.parse_args()
-  dflt = (5, 2, 2) if args.conv else (20, 5, 256)
+  dflt = (5, 2, 2) if args.conv or args.cext else (20, 5, 256)
   args.steps = dflt[0] if args.steps is None else args.steps
   args.warmup = dflt[1] if args.warmup is None else args.warmup
   args.batch = dflt[2] if args.batch is None else args.batch
+  if args.cext:
+    return cext_main(args)
   if args.conv:
     return conv_main(args)
   from snnquantprune_amd import linen as nn
