@@ -244,7 +244,8 @@ typedef struct {
  * compatible: snnqp_weight_t.cout_fire in the struct's former tail padding,
  * snnqp_set_event_half_group, snnqp_conv_event_half_group; training of CextNet's gated stages --
  * snnqp_gate_pool_grad_gate, snnqp_gate_pool_grad_input, snnqp_conv_weight_grad_f64,
- * snnqp_conv_weight_grad_f64_workspace_bytes: new entry points, nothing else moves).
+ * snnqp_conv_weight_grad_f64_workspace_bytes; the batched event front end snnqp_events_bin: new entry
+ * points, nothing else moves).
  * A binding compares snnqp_version()
  * with the SNNQP_VERSION it was written against and refuses a library of another version (_lib.py does). */
 #define SNNQP_VERSION 507
@@ -756,6 +757,37 @@ int snnqp_apply_gate(const void *x, int type, const float *g, int64_t NB, int32_
 int snnqp_events_to_frames(const int32_t *ex, const int32_t *ey, const int32_t *ep,
                            int64_t N, int32_t T, int32_t H, int32_t W, float scale,
                            int32_t *counts, uint8_t *frames_u8, snnqp_stream_t stream);
+/* replaces: preprocess_data_number (examples/input_pipeline.py:142-219) and preprocess_data_time
+ *           (:63-131) over a whole batch, in one launch and without an intermediate: B rows of
+ *           ragged event streams that live on the device -> [B][T] frames of H x W x 2 counts,
+ *           written in the format the event layer reads.  (The division by time_step *
+ *           input_scale of :137 is the caller's.)
+ * mode 0 "number", mode 1 "time".
+ * addr    one word per event: x in bits 0..13, y in bits 14..27, polarity (0 / non-zero) in bit 28;
+ *         read only inside a sample's range, so it may be null when no sample has an event
+ * times   int32 microseconds, one per event; mode 1 only (nullable in mode 0); non-decreasing
+ *         within every sample
+ * offsets int64 [S + 1]: sample s owns events offsets[s] .. offsets[s + 1] - 1
+ * sample  int32 [B]: which sample each batch row decodes (any order, repeats allowed); a value
+ *         outside [0, S) yields zero frames for that row
+ * start   int32 [B]: window origin per row, mode 1 only
+ * out     [B][T] frames of H x W x 2, as out_type SNNQP_U8 / SNNQP_EV4 / SNNQP_EV1 lays a frame out;
+ *         every byte / word is written, empty frames included (the caller zeroes nothing)
+ * flags   nullable device word, OR-ed with SNNQP_FLAG_GT_15 / SNNQP_FLAG_GT_ONE as snnqp_pack_frames does
+ * H, W are the output size: x' = floor(float(x) / scale), the same for y, and an event outside
+ * [0, W) x [0, H) is dropped.  Number mode: with n events in the sample and di = n / T, frame f takes
+ * events [f * di, (f + 1) * di) and the last frame the rest (n < T: all of them).  Time mode: frame f
+ * takes the events with start + f * step_us < t < start + (f + 1) * step_us, both ends strict (an
+ * event on a window edge is in no frame), compared in 64 bits; with unsorted times the counts are
+ * unspecified but every access stays inside the sample.  Counts are exact before they saturate:
+ * SNNQP_U8 at 255 silently, SNNQP_EV4 at 15 and SNNQP_EV1 at 1 with the flag.
+ * SNNQP_EINVAL, checked on the host before anything is launched: bad shapes (H, W in 1 .. 16384),
+ * an unknown mode or out_type, scale <= 0, and in mode 1 step_us <= 0 or a null times / start.
+ * B == 0 or T == 0 returns SNNQP_OK without a launch. */
+int snnqp_events_bin(const uint32_t *addr, const int32_t *times, const int64_t *offsets, int32_t S,
+                     const int32_t *sample, const int32_t *start, int32_t B, int mode, int32_t T,
+                     int32_t step_us, int32_t H, int32_t W, float scale,
+                     void *out, int out_type, int32_t *flags, snnqp_stream_t stream);
 /* replaces: the activation-density probes sown at examples/tcja/models.py:128-142
  *           (consumed by examples/sparsity.py:143-170): non-zero count of each of
  *           NB slices of n elements (C innermost; F32, U8 or BITS). */

@@ -1,0 +1,284 @@
+// Batched event front end (examples/input_pipeline.py:63-139 split_by = "time", :142-219
+// split_by = "number"): one launch bins B rows of ragged, device-resident event streams into
+// [B][T] frames of H x W x 2 counts, written straight in the format the event layer reads
+// (SNNQP_U8, SNNQP_EV4, SNNQP_EV1).  DESIGN.md 13.
+//
+// One workgroup per (row, frame, band).  A band is up to 16 384 consecutive pixels of the frame
+// in index order (pixel = y * W + x), one 32-bit LDS word per pixel: polarity 0 counts in bits
+// 0..15, polarity 1 in bits 16..31 -- a 128 x 128 frame is one band of 64 KiB, two workgroups per
+// CU.  Bands are cut in pixels, not rows, so every band begins on a 16-pixel boundary: a whole
+// EV1 word, 16 EV4 bytes, 32 uint8 bytes, whatever W is.  A frame of several bands (ASL-DVS,
+// 240 x 240: four) has each band's workgroup walk the same slice and keep its own pixels.
+//
+// The frame's events are a contiguous slice of the sample: arithmetic in number mode, two
+// 64-ary searches over the sample's sorted times in time mode (waves 0 and 1, one bound each,
+// three rounds of one load for 2^18 events).  The slice is streamed 16 bytes per lane and
+// counted with LDS integer atomics (integer adds commute: the result is bit-reproducible).
+// 16-bit halves stay exact because the slice is walked in chunks of 65 280 events with a clamp
+// of every half to 255 between chunks: min(min(a, 255) + b, 255) = min(a + b, 255), and every
+// format saturates at or below 255 and flags above 15 / above 1, which the clamp preserves.
+#include "kernels.h"
+
+#include <cmath>
+#include <mutex>
+
+namespace snnqp {
+
+typedef uint32_t v4u __attribute__((ext_vector_type(4)));
+typedef uint32_t v2u __attribute__((ext_vector_type(2)));
+
+constexpr int EB_BAND_PIX = 16384;        // pixels (LDS words) of a band: 64 KiB
+constexpr int EB_CHUNK = 65280;           // 65535 - 255, a multiple of 4
+
+struct EventsBinArgs {
+  const uint32_t *addr;
+  const int32_t *times;
+  const int64_t *offsets;
+  const int32_t *sample;
+  const int32_t *start;
+  void *out;
+  int32_t *flags;
+  float scale;
+  int32_t S, T, step_us, H, W, mode, nbands;
+};
+
+// First index i of [a, b) with times[i] > key (STRICT) or >= key: every round the wave probes 64
+// evenly spaced elements and keeps the stretch in front of the first that satisfies the test.
+// On unsorted times the answer means nothing, but a and b never leave the range they came with.
+template <bool STRICT>
+__device__ __forceinline__ int64_t first_index(const int32_t *__restrict__ times, int64_t a, int64_t b,
+                                               int64_t key, int lane) {
+  while (a < b) {
+    const int64_t step = (b - a + 63) >> 6;
+    const int64_t idx = a + (lane + 1) * step - 1;
+    bool hit = true;
+    if (idx < b) {
+      const int64_t t = times[idx];
+      hit = STRICT ? t > key : t >= key;
+    }
+    const uint64_t m = __ballot(hit);
+    if (m == 0) return b;
+    const int k = __builtin_ctzll(m);
+    const int64_t probe = a + (k + 1) * step - 1;      // satisfies the test, or lies beyond b
+    a += k * step;
+    b = probe < b ? probe : b;
+  }
+  return a;
+}
+
+__device__ __forceinline__ uint32_t sat_half(uint32_t v, uint32_t cap) { return v < cap ? v : cap; }
+
+template <int OUT>
+__global__ void __launch_bounds__(512)
+events_bin_kernel(const EventsBinArgs a) {
+  extern __shared__ __attribute__((aligned(16))) uint32_t hist[];
+  __shared__ int64_t range[2];
+  const int tid = threadIdx.x, nth = blockDim.x, lane = tid & 63, wave = tid >> 6;
+  const int64_t blk = blockIdx.x;
+  const int band = (int)(blk % a.nbands);
+  const int64_t fi = blk / a.nbands;                    // b * T + f
+  const int f = (int)(fi % a.T);
+  const int b = (int)(fi / a.T);
+  const int32_t npix = a.H * a.W;
+  const int32_t p0 = band * EB_BAND_PIX;
+  const int32_t np = npix - p0 < EB_BAND_PIX ? npix - p0 : EB_BAND_PIX;
+  const int32_t nalloc = (np + 15) & ~15;               // whole EV1 words; the padding stays zero
+
+  for (int i = tid * 4; i < nalloc; i += nth * 4) *(v4u *)(hist + i) = (v4u){0, 0, 0, 0};
+
+  // the sample's events, then the frame's slice of them
+  const int32_t s = a.sample[b];
+  int64_t o0 = 0, o1 = 0;
+  if (s >= 0 && s < a.S) {
+    o0 = a.offsets[s];
+    o1 = a.offsets[s + 1];
+    if (o1 < o0) o1 = o0;
+  }
+  int64_t e0, e1;
+  if (a.mode == 0) {
+    const int64_t di = (o1 - o0) / a.T;                 // n < T: everything in the last frame
+    e0 = o0 + f * di;
+    e1 = f == a.T - 1 ? o1 : e0 + di;
+  } else {
+    if (wave < 2) {
+      const int64_t lo = (int64_t)a.start[b] + (int64_t)f * a.step_us;
+      const int64_t r = wave == 0 ? first_index<true>(a.times, o0, o1, lo, lane)             // lo < t
+                                  : first_index<false>(a.times, o0, o1, lo + a.step_us, lane);  // t < hi
+      if (lane == 0) range[wave] = r;
+    }
+    __syncthreads();
+    e0 = range[0];
+    e1 = range[1];
+  }
+  __syncthreads();                                      // the histogram is zero
+
+  const bool unit = a.scale == 1.0f;
+  const float scale = a.scale;
+  const int32_t H = a.H, W = a.W;
+  auto one = [&](uint32_t w) {
+    int32_t x = (int32_t)(w & 0x3FFFu), y = (int32_t)((w >> 14) & 0x3FFFu);
+    if (!unit) {
+      x = (int32_t)fminf(floorf((float)x / scale), 65536.0f);
+      y = (int32_t)fminf(floorf((float)y / scale), 65536.0f);
+    }
+    if (x >= W || y >= H) return;                       // (never negative: scale > 0)
+    const uint32_t pb = (uint32_t)(y * W + x - p0);
+    if (pb < (uint32_t)np) atomicAdd(&hist[pb], (w >> 28) & 1u ? 0x10000u : 1u);
+  };
+  auto four = [&](const v4u &w) { one(w.x); one(w.y); one(w.z); one(w.w); };
+
+  for (int64_t c0 = e0; c0 < e1; c0 += EB_CHUNK) {
+    const int64_t c1 = c0 + EB_CHUNK < e1 ? c0 + EB_CHUNK : e1;
+    // up to three events in front of the first 16-byte boundary, whole 16-byte words, the rest
+    int64_t h = c0 + ((4 - (int)(((uintptr_t)(a.addr + c0) >> 2) & 3)) & 3);
+    if (h > c1) h = c1;
+    const int64_t nv = (c1 - h) >> 2;
+    if (c0 + tid < h) one(a.addr[c0 + tid]);
+    const v4u *bv = (const v4u *)(a.addr + h);
+    int64_t i = tid;
+    for (; i + 3 * nth < nv; i += 4 * nth) {            // four loads in flight per lane
+      const v4u w0 = bv[i], w1 = bv[i + nth], w2 = bv[i + 2 * nth], w3 = bv[i + 3 * nth];
+      four(w0);
+      four(w1);
+      four(w2);
+      four(w3);
+    }
+    for (; i < nv; i += nth) four(bv[i]);
+    const int64_t t0 = h + nv * 4;
+    if (t0 + tid < c1) one(a.addr[t0 + tid]);
+    if (c1 < e1) {                                      // more to come: make room in the halves
+      __syncthreads();
+      for (int j = tid * 4; j < nalloc; j += nth * 4) {
+        v4u w = *(v4u *)(hist + j);
+#pragma unroll
+        for (int k = 0; k < 4; ++k) w[k] = sat_half(w[k] & 0xFFFFu, 255u) | (sat_half(w[k] >> 16, 255u) << 16);
+        *(v4u *)(hist + j) = w;
+      }
+      __syncthreads();
+    }
+  }
+  __syncthreads();
+
+  // ---- the frame's band, in the wire format ------------------------------------------------------
+  uint32_t gt = 0;
+  if constexpr (OUT == SNNQP_U8) {
+    uint8_t *dst = (uint8_t *)a.out + (fi * npix + p0) * 2;
+    const int nbody = ((uintptr_t)dst & 7) == 0 ? (np & ~3) : 0;
+    auto pair = [](uint32_t w) { return sat_half(w & 0xFFFFu, 255u) | (sat_half(w >> 16, 255u) << 8); };
+    for (int i = tid * 4; i < nbody; i += nth * 4) {    // four pixels, eight bytes per lane
+      const v4u w = *(const v4u *)(hist + i);
+      *(v2u *)(dst + 2 * i) = (v2u){pair(w.x) | (pair(w.y) << 16), pair(w.z) | (pair(w.w) << 16)};
+    }
+    for (int i = nbody + tid; i < np; i += nth) {
+      const uint32_t w = hist[i];
+      dst[2 * i] = (uint8_t)sat_half(w & 0xFFFFu, 255u);
+      dst[2 * i + 1] = (uint8_t)sat_half(w >> 16, 255u);
+    }
+  } else if constexpr (OUT == SNNQP_EV4) {
+    uint8_t *dst = (uint8_t *)a.out + (fi * npix + p0);
+    const int nbody = ((uintptr_t)dst & 3) == 0 ? (np & ~3) : 0;
+    auto nib = [&](uint32_t w) {
+      const uint32_t c0 = w & 0xFFFFu, c1 = w >> 16;
+      gt |= (c0 > 15u) | (c1 > 15u);
+      return sat_half(c0, 15u) | (sat_half(c1, 15u) << 4);
+    };
+    for (int i = tid * 4; i < nbody; i += nth * 4) {    // four pixels, four bytes per lane
+      const v4u w = *(const v4u *)(hist + i);
+      *(uint32_t *)(dst + i) = nib(w.x) | (nib(w.y) << 8) | (nib(w.z) << 16) | (nib(w.w) << 24);
+    }
+    for (int i = nbody + tid; i < np; i += nth) dst[i] = (uint8_t)nib(hist[i]);
+  } else {
+    // EV1: element (pixel * 2 + polarity) is bit (i & 31) of word (i >> 5), 16 pixels a word.  A
+    // lane gathers the 8 bits of four pixels, the four lanes of a word OR theirs together (the
+    // units of a word are in the loop together: nalloc / 4 and the stride are multiples of 4).
+    const int64_t fwords = ((int64_t)npix + 15) >> 4;
+    uint32_t *dst = (uint32_t *)a.out + fi * fwords + (p0 >> 4);
+    for (int u = tid; u < nalloc / 4; u += nth) {
+      const v4u w = *(const v4u *)(hist + 4 * u);
+      uint32_t bits = 0;
+#pragma unroll
+      for (int k = 0; k < 4; ++k) {
+        const uint32_t c0 = w[k] & 0xFFFFu, c1 = w[k] >> 16;
+        gt |= (c0 > 1u) | (c1 > 1u);
+        bits |= ((c0 ? 1u : 0u) | (c1 ? 2u : 0u)) << (2 * k);
+      }
+      uint32_t word = bits << (8 * (lane & 3));
+      word |= (uint32_t)__shfl_xor((int)word, 1);
+      word |= (uint32_t)__shfl_xor((int)word, 2);
+      if ((lane & 3) == 0) dst[u >> 2] = word;
+    }
+  }
+  if constexpr (OUT != SNNQP_U8) {
+    if (a.flags && __ballot(gt != 0) != 0 && lane == 0)
+      atomicOr(a.flags, OUT == SNNQP_EV4 ? SNNQP_FLAG_GT_15 : SNNQP_FLAG_GT_ONE);
+  }
+}
+
+// more than 64 KiB of LDS (the 64 KiB band plus the two slice bounds) needs the limit raised, once per
+// device and kernel
+template <int OUT>
+static int events_bin_launch(const EventsBinArgs &a, int64_t grid, int threads, size_t lds, hipStream_t st) {
+  if (lds + 64 > 65536) {
+    static std::once_flag once[MAX_DEVICES];
+    static hipError_t raised[MAX_DEVICES];
+    const int dev = stream_device(st);
+    SNNQP_REQUIRE(dev >= 0 && dev < MAX_DEVICES, SNNQP_EHIP,
+                  "events_bin: device %d is outside the library's tables (%d devices)", dev, MAX_DEVICES);
+    std::call_once(once[dev], [dev] {
+      DeviceGuard guard(dev);
+      raised[dev] = !guard.ok ? hipErrorInvalidDevice
+                              : hipFuncSetAttribute((const void *)events_bin_kernel<OUT>,
+                                                    hipFuncAttributeMaxDynamicSharedMemorySize, EB_BAND_PIX * 4);
+      if (raised[dev] != hipSuccess) (void)hipGetLastError();
+    });
+    SNNQP_REQUIRE(raised[dev] == hipSuccess, SNNQP_EHIP, "events_bin: cannot raise the LDS limit on device %d: %s",
+                  dev, hipGetErrorString(raised[dev]));
+  }
+  hipLaunchKernelGGL(events_bin_kernel<OUT>, dim3((unsigned)grid), dim3(threads), lds, st, a);
+  SNNQP_CHECK_LAUNCH("events_bin_kernel");
+  return SNNQP_OK;
+}
+
+}  // namespace snnqp
+
+using namespace snnqp;
+
+extern "C" {
+
+int snnqp_events_bin(const uint32_t *addr, const int32_t *times, const int64_t *offsets, int32_t S,
+                     const int32_t *sample, const int32_t *start, int32_t B, int mode, int32_t T,
+                     int32_t step_us, int32_t H, int32_t W, float scale,
+                     void *out, int out_type, int32_t *flags, snnqp_stream_t stream) {
+  SNNQP_REQUIRE(S >= 0 && B >= 0 && T >= 0 && H > 0 && W > 0 && H <= 16384 && W <= 16384, SNNQP_EINVAL,
+                "events_bin: bad shape (S %d, B %d, T %d, H %d, W %d; H, W <= 16384)", S, B, T, H, W);
+  SNNQP_REQUIRE(mode == 0 || mode == 1, SNNQP_EINVAL, "events_bin: mode must be 0 (number) or 1 (time)");
+  SNNQP_REQUIRE(std::isfinite(scale) && scale > 0.0f, SNNQP_EINVAL, "events_bin: scale must be positive");
+  SNNQP_REQUIRE(out_type == SNNQP_U8 || out_type == SNNQP_EV4 || out_type == SNNQP_EV1, SNNQP_EINVAL,
+                "events_bin: out_type must be SNNQP_U8, SNNQP_EV4 or SNNQP_EV1");
+  if (mode == 1) {
+    SNNQP_REQUIRE(step_us > 0, SNNQP_EINVAL, "events_bin: step_us must be positive in time mode");
+    SNNQP_REQUIRE(times && start, SNNQP_EINVAL, "events_bin: time mode needs times and start");
+  }
+  if (B == 0 || T == 0) return SNNQP_OK;
+  // (addr may be null when no sample has an event: the kernel reads it only inside a sample's range)
+  SNNQP_REQUIRE(offsets && sample && out, SNNQP_EINVAL, "events_bin: null argument");
+  SNNQP_REQUIRE(((uintptr_t)addr & 3) == 0 && (out_type != SNNQP_EV1 || ((uintptr_t)out & 3) == 0), SNNQP_EINVAL,
+                "events_bin: addr and EV1 frames must be 4-byte aligned");
+  const int32_t npix = H * W;
+  EventsBinArgs a;
+  a.addr = addr; a.times = times; a.offsets = offsets; a.sample = sample; a.start = start;
+  a.out = out; a.flags = flags; a.scale = scale;
+  a.S = S; a.T = T; a.step_us = step_us; a.H = H; a.W = W; a.mode = mode;
+  a.nbands = (npix + EB_BAND_PIX - 1) / EB_BAND_PIX;
+  const int64_t grid = (int64_t)B * T * a.nbands;
+  SNNQP_REQUIRE(grid < (1ll << 31), SNNQP_EINVAL, "events_bin: %lld workgroups, grid too large", (long long)grid);
+  const int32_t band = npix < EB_BAND_PIX ? npix : EB_BAND_PIX;
+  const size_t lds = (size_t)((band + 15) & ~15) * 4;
+  const int threads = band <= 4096 ? 256 : 512;
+  hipStream_t st = (hipStream_t)stream;
+  if (out_type == SNNQP_U8) return events_bin_launch<SNNQP_U8>(a, grid, threads, lds, st);
+  if (out_type == SNNQP_EV4) return events_bin_launch<SNNQP_EV4>(a, grid, threads, lds, st);
+  return events_bin_launch<SNNQP_EV1>(a, grid, threads, lds, st);
+}
+
+}  // extern "C"

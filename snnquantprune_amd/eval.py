@@ -103,7 +103,10 @@ def evaluate_metrics(config, workdir: str, *, model=None, source=None, device=No
     from . import models
     model = create_model(model_cls=getattr(models, config.model),
                          num_classes=config.num_classes, config=config)
-  image_size = source["dvs_matrix"].shape[-2]                      # eval.py:98
+  if input_pipeline.is_event_source(source):                       # the scaled sensor (input_pipeline.py:87)
+    image_size = int(int(source["sensor_size"][-1]) // config.get("resolution_scale", 1))
+  else:
+    image_size = source["dvs_matrix"].shape[-2]                    # eval.py:98
   state = restore_checkpoint(None, workdir, model.apply, device)   # eval.py:104
   if state is None:
     key = torch.Generator()

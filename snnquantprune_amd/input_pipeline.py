@@ -1,8 +1,14 @@
-"""Eval-side input pipeline -- mirror of examples/input_pipeline.py for datasets that are
-already event-count frames in host memory (a `.npz` with `dvs_matrix` [N, T, H, W, 2]
-uint8 and `label` [N], e.g. synthetic Poisson frames: there is no tfds and no network on
-the boxes this runs on; turning raw events into such frames is `ops.events_to_frames`,
-input_pipeline.py:142-219).
+"""Input pipeline -- mirror of examples/input_pipeline.py for two kinds of source (there is no
+tfds and no network on the boxes this runs on):
+
+  * a FRAME source: event-count frames in host memory (a `.npz` with `dvs_matrix`
+    [N, T, H, W, 2] uint8 and `label` [N], e.g. synthetic Poisson frames), eval only, fed
+    through the host ring of feed.py;
+  * an EVENT source: the raw recordings (`addrs` [E, 3] x, y, polarity; `times` [E]
+    microseconds; `offsets` [N + 1]; `label` [N]; `sensor_size`), eval and training.  The
+    rank's slice goes resident on the device as an `ops.EventSet` and every batch is one
+    `ops.events_bin` launch (preprocess_data_number, :142-219, or preprocess_data_time,
+    :63-139): nothing crosses PCIe per batch, so there is no host ring.
 
 What is kept from the reference:
   * every PROCESS takes a contiguous slice of the split, `split_size = N // processes`,
@@ -10,7 +16,7 @@ What is kept from the reference:
     GPU here, so that slice is also the device shard (:38-46);
   * eval batches of `config.eval_batch_size // processes`, remainder dropped, repeated
     (:321-329);
-  * two batches prefetched towards the device (:17-27) -- `feed.DeviceFeeder`.
+  * two batches prefetched towards the device (:17-27) -- `feed.DeviceFeeder` (frame sources).
 What is new: `config.feed_format` ("u8" | "ev1" | "ev4") picks the wire format of the
 frames (include/snnqp.h); with `cache` the slice is packed once into page-locked memory.
 """
@@ -26,12 +32,32 @@ from . import _lib as L
 from . import feed, ops
 
 FEED_FORMATS = {"u8": None, "ev1": L.EV1, "ev4": L.EV4}
+EVENT_KEYS = ("addrs", "times", "offsets", "label", "sensor_size")
+
+
+def is_event_source(source) -> bool:
+  return all(k in source for k in EVENT_KEYS)
+
+
+def _open_source(source):
+  """The arrays of a source as a dict, unvalidated (a `.npz` path is read)."""
+  if isinstance(source, str):
+    with np.load(source) as z:
+      return {k: z[k] for k in z.files}
+  return source
 
 
 def load_source(source) -> Dict[str, np.ndarray]:
-  if isinstance(source, str):
-    with np.load(source) as z:
-      source = {k: z[k] for k in z.files}
+  source = _open_source(source)
+  if is_event_source(source):
+    off, y = np.asarray(source["offsets"]).reshape(-1), np.asarray(source["label"]).reshape(-1)
+    if off.shape[0] != y.shape[0] + 1:
+      raise ValueError("an event source needs offsets [N + 1] for its N labels, got %s / %s"
+                       % (off.shape, y.shape))
+    hw = np.asarray(source["sensor_size"]).reshape(-1)
+    return {"addrs": np.asarray(source["addrs"]), "times": np.asarray(source["times"]),
+            "offsets": off.astype(np.int64), "label": y.astype(np.int8),
+            "sensor_size": np.array([int(hw[0]), int(hw[-1])], np.int64)}
   x, y = np.asarray(source["dvs_matrix"]), np.asarray(source["label"])
   if x.ndim != 5 or x.shape[-1] != 2 or x.shape[0] != y.shape[0]:
     raise ValueError("dvs_matrix must be [N, T, H, W, 2] with one label per sample, got %s / %s"
@@ -39,9 +65,130 @@ def load_source(source) -> Dict[str, np.ndarray]:
   return {"dvs_matrix": x, "label": y.astype(np.int8)}            # :271 casts labels to int8
 
 
+def _cfg(config, key, default=None):
+  if hasattr(config, "get"):
+    return config.get(key, default)
+  return getattr(config, key, default)
+
+
+class EventPlan:
+  """Everything about an event split that is decided on the host, without a device: the frame
+  geometry, the decoder's constants and, per batch, which samples are decoded and from which
+  window origin.  Config keys are the reference's: split_by, num_frames, resolution_scale,
+  time_step (ms), input_scale, train_chunk_size / test_chunk_size (ms), batch_size /
+  eval_batch_size, seed, feed_format.
+
+  Where this differs from the reference, knowingly:
+    * the window origin of split_by = "time" is uniform on [t_min, max(t_min, t_max - 2 * chunk *
+      1000)] as there (:76-85) -- a 62-bit draw reduced modulo the range --, but from a
+      torch.Generator seeded with config.seed (+ rank); the reference draws it with TensorFlow's
+      global generator, at eval as well (:268-275, shuffle=True), which cannot be reproduced.
+      The eval split re-seeds at the start of every pass, so an eval is reproducible;
+    * the train split takes a fresh permutation of the rank's slice per epoch from the same
+      generator; the reference shuffles through a buffer of 16 batches with seed 0 (:323), an
+      order that depends on the buffer and is not reproduced either;
+    * counts saturate at 255 (uint8), as ops.events_to_frames' do; the reference keeps int32.
+  """
+
+  def __init__(self, config, sensor_size, counts_per_rank: int, train: bool, rank: int = 0, world: int = 1):
+    self.train = bool(train)
+    self.split_by = _cfg(config, "split_by", "number")
+    if self.split_by not in ("number", "time"):
+      raise ValueError("split_by must be 'number' or 'time', got %r" % (self.split_by,))
+    self.T = int(_cfg(config, "num_frames"))
+    self.scale = float(_cfg(config, "resolution_scale", 1))
+    hw = np.asarray(sensor_size).reshape(-1)
+    self.H, self.W = int(int(hw[0]) // self.scale), int(int(hw[-1]) // self.scale)   # :87, :156
+    name = _cfg(config, "feed_format", "u8")
+    if name not in FEED_FORMATS:
+      raise ValueError("feed_format must be one of %s, got %r" % (sorted(FEED_FORMATS), name))
+    self.fmt = FEED_FORMATS[name]
+    self.divisor = None                                            # float32 batches: counts / divisor
+    self.step_us = self.chunk_ms = None
+    if self.split_by == "time":
+      time_step = _cfg(config, "time_step")
+      if time_step != int(time_step) or int(time_step) <= 0:
+        raise ValueError("time_step must be a positive whole number of ms, got %r" % (time_step,))
+      self.step_us = int(time_step) * 1000                         # :93-94
+      self.chunk_ms = int(_cfg(config, "train_chunk_size" if train else "test_chunk_size"))  # :264, :273
+      product = float(time_step) * float(_cfg(config, "input_scale", 1))                     # :137
+      if product != 1.0:
+        self.divisor = np.float32(product)
+    if self.fmt is not None and (self.divisor is not None or train):
+      raise ValueError("feed_format %r holds integer counts: %s needs feed_format 'u8'"
+                       % (name, "the training split" if train else "time_step * input_scale != 1"))
+    total = int(_cfg(config, "batch_size" if train else "eval_batch_size"))
+    self.per = total // world                                      # :333, :337
+    self.n = int(counts_per_rank)
+    if self.per < 1 or self.n < self.per:
+      raise ValueError("%s %d over %d processes needs at least %d samples per process, the split has %d"
+                       % ("batch_size" if train else "eval_batch_size", total, world, max(self.per, 1), self.n))
+    self.nb = self.n // self.per                                   # drop_remainder=True
+    self.seed = int(_cfg(config, "seed", 0)) + int(rank)
+    self.gen = torch.Generator()
+    self.gen.manual_seed(self.seed)
+
+  def start_range(self, t_min, t_max):
+    """[tbegin, tend] of the window origin, both inclusive (:76-77)."""
+    t_min, t_max = np.asarray(t_min, np.int64), np.asarray(t_max, np.int64)
+    return t_min, np.maximum(t_min, t_max - 2 * self.chunk_ms * 1000)
+
+  def draw_starts(self, t_min, t_max) -> np.ndarray:
+    """One origin per row, uniform on start_range (tf.random.uniform(minval=tbegin, maxval=tend + 1))."""
+    lo, hi = self.start_range(t_min, t_max)
+    r = torch.randint(0, 1 << 62, (lo.shape[0],), generator=self.gen, dtype=torch.int64).numpy()
+    return (lo + r % (hi - lo + 1)).astype(np.int64)
+
+  def batches(self, t_min=None, t_max=None):
+    """Endless (indices, starts) pairs: int64 sample indices within the rank's slice, and the
+    window origins of those rows (None for split_by = "number")."""
+    while True:
+      if self.train:
+        order = torch.randperm(self.n, generator=self.gen).numpy()
+      else:
+        order = np.arange(self.n)
+        self.gen.manual_seed(self.seed)                            # every eval pass draws the same origins
+      for i in range(self.nb):
+        idx = order[i * self.per:(i + 1) * self.per]
+        starts = self.draw_starts(np.asarray(t_min)[idx], np.asarray(t_max)[idx]) \
+            if self.split_by == "time" else None
+        yield idx, starts
+
+
+def create_event_split(data, config, train: bool, rank: int = 0, world: int = 1,
+                       device=None) -> Iterator[Dict[str, Any]]:
+  """The batches of an event source, decoded on `device` (see EventPlan for the rules)."""
+  device = torch.device("cuda" if device is None else device)
+  n = data["label"].shape[0]
+  split = n // world                                               # :245-254
+  lo = rank * split
+  plan = EventPlan(config, data["sensor_size"], split, train, rank, world)
+  off = data["offsets"]
+  e0, e1 = int(off[lo]), int(off[lo + split])
+  events = ops.EventSet(data["addrs"][e0:e1], data["times"][e0:e1], off[lo:lo + split + 1] - e0,
+                        data["sensor_size"], device=device)
+  labels = torch.from_numpy(np.ascontiguousarray(data["label"][lo:lo + split])).to(device)
+
+  # a device divisor: torch turns a division by a host scalar into a multiplication by its reciprocal
+  divisor = None if plan.divisor is None else torch.full((), float(plan.divisor), dtype=torch.float32, device=device)
+
+  def gen():
+    for idx, starts in plan.batches(events.t_min, events.t_max):
+      x = ops.events_bin(events, idx, plan.T, plan.H, plan.W, mode=plan.split_by, start=starts,
+                         step_us=plan.step_us, scale=plan.scale, fmt=plan.fmt)
+      if plan.divisor is not None:
+        x = x.to(torch.float32) / divisor                          # :134-137
+      yield {"dvs_matrix": x, "label": labels[torch.from_numpy(idx).to(device)]}
+  return gen()
+
+
 def create_split(source, config, train: bool, cache: bool, rank: int = 0, world: int = 1,
-                 pin: bool = False) -> Iterator[Dict[str, Any]]:
-  """Host-side iterator of this process's batches (input_pipeline.py:222-345)."""
+                 pin: bool = False, device=None) -> Iterator[Dict[str, Any]]:
+  """Iterator of this process's batches (input_pipeline.py:222-345): host batches of a frame
+  source, device batches of an event source."""
+  source = _open_source(source)
+  if is_event_source(source):
+    return create_event_split(load_source(source), config, train, rank, world, device)
   if train:
     raise NotImplementedError("the training split (shuffle, augmentation) is out of scope")
   data = load_source(source)
@@ -85,6 +232,9 @@ def create_input_iter(source, config, train: bool, cache: bool, rank: int = 0, w
   """create_input_iter of input_pipeline.py:17-27: the split, prefetched two batches deep
   to this process's device."""
   device = torch.device("cuda" if torch.cuda.is_available() else "cpu") if device is None else device
+  source = _open_source(source)
+  if is_event_source(source):       # decoded on the device: nothing to prefetch
+    return create_event_split(load_source(source), config, train, rank, world, device)
   ds = create_split(source, config, train=train, cache=cache, rank=rank, world=world,
                     pin=torch.device(device).type == "cuda")
   return feed.DeviceFeeder(ds, device, 2)

@@ -1468,6 +1468,155 @@ def events_to_frames(x, y, p, T: int, H: int, W: int, scale: float = 1.0, as_u8=
   return u8 if as_u8 else counts
 
 
+EVENT_COORD_MAX = (1 << 14) - 1
+EVENT_MODES = {"number": 0, "time": 1}
+
+
+def _host_array(a, name):
+  import numpy as np
+  if isinstance(a, torch.Tensor):
+    a = a.detach().cpu().numpy()
+  a = np.asarray(a)
+  if a.size == 0:
+    a = a.astype(np.int64)
+  if a.dtype.kind not in "iu":
+    raise ValueError("%s must be integers, got %s" % (name, a.dtype))
+  return a
+
+
+class EventSet:
+  """The raw DVS events of a split, resident on `device` for `events_bin`: S ragged samples back to
+  back, sample s owning events offsets[s] .. offsets[s + 1] - 1.
+
+  addrs [N, 3] integer (x, y, polarity) rows are packed into one word per event (x in bits 0..13,
+  y in bits 14..27, polarity != 0 in bit 28; a coordinate outside 0..16383 is refused), `times`
+  are cast to int32 as the reference casts them (examples/input_pipeline.py:72; a value that
+  does not fit is refused), `offsets` must start at 0, never decrease and end at N.  A sample
+  whose times decrease somewhere is sorted stably by time, once, and `sorted_by_time` remembers
+  it: counts in time mode do not depend on the order inside a window, but in number mode the
+  order IS the result, so such a set refuses number mode.  t_min / t_max (numpy int64 [S], 0 for
+  an empty sample) stay on the host: the window origins are drawn there."""
+
+  def __init__(self, addrs, times, offsets, sensor_size, device=None):
+    import numpy as np
+    if device is None:
+      device = addrs.device if isinstance(addrs, torch.Tensor) else torch.device("cpu")
+    a = _host_array(addrs, "addrs")
+    t = _host_array(times, "times").reshape(-1)
+    off = _host_array(offsets, "offsets").reshape(-1).astype(np.int64)
+    if a.ndim != 2 or a.shape[1] != 3 or a.shape[0] != t.shape[0]:
+      raise ValueError("addrs must be [N, 3] (x, y, polarity) with one time per event, got %s / %s"
+                       % (a.shape, t.shape))
+    n = a.shape[0]
+    if off.shape[0] < 1 or off[0] != 0 or off[-1] != n or np.any(np.diff(off) < 0):
+      raise ValueError("offsets must start at 0, never decrease and end at the event count %d" % n)
+    if n and (int(a[:, :2].min()) < 0 or int(a[:, :2].max()) > EVENT_COORD_MAX):
+      raise ValueError("event coordinates must lie in 0..%d, got %d..%d"
+                       % (EVENT_COORD_MAX, int(a[:, :2].min()), int(a[:, :2].max())))
+    if n and (int(t.min()) < -2 ** 31 or int(t.max()) > 2 ** 31 - 1):
+      raise ValueError("event times %d..%d do not fit int32 microseconds" % (int(t.min()), int(t.max())))
+    t = t.astype(np.int32)
+    word = (a[:, 0].astype(np.int64) | (a[:, 1].astype(np.int64) << 14)
+            | ((a[:, 2] != 0).astype(np.int64) << 28)).astype(np.int32)
+    S = off.shape[0] - 1
+    self.sorted_by_time = False
+    if n > 1:
+      down = np.flatnonzero(np.diff(t.astype(np.int64)) < 0) + 1       # event i is earlier than event i - 1
+      down = down[~np.isin(down, off)]                                 # (a sample's first event may be)
+      for s in np.unique(np.searchsorted(off, down, side="right") - 1):
+        lo, hi = int(off[s]), int(off[s + 1])
+        order = np.argsort(t[lo:hi], kind="stable")
+        t[lo:hi], word[lo:hi] = t[lo:hi][order], word[lo:hi][order]
+        self.sorted_by_time = True
+    self.t_min, self.t_max = np.zeros(S, np.int64), np.zeros(S, np.int64)
+    full = np.flatnonzero(off[1:] > off[:-1])
+    self.t_min[full] = t[off[:-1][full]]
+    self.t_max[full] = t[off[1:][full] - 1]
+    hw = np.asarray(sensor_size).reshape(-1)
+    self.sensor_size = (int(hw[0]), int(hw[-1]))                       # (H, W); one number: square
+    self.num_samples, self.num_events = S, n
+    self.counts = np.diff(off)
+    self.addr = torch.from_numpy(word).to(device)
+    self.times = torch.from_numpy(t).to(device)
+    # what the launch is handed: a set without a single event still has an array to point at
+    self._addr_arg = self.addr if n else torch.zeros(1, dtype=torch.int32, device=device)
+    self._times_arg = self.times if n else torch.zeros(1, dtype=torch.int32, device=device)
+    self.offsets = torch.from_numpy(off).to(device)
+
+  @property
+  def device(self):
+    return self.addr.device
+
+  def unpack(self) -> torch.Tensor:
+    """The events as int32 [N, 3] (x, y, polarity 0 / 1) rows, on the device of the set."""
+    w = self.addr
+    return torch.stack([w & EVENT_COORD_MAX, (w >> 14) & EVENT_COORD_MAX, (w >> 28) & 1], 1)
+
+  def __repr__(self):
+    return "EventSet(%d samples, %d events, sensor %s, device=%s)" % (
+        self.num_samples, self.num_events, self.sensor_size, self.device)
+
+
+def _event_rows(v, name, B=None, lo=-2 ** 31, hi=2 ** 31 - 1):
+  """int32 host tensor of a per-row argument of events_bin, validated before upload."""
+  import numpy as np
+  a = _host_array(v, name).reshape(-1).astype(np.int64)
+  if B is not None and a.shape[0] != B:
+    raise ValueError("%s must have one entry per batch row (%d), got %d" % (name, B, a.shape[0]))
+  if a.size and (int(a.min()) < lo or int(a.max()) > hi):
+    raise ValueError("%s must lie in %d..%d, got %d..%d" % (name, lo, hi, int(a.min()), int(a.max())))
+  return torch.from_numpy(a.astype(np.int32))
+
+
+def events_bin(events: EventSet, sample, T: int, H: int, W: int, *, mode, start=None, step_us=None,
+               scale: float = 1.0, fmt: Optional[int] = None, flags: Optional[torch.Tensor] = None,
+               out: Optional[torch.Tensor] = None):
+  """One launch (snnqp_events_bin): row b of the batch decodes sample[b] of `events` into T frames of
+  H x W x 2 counts.  mode "number": equal-count slices (input_pipeline.py:142-219); mode "time":
+  windows of step_us microseconds from start[b], both edges strict (:63-131).  Returns uint8
+  [B, T, H, W, 2] (saturated at 255), or PackedFrames for fmt _lib.EV4 / _lib.EV1, saturated at
+  15 / 1 with FLAG_GT_15 / FLAG_GT_ONE OR-ed into the int32 device word `flags` when one is
+  given.  `sample` (each in [0, S)) and `start` (int32) are validated here, on the host.  `out`,
+  when given, is the tensor the launch writes -- uint8 [B, T, H, W, 2] or the packed data
+  [B, T, units] --, every element of it."""
+  m = EVENT_MODES.get(mode, mode)
+  if m not in (0, 1):
+    raise ValueError("mode must be 'number' or 'time', got %r" % (mode,))
+  if fmt not in (None, L.U8, L.EV1, L.EV4):
+    raise ValueError("fmt must be None (uint8), _lib.EV1 or _lib.EV4, got %r" % (fmt,))
+  if m == 0 and events.sorted_by_time:
+    raise ValueError("this EventSet had to sort a sample by time: number mode, whose result is the "
+                     "order of the events, is refused")
+  T, H, W = int(T), int(H), int(W)
+  rows = _event_rows(sample, "sample", lo=0, hi=events.num_samples - 1)
+  B = rows.shape[0]
+  if m == 1:
+    if start is None or step_us is None:
+      raise ValueError("time mode needs start and step_us")
+    starts = _event_rows(start, "start", B)
+    if int(step_us) <= 0 or int(step_us) > 2 ** 31 - 1:
+      raise ValueError("step_us must be a positive int32, got %r" % (step_us,))
+  else:
+    starts = None
+  _require_gpu(events.addr, flags, out)
+  dev = events.device
+  packed = fmt in (L.EV1, L.EV4)
+  shape = (B, T, frame_units(H, W, fmt)) if packed else (B, T, H, W, 2)
+  dtype = torch.int32 if fmt == L.EV1 else torch.uint8
+  if out is None:
+    out = torch.empty(shape, dtype=dtype, device=dev)
+  elif tuple(out.shape) != shape or out.dtype != dtype or not out.is_contiguous():
+    raise ValueError("out must be a contiguous %s tensor of shape %s" % (dtype, shape))
+  if B and T:
+    both = (rows if starts is None else torch.stack([rows, starts])).to(dev)     # one upload
+    rows_d, starts_d = (both, None) if starts is None else (both[0], both[1])
+    L.check(L.lib().snnqp_events_bin(_ptr(events._addr_arg), _ptr(events._times_arg), _ptr(events.offsets),
+                                     events.num_samples, _ptr(rows_d), _ptr(starts_d), B, m, T,
+                                     int(step_us) if m == 1 else 0, H, W, float(scale), _ptr(out),
+                                     fmt if packed else L.U8, _ptr(flags), _stream()))
+  return PackedFrames(out, H, W, fmt) if packed else out
+
+
 def density(x, lead_dims: int = 2, counts: bool = False) -> torch.Tensor:
   """Fraction of non-zero activations of each leading slice (default per [T, B]),
   the probe of examples/tcja/models.py:128-142; float32 of shape x.shape[:lead_dims]

@@ -1,0 +1,109 @@
+"""Times the batched event front end (ops.events_bin, csrc/events.hip) at DVS128-Gesture's shape --
+128 x 128, T = 20, B = 64, 2^18 uniformly random events per sample -- one launch per output
+format in both modes, against the path it replaces for the same frames: B calls of
+ops.events_to_frames (zero + scatter + narrow each) followed by ops.pack_frames.  The candidates
+alternate in one process, --reps timings each, HIP events around --steps calls.  Checks first that
+the loop and the launch give the same bytes.  Prints one JSON line: milliseconds per batch, the bytes
+a launch has to read and write, and that traffic over the CALL's time (host validation and upload
+included: a lower bound on the kernel's rate) as a fraction of --hbm-gbs.
+
+  python tools/events_time.py [--batch 64] [--frames 20] [--hw 128] [--events 262144]
+                              [--steps 10] [--warmup 3] [--reps 3] [--hbm-gbs 8000]
+"""
+import argparse
+import json
+import os
+import sys
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, ROOT)
+
+import numpy as np  # noqa: E402
+import torch  # noqa: E402
+
+
+def _time(fn, steps, warmup):
+  for _ in range(warmup):
+    fn()
+  torch.cuda.synchronize()
+  a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+  a.record()
+  for _ in range(steps):
+    fn()
+  b.record()
+  torch.cuda.synchronize()
+  return a.elapsed_time(b) / steps
+
+
+def main(argv=None):
+  ap = argparse.ArgumentParser()
+  ap.add_argument("--batch", type=int, default=64)
+  ap.add_argument("--frames", type=int, default=20)
+  ap.add_argument("--hw", type=int, default=128)
+  ap.add_argument("--events", type=int, default=1 << 18)
+  ap.add_argument("--steps", type=int, default=10)
+  ap.add_argument("--warmup", type=int, default=3)
+  ap.add_argument("--reps", type=int, default=3)
+  ap.add_argument("--hbm-gbs", type=float, default=8000.0, help="HBM rate the traffic is set against")
+  args = ap.parse_args(argv)
+  assert torch.cuda.is_available(), "events_time.py needs the GPU"
+  from snnquantprune_amd import _lib as L
+  from snnquantprune_amd import ops
+  dev = torch.device("cuda:0")
+  B, T, HW, N = args.batch, args.frames, args.hw, args.events
+  rng = np.random.Generator(np.random.PCG64(7))
+  addrs = np.stack([rng.integers(0, HW, B * N), rng.integers(0, HW, B * N), rng.integers(0, 2, B * N)], 1)
+  span = T * 1000                                       # 1 ms windows over a recording of T ms
+  times = np.sort(rng.integers(0, span, (B, N)), axis=1).reshape(-1)
+  es = ops.EventSet(addrs, times, np.arange(B + 1, dtype=np.int64) * N, (HW, HW), device=dev)
+  xyz = [torch.from_numpy(addrs[:, k].astype(np.int32)).to(dev) for k in range(3)]
+  rows = list(range(B))
+  starts = [-1] * B                                     # windows (-1, 999), (999, 1999), ...: all but the edges
+
+  def loop(fmt):
+    frames = torch.stack([ops.events_to_frames(xyz[0][b * N:(b + 1) * N], xyz[1][b * N:(b + 1) * N],
+                                               xyz[2][b * N:(b + 1) * N], T, HW, HW) for b in range(B)], 0)
+    return frames if fmt is None else ops.pack_frames(frames, fmt)
+
+  def launch(fmt, mode):
+    return ops.events_bin(es, rows, T, HW, HW, mode=mode, start=starts, step_us=1000, fmt=fmt)
+
+  formats = (("u8", None), ("ev4", L.EV4), ("ev1", L.EV1))
+  for name, fmt in formats:                             # the same frames, before any timing
+    a, b = loop(fmt), launch(fmt, "number")
+    assert torch.equal(a.data if fmt else a, b.data if fmt else b), name
+  cands = {}
+  for name, fmt in formats:
+    cands["loop_%s" % name] = lambda fmt=fmt: loop(fmt)
+    cands["bin_number_%s" % name] = lambda fmt=fmt: launch(fmt, "number")
+    cands["bin_time_%s" % name] = lambda fmt=fmt: launch(fmt, "time")
+  ms = {k: [] for k in cands}
+  for _ in range(args.reps):                            # alternating: every candidate once per round
+    for k, fn in cands.items():
+      ms[k].append(_time(fn, args.steps, args.warmup))
+  out_bytes = {"u8": B * T * HW * HW * 2, "ev4": B * T * HW * HW, "ev1": B * T * ops.frame_units(HW, HW, L.EV1) * 4}
+  # The timings are those of a whole ops.events_bin CALL (host validation and upload included), so the
+  # rates below are call-level lower bounds, not the kernel's: take the kernel's time from a kernel trace.
+  result = {"tool": "events_time", "batch": B, "frames": T, "hw": HW, "events_per_sample": N,
+            "timing": "HIP events around whole calls (host share included)",
+            "ms": {k: [round(v, 4) for v in vs] for k, vs in ms.items()}, "per_call": {}}
+  rounds, span_n = 0, max(N, 1)                         # rounds of a 64-ary search over N sorted times
+  while span_n > 0:
+    span_n, rounds = (span_n + 63) // 64 - 1, rounds + 1
+  for name, _ in formats:
+    for mode in ("number", "time"):
+      k = "bin_%s_%s" % (mode, name)
+      rd = B * N * 4                                    # the address words ...
+      if mode == "time":
+        rd += B * T * 2 * rounds * 64 * 4               # ... and the times both searches of a frame probe
+      best = min(ms[k])
+      result["per_call"][k] = {"read_bytes": rd, "write_bytes": out_bytes[name],
+                               "call_gb_per_s": round((rd + out_bytes[name]) / best / 1e6, 1),
+                               "call_fraction_of_hbm": round((rd + out_bytes[name]) / best / 1e6 / args.hbm_gbs, 4),
+                               "call_events_per_us": round(B * N / best / 1e3, 1)}
+    result.setdefault("speedup_over_loop", {})[name] = round(min(ms["loop_%s" % name]) / min(ms["bin_number_%s" % name]), 2)
+  print(json.dumps(result))
+
+
+if __name__ == "__main__":
+  main()
