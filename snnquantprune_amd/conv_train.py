@@ -87,13 +87,21 @@ def running_update(old: torch.Tensor, new_t: torch.Tensor, momentum: float) -> t
   return ra
 
 
-def conv_currents(x, pk: packing.PackedKernel, geom: ops.ConvGeom, real: bool = False) -> torch.Tensor:
+def conv_currents(x, pk: packing.PackedKernel, geom: ops.ConvGeom, real: bool = False,
+                  mfma: bool = True, cast_uint8: bool = True) -> torch.Tensor:
   """x [NB, H, W, Cin] (uint8, float32 or PackedSpikes) -> float32 [NB, OH, OW, Cout] on the eval
   connection kernels: integer codes for integer-valued inputs, the float32 kernel otherwise.
   `real`: the input is real-valued by construction (a gated raster) -- the float32 connection
-  without looking at the values, as eval runs it under packing.integer_inputs(False)."""
+  without looking at the values, as eval runs it under packing.integer_inputs(False).
+
+  The connection of every training block, conv and dense (dense_train.DenseBlock: the 1x1 case).
+  The two kinds of block differ in two launches, which the last two arguments state: the conv
+  blocks may take the MFMA-tiled codes for a bit-packed raster (`mfma`, under
+  nn.set_train_conv_mfma) and cast a uint8 input to float32 in front of the float32 connection
+  (`cast_uint8`); the dense blocks do neither -- ops.conv_forward gets the plain codes, and the
+  uint8 rows as they are."""
   w = None if real else pk.int_weight()
-  if w is not None and isinstance(x, ops.PackedSpikes) and _nn.train_conv_mfma():
+  if mfma and w is not None and isinstance(x, ops.PackedSpikes) and _nn.train_conv_mfma():
     # the bit-packed raster of the block before: the codes tiled for the MFMA currents kernel
     # (ops.conv_forward takes it where the shape allows, the direct-form launch otherwise)
     w = pk.int_weight_mfma((geom.Cout + 31) // 32 * 32) or w
@@ -106,7 +114,7 @@ def conv_currents(x, pk: packing.PackedKernel, geom: ops.ConvGeom, real: bool = 
     w = pk.float_weight()
     if isinstance(x, ops.PackedSpikes):
       x = x.to_dense().to(torch.float32)
-    elif x.dtype != torch.float32:
+    elif cast_uint8 and x.dtype != torch.float32:
       x = x.to(torch.float32)
   return ops.conv_forward(x, geom, w)
 

@@ -1,7 +1,7 @@
 """Training forward and surrogate-gradient backward of DenseSNN (configs C1 / C2).
 
-jax.grad of examples/tcja/models.py:191-255 in train mode, offline, stated as two
-torch.autograd.Functions, one per dense block:
+jax.grad of examples/tcja/models.py:191-255 in train mode, offline, stated as one
+torch.autograd.Function (DenseBlock) applied once per dense block:
 
   block 1   x0 = x * M0 (dropout, not rescaled) -> QuantDense -> multi_step_LIF -> s1
   block 2   x1 = s1 * M1 -> QuantDense -> multi_step_LIF -> s2 -> vote -> logits
@@ -10,7 +10,7 @@ Forward: the block's currents come from the eval connection kernels (the same la
 arithmetic as SpikingBlock, so the spikes are the eval spikes), then one scan writes the
 spikes and the pre-reset potential h (ops.lif_forward_save).  Backward (csrc/train_dense.hip):
 the BPTT scan (ops.lif_backward, the vote fused into block 2's), the weight gradient
-x^T gI and, for block 2, the input gradient gI Wq^T with * M1 in the epilogue.
+x^T gI and, for a block behind another, the input gradient gI Wq^T with * M1 in the epilogue.
 
 The weight transforms (DuQ, prune; quant.py:428-491) are weight-sized: their VJPs are torch ops
 on the device (weight_transform_grads).
@@ -25,6 +25,7 @@ import torch
 from . import _lib as L
 from . import ops
 from . import packing
+from .conv_train import conv_currents
 
 SURROGATES = {
     "fast_sigmoid": L.SURR_FAST_SIGMOID,
@@ -127,85 +128,50 @@ def transformed_kernel(leaf: dict, pk: packing.PackedKernel):
 
 
 # ---------------------------------------------------------------------------
-# the two blocks
+# the block
 # ---------------------------------------------------------------------------
 
 
-def _currents(x_tm: torch.Tensor, pk: packing.PackedKernel, N: int, real: bool = False) -> torch.Tensor:
-  """x [T, B, K] (uint8, float32 or PackedSpikes) -> float32 currents [T, B, N] on the eval
-  connection kernels: integer codes for integer-valued rows, the float32 kernel otherwise
-  (`real`: rows real-valued by construction -- the float32 kernel without looking at them)."""
-  T, B = x_tm.shape[0], x_tm.shape[1]
-  K = x_tm.shape[-1]
-  w = None if real else pk.int_weight()
-  if w is not None and isinstance(x_tm, torch.Tensor) and x_tm.dtype == torch.float32:
-    if bool(((x_tm == torch.round(x_tm)) & (x_tm >= 0) & (x_tm <= 255)).all()):
-      x_tm = x_tm.to(torch.uint8)
-    else:
-      w = None
-  if w is None:
-    w = pk.float_weight()
-    if isinstance(x_tm, ops.PackedSpikes):
-      x_tm = x_tm.to_dense().to(torch.float32)
-  geom = ops.ConvGeom(1, 1, K, N, 1, 1)
-  if isinstance(x_tm, ops.PackedSpikes):
-    x4 = x_tm.reshape_leading(T * B, 1, 1)
+def _currents(x, pk: packing.PackedKernel, N: int, real: bool) -> torch.Tensor:
+  """x [T, B, K] (uint8, float32 or PackedSpikes) -> float32 currents [T, B, N]: the 1x1 case of
+  conv_train.conv_currents, on the plain codes and with uint8 rows handed over as they are."""
+  T, B, K = x.shape
+  if isinstance(x, ops.PackedSpikes):
+    x4 = x.reshape_leading(T * B, 1, 1)
   else:
-    x4 = x_tm.contiguous().reshape(T * B, 1, 1, K)
-  return ops.conv_forward(x4, geom, w).reshape(T, B, N)
+    x4 = x.contiguous().reshape(T * B, 1, 1, K)
+  cur = conv_currents(x4, pk, ops.ConvGeom(1, 1, K, N, 1, 1), real, mfma=False, cast_uint8=False)
+  return cur.reshape(T, B, N)
 
 
-class DenseBlock1(torch.autograd.Function):
-  """x0 [T, B, K] (dropout applied, no gradient) -> spikes s1 float32 [T, B, N].  Gradient to the
-  transformed kernel wq [K, N] only (the model's input needs none)."""
+class DenseBlock(torch.autograd.Function):
+  """x [T, B, K], dropout mask m [T, B, K] or None -> (logits [B, N // group], s, h) with the
+  spikes s and the pre-reset potential h [T, B, N].  Gradients to x (through * m, fused into the
+  input-gradient kernel) and to the transformed kernel wq [K, N].
 
-  @staticmethod
-  def forward(ctx, wq, x0, pk, nrn, surrogate):
-    T, B, K = x0.shape
-    N = wq.shape[1]
-    cur = _currents(x0, pk, N)
-    h, s = ops.lif_forward_save(cur, nrn)
-    ctx.save_for_backward(x0, h)
-    ctx.nrn, ctx.surrogate = nrn, surrogate
-    ctx.mark_non_differentiable(h)
-    return s, h
+  The input is one of three kinds, as conv_train.ConvBlock's: spikes of the block before
+  (bit-packed when the layer has integer codes); `first`: as given, counts or spikes from
+  outside -- the integer path if the values are integers, saved in its own dtype, no gradient to
+  it; `real_input`: real-valued rows (CextNet's dense1 behind the second gate) -- not bit-packed,
+  the float32 connection without looking at the values.
 
-  @staticmethod
-  def backward(ctx, gs, _gh):
-    x0, h = ctx.saved_tensors
-    T, B, K = x0.shape
-    N = h.shape[-1]
-    gI = ops.lif_backward(h, ctx.nrn, ctx.surrogate, gs=gs)
-    gw = ops.dense_weight_grad(x0.reshape(T * B, K).to(torch.float32), gI.reshape(T * B, N))
-    return gw, None, None, None, None
-
-
-class DenseBlock2(torch.autograd.Function):
-  """s1 [T, B, K], dropout mask M1 [T, B, K] -> (logits [B, N // group], s2, h2).  Gradients to
-  s1 (through * M1, fused into the input-gradient kernel) and to the transformed kernel wq.
-
-  group None: a hidden block -- no vote; -> (s2, None, h2), and the spikes' gradient drives the
-  scan.  real_input: s1 holds real-valued rows (CextNet's dense1 behind the second gate): they are
-  not bit-packed and the currents come from the float32 connection."""
+  group None: a hidden block -- no vote; -> (s, None, h), and the spikes' gradient drives the
+  scan."""
 
   @classmethod
-  def apply(cls, s1, wq, m1, pk, nrn, surrogate, group, real_input=False):
-    return super().apply(s1, wq, m1, pk, nrn, surrogate, group, real_input)
+  def apply(cls, x, wq, m, pk, nrn, surrogate, group, first=False, real_input=False):
+    return super().apply(x, wq, m, pk, nrn, surrogate, group, first, real_input)
 
   @staticmethod
-  def forward(ctx, s1, wq, m1, pk, nrn, surrogate, group, real_input):
-    T, B, K = s1.shape
-    N = wq.shape[1]
-    x1 = s1 * m1 if m1 is not None else s1
-    if real_input:
-      cur = _currents(x1.contiguous(), pk, N, real=True)
+  def forward(ctx, x, wq, m, pk, nrn, surrogate, group, first, real_input):
+    x1 = x * m if m is not None else x
+    if first or real_input or pk.int_weight() is None:
+      xin = x1
     else:
-      xin = ops.pack_bits(x1.contiguous()) if pk.int_weight() is not None else x1
-      cur = _currents(xin, pk, N)
-    h, s = ops.lif_forward_save(cur, nrn)
-    ctx.save_for_backward(h, wq, m1)
-    ctx.x1 = x1
-    ctx.nrn, ctx.surrogate, ctx.group = nrn, surrogate, group
+      xin = ops.pack_bits(x1.contiguous())
+    h, s = ops.lif_forward_save(_currents(xin, pk, wq.shape[1], real_input), nrn)
+    ctx.save_for_backward(h, wq, m, x1)
+    ctx.nrn, ctx.surrogate, ctx.group, ctx.first = nrn, surrogate, group, first
     if group is None:
       ctx.mark_non_differentiable(h)
       return s, None, h
@@ -214,22 +180,21 @@ class DenseBlock2(torch.autograd.Function):
     return logits, s, h
 
   @staticmethod
-  def backward(ctx, glogits, _gs, _gh):
-    h, wq, m1 = ctx.saved_tensors
-    x1 = ctx.x1
+  def backward(ctx, gout, _gs, _gh):
+    h, wq, m, x1 = ctx.saved_tensors
     T, B, K = x1.shape
     N = h.shape[-1]
     if ctx.group is None:
-      gI = ops.lif_backward(h, ctx.nrn, ctx.surrogate, gs=glogits.contiguous())
+      gI = ops.lif_backward(h, ctx.nrn, ctx.surrogate, gs=gout.contiguous())
     else:
-      gI = ops.lif_backward(h, ctx.nrn, ctx.surrogate, glogits=glogits, group=ctx.group)
+      gI = ops.lif_backward(h, ctx.nrn, ctx.surrogate, glogits=gout, group=ctx.group)
     gI2 = gI.reshape(T * B, N)
-    gw = ops.dense_weight_grad(x1.reshape(T * B, K), gI2)
-    gs1 = None
-    if ctx.needs_input_grad[0]:
-      gs1 = ops.dense_input_grad(gI2, wq.detach(), None if m1 is None else m1.reshape(T * B, K))
-      gs1 = gs1.reshape(T, B, K)
-    return gs1, gw, None, None, None, None, None, None
+    gw = ops.dense_weight_grad(x1.reshape(T * B, K).to(torch.float32), gI2)
+    gx = None
+    if not ctx.first and ctx.needs_input_grad[0]:
+      gx = ops.dense_input_grad(gI2, wq.detach(), None if m is None else m.reshape(T * B, K))
+      gx = gx.reshape(T, B, K)
+    return gx, gw, None, None, None, None, None, None, None
 
 
 def dropout_mask(shape, keep: float, generator: torch.Generator, device) -> torch.Tensor:

@@ -195,7 +195,7 @@ def event_half_group() -> bool:
 
 
 # The connection alone over a bit-packed raster: the training forward of a conv
-# block (conv_train.conv_currents) and QuantConv called on its own hand ops.conv_forward the
+# block (conv_train.conv_currents with mfma=True) and QuantConv called on its own hand ops.conv_forward the
 # MFMA-tiled codes, so a 3x3 / stride 1 / pad 1 connection with Cin <= 128 runs on the currents
 # form of the bit-input MFMA conv.  On by default.
 _TRAIN_CONV_MFMA = True

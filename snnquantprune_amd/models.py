@@ -31,7 +31,6 @@ from . import ops
 from . import packing
 from .flax_qconv import QuantConv
 from .flax_qdense import QuantDense
-from .quant import DuQ
 from .spiking_learning import SpikingBlock, fused_dense_head
 
 
@@ -66,6 +65,31 @@ def _layer_bits(cfg, i):
   if "layer_bits" in q and q.layer_bits is not None:
     return int(q.layer_bits[i])
   return q.bits
+
+
+# The layers every model is made of, for the eval and the training forward alike.  Each call
+# constructs one module, which Flax auto-naming numbers in order of construction: callers
+# construct them in the reference's order.
+
+def _qconv3x3(cfg, dtype, bits):
+  return QuantConv(features=cfg.channels, kernel_size=(3, 3), padding=((1, 1), (1, 1)),
+                   use_bias=False, dtype=dtype, config=cfg.quant, bits=bits,
+                   g_scale=cfg.quant.g_scale)
+
+
+def _qconv1d(cfg, dtype, bits, features):
+  return QuantConv(features=features, kernel_size=[4], padding="SAME", use_bias=False,
+                   dtype=dtype, config=cfg.quant, bits=bits, g_scale=cfg.quant.g_scale)
+
+
+def _qdense(cfg, dtype, bits, features):
+  return QuantDense(features, use_bias=False, dtype=dtype, config=cfg.quant, bits=bits,
+                    g_scale=cfg.quant.g_scale)
+
+
+def _batchnorm(dtype, train=False):
+  return nn.BatchNorm(use_running_average=not train, momentum=0.9, epsilon=1e-5, use_bias=True,
+                      use_scale=True, dtype=dtype)
 
 
 def _probing(mod, cfg):
@@ -167,15 +191,11 @@ class DenseSNN(nn.Module):
         return ops.dense_head_forward(x, w1, K, N1, nrn1, w2, N2, nrn2, group=group, time_major=tm,
                                       fallback=fb)[0], None
     layer = SpikingBlock(
-        connection_fn=QuantDense(hidden, use_bias=False, dtype=self.dtype,
-                                 config=cfg.quant, bits=_layer_bits(cfg, 0),
-                                 g_scale=cfg.quant.g_scale),
+        connection_fn=_qdense(cfg, self.dtype, _layer_bits(cfg, 0), hidden),
         neural_dynamics=cfg.neuron_dynamics(dtype=self.dtype),
         return_state=False, batch_major_input=True)
     layer2 = SpikingBlock(
-        connection_fn=QuantDense(self.num_classes * 10, use_bias=False,
-                                 dtype=self.dtype, config=cfg.quant,
-                                 bits=_layer_bits(cfg, 1), g_scale=cfg.quant.g_scale),
+        connection_fn=_qdense(cfg, self.dtype, _layer_bits(cfg, 1), self.num_classes * 10),
         neural_dynamics=cfg.neuron_dynamics(dtype=self.dtype),
         return_state=False)
     if not probe:
@@ -208,62 +228,19 @@ class DenseSNN(nn.Module):
     through the parameter leaves (dense_train.py).  Same spikes and logits as the eval forward
     when every mask is one."""
     from . import dense_train as dt
+    from . import train_forward as fw
     cfg = self.config
-    if rng is None:
-      raise NotImplementedError("train=True needs an rng (an int seed or a torch.Generator) for "
-                                "the dropout masks; the reference splits it unconditionally")
-    if u_state is not None or online:
-      raise NotImplementedError("training: the online mode and a carried state are not supported")
-    if _probing(self, cfg):
-      raise NotImplementedError("training: density probes are not supported")
-    if "dropout" not in cfg:
-      raise ValueError("train=True needs config.dropout (the keep probability of the dropout "
-                       "masks, models.py:193-197)")
-    qw = cfg.quant.get("weight")
-    if qw is not None and getattr(qw, "func", qw) is not DuQ:
-      raise NotImplementedError("training supports the DuQ weight quantiser or none, not %r" % (qw,))
-    if not (isinstance(inputs, torch.Tensor) or hasattr(inputs, "__array__")) or isinstance(
-        inputs, (ops.PackedSpikes, ops.PackedFrames, ops.GatedSpikes)):
-      raise NotImplementedError("training takes uint8 or float32 [B, T, K] tensors")
-    x = _as_input(inputs)
-    if x.ndim != 3:
-      raise ValueError("DenseSNN expects [B, T, K] inputs, got %s" % (tuple(x.shape),))
+    x = fw.check_call(self, inputs, rng, u_state, online, frames=False)
     hidden = cfg.hidden if "hidden" in cfg else cfg.channels * 2 * 2
-    layer = SpikingBlock(
-        connection_fn=QuantDense(hidden, use_bias=False, dtype=self.dtype,
-                                 config=cfg.quant, bits=_layer_bits(cfg, 0),
-                                 g_scale=cfg.quant.g_scale),
-        neural_dynamics=cfg.neuron_dynamics(dtype=self.dtype),
-        return_state=False, batch_major_input=True)
-    layer2 = SpikingBlock(
-        connection_fn=QuantDense(self.num_classes * 10, use_bias=False,
-                                 dtype=self.dtype, config=cfg.quant,
-                                 bits=_layer_bits(cfg, 1), g_scale=cfg.quant.g_scale),
-        neural_dynamics=cfg.neuron_dynamics(dtype=self.dtype),
-        return_state=False)
-    surr1 = dt.surrogate_of(layer.neural_dynamics)
-    surr2 = dt.surrogate_of(layer2.neural_dynamics)
-    c1, c2 = layer.connection_fn, layer2.connection_fn
-    K = x.shape[-1]
-    pk1 = c1.packed_kernel(K)
-    pk2 = c2.packed_kernel(hidden)
-    params = self._root.variables["params"]
+    dense1 = fw.dense_layer(self, hidden, _layer_bits(cfg, 0), x.shape[-1])
+    dense2 = fw.dense_layer(self, self.num_classes * 10, _layer_bits(cfg, 1), hidden)
     gen = dt.generator_of(rng, x.device)
     m0 = dt.dropout_mask(x.shape, cfg.dropout, gen, x.device)           # models.py:193-197
-    x0 = dt.input_time_major(dt.apply_input_mask(x, m0))
-    wq1 = dt.transformed_kernel(params["QuantDense_0"], pk1)
-    s1, h1 = dt.DenseBlock1.apply(wq1, x0, pk1, layer.neural_dynamics.neuron(hidden), surr1)
-    m1 = dt.dropout_mask(s1.shape, cfg.dropout, gen, x.device)          # models.py:219-224
-    wq2 = dt.transformed_kernel(params["QuantDense_1"], pk2)
-    logits, s2, h2 = dt.DenseBlock2.apply(s1, wq2, m1, pk2, layer2.neural_dynamics.neuron(
-        self.num_classes * 10), surr2, 10)
     if self.is_mutable_collection("intermediates"):
       self.sow("intermediates", "dropout_0", m0)
-      self.sow("intermediates", "dropout_1", m1)
-      self.sow("intermediates", "dense1_out", s1.detach())
-      self.sow("intermediates", "dense1_h", h1)
-      self.sow("intermediates", "dense2_out", s2)
-      self.sow("intermediates", "dense2_h", h2)
+    x = dt.input_time_major(dt.apply_input_mask(x, m0))                 # [T, B, K], in x's own dtype
+    x = fw.dense_block(self, x, "dense1", dense1, None, first=True)     # models.py:200-216
+    logits = fw.dense_block(self, x, "dense2", dense2, 10, mask=(gen, 1))   # models.py:219-255
     return logits, None
 
 
@@ -280,19 +257,13 @@ class ConvDenseSNN(nn.Module):
     cfg = self.config
     x = _as_input(inputs)
     nblocks = cfg.num_conv_blocks if "num_conv_blocks" in cfg else 3
-    norm = lambda: nn.BatchNorm(use_running_average=not train, momentum=0.9,  # noqa: E731
-                                epsilon=1e-5, use_bias=True, use_scale=True,
-                                dtype=self.dtype)
     probe = _probing(self, cfg)
     compact = _compacting(self, cfg, u_state)
     for i in range(nblocks):
       layer = SpikingBlock(
-          connection_fn=QuantConv(features=cfg.channels, kernel_size=(3, 3),
-                                  padding=((1, 1), (1, 1)), use_bias=False,
-                                  dtype=self.dtype, config=cfg.quant,
-                                  bits=_layer_bits(cfg, i), g_scale=cfg.quant.g_scale),
+          connection_fn=_qconv3x3(cfg, self.dtype, _layer_bits(cfg, i)),
           neural_dynamics=cfg.neuron_dynamics(dtype=self.dtype),
-          norm_fn=norm(),
+          norm_fn=_batchnorm(self.dtype),
           pool=1 if probe else 2,       # the reduce_window max of models.py:145-147
           return_state=False,
           batch_major_input=(i == 0),   # models.py:109 swapaxes, done by strides
@@ -308,9 +279,7 @@ class ConvDenseSNN(nn.Module):
     if probe:
       _sow_density(self, "dense1_inpt", x)
     layer = SpikingBlock(
-        connection_fn=QuantDense(self.num_classes * 10, use_bias=False,
-                                 dtype=self.dtype, config=cfg.quant,
-                                 bits=_layer_bits(cfg, nblocks), g_scale=cfg.quant.g_scale),
+        connection_fn=_qdense(cfg, self.dtype, _layer_bits(cfg, nblocks), self.num_classes * 10),
         neural_dynamics=cfg.neuron_dynamics(dtype=self.dtype),
         return_state=False)
     _, x = layer(None, x)
@@ -324,65 +293,18 @@ class ConvDenseSNN(nn.Module):
     statistics, one dropout mask with keep probability config.dropout, not rescaled, in front of
     the read-out), attached to torch autograd through the parameter leaves (conv_train.py,
     dense_train.py).  Channel compaction and the fused kernels are not used."""
-    from . import conv_train as ct
     from . import dense_train as dt
-    if isinstance(inputs, (ops.PackedSpikes, ops.PackedFrames, ops.GatedSpikes)) or not (
-        isinstance(inputs, torch.Tensor) and inputs.ndim == 5
-        and inputs.dtype in (torch.uint8, torch.float32)):
-      raise NotImplementedError("training takes uint8 or float32 [B, T, H, W, C] tensors")
+    from . import train_forward as fw
+    x = fw.check_call(self, inputs, rng, u_state, online, frames=True)
     cfg = self.config
-    if rng is None:
-      raise NotImplementedError("train=True needs an rng (an int seed or a torch.Generator) for "
-                                "the dropout mask; the reference splits it unconditionally")
-    if u_state is not None or online:
-      raise NotImplementedError("training: the online mode and a carried state are not supported")
-    if _probing(self, cfg):
-      raise NotImplementedError("training: density probes are not supported")
-    if "dropout" not in cfg:
-      raise ValueError("train=True needs config.dropout (the keep probability of the dropout "
-                       "mask, models.py:219-224)")
-    qw = cfg.quant.get("weight")
-    if qw is not None and getattr(qw, "func", qw) is not DuQ:
-      raise NotImplementedError("training supports the DuQ weight quantiser or none, not %r" % (qw,))
-    x = inputs.transpose(0, 1).contiguous()               # models.py:109, [T, B, H, W, C]
+    x = x.transpose(0, 1).contiguous()                    # models.py:109, [T, B, H, W, C]
     nblocks = cfg.num_conv_blocks if "num_conv_blocks" in cfg else 3
-    params = self._root.variables["params"]
-    sowing = self.is_mutable_collection("intermediates")
-    for i in range(nblocks):
-      conv = QuantConv(features=cfg.channels, kernel_size=(3, 3), padding=((1, 1), (1, 1)),
-                       use_bias=False, dtype=self.dtype, config=cfg.quant,
-                       bits=_layer_bits(cfg, i), g_scale=cfg.quant.g_scale)
-      dyn = cfg.neuron_dynamics(dtype=self.dtype)
-      norm = nn.BatchNorm(use_running_average=False, momentum=0.9, epsilon=1e-5, use_bias=True,
-                          use_scale=True, dtype=self.dtype)
-      surr = dt.surrogate_of(dyn)
-      H, W, cin = x.shape[2], x.shape[3], x.shape[4]
-      geom = conv.geometry((H, W), cin)
-      pk = conv.packed_kernel(cin)
-      wq = dt.transformed_kernel(params["QuantConv_%d" % i], pk)
-      x, h, s, mean, var = ct.ConvBlock.apply(
-          x, wq, norm.scale_param(cfg.channels), norm.bias_param(cfg.channels), pk, geom,
-          dyn.neuron(cfg.channels), surr, float(norm.epsilon), i == 0)
-      norm.update_running(mean, var)
-      if sowing:
-        self.sow("intermediates", "conv%d_h" % i, h)
-        self.sow("intermediates", "conv%d_out" % i, s)
-        self.sow("intermediates", "bn%d_mean" % i, mean)
-        self.sow("intermediates", "bn%d_var" % i, var)
-    x = flatten_channel_major(x)
-    dense = QuantDense(self.num_classes * 10, use_bias=False, dtype=self.dtype, config=cfg.quant,
-                       bits=_layer_bits(cfg, nblocks), g_scale=cfg.quant.g_scale)
-    dyn = cfg.neuron_dynamics(dtype=self.dtype)
-    surr = dt.surrogate_of(dyn)
-    pk = dense.packed_kernel(x.shape[-1])
-    gen = dt.generator_of(rng, x.device)
-    m = dt.dropout_mask(x.shape, cfg.dropout, gen, x.device)             # models.py:219-224
-    wq = dt.transformed_kernel(params["QuantDense_0"], pk)
-    logits, s, h = dt.DenseBlock2.apply(x, wq, m, pk, dyn.neuron(self.num_classes * 10), surr, 10)
-    if sowing:
-      self.sow("intermediates", "dropout_0", m)
-      self.sow("intermediates", "dense_out", s)
-      self.sow("intermediates", "dense_h", h)
+    for i in range(nblocks):                              # models.py:111-147
+      x = fw.conv_block(self, x, i, _layer_bits(cfg, i), first=(i == 0))
+    x = flatten_channel_major(x)                          # models.py:189-190
+    dense = fw.dense_layer(self, self.num_classes * 10, _layer_bits(cfg, nblocks), x.shape[-1])
+    logits = fw.dense_block(self, x, "dense", dense, 10,
+                            mask=(dt.generator_of(rng, x.device), 0))   # models.py:219-255
     return logits, None
 
 
@@ -405,9 +327,7 @@ class CextNet(nn.Module):
     cfg = self.config
 
     def qconv1d(features, x):
-      return QuantConv(features=features, kernel_size=[4], padding="SAME", use_bias=False,
-                       dtype=self.dtype, config=cfg.quant, bits=cfg.quant.bits,
-                       g_scale=cfg.quant.g_scale)(x)
+      return _qconv1d(cfg, self.dtype, cfg.quant.bits, features)(x)
 
     probe = _probing(self, cfg)
 
@@ -444,21 +364,15 @@ class CextNet(nn.Module):
 
     def conv_block(x, first, pool, packed=None, compact=False):
       layer = SpikingBlock(
-          connection_fn=QuantConv(features=cfg.channels, kernel_size=(3, 3),
-                                  padding=((1, 1), (1, 1)), use_bias=False,
-                                  dtype=self.dtype, config=cfg.quant, bits=cfg.quant.bits,
-                                  g_scale=cfg.quant.g_scale),
+          connection_fn=_qconv3x3(cfg, self.dtype, cfg.quant.bits),
           neural_dynamics=cfg.neuron_dynamics(dtype=self.dtype),
-          norm_fn=nn.BatchNorm(use_running_average=not train, momentum=0.9, epsilon=1e-5,
-                               use_bias=True, use_scale=True, dtype=self.dtype),
+          norm_fn=_batchnorm(self.dtype),
           pool=pool, return_state=False, batch_major_input=first, packed=packed, compact=compact)
       return layer(None, x)[1]
 
     def dense_block(x, features, packed=None):
       layer = SpikingBlock(
-          connection_fn=QuantDense(features, use_bias=False, dtype=self.dtype,
-                                   config=cfg.quant, bits=cfg.quant.bits,
-                                   g_scale=cfg.quant.g_scale),
+          connection_fn=_qdense(cfg, self.dtype, cfg.quant.bits, features),
           neural_dynamics=cfg.neuron_dynamics(dtype=self.dtype), return_state=False, packed=packed)
       return layer(None, x)[1]
 
@@ -511,102 +425,25 @@ class CextNet(nn.Module):
     real-valued: those blocks run the float32 connection on the multiplied-out product, as eval
     does under config.gated_int = False.  Channel compaction, the gated integer kernels and the
     fused kernels are not used."""
-    from . import conv_train as ct
     from . import dense_train as dt
-    from . import tcja_train as tt
-    if isinstance(inputs, (ops.PackedSpikes, ops.PackedFrames, ops.GatedSpikes)) or not (
-        isinstance(inputs, torch.Tensor) and inputs.ndim == 5
-        and inputs.dtype in (torch.uint8, torch.float32)):
-      raise NotImplementedError("training takes uint8 or float32 [B, T, H, W, C] tensors")
-    if inputs.shape[2] < 32 or inputs.shape[3] < 32:
-      raise NotImplementedError("training CextNet needs frames of at least 32 x 32 (five 2x2 pools "
-                                "leave the read-out an empty raster), got %d x %d"
-                                % (inputs.shape[2], inputs.shape[3]))
+    from . import train_forward as fw
+    x = fw.check_call(self, inputs, rng, u_state, online, frames=True, min_hw=32, gpu=True)
     cfg = self.config
-    if rng is None:
-      raise NotImplementedError("train=True needs an rng (an int seed or a torch.Generator) for "
-                                "the dropout mask; the reference splits it unconditionally")
-    if u_state is not None or online:
-      raise NotImplementedError("training: the online mode and a carried state are not supported")
-    if _probing(self, cfg):
-      raise NotImplementedError("training: density probes are not supported")
-    if "dropout" not in cfg:
-      raise ValueError("train=True needs config.dropout (the keep probability of the dropout "
-                       "mask, models.py:219-224)")
-    qw = cfg.quant.get("weight")
-    if qw is not None and getattr(qw, "func", qw) is not DuQ:
-      raise NotImplementedError("training supports the DuQ weight quantiser or none, not %r" % (qw,))
-    ops._require_gpu(inputs)
-    x = inputs.transpose(0, 1).contiguous()               # models.py:109, [T, B, H, W, C]
-    params = self._root.variables["params"]
-    sowing = self.is_mutable_collection("intermediates")
-    nconv = [0]
-
-    def conv_block(x, i, pool, real_input):
-      conv = QuantConv(features=cfg.channels, kernel_size=(3, 3), padding=((1, 1), (1, 1)),
-                       use_bias=False, dtype=self.dtype, config=cfg.quant, bits=cfg.quant.bits,
-                       g_scale=cfg.quant.g_scale)
-      dyn = cfg.neuron_dynamics(dtype=self.dtype)
-      norm = nn.BatchNorm(use_running_average=False, momentum=0.9, epsilon=1e-5, use_bias=True,
-                          use_scale=True, dtype=self.dtype)
-      surr = dt.surrogate_of(dyn)
-      H, W, cin = x.shape[2], x.shape[3], x.shape[4]
-      geom = conv.geometry((H, W), cin)
-      pk = conv.packed_kernel(cin)
-      wq = dt.transformed_kernel(params["QuantConv_%d" % nconv[0]], pk)
-      nconv[0] += 1
-      y, h, s, mean, var = ct.ConvBlock.apply(
-          x, wq, norm.scale_param(cfg.channels), norm.bias_param(cfg.channels), pk, geom,
-          dyn.neuron(cfg.channels), surr, float(norm.epsilon), i == 0, pool, real_input,
-          i == 0)       # block 0's weight gradient in float64: the most rows, count frames (DESIGN.md 12)
-      norm.update_running(mean, var)
-      if sowing:
-        self.sow("intermediates", "conv%d_h" % i, h)
-        self.sow("intermediates", "conv%d_out" % i, s)
-        self.sow("intermediates", "bn%d_mean" % i, mean)
-        self.sow("intermediates", "bn%d_var" % i, var)
-      return y
-
-    def qconv1d(features, spatial, cin):
-      conv = QuantConv(features=features, kernel_size=[4], padding="SAME", use_bias=False,
-                       dtype=self.dtype, config=cfg.quant, bits=cfg.quant.bits,
-                       g_scale=cfg.quant.g_scale)
-      pk = conv.packed_kernel(cin)
-      wq = dt.transformed_kernel(params["QuantConv_%d" % nconv[0]], pk)
-      nconv[0] += 1
-      return wq, pk, conv.geometry((spatial,), cin)
-
+    bits = cfg.quant.bits
+    x = x.transpose(0, 1).contiguous()                    # models.py:109, [T, B, H, W, C]
     for i in range(3):                                    # models.py:111-147
-      x = conv_block(x, i, 2, False)
+      # block 0's weight gradient in float64: the most rows, count frames (DESIGN.md 12)
+      x = fw.conv_block(self, x, i, bits, first=(i == 0), wgrad_f64=(i == 0))
     for j in range(2):                                    # models.py:149-187
-      i = 3 + j
-      if sowing:                                          # what a test steps the oracle block on
-        self.sow("intermediates", "conv%d_in" % i, x.detach())
-      x = conv_block(x, i, 1, j == 1)
-      T, C = x.shape[0], x.shape[-1]
-      wq_t, pk_t, geom_t = qconv1d(T, C, T)               # over the channel axis, on [B, C, T]
-      wq_c, pk_c, geom_c = qconv1d(C, T, C)               # over the time axis, on [B, T, C]
-      x, gate = tt.TcjaGate.apply(x, wq_t, wq_c, pk_t, pk_c, geom_t, geom_c)
-      if sowing:
-        self.sow("intermediates", "tcja_gate_%d" % j, gate)
+      if self.is_mutable_collection("intermediates"):     # what a test steps the oracle block on
+        self.sow("intermediates", "conv%d_in" % (3 + j), x.detach())
+      x = fw.conv_block(self, x, 3 + j, bits, pool=1, real_input=(j == 1))
+      x = fw.tcja_gate(self, x, j, bits)
     x = flatten_channel_major(x)                          # models.py:189-190
     gen = dt.generator_of(rng, x.device)
-
-    def dense_block(x, n, features, group, real_input):
-      dense = QuantDense(features, use_bias=False, dtype=self.dtype, config=cfg.quant,
-                         bits=cfg.quant.bits, g_scale=cfg.quant.g_scale)
-      dyn = cfg.neuron_dynamics(dtype=self.dtype)
-      surr = dt.surrogate_of(dyn)
-      pk = dense.packed_kernel(x.shape[-1])
-      m = dt.dropout_mask(x.shape, cfg.dropout, gen, x.device)
-      wq = dt.transformed_kernel(params["QuantDense_%d" % n], pk)
-      out, s, h = dt.DenseBlock2.apply(x, wq, m, pk, dyn.neuron(features), surr, group, real_input)
-      if sowing:
-        self.sow("intermediates", "dropout_%d" % n, m)
-        self.sow("intermediates", "dense%d_out" % (n + 1), (out if group is None else s).detach())
-        self.sow("intermediates", "dense%d_h" % (n + 1), h)
-      return out
-
-    x = dense_block(x, 0, cfg.channels * 2 * 2, None, True)         # models.py:192-216
-    logits = dense_block(x, 1, self.num_classes * 10, 10, False)    # models.py:223-255
+    hidden = cfg.channels * 2 * 2
+    x = fw.dense_block(self, x, "dense1", fw.dense_layer(self, hidden, bits, x.shape[-1]), None,
+                       mask=(gen, 0), real_input=True)    # models.py:192-216
+    logits = fw.dense_block(self, x, "dense2", fw.dense_layer(self, self.num_classes * 10, bits, hidden),
+                            10, mask=(gen, 1))            # models.py:223-255
     return logits, None

@@ -132,8 +132,8 @@ def create_train_state(variables, config, model) -> TrainState:
 def train_step(state: TrainState, batch, rng, learning_rate_fn, weight_decay, smoothing,
                loss_type, online=False, burnin=0, return_grads=False):
   """One offline step (train_utils.py:249-368): loss = loss_type(logits, labels, smoothing) +
-  weight_decay * weight_decay_fn(params); gradients by the model's backward (DenseSNN:
-  dense_train.py; ConvDenseSNN: conv_train.py; CextNet: those and tcja_train.py), averaged over ranks when torch.distributed is initialised; then one update.
+  weight_decay * weight_decay_fn(params); gradients by the model's backward (the blocks
+  train_forward.py assembles: dense_train.DenseBlock, conv_train.ConvBlock, tcja_train.TcjaGate), averaged over ranks when torch.distributed is initialised; then one update.
   Returns (state, metrics) -- metrics with loss, accuracy, learning_rate and logits --, and the
   gradient tree as a third element when return_grads."""
   if online:

@@ -9,12 +9,12 @@ import torch
 from snnquantprune_amd import _lib as L
 from snnquantprune_amd import ops
 from tests import cextnet_train_reference as xr
+from tests.train_helpers import _frame_untouched, _framed, _np, mixed
 
 pytestmark = pytest.mark.gpu
 
 F32 = np.float32
 SENTINEL = -12345.5
-PAD = 4096
 CHANNELS = (1, 31, 32, 33, 64, 65, 128)
 RASTERS = ((1, 1), (2, 2), (2, 3), (3, 2), (5, 7), (8, 8), (16, 16))
 
@@ -23,28 +23,6 @@ RASTERS = ((1, 1), (2, 2), (2, 3), (3, 2), (5, 7), (8, 8), (16, 16))
 def dev():
   assert torch.cuda.is_available()
   return torch.device("cuda:0")
-
-
-def _np(t):
-  return t.detach().cpu().numpy()
-
-
-def mixed(rng, shape):
-  """Mixed magnitudes, so that the order of a float32 sum shows in its bits."""
-  return (rng.standard_normal(shape) * 2.0 ** rng.integers(-6, 7, shape)).astype(F32)
-
-
-def _framed(dev, a, fill):
-  """A device copy of `a` with a frame of `fill` before and after it: (whole, view)."""
-  whole = torch.full((a.size + 2 * PAD,), fill, dtype=torch.float32, device=dev)
-  view = whole[PAD:PAD + a.size].view(a.shape)
-  view.copy_(torch.from_numpy(np.ascontiguousarray(a)))
-  return whole, view
-
-
-def _frame_untouched(whole, n, fill):
-  edge = torch.cat([whole[:PAD], whole[PAD + n:]])
-  return bool((edge == fill).all())
 
 
 def _run(dev, x, gate, gp, gm):

@@ -8,6 +8,7 @@ import pytest
 import torch
 
 from tests import conv_train_reference as cr
+from tests.train_helpers import _grad_tree, _np, _run_train
 
 pytestmark = pytest.mark.gpu
 
@@ -23,10 +24,6 @@ def dev():
   return torch.device("cuda:0")
 
 
-def _np(t):
-  return t.detach().cpu().numpy()
-
-
 def _setup(dev, quantized, dtype="uint8", **fx):
   from snnquantprune_amd import linen as nn
   from snnquantprune_amd import models, synthetic as syn
@@ -35,28 +32,6 @@ def _setup(dev, quantized, dtype="uint8", **fx):
                         tau=cr.TAU, quantized=quantized, num_conv_blocks=cr.NBLOCKS, dropout=cr.KEEP)
   model = models.ConvDenseSNN(num_classes=cr.CLASSES, config=cfg)
   return model, v, nn.tree_from_numpy(v, dev), torch.from_numpy(x).to(dev)
-
-
-def _leaves(tree):
-  return {k: (_leaves(t) if isinstance(t, dict) else t.detach().clone().requires_grad_(True))
-          for k, t in tree.items()}
-
-
-def _run_train(model, variables, x, rng=0):
-  params = _leaves(variables["params"])
-  (logits, _), mut = model.apply({"params": params, "batch_stats": variables["batch_stats"]}, x,
-                                 train=True, rng=rng, mutable=["intermediates", "batch_stats"])
-  return params, logits, {k: v[0] for k, v in mut["intermediates"].items()}, mut["batch_stats"]
-
-
-def _grad_tree(params, prefix=()):
-  out = {}
-  for k, t in params.items():
-    if isinstance(t, dict):
-      out.update(_grad_tree(t, prefix + (k,)))
-    else:
-      out[prefix + (k,)] = None if t.grad is None else _np(t.grad)
-  return out
 
 
 _runs = {}

@@ -12,6 +12,7 @@ from snnquantprune_amd import ops
 from tests import cases
 from tests import conv_train_reference as cr
 from tests import train_reference as tr
+from tests.train_helpers import _frame_untouched, _framed, _np, mixed
 
 pytestmark = pytest.mark.gpu
 
@@ -25,32 +26,8 @@ def dev():
   return torch.device("cuda:0")
 
 
-def _np(t):
-  return t.detach().cpu().numpy()
-
-
-def mixed(rng, shape):
-  """Mixed magnitudes, so that the order of a float32 sum shows in its bits."""
-  return (rng.standard_normal(shape) * 2.0 ** rng.integers(-6, 7, shape)).astype(F32)
-
-
 def _geom(H, W, Cin, Cout, ks, st, pads):
   return ops.ConvGeom(H, W, Cin, Cout, ks[0], ks[1], tuple(st), tuple(tuple(p) for p in pads))
-
-
-def _framed(dev, a, fill):
-  """A device copy of `a` with a frame of `fill` before and after it: (whole, view)."""
-  pad = 4096
-  whole = torch.full((a.size + 2 * pad,), fill, dtype=torch.float32, device=dev)
-  view = whole[pad:pad + a.size].view(a.shape)
-  view.copy_(torch.from_numpy(np.ascontiguousarray(a)))
-  return whole, view
-
-
-def _frame_untouched(whole, n, fill):
-  pad = 4096
-  edge = torch.cat([whole[:pad], whole[pad + n:]])
-  return bool(torch.isnan(edge).all()) if np.isnan(fill) else bool((edge == fill).all())
 
 
 def _run_wgrad(dev, x, g, geom, splits):

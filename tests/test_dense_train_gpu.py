@@ -11,21 +11,19 @@ import torch
 from tests import cases
 from tests import train_reference as tr
 from tests.helpers import qweight_of
+from tests.train_helpers import _np, _run_train as _run_train_stats
 from tests.train_reference import duq_vjp as _duq_vjp, scan_vjp as _scan_vjp  # noqa: F401
 
 pytestmark = pytest.mark.gpu
 
 F64 = np.float64
+_run_train = partial(_run_train_stats, batch_stats=False)     # -> (params, logits, sown values)
 
 
 @pytest.fixture(scope="module")
 def dev():
   assert torch.cuda.is_available()
   return torch.device("cuda:0")
-
-
-def _np(t):
-  return t.detach().cpu().numpy()
 
 
 def _setup(dev, quantized=True, T=6, B=4, K=256, hidden=96, out=110, tau=2.0, v_reset=0.0,
@@ -43,20 +41,6 @@ def _setup(dev, quantized=True, T=6, B=4, K=256, hidden=96, out=110, tau=2.0, v_
                                 v_reset=v_reset, v_threshold=v_threshold)
   model = models.DenseSNN(num_classes=out // 10, config=cfg)
   return model, v, nn.tree_from_numpy(v, dev), torch.from_numpy(x).to(dev)
-
-
-def _leaves(variables):
-  return {k: {kk: ({kkk: t.detach().clone().requires_grad_(True) for kkk, t in vv.items()}
-                   if isinstance(vv, dict) else vv.detach().clone().requires_grad_(True))
-              for kk, vv in leaf.items()}
-          for k, leaf in variables["params"].items()}
-
-
-def _run_train(model, variables, x, rng=0):
-  params = _leaves(variables)
-  (logits, _), mut = model.apply({"params": params, "batch_stats": {}}, x, train=True, rng=rng,
-                                 mutable=["intermediates"])
-  return params, logits, {k: v[0] for k, v in mut["intermediates"].items()}
 
 
 def _dense(s):

@@ -2,6 +2,7 @@
 references of tests/train_reference.py, at the edges of the 16 / 32 / 64 tiles and of the
 surrogates.  Where bits cannot be promised (slayer's expf) the bound is derived, not tuned."""
 import ctypes
+from functools import partial
 
 import numpy as np
 import pytest
@@ -10,6 +11,7 @@ import torch
 from snnquantprune_amd import _lib as L
 from snnquantprune_amd import ops
 from tests import train_reference as tr
+from tests.train_helpers import _frame_untouched, _framed as _framed_at, _np, mixed
 
 pytestmark = pytest.mark.gpu
 
@@ -21,15 +23,6 @@ SENTINEL = -12345.5
 def dev():
   assert torch.cuda.is_available()
   return torch.device("cuda:0")
-
-
-def _np(t):
-  return t.detach().cpu().numpy()
-
-
-def mixed(rng, shape):
-  """Mixed magnitudes, so that the order of a float32 sum shows in its bits."""
-  return (rng.standard_normal(shape) * 2.0 ** rng.integers(-6, 7, shape)).astype(F32)
 
 
 def _a_operand(rng, kind, shape):
@@ -107,14 +100,9 @@ def test_input_grad_bit_equal_chain(dev, shape):
 
 # ---- raw ABI: strays, empties, error codes -----------------------------------------------------
 
-def _framed(dev, values, fill, pad=37):
-  """`values` as a slice of a larger device buffer filled with `fill`; the odd pad also leaves the
-  slice only 4-byte aligned.  Returns (buffer, slice)."""
-  n = int(np.prod(values.shape))
-  buf = torch.full((pad + n + pad,), float(fill), dtype=torch.float32, device=dev)
-  view = buf[pad:pad + n].view(values.shape)
-  view.copy_(torch.from_numpy(np.ascontiguousarray(values)))
-  return buf, view
+# the frame of this file is 37 elements: odd, so that the slices are only 4-byte aligned
+_framed = partial(_framed_at, pad=37)
+_frame_intact = partial(_frame_untouched, pad=37)
 
 
 def _ptr(t):
@@ -123,11 +111,6 @@ def _ptr(t):
 
 def _stream():
   return ctypes.c_void_p(torch.cuda.current_stream().cuda_stream)
-
-
-def _frame_intact(buf, n, fill, pad=37):
-  b = _np(buf)
-  return bool((b[:pad] == fill).all() and (b[pad + n:] == fill).all())
 
 
 @pytest.mark.parametrize("shape", [(17, 65, 33), (33, 15, 17), (3, 129, 1), (100, 63, 65),
