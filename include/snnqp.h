@@ -244,8 +244,8 @@ typedef struct {
  * compatible: snnqp_weight_t.cout_fire in the struct's former tail padding,
  * snnqp_set_event_half_group, snnqp_conv_event_half_group; training of CextNet's gated stages --
  * snnqp_gate_pool_grad_gate, snnqp_gate_pool_grad_input, snnqp_conv_weight_grad_f64,
- * snnqp_conv_weight_grad_f64_workspace_bytes; the batched event front end snnqp_events_bin: new entry
- * points, nothing else moves).
+ * snnqp_conv_weight_grad_f64_workspace_bytes; the batched event front end snnqp_events_bin; the host-side
+ * query snnqp_conv_float_form: new entry points, nothing else moves).
  * A binding compares snnqp_version()
  * with the SNNQP_VERSION it was written against and refuses a library of another version (_lib.py does). */
 #define SNNQP_VERSION 507
@@ -372,6 +372,26 @@ int snnqp_unpack_bits(const uint32_t *bits, int64_t rows, int32_t C, float *y,
 int snnqp_conv_forward(const void *x, int in_type, int64_t NB,
                        const snnqp_conv_geom_t *g, const snnqp_weight_t *w,
                        float *y, int32_t *acc, snnqp_stream_t stream);
+/* Which kernel snnqp_conv_forward(x, in_type, NB, g, w, y, acc = NULL) runs.  Launches nothing; `x`
+ * is looked at for its address only and never dereferenced.  A negative SNNQP_E* for a null or
+ * malformed descriptor (null g, w, w->w or x; NB outside [0, 2^31); unknown input or weight type; a
+ * geometry snnqp_conv_forward refuses).  SNNQP_FLOAT_FORM_DIRECT (0): the direct-form kernel, one
+ * thread per output -- integer codes, or a float32 kernel whose geometry the float32 MFMA
+ * connection does not serve (strided, dilated, grouped, or pad_lo + pad_hi != K - 1).  Otherwise
+ * that connection (y[m][n] = the k-ascending float32 fmaf chain from +0), as tile + mode:
+ *   SNNQP_FLOAT_FORM_TILE(f)  64 or 128: a workgroup owns tile x tile outputs.  128 when
+ *                             ceil(M / 128) * ceil(N / 128) >= 192 and N > 64, M = NB H W, N = Cout.
+ *   SNNQP_FLOAT_FORM_MODE(f)  how a chunk of 16 k is staged: 0 float32, Cin % 16 == 0; 1 float32,
+ *                             Cin % 4 == 0; 2 element by element (any type and Cin); 3 uint8 / spike
+ *                             words with one tap per chunk (a 1 x 1 kernel -- uint8: Cin % 8 == 0 --
+ *                             or Cin % 16 == 0; uint8 only when x is 8-byte aligned, else mode 2).
+ * Modes 0 and 1 read float32 x, and Cout % 4 == 0 reads w, in 16-byte units: nothing is promised
+ * for such pointers aligned below 16 bytes. */
+#define SNNQP_FLOAT_FORM_DIRECT 0
+#define SNNQP_FLOAT_FORM_TILE(f) ((f) & ~3)
+#define SNNQP_FLOAT_FORM_MODE(f) ((f) & 3)
+int snnqp_conv_float_form(const void *x, int in_type, int64_t NB,
+                          const snnqp_conv_geom_t *g, const snnqp_weight_t *w);
 /* The same call site with a choice of kernel.  On integer codes and a spike raster
  * snnqp_conv_forward runs the direct-form kernel, one thread per output; here the 3x3 / stride 1
  * / pad 1 connection over SNNQP_BITS input with 1 <= Cin <= 128 (any H, W, Cout) runs as an MFMA

@@ -95,6 +95,7 @@ _PROTOTYPES = {
     "snnqp_unpack_bits": (c_int, [c_void_p, c_int64, c_int32, c_void_p, c_void_p]),
     "snnqp_conv_forward": (c_int, [c_void_p, c_int, c_int64, POINTER(ConvGeomT),
                                    POINTER(WeightT), c_void_p, c_void_p, c_void_p]),
+    "snnqp_conv_float_form": (c_int, [c_void_p, c_int, c_int64, POINTER(ConvGeomT), POINTER(WeightT)]),
     "snnqp_conv_forward_ex": (c_int, [c_void_p, c_int, c_int64, POINTER(ConvGeomT),
                                       POINTER(WeightT), c_void_p, c_void_p, c_void_p, c_int, c_void_p]),
     "snnqp_conv_forward_if": (c_int, [c_void_p, c_void_p, c_int, c_int64, POINTER(ConvGeomT),

@@ -243,6 +243,28 @@ const char *fseq_gemm_unsupported(int in_type, const snnqp_conv_geom_t *g,
   return nullptr;
 }
 
+// The instantiation a request runs on -- decided here alone, for the launch and for
+// snnqp_conv_float_form.  `x` counts by its address only.
+FseqForm fseq_gemm_form(const void *x, int in_type, int64_t NB, const snnqp_conv_geom_t *g) {
+  const int64_t M = NB * g->H * g->W;
+  const int N = g->Cout, Cin = g->Cin;
+  FseqForm f;
+  // the small tile when the large one would leave most of the chip idle
+  const int64_t big = ceil_div64(M, 128) * ((N + 127) / 128);
+  // ... or when at most 64 columns exist (the TCJA gate's convolution along the channels has
+  // N = T = 20 outputs: three quarters of a 128-column tile would multiply zeros)
+  f.tm = (big < 192 || N <= 64) ? 1 : 2;
+  const bool one = g->KH == 1 && g->KW == 1 && g->pad_h_lo == 0 && g->pad_w_lo == 0;    // k = channel, pixel = row
+  const bool tapwise = Cin % FG_KC == 0;     // a k chunk lies in one tap
+  if (in_type == SNNQP_U8 && ((one && Cin % 8 == 0) || tapwise) && ((uintptr_t)x & 7) == 0) f.mode = 3;
+  else if (in_type == SNNQP_BITS && (one || tapwise)) f.mode = 3;
+  else if (in_type == SNNQP_U8 || in_type == SNNQP_BITS) f.mode = 2;
+  else if (tapwise) f.mode = 0;
+  else if (Cin % 4 == 0) f.mode = 1;
+  else f.mode = 2;
+  return f;
+}
+
 int run_fseq_gemm(const void *x, int in_type, int64_t NB, const snnqp_conv_geom_t *g,
                   const snnqp_weight_t *w, float *y, hipStream_t st) {
   FseqGemmArgs a;
@@ -252,27 +274,23 @@ int run_fseq_gemm(const void *x, int in_type, int64_t NB, const snnqp_conv_geom_
   a.H = g->H; a.W = g->W; a.Cin = g->Cin; a.KH = g->KH; a.KW = g->KW;
   a.pad_h = g->pad_h_lo; a.pad_w = g->pad_w_lo;
   if (a.M == 0 || a.N == 0) return SNNQP_OK;
-  // the small tile when the large one would leave most of the chip idle
-  const int64_t big = ceil_div64(a.M, 128) * ((a.N + 127) / 128);
-  // ... or when at most 64 columns exist (the TCJA gate's convolution along the channels has
-  // N = T = 20 outputs: three quarters of a 128-column tile would multiply zeros)
-  const int tm = (big < 192 || a.N <= 64) ? 1 : 2;
+  const FseqForm f = fseq_gemm_form(x, in_type, NB, g);
+  const int tm = f.tm;
   const int64_t gx = ceil_div64(a.M, 64 * tm);
   SNNQP_REQUIRE(gx < (1ll << 31), SNNQP_EINVAL, "fseq gemm: grid too large");
   const dim3 grid((unsigned)gx, (unsigned)((a.N + 64 * tm - 1) / (64 * tm)));
-  const bool one = a.KH == 1 && a.KW == 1 && a.pad_h == 0 && a.pad_w == 0;    // k = channel, pixel = row
 #define SNNQP_FG_LAUNCH(MODE, IN)                                                                  \
   do {                                                                                             \
     if (tm == 1) hipLaunchKernelGGL((fseq_gemm_kernel<MODE, IN, 1>), grid, dim3(256), 0, st, a);   \
     else hipLaunchKernelGGL((fseq_gemm_kernel<MODE, IN, 2>), grid, dim3(256), 0, st, a);           \
   } while (0)
-  const bool tapwise = a.Cin % FG_KC == 0;     // a k chunk lies in one tap
-  if (in_type == SNNQP_U8 && ((one && a.Cin % 8 == 0) || tapwise) && ((uintptr_t)x & 7) == 0) SNNQP_FG_LAUNCH(3, SNNQP_U8);
-  else if (in_type == SNNQP_BITS && (one || tapwise)) SNNQP_FG_LAUNCH(3, SNNQP_BITS);
+  // (fseq_gemm_form gives integer-typed input modes 3 and 2 only, float32 modes 0, 1 and 2)
+  if (in_type == SNNQP_U8 && f.mode == 3) SNNQP_FG_LAUNCH(3, SNNQP_U8);
+  else if (in_type == SNNQP_BITS && f.mode == 3) SNNQP_FG_LAUNCH(3, SNNQP_BITS);
   else if (in_type == SNNQP_U8) SNNQP_FG_LAUNCH(2, SNNQP_U8);
   else if (in_type == SNNQP_BITS) SNNQP_FG_LAUNCH(2, SNNQP_BITS);
-  else if (a.Cin % FG_KC == 0) SNNQP_FG_LAUNCH(0, SNNQP_F32);
-  else if (a.Cin % 4 == 0) SNNQP_FG_LAUNCH(1, SNNQP_F32);
+  else if (f.mode == 0) SNNQP_FG_LAUNCH(0, SNNQP_F32);
+  else if (f.mode == 1) SNNQP_FG_LAUNCH(1, SNNQP_F32);
   else SNNQP_FG_LAUNCH(2, SNNQP_F32);
 #undef SNNQP_FG_LAUNCH
   SNNQP_CHECK_LAUNCH("fseq_gemm_kernel");

@@ -307,6 +307,25 @@ extern "C" int snnqp_conv_forward(const void *x, int in_type, int64_t NB,
                      nullptr, nullptr, y, SNNQP_F32, acc, (hipStream_t)stream);
 }
 
+// Which kernel snnqp_conv_forward(x, in_type, NB, g, w, y, acc = NULL) runs (snnqp.h): the same
+// checks in the same order, and the form from the function the launch itself reads.
+extern "C" int snnqp_conv_float_form(const void *x, int in_type, int64_t NB,
+                                     const snnqp_conv_geom_t *g, const snnqp_weight_t *w) {
+  using namespace snnqp;
+  SNNQP_REQUIRE(g && w, SNNQP_EINVAL, "conv_float_form: null descriptor");
+  SNNQP_REQUIRE(x && w->w, SNNQP_EINVAL, "conv_float_form: null pointer");
+  SNNQP_REQUIRE(NB >= 0 && NB < (1ll << 31), SNNQP_EINVAL, "conv_float_form: bad NB");
+  SNNQP_REQUIRE(w->wtype == SNNQP_W_F32 || w->wtype == SNNQP_W_I8, SNNQP_EINVAL,
+                "conv_float_form: unknown weight type");
+  SNNQP_REQUIRE(in_type == SNNQP_F32 || in_type == SNNQP_U8 || in_type == SNNQP_BITS, SNNQP_EINVAL,
+                "conv_float_form: unknown input type %d", in_type);
+  int32_t OH, OW;
+  if (int rc = check_geom(g, &OH, &OW)) return rc;
+  if (fseq_gemm_unsupported(in_type, g, w)) return SNNQP_FLOAT_FORM_DIRECT;
+  const FseqForm f = fseq_gemm_form(x, in_type, NB, g);
+  return 64 * f.tm + f.mode;
+}
+
 // snnqp_conv_forward with a choice of kernel (snnqp.h): the currents form of the bit-input MFMA
 // conv where it can serve the request, else (or on demand) the routes above.  Every refusal
 // comes before a launch; the fallback counters are for fused blocks and stay as they are.

@@ -94,6 +94,9 @@ int64_t dq_table_fallbacks(bool reset);
 // float32 x float32 connection on the f32 MFMA (fseq_gemm.hip)
 const char *fseq_gemm_unsupported(int in_type, const snnqp_conv_geom_t *g,
                                   const snnqp_weight_t *w);
+// the instantiation a served request runs on: staging MODE 0..3, tm 1 (64 x 64 tile) or 2 (128 x 128)
+struct FseqForm { int mode, tm; };
+FseqForm fseq_gemm_form(const void *x, int in_type, int64_t NB, const snnqp_conv_geom_t *g);
 int run_fseq_gemm(const void *x, int in_type, int64_t NB, const snnqp_conv_geom_t *g,
                   const snnqp_weight_t *w, float *y, hipStream_t st);
 

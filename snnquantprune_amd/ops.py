@@ -817,6 +817,35 @@ def conv_forward(x, geom: ConvGeom, weight: Weight, want_acc: bool = False, impl
   return (y, acc) if want_acc else y
 
 
+_IN_NAMES = {L.F32: "f32", L.U8: "u8", L.BITS: "bits"}
+
+
+def conv_float_form(x, geom: ConvGeom, weight: Weight, NB: Optional[int] = None):
+  """Which kernel conv_forward(x, geom, weight) runs on the launch of snnqp_conv_forward
+  (snnqp_conv_float_form; no device work, host tensors serve as well): "direct" for the direct-form
+  kernel, else (input type "f32" / "u8" / "bits", staging mode 0..3, tile 64 or 128) of the
+  float32-MFMA connection, e.g. ("u8", 3, 128).  `x`: the contiguous [NB, H, W, Cin] tensor or
+  PackedSpikes as the library would get it -- only its address, type and NB count --, or a pair
+  (address, in_type) with `NB` given, where no tensor exists."""
+  if isinstance(x, tuple):
+    addr, in_type = int(x[0]), int(x[1])
+    if NB is None:
+      raise ValueError("conv_float_form: an (address, in_type) pair needs NB")
+  else:
+    xt, in_type = _in_desc(x)
+    if not xt.is_contiguous():
+      raise ValueError("conv_float_form: x must be contiguous (its address decides)")
+    addr = xt.data_ptr()
+    NB = xt.shape[0] if NB is None else NB
+  g, w = geom.struct(), weight.struct()
+  rc = L.lib().snnqp_conv_float_form(ctypes.c_void_p(addr), in_type, int(NB), ctypes.byref(g), ctypes.byref(w))
+  if rc < 0:
+    L.check(rc)
+  if rc == 0:
+    return "direct"
+  return _IN_NAMES[in_type], rc & 3, rc & ~3
+
+
 def conv3d_lif_forward(x, geom: Conv3dGeom, weight: Weight, neuron: Optional[Neuron] = None,
                        bn: Optional[BnCoeffs] = None, u0: Optional[torch.Tensor] = None, want_u: bool = True,
                        packed_out: bool = False, pred: Optional[torch.Tensor] = None, out=None):

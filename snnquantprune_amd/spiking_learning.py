@@ -31,6 +31,11 @@ from .flax_qdense import QuantDense
 
 Array = Any
 
+# Blocks that hold the float32 currents of a whole slice between the connection and the neuron scan
+# (SpikingBlock._float_block, ._gated_block) walk the batch in slices whose currents stay under
+# this many bytes; read at every call.
+CURRENTS_SLICE_BYTES = 1 << 30
+
 
 # ---------------------------------------------------------------------------
 # initialisers, spiking_learning.py:24-77 (host side)
@@ -651,7 +656,7 @@ class SpikingBlock(nn.Module):
     u0 = None if (u is None or isinstance(u, ZeroCarry)) else u
     packed_out = True if self.packed is None else bool(self.packed)
     per_sample = 4 * T * geom.H * geom.W * N              # bytes of float32 currents
-    step = max(1, min(B, (1 << 30) // max(per_sample, 1)))
+    step = max(1, min(B, CURRENTS_SLICE_BYTES // max(per_sample, 1)))
     us, ss = [], []
     for b0 in range(0, max(B, 1), step):      # (an empty batch: one empty slice)
       b1 = min(B, b0 + step)
@@ -735,7 +740,7 @@ class SpikingBlock(nn.Module):
     T, B = (x.shape[0], x.shape[1]) if tm else (x.shape[1], x.shape[0])
     N = geom.Cout
     per_sample = 4 * T * geom.H * geom.W * N              # bytes of float32 currents
-    step = max(1, min(B, (1 << 30) // max(per_sample, 1)))
+    step = max(1, min(B, CURRENTS_SLICE_BYTES // max(per_sample, 1)))
     tag = "%s[f32 %s]" % ("dense" if is_dense else "conv", geom.tag())
     us, ss = [], []
     for b0 in range(0, max(B, 1), step):      # (an empty batch: one empty slice)

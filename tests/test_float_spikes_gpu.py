@@ -8,6 +8,9 @@ odd pooled images included; the bit-packed result unpacks to the float32 one; no
 into the device status word.  Integer-valued input is checked against the `int` contract, input
 with a non-integer against `fseq`.  With packed=False the quantised conv and dense blocks run on the
 direct-form kernel, so the shapes stay small.
+
+Section I lowers the byte budget of the blocks that walk the batch in slices, so that the code
+behind more than one slice runs: sliced and whole must agree bit for bit, and with the oracle.
 """
 from functools import lru_cache
 
@@ -51,14 +54,15 @@ def _conv_block(bits, N, pool, packed, ks=(3, 3), padding=((1, 1), (1, 1)), bn=T
                       pool=pool, return_state=True, packed=packed, batch_major_input=batch_major)
 
 
-def _dense_block(bits, N, packed, use_bias=False):
+def _dense_block(bits, N, packed, use_bias=False, batch_major=False):
   from snnquantprune_amd import synthetic as syn
   from snnquantprune_amd.flax_qdense import QuantDense
   from snnquantprune_amd.spiking_learning import SpikingBlock
   cfg = syn.make_config(bits=bits, prune_percentage=0.5)
   return SpikingBlock(connection_fn=QuantDense(N, use_bias=use_bias, config=cfg.quant, bits=bits,
                                                g_scale=cfg.quant.g_scale),
-                      neural_dynamics=cfg.neuron_dynamics(dtype=torch.float32), return_state=True, packed=packed)
+                      neural_dynamics=cfg.neuron_dynamics(dtype=torch.float32), return_state=True, packed=packed,
+                      batch_major_input=batch_major)
 
 
 def _conv_vars(leaf, bn, dev):
@@ -525,4 +529,167 @@ def test_conv_lif_forward_float32_spikes_at_the_abi(dev, oracle):
       assert e.value.code == L.EUNSUPPORTED and "unpack" in str(e.value), str(e.value)
       after = ops.fallback_counts()
       assert after["conv_blocks"] == before["conv_blocks"], (fmt, packed_out)
+  assert ops.device_status() == 0
+
+
+# ---------------------------------------------------------------------------
+# I. the batch walked in slices (spiking_learning.CURRENTS_SLICE_BYTES)
+# ---------------------------------------------------------------------------
+# Blocks that keep a slice's float32 currents between the connection and the neuron scan walk the
+# batch under a byte budget; at the product value more than one slice needs over 1 GiB of currents.
+# Lowered here so that B = 5 walks as 2 + 2 + 1: the carried state sliced on axis 0, the batch-major
+# input sliced and transposed, potentials joined on axis 0 and rasters on axis 1.
+
+SL_T, SL_B, SL_C, SL_N = 3, 5, 32, 64
+SLICE_KINDS = ["f32_real", "u8_counts", "packed"]
+
+
+@lru_cache(maxsize=None)
+def _slice_conv_case(hw):
+  """An unquantised 3x3 conv block: (leaf, bn, u0, {kind: host input [T, B, hw, hw, C]})."""
+  from snnquantprune_amd import synthetic as syn
+  leaf = syn.quant_leaf((3, 3, SL_C, SL_N), 5.0, 1991 + hw, False, 0.5)
+  bp, bs = syn.bn_leaf(SL_N, True, 1992 + hw)
+  bn = dict(mean=bs["mean"], var=bs["var"], scale=bp["scale"], bias=bp["bias"])
+  rng = np.random.Generator(np.random.PCG64(1993 + hw))
+  shape = (SL_T, SL_B, hw, hw, SL_C)
+  xs = {"f32_real": ((rng.random(shape) < 0.3) * rng.random(shape) * 2).astype(F32),
+        "u8_counts": np.minimum(rng.poisson(0.15, shape), 255).astype(np.uint8),
+        "packed": (rng.random(shape) < 0.2).astype(np.uint8)}
+  assert xs["u8_counts"].max() > 1
+  u0 = (rng.standard_normal((SL_B, hw, hw, SL_N)) * 0.4).astype(F32)
+  return leaf, bn, u0, xs
+
+
+@lru_cache(maxsize=None)
+def _slice_conv_expected(hw, kind):
+  from oracle import snn_oracle as oracle
+  leaf, bn, u0, xs = _slice_conv_case(hw)
+  qw = qweight_of(oracle, leaf, 4, quantized=False)
+  return oracle.conv_block(xs[kind].astype(F32), qw, bn, None, "fseq", u0=u0)
+
+
+@lru_cache(maxsize=None)
+def _slice_dense_case():
+  """An unquantised dense block, K = 200 -> N = 70: (leaf, u0, {kind: host input [T, B, K]})."""
+  from snnquantprune_amd import synthetic as syn
+  K, N = 200, 70
+  leaf = syn.quant_leaf((K, N), 4.0, 2991, False, 0.5)
+  rng = np.random.Generator(np.random.PCG64(2993))
+  shape = (SL_T, SL_B, K)
+  xs = {"f32_real": ((rng.random(shape) < 0.3) * rng.random(shape) * 2).astype(F32),
+        "u8_counts": np.minimum(rng.poisson(0.15, shape), 255).astype(np.uint8),
+        "packed": (rng.random(shape) < 0.2).astype(np.uint8)}
+  u0 = (rng.standard_normal((SL_B, N)) * 0.4).astype(F32)
+  return leaf, u0, xs
+
+
+@lru_cache(maxsize=None)
+def _slice_dense_expected(kind):
+  from oracle import snn_oracle as oracle
+  leaf, u0, xs = _slice_dense_case()
+  return oracle.dense_block(xs[kind].astype(F32), qweight_of(oracle, leaf, 4, quantized=False), None, "fseq", u0=u0)
+
+
+@lru_cache(maxsize=None)
+def _slice_gated_case():
+  """A quantised Cin-32 3x3 conv block behind a gate: (leaf, bn, u0, spikes, gate, (u_T, raster))."""
+  from oracle import snn_oracle as oracle
+  from snnquantprune_amd import synthetic as syn
+  H = W = 8
+  leaf = syn.quant_leaf((3, 3, SL_C, 128), 12.0, 3971, True, 0.9)      # (32 gated inputs: rate 0.12)
+  bp, bs = syn.bn_leaf(128, True, 3972)
+  bn = dict(mean=bs["mean"], var=bs["var"], scale=bp["scale"], bias=bp["bias"])
+  rng = np.random.Generator(np.random.PCG64(3973))
+  s = (rng.random((SL_T, SL_B, H, W, SL_C)) < 0.2).astype(np.uint8)
+  gate = (1.0 / (1.0 + np.exp(-rng.standard_normal((SL_T, SL_B, SL_C)) * 1.5))).astype(F32)
+  u0 = (rng.standard_normal((SL_B, H, W, 128)) * 0.4).astype(F32)
+  exp = oracle.gated_conv_block(s.astype(F32), gate, qweight_of(oracle, leaf, 4), bn, u0=u0)
+  return leaf, bn, u0, s, gate, exp
+
+
+def _slice_input(kind, x, batch_major, dev):
+  from snnquantprune_amd import ops
+  if batch_major:
+    x = np.swapaxes(x, 0, 1)
+  t = _t(x, dev)
+  return ops.pack_bits(t) if kind == "packed" else t
+
+
+def _walk(monkeypatch, name, blocks, variables, u0, x, per_sample, T, eu, es, tag, dev):
+  """Runs each block of `blocks` (packed=False, packed=True) in one slice and with the budget at
+  2.5 samples, counts the launches of ops.<name>, and checks both runs against each other bit for
+  bit and against the oracle."""
+  from snnquantprune_amd import ops
+  from snnquantprune_amd import spiking_learning as sl
+  assert sl.CURRENTS_SLICE_BYTES == 1 << 30
+  launches = []
+  real = getattr(ops, name)
+
+  def spy(xi, *a, **k):
+    # (images of the launch: [T, nb, ...] behind a gate, T * nb rows else)
+    launches.append(int(xi.spikes.shape[1]) if isinstance(xi, ops.GatedSpikes) else int(xi.shape[0]) // T)
+    return real(xi, *a, **k)
+  monkeypatch.setattr(ops, name, spy)
+  got = {}
+  for budget, want in ((1 << 30, [SL_B]), (2 * per_sample + per_sample // 2, [2, 2, 1])):
+    monkeypatch.setattr(sl, "CURRENTS_SLICE_BYTES", budget)
+    for blk in blocks:
+      del launches[:]
+      got[budget, blk.packed] = blk.apply(variables, _t(u0, dev), x)
+      assert launches == want, (tag, budget, launches)
+  monkeypatch.setattr(sl, "CURRENTS_SLICE_BYTES", 1 << 30)
+  monkeypatch.setattr(ops, name, real)
+  for packed in (False, True):
+    (u1, s1), (u3, s3) = got[1 << 30, packed], got[2 * per_sample + per_sample // 2, packed]
+    assert tuple(u3.shape) == tuple(u1.shape) and u3.is_contiguous()
+    np.testing.assert_array_equal(_np(u3).view(np.uint32), _np(u1).view(np.uint32), err_msg=tag + " u_T sliced vs whole")
+    b1, b3 = (s1.bits, s3.bits) if packed else (s1, s3)
+    assert tuple(s3.shape) == tuple(s1.shape) and b3.is_contiguous()
+    np.testing.assert_array_equal(_np(b3), _np(b1), err_msg=tag + " raster sliced vs whole")
+  sliced = 2 * per_sample + per_sample // 2
+  _check(got[sliced, False], got[sliced, True], eu, es, tag + " sliced")
+  _check(got[1 << 30, False], got[1 << 30, True], eu, es, tag + " whole")
+
+
+@pytest.mark.parametrize("batch_major", [False, True], ids=["time_major", "batch_major"])
+@pytest.mark.parametrize("kind", SLICE_KINDS)
+@pytest.mark.parametrize("hw,pool", [(9, 1), (8, 2)], ids=["hw9_pool1", "hw8_pool2"])
+def test_float_conv_block_walks_the_batch_in_slices(dev, oracle, monkeypatch, hw, pool, kind, batch_major):
+  from snnquantprune_amd import ops
+  leaf, bn, u0, xs = _slice_conv_case(hw)
+  eu, es = _slice_conv_expected(hw, kind)
+  assert 0.01 < es.mean() < 0.6 and np.abs(eu).max() > 0
+  x = _slice_input(kind, xs[kind], batch_major, dev)
+  blocks = [_conv_block(4, SL_N, pool, p, batch_major=batch_major) for p in (False, True)]
+  _walk(monkeypatch, "conv_forward", blocks, _conv_vars(leaf, bn, dev), u0, x, 4 * SL_T * hw * hw * SL_N, SL_T,
+        eu, _pooled(oracle, es, pool), "conv %s hw %d pool %d %s" % (kind, hw, pool, "BM" if batch_major else "TM"), dev)
+  assert ops.device_status() == 0
+
+
+@pytest.mark.parametrize("batch_major", [False, True], ids=["time_major", "batch_major"])
+@pytest.mark.parametrize("kind", SLICE_KINDS)
+def test_float_dense_block_walks_the_batch_in_slices(dev, oracle, monkeypatch, kind, batch_major):
+  from snnquantprune_amd import linen as nn
+  from snnquantprune_amd import ops
+  leaf, u0, xs = _slice_dense_case()
+  eu, es = _slice_dense_expected(kind)
+  assert 0.01 < es.mean() < 0.6
+  x = _slice_input(kind, xs[kind], batch_major, dev)
+  blocks = [_dense_block(4, 70, p, batch_major=batch_major) for p in (False, True)]
+  variables = nn.tree_from_numpy({"params": {"connection_fn": leaf}}, dev)
+  _walk(monkeypatch, "conv_forward", blocks, variables, u0, x, 4 * SL_T * 70, SL_T, eu, es,
+        "dense %s %s" % (kind, "BM" if batch_major else "TM"), dev)
+  assert ops.device_status() == 0
+
+
+@pytest.mark.parametrize("pool", [1, 2], ids=["pool1", "pool2"])
+def test_gated_conv_block_walks_the_batch_in_slices(dev, oracle, monkeypatch, pool):
+  from snnquantprune_amd import ops
+  leaf, bn, u0, s, gate, (eu, es) = _slice_gated_case()
+  assert 0.01 < es.mean() < 0.6
+  x = ops.GatedSpikes(ops.pack_bits(_t(s, dev)), _t(gate, dev))
+  blocks = [_conv_block(4, 128, pool, p) for p in (False, True)]
+  _walk(monkeypatch, "conv_gated_forward", blocks, _conv_vars(leaf, bn, dev), u0, x, 4 * SL_T * 8 * 8 * 128, SL_T,
+        eu, _pooled(oracle, es, pool), "gated conv pool %d" % pool, dev)
   assert ops.device_status() == 0
