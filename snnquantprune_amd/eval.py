@@ -78,6 +78,28 @@ def restore_checkpoint(state: Optional[EvalState], workdir: str, apply_fn: Calla
                    batch_stats=tree["batch_stats"])
 
 
+def eval_pass(state, eval_iter, steps_per_eval: int, config, world: int):
+  """`steps_per_eval` batches of eval_step and their mean over ALL ranks' shards (eval.py:120-133;
+  the loop of evaluate() and of train.train_and_evaluate): (summary, loss [world, steps],
+  accuracy [world, steps, B / world]).  The only device-to-host reads are the two means."""
+  loss_fn = config.get("loss_fn", mse_loss)
+  smoothing = config.get("smoothing", 0.0)
+  losses, accs = [], []
+  for _ in range(steps_per_eval):                                  # eval.py:120-126
+    batch = next(eval_iter)
+    m = eval_step(state, batch, None, smoothing, loss_fn)
+    losses.append(m["loss"].reshape(1).to(torch.float32))
+    accs.append(m["accuracy"].to(torch.float32))
+  # stack_forest + the all-gather that stands in for pmap's stacked outputs (eval.py:128):
+  # loss [steps, world], accuracy [steps, world, B / world]
+  loss = parallel.all_gather_rows(torch.stack(losses, 1)) if losses else torch.zeros((world, 0))
+  acc = parallel.all_gather_rows(torch.stack(accs, 0).unsqueeze(0)) if accs else torch.zeros((world, 0, 0))
+  summary = {"loss": float(loss.mean()) if loss.numel() else float("nan"),
+             "accuracy": float(acc.mean()) if acc.numel() else float("nan"),
+             "samples": int(acc.numel()), "steps": int(steps_per_eval), "world": world}
+  return summary, loss, acc
+
+
 def evaluate_metrics(config, workdir: str, *, model=None, source=None, device=None):
   """The body of evaluate(): returns (state, summary, per_step) with summary =
   {'loss', 'accuracy', 'samples', 'steps'} over ALL ranks' shards."""
@@ -117,21 +139,7 @@ def evaluate_metrics(config, workdir: str, *, model=None, source=None, device=No
     state = EvalState(state.apply_fn, {"params": prune_utils.prepare_params(state.params["params"], config)},
                       state.batch_stats)
 
-  loss_fn = config.get("loss_fn", mse_loss)
-  smoothing = config.get("smoothing", 0.0)
-  losses, accs = [], []
-  for _ in range(steps_per_eval):                                  # eval.py:120-126
-    batch = next(eval_iter)
-    m = eval_step(state, batch, None, smoothing, loss_fn)
-    losses.append(m["loss"].reshape(1).to(torch.float32))
-    accs.append(m["accuracy"].to(torch.float32))
-  # stack_forest + the all-gather that stands in for pmap's stacked outputs (eval.py:128):
-  # loss [steps, world], accuracy [steps, world, B / world]
-  loss = parallel.all_gather_rows(torch.stack(losses, 1)) if losses else torch.zeros((world, 0))
-  acc = parallel.all_gather_rows(torch.stack(accs, 0).unsqueeze(0)) if accs else torch.zeros((world, 0, 0))
-  summary = {"loss": float(loss.mean()) if loss.numel() else float("nan"),
-             "accuracy": float(acc.mean()) if acc.numel() else float("nan"),
-             "samples": int(acc.numel()), "steps": int(steps_per_eval), "world": world}
+  summary, loss, acc = eval_pass(state, eval_iter, steps_per_eval, config, world)
   if rank == 0:
     logging.info("Eval loss: %.4f, accuracy: %.2f", summary["loss"], summary["accuracy"] * 100)
   if device.type == "cuda":

@@ -139,9 +139,17 @@ class EventPlan:
     r = torch.randint(0, 1 << 62, (lo.shape[0],), generator=self.gen, dtype=torch.int64).numpy()
     return (lo + r % (hi - lo + 1)).astype(np.int64)
 
-  def batches(self, t_min=None, t_max=None):
+  def batches(self, t_min=None, t_max=None, skip: int = 0):
     """Endless (indices, starts) pairs: int64 sample indices within the rank's slice, and the
-    window origins of those rows (None for split_by = "number")."""
+    window origins of those rows (None for split_by = "number").  `skip`: the first `skip` pairs
+    are drawn -- permutations and origins alike, so the generator ends up where a consumer of them
+    leaves it -- and not yielded: what follows is what a fresh plan yields from its skip-th pair
+    on.  (An eval pass re-seeds, so only skip modulo the pass is drawn there.)"""
+    skip = int(skip)
+    if skip < 0:
+      raise ValueError("skip must be >= 0, got %d" % skip)
+    if not self.train:
+      skip %= self.nb
     while True:
       if self.train:
         order = torch.randperm(self.n, generator=self.gen).numpy()
@@ -152,12 +160,16 @@ class EventPlan:
         idx = order[i * self.per:(i + 1) * self.per]
         starts = self.draw_starts(np.asarray(t_min)[idx], np.asarray(t_max)[idx]) \
             if self.split_by == "time" else None
+        if skip > 0:
+          skip -= 1
+          continue
         yield idx, starts
 
 
 def create_event_split(data, config, train: bool, rank: int = 0, world: int = 1,
-                       device=None) -> Iterator[Dict[str, Any]]:
-  """The batches of an event source, decoded on `device` (see EventPlan for the rules)."""
+                       device=None, skip: int = 0) -> Iterator[Dict[str, Any]]:
+  """The batches of an event source, decoded on `device` (see EventPlan for the rules), from the
+  `skip`-th on: the plan is advanced on the host and nothing is launched for a skipped batch."""
   device = torch.device("cuda" if device is None else device)
   n = data["label"].shape[0]
   split = n // world                                               # :245-254
@@ -173,7 +185,7 @@ def create_event_split(data, config, train: bool, rank: int = 0, world: int = 1,
   divisor = None if plan.divisor is None else torch.full((), float(plan.divisor), dtype=torch.float32, device=device)
 
   def gen():
-    for idx, starts in plan.batches(events.t_min, events.t_max):
+    for idx, starts in plan.batches(events.t_min, events.t_max, skip):
       x = ops.events_bin(events, idx, plan.T, plan.H, plan.W, mode=plan.split_by, start=starts,
                          step_us=plan.step_us, scale=plan.scale, fmt=plan.fmt)
       if plan.divisor is not None:
@@ -183,12 +195,12 @@ def create_event_split(data, config, train: bool, rank: int = 0, world: int = 1,
 
 
 def create_split(source, config, train: bool, cache: bool, rank: int = 0, world: int = 1,
-                 pin: bool = False, device=None) -> Iterator[Dict[str, Any]]:
-  """Iterator of this process's batches (input_pipeline.py:222-345): host batches of a frame
-  source, device batches of an event source."""
+                 pin: bool = False, device=None, skip: int = 0) -> Iterator[Dict[str, Any]]:
+  """Iterator of this process's batches (input_pipeline.py:222-345), from the `skip`-th on: host
+  batches of a frame source, device batches of an event source."""
   source = _open_source(source)
   if is_event_source(source):
-    return create_event_split(load_source(source), config, train, rank, world, device)
+    return create_event_split(load_source(source), config, train, rank, world, device, skip)
   if train:
     raise NotImplementedError("the training split (shuffle, augmentation) is out of scope")
   data = load_source(source)
@@ -215,8 +227,9 @@ def create_split(source, config, train: bool, cache: bool, rank: int = 0, world:
       wx, wy = feed.pinned_like(wx), feed.pinned_like(wy)
 
   def gen():
+    first = int(skip) % nb
     while True:                                                    # ds.repeat()
-      for i in range(nb):
+      for i in range(first, nb):
         if cache:
           bx = wx.narrow(0, i * per, per) if isinstance(wx, ops.PackedFrames) else wx[i * per:(i + 1) * per]
           by = wy[i * per:(i + 1) * per]
@@ -224,17 +237,18 @@ def create_split(source, config, train: bool, cache: bool, rank: int = 0, world:
           bx = wire(x[i * per:(i + 1) * per])
           by = torch.from_numpy(np.ascontiguousarray(y[i * per:(i + 1) * per]))
         yield {"dvs_matrix": bx, "label": by}
+      first = 0
   return gen()
 
 
 def create_input_iter(source, config, train: bool, cache: bool, rank: int = 0, world: int = 1,
-                      device=None):
+                      device=None, skip: int = 0):
   """create_input_iter of input_pipeline.py:17-27: the split, prefetched two batches deep
-  to this process's device."""
+  to this process's device.  `skip`: start at the skip-th batch of the stream (a resumed run)."""
   device = torch.device("cuda" if torch.cuda.is_available() else "cpu") if device is None else device
   source = _open_source(source)
   if is_event_source(source):       # decoded on the device: nothing to prefetch
-    return create_event_split(load_source(source), config, train, rank, world, device)
+    return create_event_split(load_source(source), config, train, rank, world, device, skip)
   ds = create_split(source, config, train=train, cache=cache, rank=rank, world=world,
-                    pin=torch.device(device).type == "cuda")
+                    pin=torch.device(device).type == "cuda", skip=skip)
   return feed.DeviceFeeder(ds, device, 2)

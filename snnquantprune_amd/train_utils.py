@@ -1,16 +1,21 @@
 """Step functions -- mirror of examples/train_utils.py (eval_step :370-390, compute_metrics
 :220-225, mse_loss :210-217, cross_entropy_loss :196-207, create_model :133-134, and for the
 models that train here (DenseSNN, ConvDenseSNN, CextNet) create_train_state :161-195, weight_decay_fn :228-234 and the
-offline branch of train_step :249-368).  Not ported: the optax learning-rate schedules (any
-step -> lr callable is taken), the online branch, checkpoint writing.
+offline branch of train_step :249-368), create_learning_rate_fn :44-130 with the optax schedules
+it joins as plain functions of an integer step, save_checkpoint / restore_checkpoint :30-41 of a
+TrainState and sync_batch_stats :242-246.  Not ported: the online branch.
 """
 
 from __future__ import annotations
 
 import dataclasses
+import math
+import os
+import re
 from dataclasses import dataclass
 from typing import Any, Callable, Optional
 
+import numpy as np
 import torch
 
 
@@ -172,3 +177,273 @@ def train_step(state: TrainState, batch, rng, learning_rate_fn, weight_decay, sm
   if return_grads:
     return new_state, metrics, _unflatten([(path, g) for (path, _), g in zip(items, grads)])
   return new_state, metrics
+
+
+# ---------------------------------------------------------------------------
+# learning-rate schedules (train_utils.py:44-130)
+# ---------------------------------------------------------------------------
+#
+# The optax schedules the reference joins, as functions of an integer step that compute in Python
+# floats (float64).  optax is not available here: the formulas are recalled from upstream
+# (DESIGN.md 14.2 lists them and says which conventions are recalled only).
+
+
+def linear_schedule(init_value, end_value, transition_steps):
+  """optax.linear_schedule: init -> end over transition_steps, constant after; init at every step
+  when transition_steps is 0."""
+  init, end, n = float(init_value), float(end_value), float(transition_steps)
+
+  def schedule(step):
+    if n <= 0:
+      return init
+    c = min(max(float(step), 0.0), n)
+    return (init - end) * (1.0 - c / n) + end
+  return schedule
+
+
+def cosine_decay_schedule(init_value, decay_steps):
+  """optax.cosine_decay_schedule with alpha = 0: init * (1 + cos(pi min(step, n) / n)) / 2."""
+  init, n = float(init_value), float(decay_steps)
+  if not n > 0:
+    raise ValueError("cosine_decay_schedule needs positive decay_steps, got %r" % (decay_steps,))
+
+  def schedule(step):
+    c = min(float(step), n)
+    return init * 0.5 * (1.0 + math.cos(math.pi * c / n))
+  return schedule
+
+
+def join_schedules(schedules, boundaries):
+  """optax.join_schedules: schedule i + 1 takes over at boundaries[i] and counts from there.  The
+  cascade is evaluated in order, whatever the boundaries are, so boundaries that do not increase
+  (the start_epoch = -1 case of create_learning_rate_fn) still define every step."""
+  schedules, boundaries = list(schedules), list(boundaries)
+
+  def schedule(step):
+    out = schedules[0](step)
+    for b, s in zip(boundaries, schedules[1:]):
+      out = out if step < b else s(step - b)
+    return out
+  return schedule
+
+
+def piecewise_constant_schedule(init_value, boundaries_and_scales=None):
+  """optax.piecewise_constant_schedule: init times the scale of every boundary passed.  A boundary
+  counts as passed from the step AFTER it (step > boundary); the step equal to the boundary still
+  has the old value."""
+  init = float(init_value)
+  items = sorted((float(b), float(s)) for b, s in (boundaries_and_scales or {}).items())
+
+  def schedule(step):
+    out = init
+    for b, s in items:
+      if step > b:
+        out *= s
+    return out
+  return schedule
+
+
+def sgdr_schedule(cosine_kwargs):
+  """optax.sgdr_schedule: one warmup_cosine_decay_schedule (end value 0) per dict of init_value,
+  peak_value, warmup_steps and decay_steps, each starting where the previous one's decay_steps
+  end."""
+  schedules, boundaries, at = [], [], 0
+  for kw in cosine_kwargs:
+    warm = linear_schedule(kw["init_value"], kw["peak_value"], kw["warmup_steps"])
+    cos = cosine_decay_schedule(kw["peak_value"], kw["decay_steps"] - kw["warmup_steps"])
+    schedules.append(join_schedules([warm, cos], [kw["warmup_steps"]]))
+    at += kw["decay_steps"]
+    boundaries.append(at)
+  return join_schedules(schedules, boundaries[:-1])
+
+
+def create_learning_rate_fn(config, base_learning_rate: float, steps_per_epoch: int):
+  """train_utils.py:44-130, branch for branch and in its order: lr_boundaries_scale, t_max,
+  quant.start_epoch, plain warmup + cosine.  Returns step -> learning rate (a Python float)."""
+  if "lr_boundaries_scale" in config:
+    return piecewise_constant_schedule(
+        config.learning_rate,
+        {int(k) * steps_per_epoch: v for k, v in config.lr_boundaries_scale.items()})
+  if "t_max" in config:
+    return sgdr_schedule([{"decay_steps": config.t_max * steps_per_epoch,
+                           "init_value": base_learning_rate, "peak_value": base_learning_rate,
+                           "warmup_steps": 0}] * math.ceil(config.num_epochs / config.t_max))
+  if "quant" in config and "start_epoch" in config.quant:
+    start = config.quant.start_epoch
+    cosine_fn1 = cosine_decay_schedule(
+        base_learning_rate, max(start - config.warmup_epochs, 1) * steps_per_epoch)
+    cosine_fn2 = cosine_decay_schedule(
+        base_learning_rate, max(config.num_epochs - start - config.warmup_epochs, 1) * steps_per_epoch)
+    if config.warmup_epochs != 0.0:
+      warmup_fn1 = linear_schedule(0.0, base_learning_rate, config.warmup_epochs * steps_per_epoch)
+      warmup_fn2 = linear_schedule(0.0, base_learning_rate, config.warmup_epochs * steps_per_epoch)
+      b_len = [config.warmup_epochs * steps_per_epoch,             # :96-100, as it stands there
+               (start - config.warmup_epochs) * steps_per_epoch,
+               config.warmup_epochs * steps_per_epoch]
+      b_len[1] += b_len[0]
+      b_len[2] += b_len[1]
+      return join_schedules([warmup_fn1, cosine_fn1, warmup_fn2, cosine_fn2], b_len)
+    return join_schedules([cosine_fn1, cosine_fn2], [start * steps_per_epoch])
+  cosine_fn = cosine_decay_schedule(
+      base_learning_rate, max(config.num_epochs - config.warmup_epochs, 1) * steps_per_epoch)
+  if config.warmup_epochs != 0.0:
+    warmup_fn = linear_schedule(0.0, base_learning_rate, config.warmup_epochs * steps_per_epoch)
+    return join_schedules([warmup_fn, cosine_fn], [config.warmup_epochs * steps_per_epoch])
+  return cosine_fn
+
+
+# ---------------------------------------------------------------------------
+# checkpoints of a TrainState (train_utils.py:30-41), batch statistics over ranks (:242-246)
+# ---------------------------------------------------------------------------
+
+
+def _rank() -> int:
+  import torch.distributed as dist
+  return dist.get_rank() if dist.is_available() and dist.is_initialized() else 0
+
+
+def _host(t) -> np.ndarray:
+  return np.ascontiguousarray(t.detach().cpu().numpy().astype(np.float32, copy=False))
+
+
+def _host_tree(tree):
+  return {k: (_host_tree(v) if isinstance(v, dict) else _host(v)) for k, v in tree.items()}
+
+
+def _moment_tree(state: TrainState, key: str):
+  """{'params': tree} of one per-parameter entry of the torch.optim state; zeros where the
+  optimiser has not touched a leaf yet."""
+  items = []
+  for path, p in _flatten(state.params["params"]):
+    m = state.tx.state.get(p, {}).get(key)
+    items.append((path, _host(torch.zeros_like(p) if m is None else m)))
+  return {"params": _unflatten(items)}
+
+
+def _opt_kind(tx) -> str:
+  if isinstance(tx, torch.optim.Adam):
+    return "adam"
+  if isinstance(tx, torch.optim.SGD):
+    return "sgd_momentum" if tx.param_groups[0]["momentum"] else "sgd"
+  raise ValueError("no checkpoint layout for the optimiser %s" % type(tx).__name__)
+
+
+def _opt_state_dict(state: TrainState):
+  """The optimiser state in the layout optax gives the reference's optimisers (chains of two:
+  the transform, then scale_by_schedule with its own count)."""
+  kind = _opt_kind(state.tx)
+  steps = [s["step"] for s in state.tx.state.values() if "step" in s]
+  count = np.array(int(steps[0]) if steps else int(state.step), np.int32)
+  if kind == "adam":
+    first = {"count": count, "mu": _moment_tree(state, "exp_avg"), "nu": _moment_tree(state, "exp_avg_sq")}
+  elif kind == "sgd_momentum":
+    first = {"trace": _moment_tree(state, "momentum_buffer")}
+  else:
+    first = {}
+  return {"0": first, "1": {"count": count.copy()}}
+
+
+def state_dict(state: TrainState):
+  """TrainState.to_state_dict() of the reference, leaves as float32 numpy arrays."""
+  return {"step": int(state.step), "params": {"params": _host_tree(state.params["params"])},
+          "opt_state": _opt_state_dict(state), "batch_stats": _host_tree(state.batch_stats)}
+
+
+_CKPT = re.compile(r"checkpoint_(\d+(?:\.\d+)?)")
+
+
+def save_checkpoint(state: TrainState, workdir: str, keep: int = 3) -> Optional[str]:
+  """Writes workdir/checkpoint_<step> (flax's msgpack format, checkpoint.msgpack_serialize) from
+  rank 0, atomically and over an existing file of that step, then deletes all but the `keep`
+  newest checkpoints of the directory.  Returns the path, None on the other ranks."""
+  if _rank() != 0:
+    return None
+  from . import checkpoint
+  os.makedirs(workdir, exist_ok=True)
+  path = os.path.join(workdir, "checkpoint_%d" % int(state.step))
+  tmp = path + ".tmp-%d" % os.getpid()
+  with open(tmp, "wb") as f:
+    f.write(checkpoint.msgpack_serialize(state_dict(state)))
+  os.replace(tmp, path)
+  found = []
+  for name in os.listdir(workdir):
+    m = _CKPT.fullmatch(name)
+    if m and os.path.isfile(os.path.join(workdir, name)):
+      found.append((float(m.group(1)), name))
+  for _, name in sorted(found)[:max(len(found) - int(keep), 0)]:
+    os.remove(os.path.join(workdir, name))
+  return path
+
+
+def _check_like(got, want, path):
+  """Raises ValueError naming the first path at which the restored tree `got` differs from the
+  state's tree `want` (dict against dict, array against a tensor of the same shape)."""
+  where = "/".join(path) or "<root>"
+  if isinstance(want, dict):
+    if not isinstance(got, dict):
+      raise ValueError("checkpoint does not fit the state at %s: a tree is expected" % where)
+    for k in want:
+      if k not in got:
+        raise ValueError("checkpoint does not fit the state at %s: missing" % "/".join(path + (k,)))
+      _check_like(got[k], want[k], path + (k,))
+    for k in got:
+      if k not in want:
+        raise ValueError("checkpoint does not fit the state at %s: not in the state" % "/".join(path + (k,)))
+  elif isinstance(got, dict) or tuple(np.shape(got)) != tuple(want.shape):
+    raise ValueError("checkpoint does not fit the state at %s: shape %s, the state has %s"
+                     % (where, "of a tree" if isinstance(got, dict) else tuple(np.shape(got)), tuple(want.shape)))
+
+
+def _copy_tree_(dst, src):
+  for k, v in dst.items():
+    if isinstance(v, dict):
+      _copy_tree_(v, src[k])
+    else:
+      v.copy_(torch.from_numpy(np.ascontiguousarray(src[k], dtype=np.float32)))
+
+
+def restore_checkpoint(state: TrainState, workdir: str) -> TrainState:
+  """The newest checkpoint of `workdir` over `state`, or `state` unchanged when there is none
+  (flax's behaviour).  The tensors are copied into the state's own, which the optimiser keeps
+  pointing at; the torch.optim state is rebuilt from opt_state and state.step is set."""
+  from . import checkpoint
+  from .eval import latest_checkpoint
+  path = latest_checkpoint(workdir) if workdir and os.path.isdir(workdir) else None
+  if path is None:
+    return state
+  with open(path, "rb") as f:
+    tree = checkpoint.msgpack_restore(f.read())
+  params = state.params["params"]
+  kind = _opt_kind(state.tx)
+  moments = {"adam": ("mu", "nu"), "sgd_momentum": ("trace",), "sgd": ()}[kind]
+  want_opt = {"0": dict({m: {"params": params} for m in moments},
+                        **({"count": torch.zeros(())} if kind == "adam" else {})),
+              "1": {"count": torch.zeros(())}}
+  _check_like(tree, {"step": torch.zeros(()), "params": {"params": params}, "opt_state": want_opt,
+                     "batch_stats": state.batch_stats}, ())
+  with torch.no_grad():
+    _copy_tree_(params, tree["params"]["params"])
+    _copy_tree_(state.batch_stats, tree["batch_stats"])
+    opt = tree["opt_state"]
+    count = int(opt["1"]["count"])
+    state.tx.state.clear()
+    if count > 0:            # (at count 0 torch.optim creates its state itself, as zeros)
+      got = {m: dict(_flatten(opt["0"][m]["params"])) for m in moments}
+      names = {"mu": "exp_avg", "nu": "exp_avg_sq", "trace": "momentum_buffer"}
+      for path_, p in _flatten(params):
+        entry = {names[m]: torch.from_numpy(np.ascontiguousarray(got[m][path_], dtype=np.float32)).to(p.device)
+                 for m in moments}
+        if kind == "adam":
+          entry = dict(step=torch.tensor(float(opt["0"]["count"]), dtype=torch.get_default_dtype()), **entry)
+        if entry:
+          state.tx.state[p] = entry
+  state.step = int(tree["step"])
+  return state
+
+
+def sync_batch_stats(state: TrainState) -> TrainState:
+  """train_utils.py:242-246: every batch_stats leaf becomes its mean over the ranks (one
+  all-reduce); the identity when torch.distributed is not initialised."""
+  from .parallel import mean_over_ranks
+  mean_over_ranks([t for _, t in _flatten(state.batch_stats)])
+  return state
