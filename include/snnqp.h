@@ -245,7 +245,8 @@ typedef struct {
  * snnqp_set_event_half_group, snnqp_conv_event_half_group; training of CextNet's gated stages --
  * snnqp_gate_pool_grad_gate, snnqp_gate_pool_grad_input, snnqp_conv_weight_grad_f64,
  * snnqp_conv_weight_grad_f64_workspace_bytes; the batched event front end snnqp_events_bin; the host-side
- * query snnqp_conv_float_form: new entry points, nothing else moves).
+ * query snnqp_conv_float_form; the host-side plan queries snnqp_conv_gated_plan,
+ * snnqp_dense_gated_plan, snnqp_dense_wide_plan: new entry points, nothing else moves).
  * A binding compares snnqp_version()
  * with the SNNQP_VERSION it was written against and refuses a library of another version (_lib.py does). */
 #define SNNQP_VERSION 507
@@ -470,6 +471,16 @@ int snnqp_pack_codes_gated_ex(const int8_t *w, int32_t Cin, int32_t Cout, int32_
 int snnqp_conv_gated_forward(const uint32_t *s, const float *gate, int64_t NB,
                              const snnqp_conv_geom_t *g, const snnqp_weight_t *w,
                              const void *packed, float *y, snnqp_stream_t stream);
+/* Which launches snnqp_conv_gated_forward makes for Cout outputs and w->code_max = code_max (and
+ * which layout snnqp_pack_codes_gated_ex writes).  Launches nothing.  The outputs are walked in
+ * tiles of 32, OT = ceil(Cout / 32):
+ *   full_groups  gridDim.y of the launch whose workgroups hold four tiles each (0: no such launch);
+ *                workgroup row y holds the tiles 4 y .. 4 y + 3.
+ *   rest_tiles   0..3: the tiles of the one further launch (gridDim.y = 1) on the last OT % 4 tiles.
+ *   wide         0: e2m3 codes (code_max <= 7); 1: two e3m2 digits per code and the 2^4 block scale.
+ * SNNQP_EINVAL for Cout < 1, code_max outside 1..127 or a null pointer. */
+int snnqp_conv_gated_plan(int32_t Cout, int32_t code_max, int32_t *full_groups, int32_t *rest_tiles,
+                          int32_t *wide);
 
 /* The same contraction for a QuantDense (flax_qdense.py:87-89) on the channel-major flattening of
  * gate x raster -- the first dense block behind the second TCJA gate, x[(c HW + p)] = gate[c] *
@@ -491,6 +502,12 @@ int snnqp_pack_codes_dense_gated_ex(const int8_t *w, int32_t C, int32_t HW, int3
 int snnqp_dense_gated_forward(const uint32_t *s, const float *gate, int64_t NB, int32_t HW,
                               int32_t C, int32_t N, const snnqp_weight_t *w,
                               const void *packed, float *y, snnqp_stream_t stream);
+/* The launch of snnqp_dense_gated_forward for N outputs and w->code_max = code_max (and the layout
+ * snnqp_pack_codes_dense_gated_ex writes).  Launches nothing.
+ *   grid_y  workgroups per 32 images: each holds up to 512 outputs, four tiles of 32 per wave.
+ *   wide    as snnqp_conv_gated_plan.
+ * SNNQP_EINVAL for N < 1, code_max outside 1..127 or a null pointer. */
+int snnqp_dense_gated_plan(int32_t N, int32_t code_max, int32_t *grid_y, int32_t *wide);
 
 /* ---- fused SpikingBlock ---------------------------------------------------
  * replaces: SpikingBlock.__call__ (nn.scan over T of connection -> norm ->
@@ -725,6 +742,15 @@ int snnqp_dense_lif_forward_if(const int32_t *pred, const void *x, int in_type, 
  * SNNQP_EUNSUPPORTED (nothing enqueued) unless N1 <= 512, N2 <= 128, 1 <= T <= 64 and both
  * weights are W_I8 with tiles: the caller then runs the blocks one by one. */
 int64_t snnqp_dense_head_workspace_bytes(int32_t T, int32_t B, int32_t N1);
+/* The form of the wide dense kernel for T steps, B samples and N features (N1 of the head).
+ * Launches nothing.  fused != 0: snnqp_dense_head_forward, else the stand-alone wide block
+ * (snnqp_dense_lif_forward with N > 128); may_split: a usable workspace is at hand.
+ *   rt      1..4 row tiles of 32 rows per workgroup    ct  1 or 2 column tiles of 256 per workgroup
+ *   sph     samples per lane half (a workgroup owns 2 sph samples)
+ *   csplit  1: the head's hidden columns split over two workgroups per tile of samples (ct = 1)
+ * SNNQP_EINVAL for sizes below 1 or a null pointer; SNNQP_EUNSUPPORTED for T > 64, or N > 512 fused. */
+int snnqp_dense_wide_plan(int32_t T, int32_t B, int32_t N, int fused, int may_split, int32_t *rt,
+                          int32_t *ct, int32_t *sph, int32_t *csplit);
 int snnqp_dense_head_forward(const void *x, int in_type, int64_t x_stride_t,
                              int64_t x_stride_b, int32_t T, int32_t B, int32_t K,
                              int32_t N1, const snnqp_weight_t *w1, const int8_t *wt1,

@@ -111,6 +111,10 @@ _PROTOTYPES = {
     "snnqp_pack_codes_gated_ex": (c_int, [c_void_p, c_int32, c_int32, c_int32, c_void_p, c_void_p]),
     "snnqp_conv_gated_forward": (c_int, [c_void_p, c_void_p, c_int64, POINTER(ConvGeomT),
                                          POINTER(WeightT), c_void_p, c_void_p, c_void_p]),
+    "snnqp_conv_gated_plan": (c_int, [c_int32, c_int32, POINTER(c_int32), POINTER(c_int32), POINTER(c_int32)]),
+    "snnqp_dense_gated_plan": (c_int, [c_int32, c_int32, POINTER(c_int32), POINTER(c_int32)]),
+    "snnqp_dense_wide_plan": (c_int, [c_int32, c_int32, c_int32, c_int, c_int, POINTER(c_int32), POINTER(c_int32),
+                                      POINTER(c_int32), POINTER(c_int32)]),
     "snnqp_dense_gated_packed_bytes": (c_int64, [c_int32, c_int32]),
     "snnqp_pack_codes_dense_gated": (c_int, [c_void_p, c_int32, c_int32, c_int32, c_void_p, c_void_p]),
     "snnqp_dense_gated_packed_bytes_ex": (c_int64, [c_int32, c_int32, c_int32]),

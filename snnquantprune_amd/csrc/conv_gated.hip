@@ -274,7 +274,28 @@ const char *conv_gated_unsupported(const snnqp_conv_geom_t *g, const snnqp_weigh
   return nullptr;
 }
 
+// The launches of snnqp_conv_gated_forward for Cout outputs and codes up to code_max: `full`
+// workgroup rows (gridDim.y) of conv_gated_kernel<4, wide> on four output tiles of 32 each, then one
+// row of conv_gated_kernel<rest, wide> on the last `rest` tiles (ot_base = 4 full).  wide: two e3m2
+// digits per code (packed by snnqp_pack_codes_gated_ex with the same code_max).
+struct ConvGatedPlan { int full, rest; bool wide; };
+
+static ConvGatedPlan conv_gated_plan(int32_t Cout, int32_t code_max) {
+  const int OT = (Cout + 31) / 32;
+  return ConvGatedPlan{OT / 4, OT % 4, code_max > 7};
+}
+
 }  // namespace snnqp
+
+extern "C" int snnqp_conv_gated_plan(int32_t Cout, int32_t code_max, int32_t *full_groups, int32_t *rest_tiles,
+                                     int32_t *wide) {
+  using namespace snnqp;
+  SNNQP_REQUIRE(full_groups && rest_tiles && wide, SNNQP_EINVAL, "conv_gated_plan: null argument");
+  SNNQP_REQUIRE(Cout > 0 && code_max > 0 && code_max <= 127, SNNQP_EINVAL, "conv_gated_plan: bad argument");
+  const ConvGatedPlan p = conv_gated_plan(Cout, code_max);
+  *full_groups = p.full; *rest_tiles = p.rest; *wide = p.wide ? 1 : 0;
+  return SNNQP_OK;
+}
 
 extern "C" int64_t snnqp_conv_gated_packed_bytes_ex(int32_t Cin, int32_t Cout, int32_t code_max) {
   if (Cin <= 0 || Cout <= 0 || code_max <= 0 || code_max > 127) return 0;
@@ -292,7 +313,7 @@ extern "C" int snnqp_pack_codes_gated_ex(const int8_t *w, int32_t Cin, int32_t C
   const int OT = (Cout + 31) / 32;
   const int64_t total = (int64_t)Cin * OT * 64;
   const int64_t blocks = (total + 255) / 256;
-  if (code_max <= 7)
+  if (!conv_gated_plan(Cout, code_max).wide)
     hipLaunchKernelGGL(pack_codes_gated_kernel, dim3((unsigned)(blocks < 4096 ? blocks : 4096)), dim3(256), 0,
                        (hipStream_t)stream, w, Cin, Cout, OT, (uint32_t *)packed);
   else
@@ -327,8 +348,9 @@ extern "C" int snnqp_conv_gated_forward(const uint32_t *s, const float *gate, in
   const int64_t gx = (a.npatch + CG_WAVES - 1) / CG_WAVES;
   SNNQP_REQUIRE(gx < ((int64_t)1 << 31), SNNQP_EUNSUPPORTED, "conv_gated_forward: more than 2^31 workgroups");
   // full groups of four output tiles, then the remainder (its blockIdx.y = 0 is tile group OT / 4)
-  const int full = a.OT / 4, rest = a.OT % 4;
-  const bool wide = w->code_max > 7;          // two fp8 digits per code (packed by snnqp_pack_codes_gated_ex)
+  const ConvGatedPlan plan = conv_gated_plan(g->Cout, w->code_max);
+  const int full = plan.full, rest = plan.rest;
+  const bool wide = plan.wide;
 #define SNNQP_CG_LAUNCH(NTV, ARGS, GY)                                                                  \
   do {                                                                                                  \
     if (wide) hipLaunchKernelGGL((conv_gated_kernel<NTV, true>), dim3((unsigned)gx, (unsigned)(GY)),     \

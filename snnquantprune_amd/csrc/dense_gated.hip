@@ -221,7 +221,27 @@ const char *dense_gated_unsupported(int32_t HW, int32_t C, int32_t N, const snnq
   return nullptr;
 }
 
+// The launch of snnqp_dense_gated_forward for N outputs and codes up to code_max: gridDim.y = gy
+// workgroups per 32 images, each with up to 512 outputs (4 waves x 4 output tiles of 32) of
+// dense_gated_kernel<wide>.  wide: two e3m2 digits per code (packed by
+// snnqp_pack_codes_dense_gated_ex with the same code_max).
+struct DenseGatedPlan { int gy; bool wide; };
+
+static DenseGatedPlan dense_gated_plan(int32_t N, int32_t code_max) {
+  const int OT = (N + 31) / 32;
+  return DenseGatedPlan{(OT + 15) / 16, code_max > 7};
+}
+
 }  // namespace snnqp
+
+extern "C" int snnqp_dense_gated_plan(int32_t N, int32_t code_max, int32_t *grid_y, int32_t *wide) {
+  using namespace snnqp;
+  SNNQP_REQUIRE(grid_y && wide, SNNQP_EINVAL, "dense_gated_plan: null argument");
+  SNNQP_REQUIRE(N > 0 && code_max > 0 && code_max <= 127, SNNQP_EINVAL, "dense_gated_plan: bad argument");
+  const DenseGatedPlan p = dense_gated_plan(N, code_max);
+  *grid_y = p.gy; *wide = p.wide ? 1 : 0;
+  return SNNQP_OK;
+}
 
 extern "C" int64_t snnqp_dense_gated_packed_bytes_ex(int32_t C, int32_t N, int32_t code_max) {
   if (C <= 0 || N <= 0 || code_max <= 0 || code_max > 127) return 0;
@@ -239,7 +259,7 @@ extern "C" int snnqp_pack_codes_dense_gated_ex(const int8_t *w, int32_t C, int32
   const int OT = (N + 31) / 32;
   const int64_t total = (int64_t)C * OT * 64;
   const int64_t blocks = (total + 255) / 256;
-  if (code_max <= 7)
+  if (!dense_gated_plan(N, code_max).wide)
     hipLaunchKernelGGL(pack_codes_dense_gated_kernel, dim3((unsigned)(blocks < 4096 ? blocks : 4096)), dim3(256), 0,
                        (hipStream_t)stream, w, C, HW, N, OT, (uint32_t *)packed);
   else
@@ -269,11 +289,12 @@ extern "C" int snnqp_dense_gated_forward(const uint32_t *s, const float *gate, i
   a.L = w->L; a.m = w->m;
   const int64_t gx = (NB + 31) / 32;
   SNNQP_REQUIRE(gx < ((int64_t)1 << 31), SNNQP_EUNSUPPORTED, "dense_gated_forward: more than 2^31 workgroups");
-  if (w->code_max > 7)          // two fp8 digits per code (packed by snnqp_pack_codes_dense_gated_ex)
-    hipLaunchKernelGGL(dense_gated_kernel<true>, dim3((unsigned)gx, (unsigned)((a.OT + 15) / 16)), dim3(256), 0,
+  const DenseGatedPlan plan = dense_gated_plan(N, w->code_max);
+  if (plan.wide)
+    hipLaunchKernelGGL(dense_gated_kernel<true>, dim3((unsigned)gx, (unsigned)plan.gy), dim3(256), 0,
                        (hipStream_t)stream, a);
   else
-    hipLaunchKernelGGL(dense_gated_kernel<false>, dim3((unsigned)gx, (unsigned)((a.OT + 15) / 16)), dim3(256), 0,
+    hipLaunchKernelGGL(dense_gated_kernel<false>, dim3((unsigned)gx, (unsigned)plan.gy), dim3(256), 0,
                        (hipStream_t)stream, a);
   SNNQP_CHECK_LAUNCH("dense_gated_kernel");
   return SNNQP_OK;

@@ -936,6 +936,20 @@ extern "C" int snnqp_dense_head_forward(const void *x, int in_type, int64_t x_st
   return fill_and_launch(a, in_type, true, ws, ws_bytes, (hipStream_t)stream);
 }
 
+extern "C" int snnqp_dense_wide_plan(int32_t T, int32_t B, int32_t N, int fused, int may_split, int32_t *rt,
+                                     int32_t *ct, int32_t *sph, int32_t *csplit) {
+  using namespace snnqp;
+  SNNQP_REQUIRE(rt && ct && sph && csplit, SNNQP_EINVAL, "dense_wide_plan: null argument");
+  SNNQP_REQUIRE(T >= 1 && B >= 1 && N >= 1, SNNQP_EINVAL, "dense_wide_plan: bad sizes");
+  SNNQP_REQUIRE(T <= 64 && (!fused || N <= 512), SNNQP_EUNSUPPORTED,
+                "dense_wide_plan: more than 64 timesteps, or more than 512 hidden features of the fused head");
+  DenseWideArgs a = {};
+  a.T = T; a.B = B; a.N = N;
+  const WidePlan p = plan_wide(a, fused != 0, may_split != 0);
+  *rt = p.rt; *ct = p.ct; *sph = p.sph; *csplit = p.csplit;
+  return SNNQP_OK;
+}
+
 extern "C" int64_t snnqp_dense_head_workspace_bytes(int32_t T, int32_t B, int32_t N1) {
   using namespace snnqp;
   if (T < 1 || T > 64 || B < 1 || N1 < 1 || N1 > 512) return 0;

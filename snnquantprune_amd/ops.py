@@ -962,6 +962,35 @@ def dense_gated_forward(x: GatedSpikes, weight: Weight, packed: torch.Tensor) ->
   return y
 
 
+def conv_gated_plan(cout: int, code_max: int) -> Tuple[int, int, bool]:
+  """(full_groups, rest_tiles, wide) of conv_gated_forward for `cout` outputs and codes up to
+  `code_max` (snnqp_conv_gated_plan; no device work): a launch of `full_groups` workgroup rows with
+  four output tiles of 32 each, then one with the last `rest_tiles` tiles; wide = the two-digit
+  e3m2 layout.  Raises SnnqpError(EINVAL) for cout < 1 or code_max outside 1..127."""
+  full, rest, wide = ctypes.c_int32(), ctypes.c_int32(), ctypes.c_int32()
+  L.check(L.lib().snnqp_conv_gated_plan(int(cout), int(code_max), ctypes.byref(full), ctypes.byref(rest),
+                                        ctypes.byref(wide)))
+  return full.value, rest.value, bool(wide.value)
+
+
+def dense_gated_plan(n: int, code_max: int) -> Tuple[int, bool]:
+  """(grid_y, wide) of dense_gated_forward for `n` outputs and codes up to `code_max`
+  (snnqp_dense_gated_plan; no device work): workgroups of up to 512 outputs per 32 images."""
+  gy, wide = ctypes.c_int32(), ctypes.c_int32()
+  L.check(L.lib().snnqp_dense_gated_plan(int(n), int(code_max), ctypes.byref(gy), ctypes.byref(wide)))
+  return gy.value, bool(wide.value)
+
+
+def dense_wide_plan(T: int, B: int, N: int, fused: bool = True, may_split: bool = True) -> Tuple[int, int, int, int]:
+  """(rt, ct, sph, csplit) of the wide dense kernel (snnqp_dense_wide_plan; no device work): the
+  fused head (dense_head_forward, N = its hidden width) or the stand-alone wide block; may_split =
+  the head has its workspace."""
+  rt, ct, sph, cs = ctypes.c_int32(), ctypes.c_int32(), ctypes.c_int32(), ctypes.c_int32()
+  L.check(L.lib().snnqp_dense_wide_plan(int(T), int(B), int(N), int(bool(fused)), int(bool(may_split)),
+                                        ctypes.byref(rt), ctypes.byref(ct), ctypes.byref(sph), ctypes.byref(cs)))
+  return rt.value, ct.value, sph.value, cs.value
+
+
 # ---------------------------------------------------------------------------
 # per-launch timing with HIP events on the launch stream (bench.py roofline)
 # ---------------------------------------------------------------------------

@@ -2720,9 +2720,11 @@ def test_dense_wide_kernel_neurons_and_batchnorm(dev, oracle, kind):
 
 @pytest.mark.parametrize("shape", [(20, 256, 2048, 512, 110), (6, 5, 208, 200, 70), (64, 3, 96, 300, 30),
                                    (1, 40, 64, 512, 120), (9, 131, 1040, 384, 110), (3, 77, 320, 160, 50),
-                                   (20, 3000, 96, 300, 30)],
+                                   (20, 3000, 96, 300, 30), (40, 3, 96, 300, 30), (20, 300, 96, 512, 30),
+                                   (40, 260, 96, 300, 30)],
                          ids=["c2", "small", "longest_t", "one_step", "ragged_batch", "many_per_group",
-                              "full_grid_unsplit"])
+                              "full_grid_unsplit", "three_row_tiles_split", "two_row_tiles_unsplit",
+                              "three_row_tiles_unsplit"])
 @pytest.mark.parametrize("fmt", ["u8", "bits"])
 def test_dense_head_as_one_launch(dev, oracle, shape, fmt):
   """snnqp_dense_head_forward -- QuantDense + LIF -> QuantDense + LIF -> vote
@@ -3216,8 +3218,10 @@ def _float_weight(leaf, bits, dev):
 
 
 @pytest.mark.parametrize("shape", [(20, 256, 2048, 512, 110), (6, 5, 208, 200, 70), (64, 3, 96, 300, 30),
-                                   (9, 131, 1040, 384, 110), (20, 3000, 96, 300, 30)],
-                         ids=["c2", "small", "longest_t", "ragged_batch", "full_grid_unsplit"])
+                                   (9, 131, 1040, 384, 110), (20, 3000, 96, 300, 30), (40, 3, 96, 300, 30),
+                                   (20, 300, 96, 512, 30), (40, 260, 96, 300, 30)],
+                         ids=["c2", "small", "longest_t", "ragged_batch", "full_grid_unsplit", "three_row_tiles_split",
+                              "two_row_tiles_unsplit", "three_row_tiles_unsplit"])
 def test_dense_head_on_float32_rows(dev, oracle, shape):
   """The reference's own input format into the fused head: float32 rows [T, B, K]
   (flax_qdense.py:67 casts every input to float32), staged IN PLACE by the kernel and checked on
