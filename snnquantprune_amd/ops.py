@@ -8,6 +8,7 @@ fallback and nothing in this package imports the oracle.
 from __future__ import annotations
 
 import ctypes
+import math
 from dataclasses import dataclass
 from typing import Optional, Sequence, Tuple
 
@@ -63,6 +64,22 @@ class PackedSpikes:
   def reshape_leading(self, *lead):
     out = PackedSpikes(self.bits.reshape(*lead, self.bits.shape[-1]), self.channels)
     out.chan_map = self.chan_map
+    return out
+
+  def swap_leading(self):
+    """The two leading axes exchanged: [B, T, ...] <-> [T, B, ...]."""
+    out = PackedSpikes(self.bits.transpose(0, 1).contiguous(), self.channels)
+    out.chan_map = self.chan_map
+    return out
+
+  @staticmethod
+  def cat_batch(parts):
+    """Time-major rasters [T, b_i, ...] of one block joined along the batch axis."""
+    first = parts[0]
+    assert all(p.channels == first.channels and p.chan_map is first.chan_map for p in parts), \
+        "rasters of different channel sets do not join"
+    out = PackedSpikes(torch.cat([p.bits for p in parts], 1), first.channels)
+    out.chan_map = first.chan_map
     return out
 
   def to_dense(self) -> torch.Tensor:
@@ -286,9 +303,7 @@ def pack_frames(x: torch.Tensor, fmt: int, flags: Optional[torch.Tensor] = None)
   x = x.contiguous()
   H, W = x.shape[-3], x.shape[-2]
   lead = tuple(x.shape[:-3])
-  frames = 1
-  for d in lead:
-    frames *= d
+  frames = math.prod(lead)
   data = torch.empty(lead + (frame_units(H, W, fmt),),
                      dtype=torch.int32 if fmt == L.EV1 else torch.uint8, device=x.device)
   L.check(L.lib().snnqp_pack_frames(_ptr(x), frames, H, W, fmt, _ptr(data), _ptr(flags), _stream()))
@@ -304,9 +319,7 @@ def pack_frames_checked(x: torch.Tensor) -> Tuple[PackedFrames, torch.Tensor]:
   x = x.contiguous()
   H, W = x.shape[-3], x.shape[-2]
   lead = tuple(x.shape[:-3])
-  frames = 1
-  for d in lead:
-    frames *= d
+  frames = math.prod(lead)
   data = torch.empty(lead + (frame_units(H, W, L.EV1),), dtype=torch.int32, device=x.device)
   flags = torch.empty(1, dtype=torch.int32, device=x.device)
   L.check(L.lib().snnqp_pack_frames_checked(_ptr(x), L.U8 if x.dtype == torch.uint8 else L.F32, frames, H, W,
@@ -318,9 +331,7 @@ def unpack_frames(p: PackedFrames) -> torch.Tensor:
   """PackedFrames -> uint8 [..., H, W, 2] (snnqp_unpack_frames)."""
   _require_gpu(p.data)
   lead = tuple(p.data.shape[:-1])
-  frames = 1
-  for d in lead:
-    frames *= d
+  frames = math.prod(lead)
   y = torch.empty(lead + (p.H, p.W, 2), dtype=torch.uint8, device=p.device)
   L.check(L.lib().snnqp_unpack_frames(_ptr(p.data), p.fmt, frames, p.H, p.W, _ptr(y), _stream()))
   return y
@@ -355,8 +366,23 @@ def _f32c(t: torch.Tensor) -> torch.Tensor:
   return t.contiguous()
 
 
+def _ref(st):
+  """An optional ctypes struct by reference."""
+  return None if st is None else ctypes.byref(st)
+
+
+def _out_type(packed_out: bool) -> int:
+  return L.BITS if packed_out else L.F32
+
+
+def _bits_or_f32(x):
+  """(tensor the kernel reads, its type, channels) of a PackedSpikes or a tensor taken as float32."""
+  if isinstance(x, PackedSpikes):
+    return x.bits, L.BITS, x.channels
+  return _f32c(x), L.F32, x.shape[-1]
+
+
 def is_pow2(x: float) -> bool:
-  import math
   if not (x > 0) or math.isinf(x):
     return False
   m, _ = math.frexp(x)
@@ -453,6 +479,12 @@ class ConvGeom:
 
   def tag(self) -> str:
     return "%dx%dx%d->%d" % (self.H, self.W, self.Cin, self.Cout)
+
+  def is_3x3_same(self) -> bool:
+    """3x3, stride 1, pad 1, no dilation, one group: what the event layer and the gated conv serve."""
+    return ((self.KH, self.KW) == (3, 3) and tuple(self.stride) == (1, 1)
+            and tuple(map(tuple, self.pad)) == ((1, 1), (1, 1)) and tuple(self.in_dil) == (1, 1)
+            and tuple(self.k_dil) == (1, 1) and self.groups == 1)
 
   def out_hw(self) -> Tuple[int, int]:
     oh, ow = ctypes.c_int32(), ctypes.c_int32()
@@ -869,25 +901,14 @@ def conv3d_lif_forward(x, geom: Conv3dGeom, weight: Weight, neuron: Optional[Neu
                                                ctypes.byref(w), None, None, None, None, _ptr(y), L.F32, _stream()))
     return y
   T, B = xt.shape[0], xt.shape[1]
-  if out is not None:
-    u_out, s = out
-    s = s.bits if isinstance(s, PackedSpikes) else s
-  else:
-    u_out = torch.empty((B, OD, OH, OW, geom.Cout), dtype=torch.float32, device=dev) if want_u else None
-    oshape = (T, B, OD, OH, OW)
-    s = torch.empty(oshape + (((geom.Cout + 31) // 32,) if packed_out else (geom.Cout,)),
-                    dtype=torch.int32 if packed_out else torch.float32, device=dev)
-  if u0 is not None:
-    u0 = _f32c(u0)
-    assert tuple(u0.shape) == (B, OD, OH, OW, geom.Cout), (u0.shape, (B, OD, OH, OW, geom.Cout))
-  _zero_step_carry(u_out, u0, T)
+  u0, u_out, s, spikes = _scan_outputs(dev, (T, B, OD, OH, OW), geom.Cout, u0, want_u, packed_out, out=out)
   n = neuron.struct()
   with _timed("conv3d[%s]" % geom.tag()):
     L.check(L.lib().snnqp_conv3d_lif_forward(_ptr(pred), _ptr(xt), in_type, B * unit, unit, T, B, ctypes.byref(g),
-                                             ctypes.byref(w), ctypes.byref(b) if b is not None else None,
+                                             ctypes.byref(w), _ref(b),
                                              ctypes.byref(n), _ptr(u0), _ptr(u_out), _ptr(s),
-                                             L.BITS if packed_out else L.F32, _stream()))
-  return u_out, (PackedSpikes(s, geom.Cout) if packed_out else s)
+                                             _out_type(packed_out), _stream()))
+  return u_out, spikes
 
 
 def conv_forward_speculative(x: torch.Tensor, geom: ConvGeom, int_weight: Weight, float_weight: Weight):
@@ -1055,7 +1076,7 @@ def current_min_bits(weight: Weight, bn: Optional[BnCoeffs], bound: int, cout: i
     out = torch.full((1,), 0x7F800000, dtype=torch.int32, device=weight.w.device)
     w = weight.struct()
     b = bn.struct() if bn is not None else None
-    L.check(L.lib().snnqp_current_min(ctypes.byref(w), ctypes.byref(b) if b is not None else None,
+    L.check(L.lib().snnqp_current_min(ctypes.byref(w), _ref(b),
                                       int(bound), int(cout), _ptr(out), _stream()))
     v = int(out.item()) & 0xFFFFFFFF
     _current_min_cache.put(key, extra, v)
@@ -1079,6 +1100,44 @@ def _zero_step_carry(u_out: Optional[torch.Tensor], u0: Optional[torch.Tensor], 
       u_out.copy_(u0)
 
 
+def _scan_input(x, time_major: bool, others, weight: Optional[Weight] = None,
+                fallback: Optional[FloatFallback] = None, refusal: str = ""):
+  """What a fused block reads: (contiguous tensor, in_type, T, B, x_flags).  float32 into the integer
+  codes of `weight` needs a FloatFallback (ValueError(refusal) without one) and gets the device word
+  x_flags for the kernel to report into; None otherwise."""
+  xt, in_type = _in_desc(x)
+  xt = xt.contiguous()
+  _require_gpu(xt, *others)
+  x_flags = None
+  if weight is not None and in_type == L.F32 and weight.is_int:
+    if fallback is None:
+      raise ValueError(refusal)
+    x_flags = torch.empty(1, dtype=torch.int32, device=xt.device)
+  T, B = (xt.shape[0], xt.shape[1]) if time_major else (xt.shape[1], xt.shape[0])
+  return xt, in_type, T, B, x_flags
+
+
+def _scan_outputs(dev, lead, N: int, u0, want_u: bool, packed_out: bool, state=None, out=None):
+  """What a neuron scan writes: (u0 as the kernel reads it, u_T | None, raster tensor, the raster as
+  the caller gets it: PackedSpikes iff packed_out).  lead: the raster's leading shape [T, B, ...];
+  state: the membrane state's where it is not lead[1:] (the fused pool shrinks the raster only);
+  out: the (u_T, raster) of an earlier launch to write again."""
+  shape = tuple(lead[1:] if state is None else state) + (N,)
+  if out is not None:
+    u_out, spikes = out
+    s = spikes.bits if isinstance(spikes, PackedSpikes) else spikes
+  else:
+    u_out = torch.empty(shape, dtype=torch.float32, device=dev) if want_u else None
+    s = torch.empty(tuple(lead) + (((N + 31) // 32,) if packed_out else (N,)),
+                    dtype=torch.int32 if packed_out else torch.float32, device=dev)
+    spikes = PackedSpikes(s, N) if packed_out else s
+  if u0 is not None:
+    u0 = _f32c(u0)
+    assert tuple(u0.shape) == shape, (u0.shape, shape)
+  _zero_step_carry(u_out, u0, lead[0])
+  return u0, u_out, s, spikes
+
+
 def conv_lif_forward(x, geom: ConvGeom, weight: Weight, neuron: Neuron,
                      bn: Optional[BnCoeffs] = None, u0: Optional[torch.Tensor] = None,
                      want_u: bool = True, packed_out: bool = False, pool: int = 1,
@@ -1100,18 +1159,12 @@ def conv_lif_forward(x, geom: ConvGeom, weight: Weight, neuron: Neuron,
   logical: (Cin, Cout, live outputs) of a compacted block, whose launch computes
   geom.Cin x geom.Cout channels: the profile tag keeps the logical geometry, PROFILE_NOTES[tag]
   gets the computed and live counts."""
-  xt, in_type = _in_desc(x)
-  xt = xt.contiguous()
-  _require_gpu(xt, weight.w, u0)
-  x_flags = None
-  if in_type == L.F32 and weight.is_int:
-    if fallback is None:
-      raise ValueError("float32 input into integer codes needs a FloatFallback (the float32 kernel)")
-    x_flags = torch.empty(1, dtype=torch.int32, device=xt.device)
+  xt, in_type, T, B, x_flags = _scan_input(
+      x, time_major, (weight.w, u0), weight, fallback,
+      "float32 input into integer codes needs a FloatFallback (the float32 kernel)")
   if x_seen is not None:
     assert x_seen.dtype == torch.int32 and x_seen.numel() >= 8 and x_seen.is_cuda, \
         "x_seen: eight int32 device words (snnqp.h)"
-  T, B = (xt.shape[0], xt.shape[1]) if time_major else (xt.shape[1], xt.shape[0])
   if isinstance(x, PackedFrames):        # [T, B, words / bytes of a frame]
     assert (x.H, x.W, 2) == (geom.H, geom.W, geom.Cin) and xt.ndim == 3, (x.shape, geom)
     unit = xt.shape[-1]
@@ -1120,17 +1173,8 @@ def conv_lif_forward(x, geom: ConvGeom, weight: Weight, neuron: Neuron,
   xs_t, xs_b = _tb_strides(xt, T, B, time_major, unit)
   OH, OW = geom.out_hw()
   dev = xt.device
-  u_out = torch.empty((B, OH, OW, geom.Cout), dtype=torch.float32, device=dev) \
-      if want_u else None
-  if u0 is not None:
-    u0 = _f32c(u0)
-    assert tuple(u0.shape) == (B, OH, OW, geom.Cout), (u0.shape, (B, OH, OW, geom.Cout))
-  _zero_step_carry(u_out, u0, T)
-  oshape = (T, B, OH // pool, OW // pool)
-  if packed_out:
-    s = torch.empty(oshape + ((geom.Cout + 31) // 32,), dtype=torch.int32, device=dev)
-  else:
-    s = torch.empty(oshape + (geom.Cout,), dtype=torch.float32, device=dev)
+  u0, u_out, s, spikes = _scan_outputs(dev, (T, B, OH // pool, OW // pool), geom.Cout, u0, want_u, packed_out,
+                               state=(B, OH, OW))
   g, w, n = geom.struct(), weight.struct(), neuron.struct()
   b = bn.struct() if bn is not None else None
   cin_l, cout_l = (geom.Cin, geom.Cout) if logical is None else logical[:2]
@@ -1156,7 +1200,7 @@ def conv_lif_forward(x, geom: ConvGeom, weight: Weight, neuron: Neuron,
       try:
         L.check(L.lib().snnqp_conv_lif_forward(
             _ptr(pf.data), L.EV1, ps_t, ps_b, T, B, ctypes.byref(g), ctypes.byref(w),
-            _ptr(weight.wt), ctypes.byref(b) if b is not None else None, ctypes.byref(n),
+            _ptr(weight.wt), _ref(b), ctypes.byref(n),
             _ptr(u0), _ptr(u_out), _ptr(s), L.BITS, pool, impl, 1, None, None, _stream()))
       except L.SnnqpError as e:
         # the bit-packed variant refused the block: nothing has been written to the outputs (only
@@ -1168,14 +1212,14 @@ def conv_lif_forward(x, geom: ConvGeom, weight: Weight, neuron: Neuron,
       # ... and the frames as they are, iff a value was not 0 or 1
       L.check(L.lib().snnqp_conv_lif_forward_pred(
           _ptr(not_binary), _ptr(xt), in_type, xs_t, xs_b, T, B, ctypes.byref(g), ctypes.byref(w),
-          _ptr(weight.wt), ctypes.byref(b) if b is not None else None, ctypes.byref(n),
+          _ptr(weight.wt), _ref(b), ctypes.byref(n),
           _ptr(u0), _ptr(u_out), _ptr(s), L.BITS, pool,
           int(x_max), _ptr(x_seen), _ptr(x_flags), _stream()))
     else:
       L.check(L.lib().snnqp_conv_lif_forward(
           _ptr(xt), in_type, xs_t, xs_b, T, B, ctypes.byref(g), ctypes.byref(w),
-          _ptr(weight.wt), ctypes.byref(b) if b is not None else None, ctypes.byref(n),
-          _ptr(u0), _ptr(u_out), _ptr(s), L.BITS if packed_out else L.F32, pool, impl,
+          _ptr(weight.wt), _ref(b), ctypes.byref(n),
+          _ptr(u0), _ptr(u_out), _ptr(s), _out_type(packed_out), pool, impl,
           int(x_max), _ptr(x_seen), _ptr(x_flags), _stream()))
   if fallback is not None:
     # the same block on the float32 kernel, executed only if the word says so (snnqp.h)
@@ -1185,9 +1229,9 @@ def conv_lif_forward(x, geom: ConvGeom, weight: Weight, neuron: Neuron,
     fs_t, fs_b = _tb_strides(xf, T, B, time_major, geom.H * geom.W * geom.Cin)
     L.check(L.lib().snnqp_conv_lif_forward_if(
         _ptr(pred), _ptr(xf), L.F32, fs_t, fs_b, T, B, ctypes.byref(g), ctypes.byref(fw),
-        ctypes.byref(b) if b is not None else None, ctypes.byref(n), _ptr(u0), _ptr(u_out), _ptr(s),
-        L.BITS if packed_out else L.F32, pool, _stream()))
-  return u_out, (PackedSpikes(s, geom.Cout) if packed_out else s)
+        _ref(b), ctypes.byref(n), _ptr(u0), _ptr(u_out), _ptr(s),
+        _out_type(packed_out), pool, _stream()))
+  return u_out, spikes
 
 
 def dense_lif_forward(x, weight: Weight, K: int, N: int, neuron: Neuron,
@@ -1196,26 +1240,12 @@ def dense_lif_forward(x, weight: Weight, K: int, N: int, neuron: Neuron,
                       impl: int = L.IMPL_AUTO, time_major: bool = True,
                       fallback: Optional[FloatFallback] = None):
   """x [T, B, K] -> (u_T [B, N] | None, spikes [T, B, N]).  fallback: as conv_lif_forward."""
-  xt, in_type = _in_desc(x)
-  xt = xt.contiguous()
-  _require_gpu(xt, weight.w, u0)
-  x_flags = None
-  if in_type == L.F32 and weight.is_int:
-    if fallback is None:
-      raise ValueError("float32 rows into integer codes need a FloatFallback (the float32 kernel)")
-    x_flags = torch.empty(1, dtype=torch.int32, device=xt.device)
-  T, B = (xt.shape[0], xt.shape[1]) if time_major else (xt.shape[1], xt.shape[0])
+  xt, in_type, T, B, x_flags = _scan_input(
+      x, time_major, (weight.w, u0), weight, fallback,
+      "float32 rows into integer codes need a FloatFallback (the float32 kernel)")
   xs_t, xs_b = _tb_strides(xt, T, B, time_major, xt.shape[-1])
   dev = xt.device
-  u_out = torch.empty((B, N), dtype=torch.float32, device=dev) if want_u else None
-  if u0 is not None:
-    u0 = _f32c(u0)
-    assert tuple(u0.shape) == (B, N)
-  _zero_step_carry(u_out, u0, T)
-  if packed_out:
-    s = torch.empty((T, B, (N + 31) // 32), dtype=torch.int32, device=dev)
-  else:
-    s = torch.empty((T, B, N), dtype=torch.float32, device=dev)
+  u0, u_out, s, spikes = _scan_outputs(dev, (T, B), N, u0, want_u, packed_out)
   w, n = weight.struct(), neuron.struct()
   b = bn.struct() if bn is not None else None
   # a long contraction over few rows (the read-out) splits K over workgroups through a workspace
@@ -1224,8 +1254,8 @@ def dense_lif_forward(x, weight: Weight, K: int, N: int, neuron: Neuron,
   with _timed("dense[%d->%d]" % (K, N)):
     L.check(L.lib().snnqp_dense_lif_forward_ws(
         _ptr(xt), in_type, xs_t, xs_b, T, B, K, N, ctypes.byref(w), _ptr(weight.wt),
-        ctypes.byref(b) if b is not None else None, ctypes.byref(n), _ptr(u0),
-        _ptr(u_out), _ptr(s), L.BITS if packed_out else L.F32, impl, _ptr(x_flags),
+        _ref(b), ctypes.byref(n), _ptr(u0),
+        _ptr(u_out), _ptr(s), _out_type(packed_out), impl, _ptr(x_flags),
         _ptr(ws), 0 if ws is None else ws.numel(), _stream()))
   if fallback is not None:
     xf = _f32c(xt if fallback.x is None else fallback.x)
@@ -1233,9 +1263,9 @@ def dense_lif_forward(x, weight: Weight, K: int, N: int, neuron: Neuron,
     fw = fallback.weight.struct()
     L.check(L.lib().snnqp_dense_lif_forward_if(
         _ptr(pred), _ptr(xf), L.F32, xs_t, xs_b, T, B, K, N, ctypes.byref(fw),
-        ctypes.byref(b) if b is not None else None, ctypes.byref(n), _ptr(u0), _ptr(u_out), _ptr(s),
-        L.BITS if packed_out else L.F32, _stream()))
-  return u_out, (PackedSpikes(s, N) if packed_out else s)
+        _ref(b), ctypes.byref(n), _ptr(u0), _ptr(u_out), _ptr(s),
+        _out_type(packed_out), _stream()))
+  return u_out, spikes
 
 
 _dense_ws = {}
@@ -1278,10 +1308,7 @@ def dense_head_forward(x, w1: Weight, K: int, N1: int, nrn1: Neuron, w2: Weight,
   place; `fallback` = the float32 kernel of the FIRST block) -> (logits [B, N2 // group], hidden
   raster | None, output raster | None).  Raises SnnqpError(EUNSUPPORTED) when the head does not fit the fused
   kernel; the caller then runs the two blocks and the vote one by one."""
-  xt, in_type = _in_desc(x)
-  xt = xt.contiguous()
-  _require_gpu(xt, w1.w, w2.w)
-  T, B = (xt.shape[0], xt.shape[1]) if time_major else (xt.shape[1], xt.shape[0])
+  xt, in_type, T, B, _ = _scan_input(x, time_major, (w1.w, w2.w))   # (its own float32 rule: below)
   xs_t, xs_b = _tb_strides(xt, T, B, time_major, xt.shape[-1])
   dev = xt.device
   if N2 % group:
@@ -1412,22 +1439,13 @@ def lif_forward(x: torch.Tensor, neuron: Neuron, bn: Optional[BnCoeffs] = None,
   _require_gpu(x, u0)
   T, C = x.shape[0], x.shape[-1]
   R = (x.numel() // (T * C)) if T * C else 0
-  u_out = torch.empty(x.shape[1:], dtype=torch.float32, device=x.device) if want_u else None
-  if u0 is not None:
-    u0 = _f32c(u0)
-    assert tuple(u0.shape) == tuple(x.shape[1:])
-  _zero_step_carry(u_out, u0, T)
-  if packed_out:
-    s = torch.empty(tuple(x.shape[:-1]) + ((C + 31) // 32,), dtype=torch.int32,
-                    device=x.device)
-  else:
-    s = torch.empty_like(x)
+  u0, u_out, s, spikes = _scan_outputs(x.device, x.shape[:-1], C, u0, want_u, packed_out)
   n = neuron.struct()
   b = bn.struct() if bn is not None else None
   L.check(L.lib().snnqp_lif_forward(
-      _ptr(x), T, R, C, ctypes.byref(b) if b is not None else None, ctypes.byref(n),
-      _ptr(u0), _ptr(u_out), _ptr(s), L.BITS if packed_out else L.F32, _stream()))
-  return u_out, (PackedSpikes(s, C) if packed_out else s)
+      _ptr(x), T, R, C, _ref(b), ctypes.byref(n),
+      _ptr(u0), _ptr(u_out), _ptr(s), _out_type(packed_out), _stream()))
+  return u_out, spikes
 
 
 def batchnorm_forward(x: torch.Tensor, bn: BnCoeffs) -> torch.Tensor:
@@ -1443,45 +1461,23 @@ def batchnorm_forward(x: torch.Tensor, bn: BnCoeffs) -> torch.Tensor:
 
 def maxpool2x2(x):
   """[..., H, W, C] -> [..., H/2, W/2, C] for float32 tensors or PackedSpikes."""
-  if isinstance(x, PackedSpikes):
-    bits = x.bits
-    _require_gpu(bits)
-    H, W = bits.shape[-3], bits.shape[-2]
-    lead = tuple(bits.shape[:-3])
-    NB = 1
-    for d in lead:
-      NB *= d
-    y = torch.empty(lead + (H // 2, W // 2, bits.shape[-1]), dtype=torch.int32,
-                    device=bits.device)
-    L.check(L.lib().snnqp_maxpool2x2(_ptr(bits), L.BITS, NB, H, W, x.channels, _ptr(y),
-                                     _stream()))
-    return PackedSpikes(y, x.channels)
-  x = _f32c(x)
-  _require_gpu(x)
-  H, W, C = x.shape[-3:]
-  lead = tuple(x.shape[:-3])
-  NB = 1
-  for d in lead:
-    NB *= d
-  y = torch.empty(lead + (H // 2, W // 2, C), dtype=torch.float32, device=x.device)
-  L.check(L.lib().snnqp_maxpool2x2(_ptr(x), L.F32, NB, H, W, C, _ptr(y), _stream()))
-  return y
+  t, typ, C = _bits_or_f32(x)
+  _require_gpu(t)
+  H, W = t.shape[-3], t.shape[-2]
+  lead = tuple(t.shape[:-3])
+  y = torch.empty(lead + (H // 2, W // 2, t.shape[-1]), dtype=t.dtype, device=t.device)
+  L.check(L.lib().snnqp_maxpool2x2(_ptr(t), typ, math.prod(lead), H, W, C, _ptr(y), _stream()))
+  return PackedSpikes(y, C) if typ == L.BITS else y
 
 
 def spatial_mean(x) -> torch.Tensor:
   """[..., H, W, C] (float32 or PackedSpikes) -> float32 [..., C] (mean over H, W)."""
-  if isinstance(x, PackedSpikes):
-    t, typ, C = x.bits, L.BITS, x.channels
-  else:
-    t, typ, C = _f32c(x), L.F32, x.shape[-1]
+  t, typ, C = _bits_or_f32(x)
   _require_gpu(t)
   lead = tuple(t.shape[:-3])
   HW = t.shape[-3] * t.shape[-2]
-  NB = 1
-  for d in lead:
-    NB *= d
   y = torch.empty(lead + (C,), dtype=torch.float32, device=t.device)
-  L.check(L.lib().snnqp_spatial_mean(_ptr(t), typ, NB, HW, C, _ptr(y), _stream()))
+  L.check(L.lib().snnqp_spatial_mean(_ptr(t), typ, math.prod(lead), HW, C, _ptr(y), _stream()))
   return y
 
 
@@ -1496,20 +1492,14 @@ def sigmoid_gate(a: torch.Tensor, b: torch.Tensor) -> torch.Tensor:
 
 def apply_gate(x, g: torch.Tensor) -> torch.Tensor:
   """x [..., H, W, C] * g [..., C] broadcast over H, W -> float32."""
-  if isinstance(x, PackedSpikes):
-    t, typ, C = x.bits, L.BITS, x.channels
-  else:
-    t, typ, C = _f32c(x), L.F32, x.shape[-1]
+  t, typ, C = _bits_or_f32(x)
   g = _f32c(g)
   _require_gpu(t, g)
   lead = tuple(t.shape[:-3])
   H, W = t.shape[-3], t.shape[-2]
   assert tuple(g.shape) == lead + (C,), (g.shape, lead, C)
-  NB = 1
-  for d in lead:
-    NB *= d
   y = torch.empty(lead + (H, W, C), dtype=torch.float32, device=t.device)
-  L.check(L.lib().snnqp_apply_gate(_ptr(t), typ, _ptr(g), NB, H * W, C, _ptr(y), _stream()))
+  L.check(L.lib().snnqp_apply_gate(_ptr(t), typ, _ptr(g), math.prod(lead), H * W, C, _ptr(y), _stream()))
   return y
 
 
@@ -1691,9 +1681,7 @@ def density(x, lead_dims: int = 2, counts: bool = False) -> torch.Tensor:
     t, typ, C, shape = _f32c(x), L.F32, x.shape[-1], tuple(x.shape)
   _require_gpu(t)
   lead = tuple(shape[:lead_dims])
-  NB = 1
-  for d in lead:
-    NB *= d
+  NB = math.prod(lead)
   n = 1
   for d in shape[lead_dims:]:
     n *= d
@@ -1706,10 +1694,7 @@ def density(x, lead_dims: int = 2, counts: bool = False) -> torch.Tensor:
 
 def vote(s, group: int = 10) -> torch.Tensor:
   """spikes [T, B, N] -> logits float32 [B, N // group] (models.py:253-255)."""
-  if isinstance(s, PackedSpikes):
-    t, typ, N = s.bits, L.BITS, s.channels
-  else:
-    t, typ, N = _f32c(s), L.F32, s.shape[-1]
+  t, typ, N = _bits_or_f32(s)
   _require_gpu(t)
   T, B = t.shape[0], t.shape[1]
   if N % group:

@@ -99,7 +99,7 @@ class _NeuronBase(nn.Module):
     """One time step (u, s_in) -> (u, s), via the T = 1 scan kernel."""
     s_in = torch.as_tensor(s_in, dtype=torch.float32)
     nrn = self.neuron(s_in.shape[-1])
-    u0 = None if u is None or isinstance(u, ZeroCarry) else u
+    u0 = _given_carry(u)
     x = s_in.unsqueeze(0)
     if x.ndim == 2:                      # 1-D state: [T=1, C]
       x = x.unsqueeze(1)
@@ -184,6 +184,18 @@ class ZeroCarry:
 
   def __repr__(self):
     return "ZeroCarry(shape=%s)" % (self.shape,)
+
+
+def _given_carry(u):
+  """The membrane state a block was handed, or None where its scan starts from zero."""
+  return None if (u is None or isinstance(u, ZeroCarry)) else u
+
+
+def batch_slices(B, per_sample_bytes):
+  """[(b0, b1), ...]: the batch cut into slices of at most CURRENTS_SLICE_BYTES (read now), at
+  least one sample each; an empty batch is one empty slice."""
+  step = max(1, min(B, CURRENTS_SLICE_BYTES // max(per_sample_bytes, 1)))
+  return [(b0, min(B, b0 + step)) for b0 in range(0, max(B, 1), step)]
 
 
 _flat_perm_cache = {}
@@ -314,9 +326,14 @@ class SpikingBlock(nn.Module):
   @staticmethod
   def _event_layer_geometry(g: ops.ConvGeom) -> bool:
     """What conv3x3_u8c2_kernel serves (snnqp.h, IMPL_MFMA): 3x3, stride 1, pad 1, Cin = 2."""
-    return (g.Cin == 2 and (g.KH, g.KW) == (3, 3) and tuple(g.stride) == (1, 1)
-            and tuple(map(tuple, g.pad)) == ((1, 1), (1, 1)) and tuple(g.in_dil) == (1, 1)
-            and tuple(g.k_dil) == (1, 1) and g.groups == 1)
+    return g.Cin == 2 and g.is_3x3_same()
+
+  def _scan_setup(self, N, packed_default):
+    """(neuron constants, BatchNorm coefficients | None, packed_out) of a block of N features;
+    packed_default: what packed=None means for the block's input."""
+    norm = self.norm_fn
+    return (self.neural_dynamics.neuron(N), norm.coeffs(N) if norm is not None else None,
+            bool(packed_default) if self.packed is None else bool(self.packed))
 
   def __call__(self, u, inputs):
     if self.pool not in (1, 2):
@@ -360,7 +377,7 @@ class SpikingBlock(nn.Module):
 
   # -- one launch ---------------------------------------------------------------
   def _fused(self, u, inputs):
-    conn, norm = self.connection_fn, self.norm_fn
+    conn = self.connection_fn
     if isinstance(inputs, ops.GatedSpikes):
       out = self._gated_block(u, inputs)
       if out is not None:
@@ -373,7 +390,7 @@ class SpikingBlock(nn.Module):
     spec = integer is packing.SPECULATE      # float32 that may hold integers: decided on the device
     if flat is not None:
       x.flat_perm = flat
-    u0 = None if (u is None or isinstance(u, ZeroCarry)) else u
+    u0 = _given_carry(u)
     tm = not self.batch_major_input
     is_dense = isinstance(conn, QuantDense)
     cmap_in = getattr(x, "chan_map", None)
@@ -392,7 +409,7 @@ class SpikingBlock(nn.Module):
         x, cmap_in = ops.truncate_silent_channels(x)
     cin = x.shape[-1]
     pk = conn.packed_kernel(cin if cmap_in is None else full_cin)
-    packed_out = bool(integer) if self.packed is None else bool(self.packed)
+    nrn, bn, packed_out = self._scan_setup(conn.features, integer)
     rows = None
     if cmap_in is not None:
       rows = cmap_in.index
@@ -404,9 +421,7 @@ class SpikingBlock(nn.Module):
     if (self.compact and nn.channel_compaction() and not is_dense and integer is True and u0 is None
         and not self.return_state and packed_out and len(conn._ksize()) == 2 and x_bound is not None
         and self.impl != L.IMPL_GENERIC and pk.int_weight() is not None):
-      cmap_out = self._channel_plan(pk, self.neural_dynamics.neuron(conn.features),
-                                    self.norm_fn.coeffs(conn.features) if self.norm_fn is not None else None,
-                                    x_bound, cmap_in)
+      cmap_out = self._channel_plan(pk, nrn, bn, x_bound, cmap_in)
     if rows is not None or cmap_out is not None:
       fire = 0
       if cmap_out is not None and cin == 2:
@@ -471,8 +486,6 @@ class SpikingBlock(nn.Module):
       d = x.to_dense() if isinstance(x, ops.PackedSpikes) else x.to(torch.float32)
       d = d.reshape(d.shape[0], d.shape[1], h, ww, c).permute(0, 1, 4, 2, 3)
       x = d.reshape(d.shape[0], d.shape[1], c * h * ww).contiguous()
-    nrn = self.neural_dynamics.neuron(conn.features)
-    bn = norm.coeffs(conn.features) if norm is not None else None
     if cmap_out is not None and bn is not None:
       bn = _sliced_bn(bn, cmap_out)
 
@@ -513,19 +526,18 @@ class SpikingBlock(nn.Module):
     if is_dense:
       if x.ndim != 3:
         raise ValueError("QuantDense block expects [T, B, K] inputs, got %s" % (x.shape,))
+      def launch(x, fb):
+        return ops.dense_lif_forward(x, w, cin, conn.features, nrn, bn=bn, u0=u0,
+                                     want_u=self.return_state, packed_out=packed_out,
+                                     impl=self.impl, time_major=tm, fallback=fb)
       try:
-        u_out, s = ops.dense_lif_forward(x, w, cin, conn.features, nrn, bn=bn, u0=u0,
-                                         want_u=self.return_state, packed_out=packed_out,
-                                         impl=self.impl, time_major=tm, fallback=fb)
+        u_out, s = launch(x, fb)
       except L.SnnqpError as e:
         # a float32 tensor the integer kernel turned out not to stage in place (a shape the
         # predicate above does not know): narrow it and launch again -- nothing has run yet
         if e.code != L.EUNSUPPORTED or not spec:
           raise
-        x, fb = narrowed()
-        u_out, s = ops.dense_lif_forward(x, w, cin, conn.features, nrn, bn=bn, u0=u0,
-                                         want_u=self.return_state, packed_out=packed_out,
-                                         impl=self.impl, time_major=tm, fallback=fb)
+        u_out, s = launch(*narrowed())
       if self.pool == 2:
         raise ValueError("pool=2 needs a convolutional block")
       return u_out, s
@@ -580,13 +592,16 @@ class SpikingBlock(nn.Module):
       w = dataclasses.replace(w, min_current_bits=ops.current_min_bits(
           w, bn, int(w.abs_sum_max), geom.Cout))
     x_seen = hint.seen_word() if hint is not None else None
+    def launch(pool):
+      # (x, x_max, x_seen, fb and binary_first as they stand at the call: the float32 retry resets them)
+      return ops.conv_lif_forward(x, geom, w, nrn, bn=bn, u0=u0,
+                                  want_u=self.return_state, packed_out=packed_out,
+                                  pool=pool, impl=impl, time_major=tm,
+                                  x_max=x_max, x_seen=x_seen, fallback=fb, binary_first=binary_first,
+                                  logical=logical)
     for attempt in (0, 1):
       try:
-        u_out, s = ops.conv_lif_forward(x, geom, w, nrn, bn=bn, u0=u0,
-                                        want_u=self.return_state, packed_out=packed_out,
-                                        pool=self.pool, impl=impl, time_major=tm,
-                                        x_max=x_max, x_seen=x_seen, fallback=fb, binary_first=binary_first,
-                                        logical=logical)
+        u_out, s = launch(self.pool)
         break
       except L.SnnqpError as e:
         if (e.code == L.EUNSUPPORTED and spec and attempt == 0 and isinstance(x, torch.Tensor)
@@ -600,11 +615,7 @@ class SpikingBlock(nn.Module):
           continue
         if e.code != L.EUNSUPPORTED or self.pool != 2 or impl == L.IMPL_MFMA:
           raise
-        u_out, s = ops.conv_lif_forward(x, geom, w, nrn, bn=bn, u0=u0,
-                                        want_u=self.return_state, packed_out=packed_out,
-                                        pool=1, impl=impl, time_major=tm, x_max=x_max,
-                                        x_seen=x_seen, fallback=fb, binary_first=binary_first,
-                                        logical=logical)
+        u_out, s = launch(1)
         s = ops.maxpool2x2(s)
         break
     if hint is not None:
@@ -631,7 +642,7 @@ class SpikingBlock(nn.Module):
     a channel are summed as integers, the gates applied in one float32 chain
     (ops.conv_gated_forward; oracle gated_conv); BatchNorm and the neuron follow as the scan.
     None when the block is not a shape that kernel serves."""
-    conn, norm = self.connection_fn, self.norm_fn
+    conn = self.connection_fn
     if self.batch_major_input or self.impl == L.IMPL_GENERIC:
       return None
     if x.flat:
@@ -642,41 +653,18 @@ class SpikingBlock(nn.Module):
     geom = conn.geometry(tuple(x.shape[2:-1]), cin)
     pk = conn.packed_kernel(cin)
     w = pk.int_weight()
-    if w is None or not (geom.KH == geom.KW == 3 and tuple(geom.stride) == (1, 1)
-                         and tuple(map(tuple, geom.pad)) == ((1, 1), (1, 1)) and tuple(geom.in_dil) == (1, 1)
-                         and tuple(geom.k_dil) == (1, 1) and geom.groups == 1 and cin in (32, 64, 96, 128)):
+    if w is None or not (geom.is_3x3_same() and cin in (32, 64, 96, 128)):
       return None
     packed = pk.gated_codes()
     if packed is None:
       return None
     T, B = x.shape[0], x.shape[1]
-    N = geom.Cout
-    nrn = self.neural_dynamics.neuron(N)
-    bn = norm.coeffs(N) if norm is not None else None
-    u0 = None if (u is None or isinstance(u, ZeroCarry)) else u
-    packed_out = True if self.packed is None else bool(self.packed)
-    per_sample = 4 * T * geom.H * geom.W * N              # bytes of float32 currents
-    step = max(1, min(B, CURRENTS_SLICE_BYTES // max(per_sample, 1)))
-    us, ss = [], []
-    for b0 in range(0, max(B, 1), step):      # (an empty batch: one empty slice)
-      b1 = min(B, b0 + step)
-      xs = x if (b0 == 0 and b1 == B) else ops.GatedSpikes(
-          ops.PackedSpikes(x.spikes.bits[:, b0:b1].contiguous(), x.spikes.channels), x.gate[:, b0:b1].contiguous())
-      y = ops.conv_gated_forward(xs, geom, w, packed)
-      u_out, s = ops.lif_forward(y, nrn, bn=bn, u0=None if u0 is None else u0[b0:b1],
-                                 want_u=self.return_state, packed_out=packed_out)
-      del y
-      if self.pool == 2:
-        s = ops.maxpool2x2(s)
-      us.append(u_out)
-      ss.append(s)
-    if len(ss) == 1:
-      return us[0], ss[0]
-    if isinstance(ss[0], ops.PackedSpikes):
-      s = ops.PackedSpikes(torch.cat([p.bits for p in ss], 1), ss[0].channels)
-    else:
-      s = torch.cat(ss, 1)
-    return (None if us[0] is None else torch.cat(us, 0)), s
+    nrn, bn, packed_out = self._scan_setup(geom.Cout, True)
+
+    def currents(b0, b1):
+      xs = x if (b0 == 0 and b1 == B) else ops.GatedSpikes(x.spikes[:, b0:b1], x.gate[:, b0:b1])
+      return ops.conv_gated_forward(xs, geom, w, packed)
+    return self._scan_slices(T, B, geom, currents, nrn, bn, _given_carry(u), packed_out)
 
   # -- 3-D convolution: the direct-form kernel with a depth axis -----------------------------------
   def _conv3d_block(self, u, inputs):
@@ -684,7 +672,7 @@ class SpikingBlock(nn.Module):
     (flax_qconv.py:93-171 inside spiking_learning.py:446-462): one launch of the direct-form
     kernel (snnqp_conv3d_lif_forward); float32 inputs speculate on the integer codes like every
     other block (narrowing pass + predicated float32 launch into the same outputs)."""
-    conn, norm = self.connection_fn, self.norm_fn
+    conn = self.connection_fn
     if self.pool != 1:
       raise ValueError("the fused 2x2 pool is 2-D")
     if isinstance(inputs, (ops.PackedFrames, ops.GatedSpikes)):
@@ -693,8 +681,7 @@ class SpikingBlock(nn.Module):
     if x.ndim != 6:
       raise ValueError("QuantConv block expects [T, B, spatial..., C] inputs, got %s" % (x.shape,))
     if self.batch_major_input:
-      x = ops.PackedSpikes(x.bits.transpose(0, 1).contiguous(), x.channels) if isinstance(x, ops.PackedSpikes) \
-          else x.transpose(0, 1).contiguous()
+      x = x.swap_leading() if isinstance(x, ops.PackedSpikes) else x.transpose(0, 1).contiguous()
     cin = x.shape[-1]
     pk = conn.packed_kernel(cin)
     geom = conn.geometry(tuple(x.shape[2:-1]), cin)
@@ -702,10 +689,8 @@ class SpikingBlock(nn.Module):
     spec = integer is packing.SPECULATE and w is not None
     if w is None:
       w = pk.float_weight()
-    nrn = self.neural_dynamics.neuron(conn.features)
-    bn = norm.coeffs(conn.features) if norm is not None else None
-    u0 = None if (u is None or isinstance(u, ZeroCarry)) else u
-    packed_out = bool(integer) if self.packed is None else bool(self.packed)
+    nrn, bn, packed_out = self._scan_setup(conn.features, integer)
+    u0 = _given_carry(u)
     if spec:
       x8, pred = ops.narrow_f32_async(x)
       out = ops.conv3d_lif_forward(x8, geom, w, nrn, bn=bn, u0=u0, want_u=self.return_state, packed_out=packed_out)
@@ -718,7 +703,7 @@ class SpikingBlock(nn.Module):
     flattening of gate x raster, the positions of a channel summed as integers and the gates
     applied in one float32 chain (ops.dense_gated_forward; oracle gated_dense).  None when the
     block is not a shape that kernel serves."""
-    conn, norm = self.connection_fn, self.norm_fn
+    conn = self.connection_fn
     if not isinstance(conn, QuantDense) or self.pool != 1:
       return None
     T, B, H, W, C = x.spikes.shape
@@ -727,32 +712,22 @@ class SpikingBlock(nn.Module):
     packed = pk.gated_dense_codes(C, H * W) if w is not None else None
     if packed is None:
       return None
-    N = conn.features
-    nrn = self.neural_dynamics.neuron(N)
-    bn = norm.coeffs(N) if norm is not None else None
-    u0 = None if (u is None or isinstance(u, ZeroCarry)) else u
-    packed_out = True if self.packed is None else bool(self.packed)
+    nrn, bn, packed_out = self._scan_setup(conn.features, True)
     y = ops.dense_gated_forward(x, w, packed)
-    return ops.lif_forward(y, nrn, bn=bn, u0=u0, want_u=self.return_state, packed_out=packed_out)
+    return ops.lif_forward(y, nrn, bn=bn, u0=_given_carry(u), want_u=self.return_state, packed_out=packed_out)
 
   # -- float32 kernel: f32-MFMA connection + neuron scan, batch slice by batch slice ----
   def _float_block(self, x, tm, is_dense, geom, w, nrn, bn, u0, packed_out):
     T, B = (x.shape[0], x.shape[1]) if tm else (x.shape[1], x.shape[0])
     N = geom.Cout
-    per_sample = 4 * T * geom.H * geom.W * N              # bytes of float32 currents
-    step = max(1, min(B, CURRENTS_SLICE_BYTES // max(per_sample, 1)))
     tag = "%s[f32 %s]" % ("dense" if is_dense else "conv", geom.tag())
-    us, ss = [], []
-    for b0 in range(0, max(B, 1), step):      # (an empty batch: one empty slice)
-      b1 = min(B, b0 + step)
+
+    def currents(b0, b1):
       if tm:
         xs = x[(slice(None), slice(b0, b1))]
       else:                                               # [B, T, ...] -> time-major slice
         xs = x[b0:b1]
-        if isinstance(xs, ops.PackedSpikes):
-          xs = ops.PackedSpikes(xs.bits.transpose(0, 1).contiguous(), xs.channels)
-        else:
-          xs = xs.transpose(0, 1)
+        xs = xs.swap_leading() if isinstance(xs, ops.PackedSpikes) else xs.transpose(0, 1)
       if isinstance(xs, torch.Tensor):
         xs = xs.contiguous()
       nb = b1 - b0
@@ -762,10 +737,18 @@ class SpikingBlock(nn.Module):
         xi = xs.reshape((T * nb,) + ((1, 1, geom.Cin) if is_dense else (geom.H, geom.W, geom.Cin)))
       with ops._timed(tag):
         y = ops.conv_forward(xi, geom, w)
-      y = y.reshape((T, nb) + ((N,) if is_dense else (geom.H, geom.W, N)))
-      u0s = None if u0 is None else u0[b0:b1]
-      u_out, s = ops.lif_forward(y, nrn, bn=bn, u0=u0s, want_u=self.return_state,
-                                 packed_out=packed_out)
+      return y.reshape((T, nb) + ((N,) if is_dense else (geom.H, geom.W, N)))
+    return self._scan_slices(T, B, geom, currents, nrn, bn, u0, packed_out)
+
+  def _scan_slices(self, T, B, geom, currents, nrn, bn, u0, packed_out):
+    """The neuron scan (and the pool) over the float32 currents [T, nb, ..., N] that currents(b0, b1)
+    returns for each batch slice, the slices joined: potentials on axis 0, rasters on axis 1."""
+    per_sample = 4 * T * geom.H * geom.W * geom.Cout      # bytes of float32 currents
+    us, ss = [], []
+    for b0, b1 in batch_slices(B, per_sample):
+      y = currents(b0, b1)
+      u_out, s = ops.lif_forward(y, nrn, bn=bn, u0=None if u0 is None else u0[b0:b1],
+                                 want_u=self.return_state, packed_out=packed_out)
       del y
       if self.pool == 2:
         s = ops.maxpool2x2(s)
@@ -773,12 +756,8 @@ class SpikingBlock(nn.Module):
       ss.append(s)
     if len(ss) == 1:
       return us[0], ss[0]
-    if isinstance(ss[0], ops.PackedSpikes):
-      s = ops.PackedSpikes(torch.cat([p.bits for p in ss], 1), ss[0].channels)
-    else:
-      s = torch.cat(ss, 1)
-    u_out = None if us[0] is None else torch.cat(us, 0)
-    return u_out, s
+    s = ops.PackedSpikes.cat_batch(ss) if isinstance(ss[0], ops.PackedSpikes) else torch.cat(ss, 1)
+    return (None if us[0] is None else torch.cat(us, 0)), s
 
   # -- arbitrary connection / norm / neuron: compose the stand-alone ops -----------
   def _composed(self, u, inputs):
@@ -797,13 +776,13 @@ class SpikingBlock(nn.Module):
         x = norm(x)
       xs.append(x)
     x = torch.stack(xs, 0)
+    u = _given_carry(u)
     if isinstance(nrn_mod, _NeuronBase):
-      u0 = None if (u is None or isinstance(u, ZeroCarry)) else u
       packed_out = bool(self.packed)
-      u_out, s = ops.lif_forward(x, nrn_mod.neuron(x.shape[-1]), u0=u0,
+      u_out, s = ops.lif_forward(x, nrn_mod.neuron(x.shape[-1]), u0=u,
                                  want_u=self.return_state, packed_out=packed_out)
     else:                       # foreign neuron callable: explicit time loop
-      if isinstance(u, ZeroCarry) or u is None:
+      if u is None:
         u = torch.zeros_like(x[0])
       out = []
       for t in range(T):

@@ -970,3 +970,71 @@ def test_table_slots_balance_the_bank_columns():
   ranges = (rng.poisson(1.8, 128) * rng.integers(1, 8, 128)).astype(np.int64)
   _, stack = packing.table_slots(ranges)
   assert stack <= 1.35 * ranges.sum() / 32 + ranges.max() / 2 < ranges.reshape(4, 32).sum(0).max()
+
+
+def test_batch_slices_cut_the_batch_by_the_currents_budget(monkeypatch):
+  """spiking_learning.batch_slices: the walk of SpikingBlock._float_block / ._gated_block, with
+  CURRENTS_SLICE_BYTES read at the call."""
+  from snnquantprune_amd import spiking_learning as sl
+  per = 1000
+  monkeypatch.setattr(sl, "CURRENTS_SLICE_BYTES", 2500)              # 2.5 samples
+  assert sl.batch_slices(5, per) == [(0, 2), (2, 4), (4, 5)]
+  for budget in (5000, 5001, 1 << 30):                               # at least the whole batch
+    monkeypatch.setattr(sl, "CURRENTS_SLICE_BYTES", budget)
+    assert sl.batch_slices(5, per) == [(0, 5)]
+  assert sl.batch_slices(0, per) == [(0, 0)]                         # the empty batch: one empty slice
+  monkeypatch.setattr(sl, "CURRENTS_SLICE_BYTES", 999)               # less than one sample
+  assert sl.batch_slices(5, per) == [(0, 1), (1, 2), (2, 3), (3, 4), (4, 5)]
+  monkeypatch.setattr(sl, "CURRENTS_SLICE_BYTES", 0)
+  assert sl.batch_slices(5, per) == [(b, b + 1) for b in range(5)]
+  for budget in (2500, 5):                                           # (a sample of no bytes counts as one byte)
+    monkeypatch.setattr(sl, "CURRENTS_SLICE_BYTES", budget)
+    assert sl.batch_slices(5, 0) == [(0, 5)]                         # nothing to hold: one slice
+
+
+def _pack_rows_host(dense):
+  """uint8 / bool [..., C] -> PackedSpikes in host memory: channel c in bit c & 31 of word c >> 5."""
+  from snnquantprune_amd import ops
+  C = dense.shape[-1]
+  cw = (C + 31) // 32
+  b = np.packbits(np.asarray(dense, np.uint8), axis=-1, bitorder="little")
+  b = np.concatenate([b, np.zeros(b.shape[:-1] + (4 * cw - b.shape[-1],), np.uint8)], -1)
+  return ops.PackedSpikes(torch.from_numpy(np.ascontiguousarray(b).view(np.int32)), C)
+
+
+def test_packed_spikes_swap_leading_and_cat_batch():
+  from snnquantprune_amd import ops
+  rng = np.random.Generator(np.random.PCG64(40))
+  dense = rng.integers(0, 2, (2, 3, 4, 40)).astype(np.uint8)
+  p = _pack_rows_host(dense)
+  assert p.shape == (2, 3, 4, 40)
+  cmap = ops.ChannelMap(np.arange(40), np.ones(40, bool), 64)
+  p.chan_map = cmap
+  sw = p.swap_leading()
+  assert sw.shape == (3, 2, 4, 40) and sw.bits.is_contiguous() and sw.chan_map is cmap
+  assert torch.equal(sw.bits, _pack_rows_host(dense.swapaxes(0, 1)).bits)
+  assert torch.equal(sw.swap_leading().bits, p.bits)
+  parts = [p[:, 0:2], p[:, 2:3]]
+  assert [q.shape for q in parts] == [(2, 2, 4, 40), (2, 1, 4, 40)]
+  joined = ops.PackedSpikes.cat_batch(parts)
+  assert joined.shape == p.shape and joined.bits.is_contiguous() and joined.chan_map is cmap
+  assert torch.equal(joined.bits, p.bits)
+  # rasters of different channel sets have no join
+  parts[1].chan_map = ops.ChannelMap(np.arange(40), np.ones(40, bool), 64)
+  with pytest.raises(AssertionError):
+    ops.PackedSpikes.cat_batch(parts)
+  with pytest.raises(AssertionError):
+    ops.PackedSpikes.cat_batch([p[:, 0:2], _pack_rows_host(dense[:, 2:3, :, :33])])
+
+
+def test_conv_geom_is_3x3_same_refuses_every_single_deviation():
+  import dataclasses
+  from snnquantprune_amd import ops
+  g = ops.ConvGeom(8, 8, 32, 64, 3, 3, pad=((1, 1), (1, 1)))
+  assert g.is_3x3_same()
+  assert dataclasses.replace(g, stride=[1, 1], pad=[[1, 1], [1, 1]]).is_3x3_same()     # lists as well
+  for change in (dict(KH=1, KW=1), dict(KH=1), dict(KW=5), dict(stride=(2, 2)), dict(stride=(1, 2)),
+                 dict(pad=((0, 0), (0, 0))), dict(pad=((1, 0), (1, 1))), dict(pad=((1, 1), (0, 1))),
+                 dict(in_dil=(2, 2)), dict(in_dil=(1, 2)), dict(k_dil=(2, 2)), dict(k_dil=(2, 1)),
+                 dict(groups=2)):
+    assert not dataclasses.replace(g, **change).is_3x3_same(), change
