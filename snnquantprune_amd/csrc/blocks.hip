@@ -43,8 +43,42 @@ snnqp_conv_geom_t dense_geom(int32_t K, int32_t N) {
 
 #define SNNQP_CHECK_NEURON_KIND(nrn, who)                                                      \
   SNNQP_REQUIRE((nrn)->kind >= SNNQP_NEURON_MULTI_STEP_LIF && (nrn)->kind <= SNNQP_NEURON_LIF, \
-                SNNQP_EINVAL, who ": unknown neuron kind %d", (nrn)->kind)
+                SNNQP_EINVAL, "%s: unknown neuron kind %d", who, (nrn)->kind)
+
+// the preamble of the three conv entry points (the x_flags rule: the forms that stage float32 frames)
+int conv_preamble(const char *who, const BlockCall &c, bool predicated, bool stages_f32) {
+  SNNQP_REQUIRE((c.pred || !predicated) && c.g && c.w && c.nrn, SNNQP_EINVAL, "%s: null %s", who,
+                predicated ? "argument" : "descriptor");
+  if (stages_f32 && c.in_type == SNNQP_F32 && c.w->wtype == SNNQP_W_I8)
+    SNNQP_REQUIRE(c.x_flags, SNNQP_EINVAL, "%s: float32 input into integer codes needs x_flags (snnqp.h)", who);
+  if (int rc = refuse_after_device_report(c.st, who)) return rc;
+  SNNQP_CHECK_NEURON_KIND(c.nrn, who);
+  SNNQP_REQUIRE(c.pool == 1 || c.pool == 2, SNNQP_EINVAL, "%s: pool must be 1 or 2", who);
+  return SNNQP_OK;
+}
 }  // namespace
+
+namespace snnqp {
+int block_entry(const char *who, const BlockCall &c, bool ptrs) {
+  const bool empty = c.T == 0 || c.B == 0;
+  SNNQP_REQUIRE(ptrs && ((c.x && c.s_out) || empty), SNNQP_EINVAL, "%s: null pointer", who);
+  SNNQP_REQUIRE(c.T >= 0 && c.B >= 0, SNNQP_EINVAL, "%s: negative T/B", who);
+  SNNQP_REQUIRE(c.w->L >= 1.0f, SNNQP_EINVAL, "dequant L must be >= 1");
+  SNNQP_CHECK_BN(c.bn);
+  return empty ? BLOCK_EMPTY : SNNQP_OK;
+}
+
+int dense_rows_broken(const BlockCall &c, int in_type, int samples, int64_t steps, int64_t extent) {
+  const int64_t align = in_type == SNNQP_U8 ? 16 : 4;       // of the strides, in elements: 16 bytes
+  int broken = c.xs_t < 0 || c.xs_b < 0 ? ROWS_NEGATIVE : 0;
+  if ((in_type == SNNQP_U8 || in_type == SNNQP_F32) &&
+      ((((uintptr_t)c.x) & 15) != 0 || c.xs_t % align != 0 || c.xs_b % align != 0))
+    broken |= ROWS_UNALIGNED;
+  if ((steps * c.xs_t + samples * c.xs_b + extent) * (in_type == SNNQP_F32 ? 4 : 1) >= ((int64_t)1 << 31))
+    broken |= ROWS_REACH;
+  return broken;
+}
+}  // namespace snnqp
 
 extern "C" {
 
@@ -86,23 +120,15 @@ int snnqp_conv_lif_forward(const void *x, int in_type, int64_t x_stride_t,
                            const float *u0, float *u_out, void *s_out,
                            int s_type, int pool, int impl, int x_max, int32_t *x_seen,
                            int32_t *x_flags, snnqp_stream_t stream) {
-  SNNQP_REQUIRE(g && w && nrn, SNNQP_EINVAL, "conv_lif_forward: null descriptor");
-  if (in_type == SNNQP_F32 && w->wtype == SNNQP_W_I8)
-    SNNQP_REQUIRE(x_flags != nullptr, SNNQP_EINVAL,
-                  "conv_lif_forward: float32 input into integer codes needs x_flags (snnqp.h)");
-  if (int rc = refuse_after_device_report((hipStream_t)stream, "conv_lif_forward")) return rc;
-  SNNQP_CHECK_NEURON_KIND(nrn, "conv_lif_forward");
-  SNNQP_REQUIRE(pool == 1 || pool == 2, SNNQP_EINVAL,
-                "conv_lif_forward: pool must be 1 or 2");
+  const BlockCall c{x, in_type, x_stride_t, x_stride_b, T, B, w, wt, bn, nrn, u0, u_out, s_out, s_type,
+                    x_flags, nullptr, (hipStream_t)stream, g, pool, x_max, x_seen};
+  if (int rc = conv_preamble("conv_lif_forward", c, false, true)) return rc;
   SNNQP_REQUIRE(impl >= SNNQP_IMPL_AUTO && impl <= SNNQP_IMPL_MFMA, SNNQP_EINVAL,
                 "conv_lif_forward: unknown impl %d", impl);
-  const char *why = conv3x3_mfma_unsupported(in_type, g, w, wt, nrn, s_type);
+  const char *why = conv3x3_mfma_unsupported(c);
   if (impl == SNNQP_IMPL_MFMA)
     SNNQP_REQUIRE(!why, SNNQP_EUNSUPPORTED, "conv_lif_forward: MFMA kernel: %s", why);
-  if (!why && impl != SNNQP_IMPL_GENERIC)
-    return run_conv3x3_mfma(x, in_type, x_stride_t, x_stride_b, T, B, g, w, wt, bn,
-                            nrn, u0, u_out, (uint32_t *)s_out, pool, x_max, x_seen, x_flags,
-                            (hipStream_t)stream);
+  if (!why && impl != SNNQP_IMPL_GENERIC) return run_conv3x3_mfma(c);
   // the direct-form kernel reads no packed event frames: refused here, before it counts as a fallback
   SNNQP_REQUIRE(in_type != SNNQP_EV1 && in_type != SNNQP_EV4, SNNQP_EUNSUPPORTED,
                 "conv_lif_forward: packed event frames need bit-packed spike output; unpack them first "
@@ -115,8 +141,7 @@ int snnqp_conv_lif_forward(const void *x, int in_type, int64_t x_stride_t,
                 "conv_lif_forward: the direct-form kernel does not fuse the "
                 "max-pool; call snnqp_maxpool2x2 after it");
   if (impl == SNNQP_IMPL_AUTO) note_fallback(false, why);
-  return run_generic(x, in_type, x_stride_t, x_stride_b, T, B, g, w, bn, nrn, u0,
-                     u_out, s_out, s_type, nullptr, (hipStream_t)stream);
+  return run_generic(c, nullptr, nullptr);
 }
 
 int snnqp_conv_lif_forward_pred(const int32_t *pred, const void *x, int in_type, int64_t x_stride_t,
@@ -127,19 +152,14 @@ int snnqp_conv_lif_forward_pred(const int32_t *pred, const void *x, int in_type,
                                 const float *u0, float *u_out, void *s_out,
                                 int s_type, int pool, int x_max, int32_t *x_seen,
                                 int32_t *x_flags, snnqp_stream_t stream) {
-  SNNQP_REQUIRE(pred && g && w && nrn, SNNQP_EINVAL, "conv_lif_forward_pred: null argument");
-  if (in_type == SNNQP_F32 && w->wtype == SNNQP_W_I8)
-    SNNQP_REQUIRE(x_flags != nullptr, SNNQP_EINVAL,
-                  "conv_lif_forward_pred: float32 input into integer codes needs x_flags (snnqp.h)");
-  if (int rc = refuse_after_device_report((hipStream_t)stream, "conv_lif_forward_pred")) return rc;
-  SNNQP_CHECK_NEURON_KIND(nrn, "conv_lif_forward_pred");
-  SNNQP_REQUIRE(pool == 1 || pool == 2, SNNQP_EINVAL, "conv_lif_forward_pred: pool must be 1 or 2");
+  const BlockCall c{x, in_type, x_stride_t, x_stride_b, T, B, w, wt, bn, nrn, u0, u_out, s_out, s_type,
+                    x_flags, pred, (hipStream_t)stream, g, pool, x_max, x_seen};
+  if (int rc = conv_preamble("conv_lif_forward_pred", c, true, true)) return rc;
   SNNQP_REQUIRE(in_type == SNNQP_U8 || in_type == SNNQP_F32 || in_type == SNNQP_EV4, SNNQP_EUNSUPPORTED,
                 "conv_lif_forward_pred: byte, nibble or float32 frames (the event layer's own formats)");
-  const char *why = conv3x3_mfma_unsupported(in_type, g, w, wt, nrn, s_type);
+  const char *why = conv3x3_mfma_unsupported(c);
   SNNQP_REQUIRE(!why, SNNQP_EUNSUPPORTED, "conv_lif_forward_pred: MFMA kernel: %s", why);
-  return run_conv3x3_mfma(x, in_type, x_stride_t, x_stride_b, T, B, g, w, wt, bn, nrn, u0, u_out,
-                          (uint32_t *)s_out, pool, x_max, x_seen, x_flags, (hipStream_t)stream, pred);
+  return run_conv3x3_mfma(c);
 }
 
 int snnqp_conv_lif_forward_if(const int32_t *pred, const void *x, int in_type, int64_t x_stride_t,
@@ -148,12 +168,10 @@ int snnqp_conv_lif_forward_if(const int32_t *pred, const void *x, int in_type, i
                               const snnqp_bn_t *bn, const snnqp_neuron_t *nrn, const float *u0,
                               float *u_out, void *s_out, int s_type, int pool,
                               snnqp_stream_t stream) {
-  SNNQP_REQUIRE(pred && g && w && nrn, SNNQP_EINVAL, "conv_lif_forward_if: null argument");
-  if (int rc = refuse_after_device_report((hipStream_t)stream, "conv_lif_forward_if")) return rc;
-  SNNQP_CHECK_NEURON_KIND(nrn, "conv_lif_forward_if");
-  SNNQP_REQUIRE(pool == 1 || pool == 2, SNNQP_EINVAL, "conv_lif_forward_if: pool must be 1 or 2");
-  return run_generic(x, in_type, x_stride_t, x_stride_b, T, B, g, w, bn, nrn, u0, u_out, s_out, s_type,
-                     nullptr, (hipStream_t)stream, pool, pred);
+  const BlockCall c{x, in_type, x_stride_t, x_stride_b, T, B, w, nullptr, bn, nrn, u0, u_out, s_out, s_type,
+                    nullptr, pred, (hipStream_t)stream, g, pool};
+  if (int rc = conv_preamble("conv_lif_forward_if", c, true, false)) return rc;
+  return run_generic(c, nullptr, nullptr);
 }
 
 int snnqp_dense_lif_forward_if(const int32_t *pred, const void *x, int in_type, int64_t x_stride_t,
@@ -165,8 +183,9 @@ int snnqp_dense_lif_forward_if(const int32_t *pred, const void *x, int in_type, 
   if (int rc = refuse_after_device_report((hipStream_t)stream, "dense_lif_forward_if")) return rc;
   SNNQP_CHECK_NEURON_KIND(nrn, "dense_lif_forward_if");
   const snnqp_conv_geom_t g = dense_geom(K, N);
-  return run_generic(x, in_type, x_stride_t, x_stride_b, T, B, &g, w, bn, nrn, u0, u_out, s_out, s_type,
-                     nullptr, (hipStream_t)stream, 1, pred);
+  const BlockCall c{x, in_type, x_stride_t, x_stride_b, T, B, w, nullptr, bn, nrn, u0, u_out, s_out, s_type,
+                    nullptr, pred, (hipStream_t)stream, &g};
+  return run_generic(c, nullptr, nullptr);
 }
 
 int snnqp_current_min(const snnqp_weight_t *w, const snnqp_bn_t *bn, int32_t bound,
@@ -176,9 +195,7 @@ int snnqp_current_min(const snnqp_weight_t *w, const snnqp_bn_t *bn, int32_t bou
 
 int64_t snnqp_dense_workspace_bytes(int in_type, int32_t T, int32_t B, int32_t K, int32_t N,
                                     const snnqp_weight_t *w) {
-  if (!w || in_type != SNNQP_BITS || w->wtype != SNNQP_W_I8 || !w->wt_fp6 || w->code_max <= 0 ||
-      w->code_max > 7 || K <= 0 || N <= 0)
-    return 0;
+  if (!w || dense_fp6_unsupported(in_type, K, N, w)) return 0;
   return dense_fp6_workspace_bytes(T, B, K, N);
 }
 
@@ -210,43 +227,25 @@ int snnqp_dense_lif_forward_ws(const void *x, int in_type, int64_t x_stride_t,
   SNNQP_CHECK_NEURON_KIND(nrn, "dense_lif_forward");
   SNNQP_REQUIRE(impl >= SNNQP_IMPL_AUTO && impl <= SNNQP_IMPL_MFMA, SNNQP_EINVAL,
                 "dense_lif_forward: unknown impl %d", impl);
-  // codes that fit fp6, packed as fp6 tiles, over bit-packed rows: the f8f6f4 kernel
-  if (impl != SNNQP_IMPL_GENERIC && in_type == SNNQP_BITS && s_type == SNNQP_BITS &&
-      w->wtype == SNNQP_W_I8 && w->wt_fp6 && w->code_max > 0 && w->code_max <= 7 && T <= 160 &&
-      (int64_t)7 * K < ((int64_t)1 << 24) &&      // every partial sum an integer float32 holds exactly
-      !(nrn->kind == SNNQP_NEURON_LIF && !nrn->decay) && x_stride_t >= 0 && x_stride_b >= 0 &&
-      (int64_t)(T > 0 ? T - 1 : 0) * x_stride_t + 160 * x_stride_b + (K + 31) / 32 < ((int64_t)1 << 31))
-    return run_dense_fp6(x, x_stride_t, x_stride_b, T, B, K, N, w, bn, nrn, u0, u_out,
-                         (uint32_t *)s_out, 0, ws, ws_bytes, (hipStream_t)stream);
-  // more than 128 features: a workgroup per 256 / 512-column block, every row read once
-  if (impl != SNNQP_IMPL_GENERIC &&
-      !dense_wide_unsupported(in_type, T, K, N, x_stride_t, x_stride_b, x, w, wt, nrn, s_type))
-    return run_dense_wide(x, in_type, x_stride_t, x_stride_b, T, B, K, N, w, wt, bn, nrn, u0, u_out,
-                          (uint32_t *)s_out, x_flags, (hipStream_t)stream);
+  const snnqp_conv_geom_t g = dense_geom(K, N);
+  const BlockCall c{x, in_type, x_stride_t, x_stride_b, T, B, w, wt, bn, nrn, u0, u_out, s_out, s_type,
+                    x_flags, nullptr, (hipStream_t)stream, &g, 1, 0, nullptr, K, N, ws, ws_bytes};
+  // The routes, best first: fp6 tiles over bit-packed rows; more than 128 features, every row read
+  // once; then the 128-column kernel, the one whose reason a caller gets to see.
+  if (impl != SNNQP_IMPL_GENERIC) {
+    if (!dense_fp6_unsupported(c)) return run_dense_fp6(c);
+    if (!dense_wide_unsupported(c)) return run_dense_wide(c);
+  }
   SNNQP_REQUIRE(!f32_int, SNNQP_EUNSUPPORTED,
                 "dense_lif_forward: float32 rows into integer codes are staged by the wide MFMA kernel only "
                 "(more than 128 features, T <= 64, K %% 16 == 0, 16-byte aligned rows); narrow them first "
                 "(snnqp_narrow_f32)");
-  const char *why = dense_mfma_unsupported(in_type, K, N, w, wt, nrn, s_type);
-  if (!why && T > (in_type == SNNQP_U8 ? 64 : 96))
-    why = "more than 96 (uint8 input: 64) timesteps (one sample must fit a row tile)";
-  if (!why && in_type == SNNQP_U8 &&
-      ((((uintptr_t)x) & 15) != 0 || x_stride_t % 16 != 0 || x_stride_b % 16 != 0))
-    why = "uint8 rows not 16-byte aligned";
-  // the fused kernel addresses the rows of one workgroup (at most 96 samples) with 32-bit
-  // word offsets from the workgroup's first sample
-  if (!why && ((int64_t)(T > 0 ? T - 1 : 0) * x_stride_t + 96 * x_stride_b + (K + 31) / 32 >= ((int64_t)1 << 31) ||
-               x_stride_t < 0 || x_stride_b < 0))
-    why = "input strides beyond 32-bit word offsets within a workgroup";
+  const char *why = dense_mfma_unsupported(c);
   if (impl == SNNQP_IMPL_MFMA)
     SNNQP_REQUIRE(!why, SNNQP_EUNSUPPORTED, "dense_lif_forward: MFMA kernel: %s", why);
-  if (!why && impl != SNNQP_IMPL_GENERIC)
-    return run_dense_mfma(x, in_type, x_stride_t, x_stride_b, T, B, K, N, w, wt, bn, nrn,
-                          u0, u_out, (uint32_t *)s_out, (hipStream_t)stream);
+  if (!why && impl != SNNQP_IMPL_GENERIC) return run_dense_mfma(c);
   if (impl == SNNQP_IMPL_AUTO) note_fallback(true, why);
-  const snnqp_conv_geom_t g = dense_geom(K, N);
-  return run_generic(x, in_type, x_stride_t, x_stride_b, T, B, &g, w, bn, nrn, u0,
-                     u_out, s_out, s_type, nullptr, (hipStream_t)stream);
+  return run_generic(c, nullptr, nullptr);
 }
 
 }  // extern "C"

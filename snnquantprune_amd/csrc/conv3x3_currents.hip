@@ -210,15 +210,7 @@ static void launch_currents_wpp(const ConvMfmaArgs &a, int wpp, int32_t *acc, un
 const char *conv3x3_currents_unsupported(int in_type, int64_t NB, const snnqp_conv_geom_t *g,
                                          const snnqp_weight_t *w, const int8_t *wt) {
   if (w->wtype != SNNQP_W_I8) return "weights are not int8 codes";
-  if (g->KH != 3 || g->KW != 3) return "kernel is not 3x3";
-  if (g->stride_h != 1 || g->stride_w != 1) return "stride is not 1";
-  if (g->pad_h_lo != 1 || g->pad_h_hi != 1 || g->pad_w_lo != 1 || g->pad_w_hi != 1)
-    return "padding is not ((1,1),(1,1))";
-  if (g->in_dil_h != 1 || g->in_dil_w != 1 || g->k_dil_h != 1 || g->k_dil_w != 1)
-    return "dilated convolution";
-  if (g->groups != 1) return "grouped convolution";
-  if (g->H <= 0 || g->W <= 0) return "empty image";
-  if (g->Cout <= 0) return "no output channels";
+  if (const char *why = conv3x3_geometry_unsupported(g)) return why;
   if (in_type != SNNQP_BITS) return "input must be bit-packed spikes";
   if (g->Cin < 1 || g->Cin > 128) return "bit input needs Cin <= 128";
   if (!wt) return "MFMA-tiled codes `wt` not given";

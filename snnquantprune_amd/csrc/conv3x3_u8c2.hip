@@ -673,8 +673,11 @@ int conv3x3_event_half_group(int in_type, int32_t T, const snnqp_conv_geom_t *g,
   SNNQP_REQUIRE(pool == 1 || pool == 2, SNNQP_EINVAL, "conv_event_half_group: pool must be 1 or 2");
   SNNQP_REQUIRE(T >= 0, SNNQP_EINVAL, "conv_event_half_group: negative T");
   if (in_type != SNNQP_EV1 || T == 0) return 0;
-  if (conv3x3_mfma_unsupported(in_type, g, w, nullptr, nrn, SNNQP_BITS)) return 0;
-  if (int rc = conv3x3_check_weight("conv_event_half_group", w, nullptr, g->Cout)) return rc;
+  BlockCall c;
+  c.in_type = in_type; c.g = g; c.w = w; c.nrn = nrn;
+  if (conv3x3_mfma_unsupported(c)) return 0;
+  SNNQP_REQUIRE(w->L >= 1.0f, SNNQP_EINVAL, "dequant L must be >= 1");
+  if (int rc = conv3x3_check_cout_fire("conv_event_half_group", w, g->Cout)) return rc;
   return u8c2_plan(in_type, T, g->Cout, w, neuron_form(make_neuron(nrn)), has_state, pool == 2, x_max).half ? 1 : 0;
 }
 

@@ -630,10 +630,10 @@ static inline void launch_persistent(K kernel, ConvMfmaArgs a, unsigned gy, hipS
   if (a.sched) sched_release(dev, slot, st);
 }
 
-// The checks run_conv3x3_mfma and snnqp_conv_event_half_group share: the dequantisation step, the
-// BatchNorm descriptor (nullable) and the caller's silent channels (snnqp.h) -- a malformed value is
-// refused before anything runs.  `who` opens the message.  (conv3x3_mfma.hip)
-int conv3x3_check_weight(const char *who, const snnqp_weight_t *w, const snnqp_bn_t *bn, int32_t Cout);
+// The check of the caller's silent channels (snnqp.h) that run_conv3x3_mfma and
+// snnqp_conv_event_half_group share -- a malformed value is refused before anything runs.  `who`
+// opens the message.  (conv3x3_mfma.hip)
+int conv3x3_check_cout_fire(const char *who, const snnqp_weight_t *w, int32_t Cout);
 // the input channels `wt` is padded to: one 32-channel group per int8 tile of a tap
 inline int wt_cin_pad(const snnqp_weight_t *w, int32_t Cin) { return w->wt_cin ? w->wt_cin : (Cin + 31) / 32 * 32; }
 

@@ -407,35 +407,41 @@ int64_t dense_fp6_workspace_bytes(int32_t T, int32_t B, int32_t K, int32_t N) {
   return fp6_workspace_bytes(pick_fp6_plan(T, B, K, gy, true), T, B, gy);
 }
 
-int run_dense_fp6(const void *x, int64_t xs_t, int64_t xs_b, int32_t T, int32_t B, int32_t K,
-                  int32_t N, const snnqp_weight_t *w, const snnqp_bn_t *bn,
-                  const snnqp_neuron_t *nrn, const float *u0, float *u_out, uint32_t *s_out,
-                  int row_tiles, void *ws, int64_t ws_bytes, hipStream_t st) {
-  SNNQP_REQUIRE(w->wt_fp6 && ((x && s_out) || T == 0 || B == 0), SNNQP_EINVAL, "dense fp6: null pointer");
-  SNNQP_REQUIRE(T >= 0 && B >= 0, SNNQP_EINVAL, "dense fp6: negative T/B");
-  SNNQP_REQUIRE(w->L >= 1.0f, SNNQP_EINVAL, "dequant L must be >= 1");
-  SNNQP_CHECK_BN(bn);
-  if (T == 0 || B == 0) return SNNQP_OK;
-  SNNQP_REQUIRE(T <= 160, SNNQP_EUNSUPPORTED, "dense fp6: T > 160");
+const char *dense_fp6_unsupported(int in_type, int32_t K, int32_t N, const snnqp_weight_t *w) {
+  if (in_type != SNNQP_BITS || w->wtype != SNNQP_W_I8) return "not int8 codes over bit-packed rows";
+  if (!w->wt_fp6 || w->code_max <= 0 || w->code_max > 7) return "no fp6 tiles of codes known to fit fp6";
+  return K <= 0 || N <= 0 ? "bad K/N" : nullptr;
+}
+
+const char *dense_fp6_unsupported(const BlockCall &c) {
+  if (const char *why = dense_fp6_unsupported(c.in_type, c.K, c.N, c.w)) return why;
+  if (c.s_type != SNNQP_BITS) return "spike output must be bit-packed";
+  if (c.T > 160) return "more than 160 timesteps";
+  if ((int64_t)7 * c.K >= ((int64_t)1 << 24)) return "a partial sum float32 may not hold exactly";
+  if (c.nrn->kind == SNNQP_NEURON_LIF && !c.nrn->decay) return "LIF without decay";
+  if (dense_rows_broken(c, SNNQP_BITS, 160, c.T > 0 ? c.T - 1 : 0, (c.K + 31) / 32))
+    return "input strides beyond 32-bit word offsets within a workgroup";
+  return nullptr;
+}
+
+int run_dense_fp6(const BlockCall &c) {
+  if (int rc = block_entry("dense fp6", c, c.w->wt_fp6 != nullptr)) return rc < 0 ? rc : SNNQP_OK;
+  const int32_t T = c.T, B = c.B, K = c.K, N = c.N;
   DenseFp6Args a = {};
-  a.x = (const uint32_t *)x; a.xs_t = xs_t; a.xs_b = xs_b;
-  a.T = T; a.B = B; a.K = K; a.N = N; a.KW = (K + 31) / 32; a.KS = (K + 63) / 64;
-  a.wt6 = (const uint8_t *)w->wt_fp6;
-  a.dq = make_dequant(w->L, w->m);
-  a.bn = make_bn(bn); a.nrn = make_neuron(nrn);
-  a.u0 = u0; a.u_out = u_out; a.s_out = s_out;
+  fill_block_args(a, c);
+  a.K = K; a.N = N; a.KW = (K + 31) / 32; a.KS = (K + 63) / 64;
+  a.wt6 = (const uint8_t *)c.w->wt_fp6;
   const unsigned gy = (unsigned)((N + 127) / 128);
   // the workspace decides: the plan with a K split when the caller brought enough of it
   // (snnqp_dense_workspace_bytes, zero-filled once), else the best plan without
-  Fp6Plan plan = pick_fp6_plan(T, B, K, gy, ws != nullptr);
-  if (const char *e = ws ? std::getenv("SNNQP_DENSE_FP6_PLAN") : nullptr) {     // "rt,ks": measurement knob
+  Fp6Plan plan = pick_fp6_plan(T, B, K, gy, c.ws != nullptr);
+  if (const char *e = c.ws ? std::getenv("SNNQP_DENSE_FP6_PLAN") : nullptr) {     // "rt,ks": measurement knob
     int r = 0, k = 0;
     if (std::sscanf(e, "%d,%d", &r, &k) == 2 && r >= 1 && r <= 5 && r * 32 >= T && (k == 1 || k == 2 || k == 4))
       plan = Fp6Plan{r, k};
   }
-  if (plan.ks > 1 && (fp6_workspace_bytes(plan, T, B, gy) > ws_bytes || ((uintptr_t)ws & 255) != 0))
+  if (plan.ks > 1 && (fp6_workspace_bytes(plan, T, B, gy) > c.ws_bytes || ((uintptr_t)c.ws & 255) != 0))
     plan = pick_fp6_plan(T, B, K, gy, false);
-  if (row_tiles >= 1 && row_tiles <= 5 && row_tiles * 32 >= T) plan = Fp6Plan{row_tiles, 1};
   const int rt = plan.rt;
   SNNQP_REQUIRE(rt > 0, SNNQP_EUNSUPPORTED, "dense fp6: T too large");
   a.SB = rt * 32 / T;
@@ -446,21 +452,21 @@ int run_dense_fp6(const void *x, int64_t xs_t, int64_t xs_b, int32_t T, int32_t 
     const int ngc_all = (nchunks + F6_KGROUPS - 1) / F6_KGROUPS;
     a.gcz = (ngc_all + plan.ks - 1) / plan.ks;
     const int64_t tiles = (int64_t)gx * gy;
-    a.tickets = (uint32_t *)ws;
-    a.slabs = (float *)((uint8_t *)ws + F6_TICKET_BYTES);
-    a.status = device_status_word(stream_device(st));
+    a.tickets = (uint32_t *)c.ws;
+    a.slabs = (float *)((uint8_t *)c.ws + F6_TICKET_BYTES);
+    a.status = device_status_word(stream_device(c.st));
     // the tickets are zeroed on the stream in front of EVERY launch (a kernel node when the stream
     // is being captured: zero_words_async, kernels.h): whatever an earlier launch, an aborted replay or a stray store left in
     // them, this launch starts from zero (cdna_hip_programming.md, hand-off recipe: "zero the
     // counter per call; a reset by the last arriver alone fails the first, poisoned launch")
-    if (int rc = zero_words_async((uint32_t *)ws, tiles, st)) return rc;
+    if (int rc = zero_words_async((uint32_t *)c.ws, tiles, c.st)) return rc;
   }
   switch (rt) {
-    case 5: launch_dense_fp6<5>(a, gx, gy, st); break;
-    case 4: launch_dense_fp6<4>(a, gx, gy, st); break;
-    case 3: launch_dense_fp6<3>(a, gx, gy, st); break;
-    case 2: launch_dense_fp6<2>(a, gx, gy, st); break;
-    default: launch_dense_fp6<1>(a, gx, gy, st); break;
+    case 5: launch_dense_fp6<5>(a, gx, gy, c.st); break;
+    case 4: launch_dense_fp6<4>(a, gx, gy, c.st); break;
+    case 3: launch_dense_fp6<3>(a, gx, gy, c.st); break;
+    case 2: launch_dense_fp6<2>(a, gx, gy, c.st); break;
+    default: launch_dense_fp6<1>(a, gx, gy, c.st); break;
   }
   SNNQP_CHECK_LAUNCH("dense_fp6_kernel");
   return SNNQP_OK;

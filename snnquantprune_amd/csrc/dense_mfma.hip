@@ -289,22 +289,31 @@ dense_mfma_kernel(DenseMfmaArgs a) {
                          a.s_out, 256 * KGROUPS);
 }
 
-const char *dense_mfma_unsupported(int in_type, int32_t K, int32_t N,
-                                   const snnqp_weight_t *w, const int8_t *wt,
-                                   const snnqp_neuron_t *nrn, int s_type) {
-  if (w->wtype != SNNQP_W_I8) return "weights are not int8 codes";
-  if (!wt) return "MFMA-tiled codes `wt` not given";
+const char *dense_codes_unsupported(const BlockCall &c, int in_type) {
+  if (c.w->wtype != SNNQP_W_I8) return "weights are not int8 codes";
+  if (!c.wt) return "MFMA-tiled codes `wt` not given";
   if (in_type != SNNQP_BITS && in_type != SNNQP_U8) return "input must be bit-packed or uint8";
-  if (s_type != SNNQP_BITS) return "spike output must be bit-packed";
+  if (c.s_type != SNNQP_BITS) return "spike output must be bit-packed";
   if (in_type == SNNQP_U8) {
     // uint8 rows are read in 16-byte pieces, as x - 128 against the int8 codes
-    if (!w->col_sum) return "uint8 input needs snnqp_weight_t.col_sum";
-    if (K % 16) return "uint8 input needs K % 16 == 0";
-    if (K > 65536) return "uint8 input needs K <= 65536 (int32 accumulator)";
+    if (!c.w->col_sum) return "uint8 input needs snnqp_weight_t.col_sum";
+    if (c.K % 16) return "uint8 input needs K % 16 == 0";
+    if (c.K > 65536) return "uint8 input needs K <= 65536 (int32 accumulator)";
   }
   // bit-packed: any K -- the tiles `wt` are zero-padded to ceil(K / 32) k-steps and the packed
   // input rows carry zero bits beyond K
-  if (nrn->kind == SNNQP_NEURON_LIF && !nrn->decay) return "LIF without decay";
+  if (c.nrn->kind == SNNQP_NEURON_LIF && !c.nrn->decay) return "LIF without decay";
+  return nullptr;
+}
+
+const char *dense_mfma_unsupported(const BlockCall &c) {
+  if (const char *why = dense_codes_unsupported(c, c.in_type)) return why;
+  if (c.T > (c.in_type == SNNQP_U8 ? 64 : 96))
+    return "more than 96 (uint8 input: 64) timesteps (one sample must fit a row tile)";
+  // 32-bit word offsets from the workgroup's first sample (at most 96); a row: ceil(K / 32) units of any type
+  const int rows = dense_rows_broken(c, c.in_type, 96, c.T > 0 ? c.T - 1 : 0, (c.K + 31) / 32);
+  if (rows & ROWS_UNALIGNED) return "uint8 rows not 16-byte aligned";
+  if (rows) return "input strides beyond 32-bit word offsets within a workgroup";
   return nullptr;
 }
 
@@ -313,28 +322,17 @@ static void launch_dense(const DenseMfmaArgs &a, unsigned gx, unsigned gy, hipSt
   hipLaunchKernelGGL((dense_mfma_kernel<RT, IN>), dim3(gx, gy), dim3(256 * KGROUPS), 0, st, a);
 }
 
-int run_dense_mfma(const void *x, int in_type, int64_t xs_t, int64_t xs_b, int32_t T, int32_t B,
-                   int32_t K, int32_t N, const snnqp_weight_t *w, const int8_t *wt,
-                   const snnqp_bn_t *bn, const snnqp_neuron_t *nrn, const float *u0,
-                   float *u_out, uint32_t *s_out, hipStream_t st) {
-  SNNQP_REQUIRE((x && s_out) || T == 0 || B == 0, SNNQP_EINVAL, "dense mfma: null pointer");
-  SNNQP_REQUIRE(T >= 0 && B >= 0, SNNQP_EINVAL, "dense mfma: negative T/B");
-  SNNQP_REQUIRE(w->L >= 1.0f, SNNQP_EINVAL, "dequant L must be >= 1");
-  SNNQP_CHECK_BN(bn);
-  if (T == 0 || B == 0) return SNNQP_OK;
-  SNNQP_REQUIRE(T <= 96, SNNQP_EUNSUPPORTED, "dense mfma: T > 96");
-  const bool u8 = in_type == SNNQP_U8;
+int run_dense_mfma(const BlockCall &c) {
+  if (int rc = block_entry("dense mfma", c, true)) return rc < 0 ? rc : SNNQP_OK;
+  const int32_t T = c.T, B = c.B, N = c.N;
+  const bool u8 = c.in_type == SNNQP_U8;
   if (u8)
-    SNNQP_REQUIRE(((uintptr_t)x & 15) == 0 && xs_t % 16 == 0 && xs_b % 16 == 0, SNNQP_EUNSUPPORTED,
+    SNNQP_REQUIRE(((uintptr_t)c.x & 15) == 0 && c.xs_t % 16 == 0 && c.xs_b % 16 == 0, SNNQP_EUNSUPPORTED,
                   "dense mfma: uint8 rows must be 16-byte aligned");
   DenseMfmaArgs a;
-  a.x = (const uint32_t *)x; a.xs_t = xs_t; a.xs_b = xs_b;
-  a.col_sum = w->col_sum;
-  a.T = T; a.B = B; a.K = K; a.N = N; a.KS = (K + 31) / 32;
-  a.wt = wt;
-  a.dq = make_dequant(w->L, w->m);
-  a.bn = make_bn(bn); a.nrn = make_neuron(nrn);
-  a.u0 = u0; a.u_out = u_out; a.s_out = s_out;
+  fill_block_args(a, c);
+  a.K = c.K; a.N = N; a.KS = (c.K + 31) / 32;
+  a.wt = c.wt; a.col_sum = c.w->col_sum;
   const unsigned gy = (unsigned)((N + 127) / 128);
   // largest row tile that still gives the chip enough workgroups, else the
   // smallest one that holds a whole sample (most workgroups); uint8 rows: at most 64 rows
@@ -351,13 +349,13 @@ int run_dense_mfma(const void *x, int in_type, int64_t xs_t, int64_t xs_b, int32
   a.SB = rt * 32 / T;
   const unsigned gx = (unsigned)((B + a.SB - 1) / a.SB);
   if (u8) {
-    if (rt == 2) launch_dense<2, SNNQP_U8>(a, gx, gy, st);
-    else launch_dense<1, SNNQP_U8>(a, gx, gy, st);
+    if (rt == 2) launch_dense<2, SNNQP_U8>(a, gx, gy, c.st);
+    else launch_dense<1, SNNQP_U8>(a, gx, gy, c.st);
   } else {
     switch (rt) {
-      case 3: launch_dense<3, SNNQP_BITS>(a, gx, gy, st); break;
-      case 2: launch_dense<2, SNNQP_BITS>(a, gx, gy, st); break;
-      default: launch_dense<1, SNNQP_BITS>(a, gx, gy, st); break;
+      case 3: launch_dense<3, SNNQP_BITS>(a, gx, gy, c.st); break;
+      case 2: launch_dense<2, SNNQP_BITS>(a, gx, gy, c.st); break;
+      default: launch_dense<1, SNNQP_BITS>(a, gx, gy, c.st); break;
     }
   }
   SNNQP_CHECK_LAUNCH("dense_mfma_kernel");

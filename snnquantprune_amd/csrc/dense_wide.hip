@@ -738,24 +738,24 @@ static int pick_wide_rt(int T, int B, int CT, unsigned gy, int sph_cap, int *sph
   return best;
 }
 
-const char *dense_wide_unsupported(int in_type, int32_t T, int32_t K, int32_t N, int64_t xs_t,
-                                   int64_t xs_b, const void *x, const snnqp_weight_t *w,
-                                   const int8_t *wt, const snnqp_neuron_t *nrn, int s_type) {
-  // (float32 rows are staged as the uint8 ones are: the same requirements on K and col_sum)
-  const char *why = dense_mfma_unsupported(in_type == SNNQP_F32 ? SNNQP_U8 : in_type, K, N, w, wt, nrn, s_type);
-  if (why) return why;
-  if (T > 64) return "more than 64 timesteps (a sample must fit the rows of one lane half)";
-  if (N <= 128) return "at most 128 features: the 128-column kernel";
-  if (xs_t < 0 || xs_b < 0) return "negative strides";
-  if (in_type == SNNQP_U8 && ((((uintptr_t)x) & 15) != 0 || xs_t % 16 != 0 || xs_b % 16 != 0))
-    return "uint8 rows not 16-byte aligned";
-  if (in_type == SNNQP_F32 && ((((uintptr_t)x) & 15) != 0 || xs_t % 4 != 0 || xs_b % 4 != 0))
-    return "float32 rows not 16-byte aligned";
-  // 32-bit offsets from the workgroup's first sample (at most 128 samples)
-  if (((int64_t)(T - 1) * xs_t + 128 * xs_b + (in_type == SNNQP_BITS ? (K + 31) / 32 : K)) *
-          (in_type == SNNQP_F32 ? 4 : 1) >= ((int64_t)1 << 31))
-    return "input strides beyond 32-bit offsets within a workgroup";
+// float32 rows are staged as the uint8 ones are: the same requirements on K and col_sum
+static int staged_as(int in_type) { return in_type == SNNQP_F32 ? SNNQP_U8 : in_type; }
+
+// the rows of a workgroup, for the kernel alone and the fused head: at most 128 samples, 32-bit offsets
+static const char *wide_rows_unsupported(const BlockCall &c, int64_t extent) {
+  const int rows = dense_rows_broken(c, c.in_type, 128, c.T - 1, extent);
+  if (rows & ROWS_NEGATIVE) return "negative strides";
+  if (rows & ROWS_UNALIGNED) return c.in_type == SNNQP_U8 ? "uint8 rows not 16-byte aligned" : "float32 rows not 16-byte aligned";
+  if (c.in_type == SNNQP_F32 && !c.x_flags) return "float32 rows need x_flags";
+  if (rows & ROWS_REACH) return "input strides beyond 32-bit offsets within a workgroup";
   return nullptr;
+}
+
+const char *dense_wide_unsupported(const BlockCall &c) {
+  if (const char *why = dense_codes_unsupported(c, staged_as(c.in_type))) return why;
+  if (c.T > 64) return "more than 64 timesteps (a sample must fit the rows of one lane half)";
+  if (c.N <= 128) return "at most 128 features: the 128-column kernel";
+  return wide_rows_unsupported(c, c.in_type == SNNQP_BITS ? (c.K + 31) / 32 : c.K);
 }
 
 template <int RT, int CT, int IN, bool FUSE>
@@ -852,24 +852,18 @@ static int fill_and_launch(DenseWideArgs &a, int in_type, bool fuse, void *ws, i
   return SNNQP_OK;
 }
 
-int run_dense_wide(const void *x, int in_type, int64_t xs_t, int64_t xs_b, int32_t T, int32_t B,
-                   int32_t K, int32_t N, const snnqp_weight_t *w, const int8_t *wt,
-                   const snnqp_bn_t *bn, const snnqp_neuron_t *nrn, const float *u0,
-                   float *u_out, uint32_t *s_out, int32_t *x_flags, hipStream_t st) {
-  SNNQP_REQUIRE((x && s_out) || T == 0 || B == 0, SNNQP_EINVAL, "dense wide: null pointer");
-  SNNQP_REQUIRE(T >= 0 && B >= 0, SNNQP_EINVAL, "dense wide: negative T/B");
-  SNNQP_REQUIRE(w->L >= 1.0f, SNNQP_EINVAL, "dequant L must be >= 1");
-  SNNQP_CHECK_BN(bn);
-  if (T == 0 || B == 0) return SNNQP_OK;
+// the first block's fields of the argument struct (the fused head adds its second block)
+static void fill_wide_args(DenseWideArgs &a, const BlockCall &c) {
+  fill_block_args(a, c);
+  a.K = c.K; a.N = c.N; a.KS = (c.K + 31) / 32; a.KW = (c.K + 31) / 32;
+  a.wt = c.wt; a.col_sum = c.w->col_sum; a.x_flags = c.x_flags;
+}
+
+int run_dense_wide(const BlockCall &c) {
+  if (int rc = block_entry("dense wide", c, true)) return rc < 0 ? rc : SNNQP_OK;
   DenseWideArgs a = {};
-  a.x = x; a.xs_t = xs_t; a.xs_b = xs_b;
-  a.T = T; a.B = B; a.K = K; a.N = N; a.KS = (K + 31) / 32; a.KW = (K + 31) / 32;
-  a.wt = wt; a.col_sum = w->col_sum;
-  a.dq = make_dequant(w->L, w->m);
-  a.bn = make_bn(bn); a.nrn = make_neuron(nrn);
-  a.u0 = u0; a.u_out = u_out; a.s_out = s_out;
-  a.x_flags = x_flags;
-  return fill_and_launch(a, in_type, false, nullptr, 0, st);
+  fill_wide_args(a, c);
+  return fill_and_launch(a, c.in_type, false, nullptr, 0, c.st);
 }
 
 }  // namespace snnqp
@@ -886,11 +880,7 @@ extern "C" int snnqp_dense_head_forward(const void *x, int in_type, int64_t x_st
   using namespace snnqp;
   SNNQP_REQUIRE(w1 && w2 && nrn1 && nrn2 && ((x && logits) || T == 0 || B == 0), SNNQP_EINVAL,
                 "dense_head_forward: null argument");
-  if (const uint32_t code = device_status_read(stream_device((hipStream_t)stream))) {
-    set_error("dense_head_forward: device status 0x%x: %s (snnqp_device_status(..., reset = 1) clears it)",
-              (unsigned)code, device_status_text(code));
-    return SNNQP_EHIP;
-  }
+  if (int rc = refuse_after_device_report((hipStream_t)stream, "dense_head_forward")) return rc;
   SNNQP_REQUIRE(T >= 0 && B >= 0 && K > 0 && N1 > 0 && N2 > 0 && group > 0, SNNQP_EINVAL,
                 "dense_head_forward: bad sizes");
   SNNQP_REQUIRE(N2 % group == 0, SNNQP_EINVAL, "dense_head_forward: N2=%d not divisible by group=%d", N2, group);
@@ -898,41 +888,27 @@ extern "C" int snnqp_dense_head_forward(const void *x, int in_type, int64_t x_st
     SNNQP_REQUIRE(nr->kind >= SNNQP_NEURON_MULTI_STEP_LIF && nr->kind <= SNNQP_NEURON_LIF, SNNQP_EINVAL,
                   "dense_head_forward: unknown neuron kind %d", nr->kind);
   SNNQP_REQUIRE(w1->L >= 1.0f && w2->L >= 1.0f, SNNQP_EINVAL, "dequant L must be >= 1");
+  // the two blocks as two requests: the first reads the caller's rows, the second the hidden raster
+  BlockCall c1, c2;
+  c1.x = x; c1.in_type = in_type; c1.xs_t = x_stride_t; c1.xs_b = x_stride_b; c1.T = T; c1.B = B;
+  c1.K = K; c1.N = N1; c1.w = w1; c1.wt = wt1; c1.nrn = nrn1; c1.s_out = s1_out; c1.x_flags = x_flags;
+  c2.K = N1; c2.N = N2; c2.w = w2; c2.wt = wt2; c2.nrn = nrn2;
   const char *why = nullptr;
   if (N1 > 512) why = "more than 512 hidden features";
   else if (N2 > 128) why = "more than 128 output features";
   else if (T > 64) why = "more than 64 timesteps";
   else if (T < 1) why = "no timestep";
-  if (!why) {
-    // (the 128-feature floor of the stand-alone wide kernel does not apply to the fused head)
-    why = dense_mfma_unsupported(in_type == SNNQP_F32 ? SNNQP_U8 : in_type, K, N1, w1, wt1, nrn1, SNNQP_BITS);
-    if (!why) why = dense_mfma_unsupported(SNNQP_BITS, N1, N2, w2, wt2, nrn2, SNNQP_BITS);
-    if (!why && (x_stride_t < 0 || x_stride_b < 0)) why = "negative strides";
-    if (!why && in_type == SNNQP_U8 &&
-        ((((uintptr_t)x) & 15) != 0 || x_stride_t % 16 != 0 || x_stride_b % 16 != 0))
-      why = "uint8 rows not 16-byte aligned";
-    if (!why && in_type == SNNQP_F32 &&
-        ((((uintptr_t)x) & 15) != 0 || x_stride_t % 4 != 0 || x_stride_b % 4 != 0))
-      why = "float32 rows not 16-byte aligned";
-    if (!why && in_type == SNNQP_F32 && !x_flags) why = "float32 rows need x_flags";
-    if (!why && ((int64_t)(T - 1) * x_stride_t + 128 * x_stride_b + K) * (in_type == SNNQP_F32 ? 4 : 1) >=
-                    ((int64_t)1 << 31))
-      why = "input strides beyond 32-bit offsets within a workgroup";
-  }
+  // (the stand-alone kernel's 128-feature floor does not apply; every row, a bit row too, counts K units)
+  if (!why) why = dense_codes_unsupported(c1, staged_as(in_type));
+  if (!why) why = dense_codes_unsupported(c2, SNNQP_BITS);
+  if (!why) why = wide_rows_unsupported(c1, K);
   SNNQP_REQUIRE(!why, SNNQP_EUNSUPPORTED, "dense_head_forward: %s", why);
   if (B == 0) return SNNQP_OK;
   DenseWideArgs a = {};
-  a.x = x; a.xs_t = x_stride_t; a.xs_b = x_stride_b;
-  a.T = T; a.B = B; a.K = K; a.N = N1; a.KS = (K + 31) / 32; a.KW = (K + 31) / 32;
-  a.wt = wt1; a.col_sum = w1->col_sum;
-  a.dq = make_dequant(w1->L, w1->m);
-  a.bn = make_bn(nullptr); a.bn.mean = nullptr;
-  a.nrn = make_neuron(nrn1);
-  a.s_out = s1_out;
+  fill_wide_args(a, c1);
   a.N2 = N2; a.KS2 = (N1 + 31) / 32; a.group = group;
   a.wt2 = wt2; a.dq2 = make_dequant(w2->L, w2->m); a.nrn2 = make_neuron(nrn2);
   a.s2_out = s2_out; a.logits = logits;
-  a.x_flags = x_flags;
   return fill_and_launch(a, in_type, true, ws, ws_bytes, (hipStream_t)stream);
 }
 

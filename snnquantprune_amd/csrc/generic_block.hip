@@ -205,24 +205,24 @@ int check_geom(const snnqp_conv_geom_t *g, int32_t *OH, int32_t *OW) {
 }
 
 // Shared by snnqp_conv_forward / snnqp_conv_lif_forward / snnqp_dense_lif_forward.
-int run_generic(const void *x, int in_type, int64_t xs_t, int64_t xs_b, int32_t T,
-                int32_t B, const snnqp_conv_geom_t *g, const snnqp_weight_t *w,
-                const snnqp_bn_t *bn, const snnqp_neuron_t *nrn, const float *u0,
-                float *u_out, void *s_out, int s_type, int32_t *acc_out,
-                hipStream_t st, int pool, const int32_t *pred, const GenericDepth *dz) {
+int run_generic(const BlockCall &c, int32_t *acc_out, const GenericDepth *dz) {
+  const snnqp_conv_geom_t *g = c.g;
+  const snnqp_weight_t *w = c.w;
+  const int32_t T = c.T, B = c.B, in_type = c.in_type, s_type = c.s_type, pool = c.pool;
   int32_t OH, OW;
   int rc = check_geom(g, &OH, &OW);
   if (rc) return rc;
   SNNQP_REQUIRE(!dz || pool == 1, SNNQP_EINVAL, "generic block: the fused pool is 2-D");
-  SNNQP_REQUIRE(pool == 1 || (pool == 2 && nrn && nrn->kind != SNNQP_NEURON_NONE), SNNQP_EINVAL,
+  SNNQP_REQUIRE(pool == 1 || (pool == 2 && c.nrn && c.nrn->kind != SNNQP_NEURON_NONE), SNNQP_EINVAL,
                 "generic block: pool must be 1, or 2 with a neuron");
-  SNNQP_REQUIRE(w && w->w && ((x && s_out) || T == 0 || B == 0), SNNQP_EINVAL, "generic block: null pointer");
+  SNNQP_REQUIRE(w && w->w && ((c.x && c.s_out) || T == 0 || B == 0), SNNQP_EINVAL, "generic block: null pointer");
   SNNQP_REQUIRE(T >= 0 && B >= 0, SNNQP_EINVAL, "generic block: negative T/B");
   GenericArgs a;
-  a.x = x; a.xs_t = xs_t; a.xs_b = xs_b; a.T = T; a.B = B; a.g = *g;
+  fill_block_args(a, c);
+  a.g = *g;
   a.FH = OH; a.FW = OW;
   a.OH = OH / pool; a.OW = OW / pool;
-  a.pred = pred;
+  a.pred = c.pred;
   a.D = dz ? dz->D : 1; a.KD = dz ? dz->KD : 1; a.OD = dz ? dz->OD : 1;
   a.stride_d = dz ? dz->stride : 1; a.pad_d_lo = dz ? dz->pad_lo : 0;
   a.in_dil_d = dz ? dz->in_dil : 1; a.k_dil_d = dz ? dz->k_dil : 1;
@@ -232,19 +232,16 @@ int run_generic(const void *x, int in_type, int64_t xs_t, int64_t xs_b, int32_t 
   a.CinG = g->Cin / g->groups; a.CoutG = g->Cout / g->groups;
   a.CWin = (g->Cin + 31) / 32;
   a.w = w->w;
-  a.dq = make_dequant(w->wtype == SNNQP_W_I8 ? w->L : 1.0f,
-                      w->wtype == SNNQP_W_I8 ? w->m : 1.0f);
-  a.bn = make_bn(bn); a.nrn = make_neuron(nrn);
-  a.u0 = u0; a.u_out = u_out; a.s_out = s_out; a.s_type = s_type;
+  a.s_type = s_type;
   a.acc_out = acc_out;
   a.WH = a.OH; a.WW = a.OW;
-  if (pool == 2 && u_out) { a.WH = (OH + 1) / 2; a.WW = (OW + 1) / 2; }
+  if (pool == 2 && c.u_out) { a.WH = (OH + 1) / 2; a.WW = (OW + 1) / 2; }
   a.total_out = (int64_t)B * a.OD * a.OH * a.OW * g->Cout;
   a.total = (int64_t)B * a.OD * a.WH * a.WW * g->Cout;
   if (a.total == 0 || T == 0) return SNNQP_OK;
   if (a.nrn.kind == SNNQP_NEURON_LIF)
     SNNQP_REQUIRE(a.nrn.decay, SNNQP_EINVAL, "LIF neuron needs a decay vector");
-  SNNQP_CHECK_BN(bn);
+  SNNQP_CHECK_BN(c.bn);
   if (a.nrn.kind != SNNQP_NEURON_NONE) {
     SNNQP_REQUIRE(s_type == SNNQP_F32 || s_type == SNNQP_BITS, SNNQP_EINVAL,
                   "spike output type must be F32 or BITS");
@@ -268,17 +265,17 @@ int run_generic(const void *x, int in_type, int64_t xs_t, int64_t xs_b, int32_t 
   if (a.nrn.kind != SNNQP_NEURON_NONE && s_type == SNNQP_BITS && (g->Cout & 31) != 0) {
     const int64_t words = (int64_t)T * B * a.OD * a.OH * a.OW * ((g->Cout + 31) / 32);
     const int64_t zb = (words + 255) / 256;
-    hipLaunchKernelGGL(zero_words_if_kernel, dim3((unsigned)(zb < 4096 ? zb : 4096)), dim3(256), 0, st,
-                       pred, (uint32_t *)s_out, words);
+    hipLaunchKernelGGL(zero_words_if_kernel, dim3((unsigned)(zb < 4096 ? zb : 4096)), dim3(256), 0, c.st,
+                       c.pred, (uint32_t *)c.s_out, words);
     SNNQP_CHECK_LAUNCH("zero_words_if_kernel");
   }
   if (intpath)
-    return in_type == SNNQP_U8 ? launch_generic<SNNQP_U8, true>(a, pool, st)
-                               : launch_generic<SNNQP_BITS, true>(a, pool, st);
+    return in_type == SNNQP_U8 ? launch_generic<SNNQP_U8, true>(a, pool, c.st)
+                               : launch_generic<SNNQP_BITS, true>(a, pool, c.st);
   switch (in_type) {
-    case SNNQP_F32: return launch_generic<SNNQP_F32, false>(a, pool, st);
-    case SNNQP_U8: return launch_generic<SNNQP_U8, false>(a, pool, st);
-    case SNNQP_BITS: return launch_generic<SNNQP_BITS, false>(a, pool, st);
+    case SNNQP_F32: return launch_generic<SNNQP_F32, false>(a, pool, c.st);
+    case SNNQP_U8: return launch_generic<SNNQP_U8, false>(a, pool, c.st);
+    case SNNQP_BITS: return launch_generic<SNNQP_BITS, false>(a, pool, c.st);
   }
   set_error("unknown input type %d", in_type);
   return SNNQP_EINVAL;
@@ -303,8 +300,9 @@ extern "C" int snnqp_conv_forward(const void *x, int in_type, int64_t NB,
     return run_fseq_gemm(x, in_type, NB, g, w, y, (hipStream_t)stream);
   }
   // the NB images are the "batch"; T = 1
-  return run_generic(x, in_type, 0, img, 1, (int32_t)NB, g, w, nullptr, nullptr,
-                     nullptr, nullptr, y, SNNQP_F32, acc, (hipStream_t)stream);
+  const BlockCall c{x, in_type, 0, img, 1, (int32_t)NB, w, nullptr, nullptr, nullptr, nullptr, nullptr, y,
+                    SNNQP_F32, nullptr, nullptr, (hipStream_t)stream, g};
+  return run_generic(c, acc, nullptr);
 }
 
 // Which kernel snnqp_conv_forward(x, in_type, NB, g, w, y, acc = NULL) runs (snnqp.h): the same
@@ -359,8 +357,9 @@ extern "C" int snnqp_conv_forward_if(const int32_t *pred, const void *x, int in_
   if (int rc = refuse_after_device_report((hipStream_t)stream, "conv_forward_if")) return rc;
   const int64_t pix = (in_type == SNNQP_BITS) ? (g->Cin + 31) / 32 : g->Cin;
   const int64_t img = (int64_t)g->H * g->W * pix;
-  return run_generic(x, in_type, 0, img, 1, (int32_t)NB, g, w, nullptr, nullptr, nullptr, nullptr, y,
-                     SNNQP_F32, nullptr, (hipStream_t)stream, 1, pred);
+  const BlockCall c{x, in_type, 0, img, 1, (int32_t)NB, w, nullptr, nullptr, nullptr, nullptr, nullptr, y,
+                    SNNQP_F32, nullptr, pred, (hipStream_t)stream, g};
+  return run_generic(c, nullptr, nullptr);
 }
 
 // ---- 3-D convolutions (flax_qconv.py:93-171 with three spatial axes) --------------------------
@@ -410,6 +409,7 @@ extern "C" int snnqp_conv3d_lif_forward(const int32_t *pred, const void *x, int 
   if (int rc = refuse_after_device_report((hipStream_t)stream, "conv3d_lif_forward")) return rc;
   SNNQP_REQUIRE(!nrn || (nrn->kind >= SNNQP_NEURON_NONE && nrn->kind <= SNNQP_NEURON_LIF), SNNQP_EINVAL,
                 "conv3d_lif_forward: unknown neuron kind %d", nrn ? nrn->kind : -1);
-  return run_generic(x, in_type, x_stride_t, x_stride_b, T, B, &g, w, bn, nrn, u0, u_out, s_out, s_type,
-                     nullptr, (hipStream_t)stream, 1, pred, &dz);
+  const BlockCall c{x, in_type, x_stride_t, x_stride_b, T, B, w, nullptr, bn, nrn, u0, u_out, s_out, s_type,
+                    nullptr, pred, (hipStream_t)stream, &g};
+  return run_generic(c, nullptr, &dz);
 }

@@ -5,22 +5,59 @@
 
 namespace snnqp {
 
+// What an entry point of a fused block received (include/snnqp.h names every item), initialised in
+// place by the extern "C" function and handed down by reference: the predicates read it, the run_*
+// functions check it (block_entry) and copy it into their kernel's arguments (fill_block_args).
+struct BlockCall {
+  const void *x = nullptr;
+  int in_type = SNNQP_BITS;
+  int64_t xs_t = 0, xs_b = 0;
+  int32_t T = 0, B = 0;
+  const snnqp_weight_t *w = nullptr;
+  const int8_t *wt = nullptr;
+  const snnqp_bn_t *bn = nullptr;
+  const snnqp_neuron_t *nrn = nullptr;
+  const float *u0 = nullptr;
+  float *u_out = nullptr;
+  void *s_out = nullptr;
+  int s_type = SNNQP_BITS;
+  int32_t *x_flags = nullptr;
+  const int32_t *pred = nullptr;
+  hipStream_t st = nullptr;
+  const snnqp_conv_geom_t *g = nullptr;      // conv blocks: g, pool, x_max, x_seen
+  int pool = 1, x_max = 0;
+  int32_t *x_seen = nullptr;
+  int32_t K = 0, N = 0;                      // dense blocks: K, N and the workspace
+  void *ws = nullptr;
+  int64_t ws_bytes = 0;
+};
+// The first checks of a fused kernel's run_* function, in this order: buffers (`ptrs`: the kernel's
+// own) unless the batch is empty, T and B not negative, L >= 1, a sound BatchNorm descriptor.  SNNQP_OK,
+// BLOCK_EMPTY (nothing to launch: the caller returns SNNQP_OK) or the refusal, opened by `who`.
+constexpr int BLOCK_EMPTY = 1;
+int block_entry(const char *who, const BlockCall &c, bool ptrs);
+// the fields every fused kernel's arguments have (float32 kernels, direct form only: L = m = 1)
+template <typename A>
+void fill_block_args(A &a, const BlockCall &c) {
+  const bool codes = c.w->wtype == SNNQP_W_I8;
+  a.x = (decltype(a.x))c.x; a.xs_t = c.xs_t; a.xs_b = c.xs_b; a.T = c.T; a.B = c.B;
+  a.dq = make_dequant(codes ? c.w->L : 1.0f, codes ? c.w->m : 1.0f);
+  a.bn = make_bn(c.bn); a.nrn = make_neuron(c.nrn);
+  a.u0 = c.u0; a.u_out = c.u_out; a.s_out = (decltype(a.s_out))c.s_out;
+}
+
 // depth axis of a 3-D convolution for the direct-form kernel (OD resolved by the caller)
 struct GenericDepth {
   int32_t D, KD, OD, stride, pad_lo, in_dil, k_dil;
 };
-int run_generic(const void *x, int in_type, int64_t xs_t, int64_t xs_b, int32_t T,
-                int32_t B, const snnqp_conv_geom_t *g, const snnqp_weight_t *w,
-                const snnqp_bn_t *bn, const snnqp_neuron_t *nrn, const float *u0,
-                float *u_out, void *s_out, int s_type, int32_t *acc_out,
-                hipStream_t st, int pool = 1, const int32_t *pred = nullptr,
-                const GenericDepth *dz = nullptr);
+// the direct-form kernel on c.g (nullable: int32 accumulators of the no-neuron form, depth axis)
+int run_generic(const BlockCall &c, int32_t *acc_out, const GenericDepth *dz);
 
+// the geometry both 3x3 MFMA conv predicates below ask for (conv3x3_mfma.hip)
+const char *conv3x3_geometry_unsupported(const snnqp_conv_geom_t *g);
 // nullptr when a fused 3x3 MFMA kernel can serve the request, else the reason; run_conv3x3_mfma
 // below checks the launch and hands it to the kernel of its input format (conv3x3_mfma.hip).
-const char *conv3x3_mfma_unsupported(int in_type, const snnqp_conv_geom_t *g,
-                                     const snnqp_weight_t *w, const int8_t *wt,
-                                     const snnqp_neuron_t *nrn, int s_type);
+const char *conv3x3_mfma_unsupported(const BlockCall &c);
 // The same for the currents form of the bit-input 3x3 conv (conv3x3_currents.hip): the connection
 // alone, NB images, float32 currents (and nullable int32 accumulators) out.
 const char *conv3x3_currents_unsupported(int in_type, int64_t NB, const snnqp_conv_geom_t *g,
@@ -36,13 +73,7 @@ int conv3x3_bits_dequant_form(const snnqp_weight_t *w, const snnqp_neuron_t *nrn
 // snnqp_conv_event_half_group: 1 / 0, or a negative error (conv3x3_u8c2.hip)
 int conv3x3_event_half_group(int in_type, int32_t T, const snnqp_conv_geom_t *g, const snnqp_weight_t *w,
                              const snnqp_neuron_t *nrn, bool has_state, int pool, int x_max);
-int run_conv3x3_mfma(const void *x, int in_type, int64_t xs_t, int64_t xs_b,
-                     int32_t T, int32_t B, const snnqp_conv_geom_t *g,
-                     const snnqp_weight_t *w, const int8_t *wt,
-                     const snnqp_bn_t *bn, const snnqp_neuron_t *nrn,
-                     const float *u0, float *u_out, uint32_t *s_out, int pool,
-                     int x_max, int32_t *x_seen, int32_t *x_flags, hipStream_t st,
-                     const int32_t *pred = nullptr);
+int run_conv3x3_mfma(const BlockCall &c);
 
 // per-device state and helpers (runtime.hip): the status word kernels report broken invariants
 // into, the probe of the matrix pipe's denormal arithmetic behind DQ_TABLE
@@ -100,35 +131,33 @@ FseqForm fseq_gemm_form(const void *x, int in_type, int64_t NB, const snnqp_conv
 int run_fseq_gemm(const void *x, int in_type, int64_t NB, const snnqp_conv_geom_t *g,
                   const snnqp_weight_t *w, float *y, hipStream_t st);
 
-const char *dense_mfma_unsupported(int in_type, int32_t K, int32_t N,
-                                   const snnqp_weight_t *w, const int8_t *wt,
-                                   const snnqp_neuron_t *nrn, int s_type);
-int run_dense_mfma(const void *x, int in_type, int64_t xs_t, int64_t xs_b, int32_t T, int32_t B,
-                   int32_t K, int32_t N, const snnqp_weight_t *w, const int8_t *wt,
-                   const snnqp_bn_t *bn, const snnqp_neuron_t *nrn, const float *u0,
-                   float *u_out, uint32_t *s_out, hipStream_t st);
+// The row rules of the dense MFMA kernels, as a mask of the broken ones: strides not negative; uint8 /
+// float32 rows 16-byte aligned; the offsets of one workgroup (`steps` timestep and `samples` sample
+// strides, a row of `extent` units; float32: in bytes) below 2^31.  The caller words the refusal.
+enum { ROWS_NEGATIVE = 1, ROWS_UNALIGNED = 2, ROWS_REACH = 4 };
+int dense_rows_broken(const BlockCall &c, int in_type, int samples, int64_t steps, int64_t extent);
+
+// codes, formats and neuron as every int8 dense MFMA kernel needs them, for rows staged as `in_type`
+const char *dense_codes_unsupported(const BlockCall &c, int in_type);
+// 128 columns per workgroup (dense_mfma.hip): the above, T and the rows; nullptr when it can serve
+const char *dense_mfma_unsupported(const BlockCall &c);
+int run_dense_mfma(const BlockCall &c);
 
 // all the columns of a 256 / 512-column block per workgroup, neuron from the accumulator
 // registers (dense_wide.hip); nullptr when it can serve the request
-const char *dense_wide_unsupported(int in_type, int32_t T, int32_t K, int32_t N, int64_t xs_t,
-                                   int64_t xs_b, const void *x, const snnqp_weight_t *w,
-                                   const int8_t *wt, const snnqp_neuron_t *nrn, int s_type);
-int run_dense_wide(const void *x, int in_type, int64_t xs_t, int64_t xs_b, int32_t T, int32_t B,
-                   int32_t K, int32_t N, const snnqp_weight_t *w, const int8_t *wt,
-                   const snnqp_bn_t *bn, const snnqp_neuron_t *nrn, const float *u0,
-                   float *u_out, uint32_t *s_out, int32_t *x_flags, hipStream_t st);
+const char *dense_wide_unsupported(const BlockCall &c);
+int run_dense_wide(const BlockCall &c);
 
 // 3x3 convolution on gate x raster (conv_gated.hip); nullptr when it can serve the request
 const char *conv_gated_unsupported(const snnqp_conv_geom_t *g, const snnqp_weight_t *w);
 // dense connection on the channel-major flattening of gate x raster (dense_gated.hip)
 const char *dense_gated_unsupported(int32_t HW, int32_t C, int32_t N, const snnqp_weight_t *w);
 
-// codes of magnitude <= 7 on the f8f6f4 MFMA (dense_fp6.hip); row_tiles 0 = choose
-// (ws / ws_bytes: optional workspace for a K split over workgroups, dense_fp6_workspace_bytes)
-int run_dense_fp6(const void *x, int64_t xs_t, int64_t xs_b, int32_t T, int32_t B, int32_t K,
-                  int32_t N, const snnqp_weight_t *w, const snnqp_bn_t *bn,
-                  const snnqp_neuron_t *nrn, const float *u0, float *u_out, uint32_t *s_out,
-                  int row_tiles, void *ws, int64_t ws_bytes, hipStream_t st);
+// codes of magnitude <= 7 on the f8f6f4 MFMA (dense_fp6.hip); the first predicate is the part a size
+// query knows (snnqp_dense_workspace_bytes); c.ws: optional workspace for a K split over workgroups
+const char *dense_fp6_unsupported(int in_type, int32_t K, int32_t N, const snnqp_weight_t *w);
+const char *dense_fp6_unsupported(const BlockCall &c);
+int run_dense_fp6(const BlockCall &c);
 int64_t dense_fp6_workspace_bytes(int32_t T, int32_t B, int32_t K, int32_t N);
 
 }  // namespace snnqp
