@@ -244,7 +244,8 @@ typedef struct {
  * compatible: snnqp_weight_t.cout_fire in the struct's former tail padding,
  * snnqp_set_event_half_group, snnqp_conv_event_half_group; training of CextNet's gated stages --
  * snnqp_gate_pool_grad_gate, snnqp_gate_pool_grad_input, snnqp_conv_weight_grad_f64,
- * snnqp_conv_weight_grad_f64_workspace_bytes; the batched event front end snnqp_events_bin; the host-side
+ * snnqp_conv_weight_grad_f64_workspace_bytes; the batched event front end snnqp_events_bin and its augmenting
+ * form snnqp_events_bin_aug with snnqp_event_aug_t; the host-side
  * query snnqp_conv_float_form; the host-side plan queries snnqp_conv_gated_plan,
  * snnqp_dense_gated_plan, snnqp_dense_wide_plan: new entry points, nothing else moves).
  * A binding compares snnqp_version()
@@ -834,6 +835,44 @@ int snnqp_events_bin(const uint32_t *addr, const int32_t *times, const int64_t *
                      const int32_t *sample, const int32_t *start, int32_t B, int mode, int32_t T,
                      int32_t step_us, int32_t H, int32_t W, float scale,
                      void *out, int out_type, int32_t *flags, snnqp_stream_t stream);
+/* One row's event augmentation for snnqp_events_bin_aug: 48 bytes, a device array of B records. */
+typedef struct snnqp_event_aug {
+  uint32_t flags;                              /* bit 0 flip x, bit 1 flip y, bit 2 swap polarity; other bits 0 */
+  int32_t dx, dy;                              /* |dx|, |dy| <= 16384 */
+  int32_t cut_x0, cut_y0, cut_x1, cut_y1;      /* half-open, frame pixels */
+  int32_t f0, f1;                              /* frames [f0, f1) come out empty */
+  uint32_t drop_below, seed, reserved;         /* reserved = 0 */
+} snnqp_event_aug_t;
+/* replaces: nothing in the reference (it trains on the recordings as they are); the usual event
+ *           augmentations -- flips, translation, cutout, EventDrop's random / area / time drops,
+ *           polarity swap -- as per-event decisions inside snnqp_events_bin's launch.
+ * Arguments, checks (SNNQP_EINVAL, on the host, before anything is launched), formats and flags are
+ * snnqp_events_bin's; aug == NULL is exactly snnqp_events_bin.
+ * aug     [B] records on the device, 4-byte aligned; row b is decoded under aug[b]
+ * A frame f of row b with f0 <= f < f1 is all zero.  Every other frame takes the slice
+ * snnqp_events_bin gives it -- that of the untouched sample: number mode cuts equal counts over all
+ * its events, time mode searches the same times -- and passes each event through, in this order:
+ *   1. x' = floor(float(x) / scale), the same for y; outside [0, W) x [0, H): dropped
+ *   2. flip:   x = W - 1 - x (bit 0), y = H - 1 - y (bit 1)
+ *   3. shift:  x += dx, y += dy; outside the frame: dropped (zero fill, no wrap-around)
+ *   4. cutout: dropped if cut_x0 <= x < cut_x1 and cut_y0 <= y < cut_y1 (final frame pixels; empty
+ *      when cut_x1 <= cut_x0 or cut_y1 <= cut_y0)
+ *   5. drop:   dropped if fmix32(fmix32(seed) ^ (uint32_t)i) < drop_below (0: nothing is dropped;
+ *      2^32 - 1: all but the events whose hash is 2^32 - 1), i the event's index within its sample
+ *      (0 for the sample's first event), low 32 bits, and fmix32 the murmur3 finaliser in 32-bit
+ *      unsigned arithmetic:  h ^= h >> 16; h *= 0x85EBCA6B; h ^= h >> 13; h *= 0xC2B2AE35; h ^= h >> 16
+ *   6. swap:   with bit 2 an event of polarity 0 counts in channel 1 and the reverse
+ *   7. counted as snnqp_events_bin counts it: exact before it saturates, the same flags.
+ * Integer adds commute: two launches give the same bytes.
+ * The records live on the device, so nothing in them is checked.  Out of range they do this and no
+ * more: the shift is added modulo 2^32, so |dx| >= W or |dy| >= H drops every event of the row;
+ * the rectangle and [f0, f1) are compared as signed 32-bit values, whatever they hold; bits 3..31
+ * of flags and `reserved` are ignored.  Whatever the records hold, the launch reads aug[0 .. B - 1]
+ * and the events snnqp_events_bin would read, and writes `out` and `flags` only. */
+int snnqp_events_bin_aug(const uint32_t *addr, const int32_t *times, const int64_t *offsets, int32_t S,
+                         const int32_t *sample, const int32_t *start, int32_t B, int mode, int32_t T,
+                         int32_t step_us, int32_t H, int32_t W, float scale, const snnqp_event_aug_t *aug,
+                         void *out, int out_type, int32_t *flags, snnqp_stream_t stream);
 /* replaces: the activation-density probes sown at examples/tcja/models.py:128-142
  *           (consumed by examples/sparsity.py:143-170): non-zero count of each of
  *           NB slices of n elements (C innermost; F32, U8 or BITS). */

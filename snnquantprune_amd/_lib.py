@@ -178,6 +178,9 @@ _PROTOTYPES = {
     "snnqp_events_bin": (c_int, [c_void_p, c_void_p, c_void_p, c_int32, c_void_p, c_void_p, c_int32, c_int,
                                  c_int32, c_int32, c_int32, c_int32, c_float, c_void_p, c_int, c_void_p,
                                  c_void_p]),
+    "snnqp_events_bin_aug": (c_int, [c_void_p, c_void_p, c_void_p, c_int32, c_void_p, c_void_p, c_int32, c_int,
+                                     c_int32, c_int32, c_int32, c_int32, c_float, c_void_p, c_void_p, c_int,
+                                     c_void_p, c_void_p]),
     "snnqp_density": (c_int, [c_void_p, c_int, c_int64, c_int64, c_int32, c_void_p, c_void_p]),
     "snnqp_vote": (c_int, [c_void_p, c_int, c_int32, c_int32, c_int32, c_int32,
                            c_void_p, c_void_p]),

@@ -17,10 +17,18 @@
 // 16-bit halves stay exact because the slice is walked in chunks of 65 280 events with a clamp
 // of every half to 255 between chunks: min(min(a, 255) + b, 255) = min(a + b, 255), and every
 // format saturates at or below 255 and flags above 15 / above 1, which the clamp preserves.
+//
+// AUG (snnqp_events_bin_aug): the row's snnqp_event_aug_t record, read once per
+// workgroup (b is uniform: scalar loads), turns every event's decode into flip, shift, cutout,
+// hashed drop and polarity swap before the same LDS add -- per-event integer decisions on values
+// the lane already holds.  The slice, the searches, the chunks and the clamp are those of the
+// untouched sample (the clamp then counts walked events, dropped ones included: only more
+// conservative); a frame the record empties walks nothing and writes its zero band.
 #include "kernels.h"
 
 #include <cmath>
 #include <mutex>
+#include <type_traits>
 
 namespace snnqp {
 
@@ -41,6 +49,12 @@ struct EventsBinArgs {
   float scale;
   int32_t S, T, step_us, H, W, mode, nbands;
 };
+// the augmenting kernel's: the plain kernel keeps the argument block it had
+struct EventsBinAugArgs : EventsBinArgs {
+  const snnqp_event_aug_t *aug;
+};
+template <bool AUG>
+using EventsBinKernelArgs = std::conditional_t<AUG, EventsBinAugArgs, EventsBinArgs>;
 
 // First index i of [a, b) with times[i] > key (STRICT) or >= key: every round the wave probes 64
 // evenly spaced elements and keeps the stretch in front of the first that satisfies the test.
@@ -68,9 +82,19 @@ __device__ __forceinline__ int64_t first_index(const int32_t *__restrict__ times
 
 __device__ __forceinline__ uint32_t sat_half(uint32_t v, uint32_t cap) { return v < cap ? v : cap; }
 
-template <int OUT>
+// the murmur3 finaliser (include/snnqp.h states it as part of snnqp_events_bin_aug's contract)
+__device__ __forceinline__ uint32_t fmix32(uint32_t h) {
+  h ^= h >> 16;
+  h *= 0x85EBCA6Bu;
+  h ^= h >> 13;
+  h *= 0xC2B2AE35u;
+  h ^= h >> 16;
+  return h;
+}
+
+template <int OUT, bool AUG>
 __global__ void __launch_bounds__(512)
-events_bin_kernel(const EventsBinArgs a) {
+events_bin_kernel(const EventsBinKernelArgs<AUG> a) {
   extern __shared__ __attribute__((aligned(16))) uint32_t hist[];
   __shared__ int64_t range[2];
   const int tid = threadIdx.x, nth = blockDim.x, lane = tid & 63, wave = tid >> 6;
@@ -86,10 +110,20 @@ events_bin_kernel(const EventsBinArgs a) {
 
   for (int i = tid * 4; i < nalloc; i += nth * 4) *(v4u *)(hist + i) = (v4u){0, 0, 0, 0};
 
+  // the row's record; a frame it empties keeps o0 = o1 = 0: no search round, no walk, a zero band
+  snnqp_event_aug_t g = {};
+  bool live = true;
+  uint32_t hseed = 0;
+  if constexpr (AUG) {
+    g = a.aug[b];
+    live = !(f >= g.f0 && f < g.f1);
+    hseed = fmix32(g.seed);
+  }
+
   // the sample's events, then the frame's slice of them
   const int32_t s = a.sample[b];
   int64_t o0 = 0, o1 = 0;
-  if (s >= 0 && s < a.S) {
+  if (s >= 0 && s < a.S && live) {
     o0 = a.offsets[s];
     o1 = a.offsets[s + 1];
     if (o1 < o0) o1 = o0;
@@ -115,17 +149,30 @@ events_bin_kernel(const EventsBinArgs a) {
   const bool unit = a.scale == 1.0f;
   const float scale = a.scale;
   const int32_t H = a.H, W = a.W;
-  auto one = [&](uint32_t w) {
+  // n: the event's index in the stream (AUG: its index within the sample is what the drop hashes)
+  auto one = [&](uint32_t w, int64_t n) {
     int32_t x = (int32_t)(w & 0x3FFFu), y = (int32_t)((w >> 14) & 0x3FFFu);
     if (!unit) {
       x = (int32_t)fminf(floorf((float)x / scale), 65536.0f);
       y = (int32_t)fminf(floorf((float)y / scale), 65536.0f);
     }
     if (x >= W || y >= H) return;                       // (never negative: scale > 0)
+    if constexpr (AUG) {
+      if (g.flags & 1u) x = W - 1 - x;
+      if (g.flags & 2u) y = H - 1 - y;
+      // the shift in unsigned arithmetic, so that no record overflows: a dx outside (-W, W) lands
+      // outside [0, W) modulo 2^32 as well.  One unsigned test per axis catches the negatives.
+      x = (int32_t)((uint32_t)x + (uint32_t)g.dx);
+      y = (int32_t)((uint32_t)y + (uint32_t)g.dy);
+      if ((uint32_t)x >= (uint32_t)W || (uint32_t)y >= (uint32_t)H) return;
+      if (x >= g.cut_x0 && x < g.cut_x1 && y >= g.cut_y0 && y < g.cut_y1) return;
+      if (fmix32(hseed ^ (uint32_t)(n - o0)) < g.drop_below) return;
+      w ^= (g.flags & 4u) << 26;                        // bit 2 onto the polarity, bit 28
+    }
     const uint32_t pb = (uint32_t)(y * W + x - p0);
     if (pb < (uint32_t)np) atomicAdd(&hist[pb], (w >> 28) & 1u ? 0x10000u : 1u);
   };
-  auto four = [&](const v4u &w) { one(w.x); one(w.y); one(w.z); one(w.w); };
+  auto four = [&](const v4u &w, int64_t n) { one(w.x, n); one(w.y, n + 1); one(w.z, n + 2); one(w.w, n + 3); };
 
   for (int64_t c0 = e0; c0 < e1; c0 += EB_CHUNK) {
     const int64_t c1 = c0 + EB_CHUNK < e1 ? c0 + EB_CHUNK : e1;
@@ -133,19 +180,19 @@ events_bin_kernel(const EventsBinArgs a) {
     int64_t h = c0 + ((4 - (int)(((uintptr_t)(a.addr + c0) >> 2) & 3)) & 3);
     if (h > c1) h = c1;
     const int64_t nv = (c1 - h) >> 2;
-    if (c0 + tid < h) one(a.addr[c0 + tid]);
+    if (c0 + tid < h) one(a.addr[c0 + tid], c0 + tid);
     const v4u *bv = (const v4u *)(a.addr + h);
     int64_t i = tid;
     for (; i + 3 * nth < nv; i += 4 * nth) {            // four loads in flight per lane
       const v4u w0 = bv[i], w1 = bv[i + nth], w2 = bv[i + 2 * nth], w3 = bv[i + 3 * nth];
-      four(w0);
-      four(w1);
-      four(w2);
-      four(w3);
+      four(w0, h + 4 * i);
+      four(w1, h + 4 * (i + nth));
+      four(w2, h + 4 * (i + 2 * nth));
+      four(w3, h + 4 * (i + 3 * nth));
     }
-    for (; i < nv; i += nth) four(bv[i]);
+    for (; i < nv; i += nth) four(bv[i], h + 4 * i);
     const int64_t t0 = h + nv * 4;
-    if (t0 + tid < c1) one(a.addr[t0 + tid]);
+    if (t0 + tid < c1) one(a.addr[t0 + tid], t0 + tid);
     if (c1 < e1) {                                      // more to come: make room in the halves
       __syncthreads();
       for (int j = tid * 4; j < nalloc; j += nth * 4) {
@@ -216,8 +263,9 @@ events_bin_kernel(const EventsBinArgs a) {
 
 // more than 64 KiB of LDS (the 64 KiB band plus the two slice bounds) needs the limit raised, once per
 // device and kernel
-template <int OUT>
-static int events_bin_launch(const EventsBinArgs &a, int64_t grid, int threads, size_t lds, hipStream_t st) {
+template <int OUT, bool AUG>
+static int events_bin_launch(const EventsBinArgs &a, const snnqp_event_aug_t *aug, int64_t grid, int threads,
+                             size_t lds, hipStream_t st) {
   if (lds + 64 > 65536) {
     static std::once_flag once[MAX_DEVICES];
     static hipError_t raised[MAX_DEVICES];
@@ -227,28 +275,33 @@ static int events_bin_launch(const EventsBinArgs &a, int64_t grid, int threads, 
     std::call_once(once[dev], [dev] {
       DeviceGuard guard(dev);
       raised[dev] = !guard.ok ? hipErrorInvalidDevice
-                              : hipFuncSetAttribute((const void *)events_bin_kernel<OUT>,
+                              : hipFuncSetAttribute((const void *)events_bin_kernel<OUT, AUG>,
                                                     hipFuncAttributeMaxDynamicSharedMemorySize, EB_BAND_PIX * 4);
       if (raised[dev] != hipSuccess) (void)hipGetLastError();
     });
     SNNQP_REQUIRE(raised[dev] == hipSuccess, SNNQP_EHIP, "events_bin: cannot raise the LDS limit on device %d: %s",
                   dev, hipGetErrorString(raised[dev]));
   }
-  hipLaunchKernelGGL(events_bin_kernel<OUT>, dim3((unsigned)grid), dim3(threads), lds, st, a);
+  EventsBinKernelArgs<AUG> ka;
+  static_cast<EventsBinArgs &>(ka) = a;
+  if constexpr (AUG) ka.aug = aug;
+  hipLaunchKernelGGL((events_bin_kernel<OUT, AUG>), dim3((unsigned)grid), dim3(threads), lds, st, ka);
   SNNQP_CHECK_LAUNCH("events_bin_kernel");
   return SNNQP_OK;
 }
 
-}  // namespace snnqp
+template <int OUT>
+static int events_bin_launch(const EventsBinArgs &a, const snnqp_event_aug_t *aug, int64_t grid, int threads,
+                             size_t lds, hipStream_t st) {
+  return aug ? events_bin_launch<OUT, true>(a, aug, grid, threads, lds, st)
+             : events_bin_launch<OUT, false>(a, nullptr, grid, threads, lds, st);
+}
 
-using namespace snnqp;
-
-extern "C" {
-
-int snnqp_events_bin(const uint32_t *addr, const int32_t *times, const int64_t *offsets, int32_t S,
-                     const int32_t *sample, const int32_t *start, int32_t B, int mode, int32_t T,
-                     int32_t step_us, int32_t H, int32_t W, float scale,
-                     void *out, int out_type, int32_t *flags, snnqp_stream_t stream) {
+// both entry points: the checks, the geometry and the launch (aug null: the plain kernel)
+static int events_bin(const uint32_t *addr, const int32_t *times, const int64_t *offsets, int32_t S,
+                      const int32_t *sample, const int32_t *start, int32_t B, int mode, int32_t T,
+                      int32_t step_us, int32_t H, int32_t W, float scale, const snnqp_event_aug_t *aug,
+                      void *out, int out_type, int32_t *flags, snnqp_stream_t stream) {
   SNNQP_REQUIRE(S >= 0 && B >= 0 && T >= 0 && H > 0 && W > 0 && H <= 16384 && W <= 16384, SNNQP_EINVAL,
                 "events_bin: bad shape (S %d, B %d, T %d, H %d, W %d; H, W <= 16384)", S, B, T, H, W);
   SNNQP_REQUIRE(mode == 0 || mode == 1, SNNQP_EINVAL, "events_bin: mode must be 0 (number) or 1 (time)");
@@ -264,6 +317,7 @@ int snnqp_events_bin(const uint32_t *addr, const int32_t *times, const int64_t *
   SNNQP_REQUIRE(offsets && sample && out, SNNQP_EINVAL, "events_bin: null argument");
   SNNQP_REQUIRE(((uintptr_t)addr & 3) == 0 && (out_type != SNNQP_EV1 || ((uintptr_t)out & 3) == 0), SNNQP_EINVAL,
                 "events_bin: addr and EV1 frames must be 4-byte aligned");
+  SNNQP_REQUIRE(((uintptr_t)aug & 3) == 0, SNNQP_EINVAL, "events_bin: the aug records must be 4-byte aligned");
   const int32_t npix = H * W;
   EventsBinArgs a;
   a.addr = addr; a.times = times; a.offsets = offsets; a.sample = sample; a.start = start;
@@ -276,9 +330,31 @@ int snnqp_events_bin(const uint32_t *addr, const int32_t *times, const int64_t *
   const size_t lds = (size_t)((band + 15) & ~15) * 4;
   const int threads = band <= 4096 ? 256 : 512;
   hipStream_t st = (hipStream_t)stream;
-  if (out_type == SNNQP_U8) return events_bin_launch<SNNQP_U8>(a, grid, threads, lds, st);
-  if (out_type == SNNQP_EV4) return events_bin_launch<SNNQP_EV4>(a, grid, threads, lds, st);
-  return events_bin_launch<SNNQP_EV1>(a, grid, threads, lds, st);
+  if (out_type == SNNQP_U8) return events_bin_launch<SNNQP_U8>(a, aug, grid, threads, lds, st);
+  if (out_type == SNNQP_EV4) return events_bin_launch<SNNQP_EV4>(a, aug, grid, threads, lds, st);
+  return events_bin_launch<SNNQP_EV1>(a, aug, grid, threads, lds, st);
+}
+
+}  // namespace snnqp
+
+using namespace snnqp;
+
+extern "C" {
+
+int snnqp_events_bin(const uint32_t *addr, const int32_t *times, const int64_t *offsets, int32_t S,
+                     const int32_t *sample, const int32_t *start, int32_t B, int mode, int32_t T,
+                     int32_t step_us, int32_t H, int32_t W, float scale,
+                     void *out, int out_type, int32_t *flags, snnqp_stream_t stream) {
+  return events_bin(addr, times, offsets, S, sample, start, B, mode, T, step_us, H, W, scale, nullptr, out, out_type,
+                    flags, stream);
+}
+
+int snnqp_events_bin_aug(const uint32_t *addr, const int32_t *times, const int64_t *offsets, int32_t S,
+                         const int32_t *sample, const int32_t *start, int32_t B, int mode, int32_t T,
+                         int32_t step_us, int32_t H, int32_t W, float scale, const snnqp_event_aug_t *aug,
+                         void *out, int out_type, int32_t *flags, snnqp_stream_t stream) {
+  return events_bin(addr, times, offsets, S, sample, start, B, mode, T, step_us, H, W, scale, aug, out, out_type,
+                    flags, stream);
 }
 
 }  // extern "C"

@@ -88,7 +88,26 @@ class EventPlan:
       generator; the reference shuffles through a buffer of 16 batches with seed 0 (:323), an
       order that depends on the buffer and is not reproduced either;
     * counts saturate at 255 (uint8), as ops.events_to_frames' do; the reference keeps int32.
+
+  Augmentation (train split only; the reference has none).  `config.augment` is a mapping of the
+  keys below; the eval split ignores it, and absent or with every value 0 the plan draws nothing
+  for it: its generator stream and its batches are those of a plan without the key.  Otherwise
+  every batch -- a skipped one too -- draws from `plan.gen`, after the batch's origins, one array
+  of `per` values per line, in this order, a key whose value is 0 drawing nothing:
+    flip_x         probability: 1 draw (float64 uniform < p)
+    flip_y         probability: 1 draw
+    swap_polarity  probability: 1 draw
+    shift          whole pixels: dx, then dy, uniform on [-shift, shift]
+    drop_event     probability: u (float64 uniform), the row's p = u * drop_event and drop_below =
+                   floor(p * 2^32) in float64; then seed, 32 bits
+    cutout         largest side as a fraction of the frame: width uniform on 0 .. floor(cutout * W),
+                   height on 0 .. floor(cutout * H), then x0 on 0 .. W - width, y0 on 0 .. H - height
+    drop_frames    whole frames: n uniform on 0 .. drop_frames, then f0 on 0 .. T - n
+  Integers are 62-bit draws reduced modulo the range, as the origins are.  `augmented_batches`
+  yields the batch's ops.EventAugment beside the indices and origins; `batches` yields the pairs.
   """
+
+  AUGMENT_KEYS = ("flip_x", "flip_y", "swap_polarity", "shift", "drop_event", "cutout", "drop_frames")
 
   def __init__(self, config, sensor_size, counts_per_rank: int, train: bool, rank: int = 0, world: int = 1):
     self.train = bool(train)
@@ -127,6 +146,70 @@ class EventPlan:
     self.seed = int(_cfg(config, "seed", 0)) + int(rank)
     self.gen = torch.Generator()
     self.gen.manual_seed(self.seed)
+    aug = self._augment_config(_cfg(config, "augment"))            # validated for either split
+    self.augment = {k: v for k, v in aug.items() if v} if self.train else {}
+
+  def _augment_config(self, aug) -> Dict[str, Any]:
+    if aug is None:
+      return {}
+    if not hasattr(aug, "keys"):
+      raise ValueError("augment must be a mapping of %s, got %r" % (list(self.AUGMENT_KEYS), aug))
+    unknown = sorted(set(aug.keys()) - set(self.AUGMENT_KEYS))
+    if unknown:
+      raise ValueError("augment has unknown keys %s (known: %s)" % (unknown, list(self.AUGMENT_KEYS)))
+    out = {}
+    for k in self.AUGMENT_KEYS:
+      if k not in aug.keys():
+        continue
+      v = aug[k]
+      if k in ("shift", "drop_frames"):
+        limit = ops.EVENT_SHIFT_MAX if k == "shift" else self.T
+        if isinstance(v, bool) or v != int(v) or not 0 <= int(v) <= limit:
+          raise ValueError("augment.%s must be a whole number in 0..%d, got %r" % (k, limit, v))
+        out[k] = int(v)
+      else:
+        if isinstance(v, bool) or not 0.0 <= float(v) <= 1.0:        # (a NaN fails both comparisons)
+          raise ValueError("augment.%s must lie in [0, 1], got %r" % (k, v))
+        out[k] = float(v)
+    return out
+
+  def _uniform_int(self, lo, hi) -> np.ndarray:
+    """One integer per row, uniform on [lo, hi] (arrays or scalars), as draw_starts draws."""
+    lo = np.broadcast_to(np.asarray(lo, np.int64), (self.per,))
+    hi = np.broadcast_to(np.asarray(hi, np.int64), (self.per,))
+    r = torch.randint(0, 1 << 62, (self.per,), generator=self.gen, dtype=torch.int64).numpy()
+    return (lo + r % (hi - lo + 1)).astype(np.int64)
+
+  def _uniform(self) -> np.ndarray:
+    return torch.rand(self.per, generator=self.gen, dtype=torch.float64).numpy()
+
+  def draw_augment(self):
+    """The batch's ops.EventAugment in the order the class docstring fixes, or None for a plan that
+    does not augment (nothing is drawn then)."""
+    a = self.augment
+    if not a:
+      return None
+    kw = {}
+    for k in ("flip_x", "flip_y", "swap_polarity"):
+      if k in a:
+        kw[k] = self._uniform() < a[k]
+    if "shift" in a:
+      kw["dx"] = self._uniform_int(-a["shift"], a["shift"])
+      kw["dy"] = self._uniform_int(-a["shift"], a["shift"])
+    if "drop_event" in a:
+      p = self._uniform() * a["drop_event"]
+      kw["drop_below"] = np.minimum(np.floor(p * 2.0 ** 32), 2.0 ** 32 - 1).astype(np.int64)
+      kw["seed"] = torch.randint(0, 1 << 32, (self.per,), generator=self.gen, dtype=torch.int64).numpy()
+    if "cutout" in a:
+      w = self._uniform_int(0, int(np.floor(a["cutout"] * self.W)))
+      h = self._uniform_int(0, int(np.floor(a["cutout"] * self.H)))
+      x0, y0 = self._uniform_int(0, self.W - w), self._uniform_int(0, self.H - h)
+      kw["cutout"] = np.stack([x0, y0, x0 + w, y0 + h], 1)
+    if "drop_frames" in a:
+      n = self._uniform_int(0, a["drop_frames"])
+      f0 = self._uniform_int(0, self.T - n)
+      kw["frames"] = np.stack([f0, f0 + n], 1)
+    return ops.EventAugment(self.per, **kw)
 
   def start_range(self, t_min, t_max):
     """[tbegin, tend] of the window origin, both inclusive (:76-77)."""
@@ -145,6 +228,12 @@ class EventPlan:
     are drawn -- permutations and origins alike, so the generator ends up where a consumer of them
     leaves it -- and not yielded: what follows is what a fresh plan yields from its skip-th pair
     on.  (An eval pass re-seeds, so only skip modulo the pass is drawn there.)"""
+    for idx, starts, _ in self.augmented_batches(t_min, t_max, skip):
+      yield idx, starts
+
+  def augmented_batches(self, t_min=None, t_max=None, skip: int = 0):
+    """`batches` with each batch's ops.EventAugment as a third element (None when the plan does not
+    augment), drawn after the batch's origins -- for a skipped batch too."""
     skip = int(skip)
     if skip < 0:
       raise ValueError("skip must be >= 0, got %d" % skip)
@@ -160,10 +249,11 @@ class EventPlan:
         idx = order[i * self.per:(i + 1) * self.per]
         starts = self.draw_starts(np.asarray(t_min)[idx], np.asarray(t_max)[idx]) \
             if self.split_by == "time" else None
+        aug = self.draw_augment()
         if skip > 0:
           skip -= 1
           continue
-        yield idx, starts
+        yield idx, starts, aug
 
 
 def create_event_split(data, config, train: bool, rank: int = 0, world: int = 1,
@@ -185,9 +275,9 @@ def create_event_split(data, config, train: bool, rank: int = 0, world: int = 1,
   divisor = None if plan.divisor is None else torch.full((), float(plan.divisor), dtype=torch.float32, device=device)
 
   def gen():
-    for idx, starts in plan.batches(events.t_min, events.t_max, skip):
+    for idx, starts, aug in plan.augmented_batches(events.t_min, events.t_max, skip):
       x = ops.events_bin(events, idx, plan.T, plan.H, plan.W, mode=plan.split_by, start=starts,
-                         step_us=plan.step_us, scale=plan.scale, fmt=plan.fmt)
+                         step_us=plan.step_us, scale=plan.scale, fmt=plan.fmt, augment=aug)
       if plan.divisor is not None:
         x = x.to(torch.float32) / divisor                          # :134-137
       yield {"dvs_matrix": x, "label": labels[torch.from_numpy(idx).to(device)]}

@@ -1616,9 +1616,87 @@ def _event_rows(v, name, B=None, lo=-2 ** 31, hi=2 ** 31 - 1):
   return torch.from_numpy(a.astype(np.int32))
 
 
+EVENT_SHIFT_MAX = 1 << 14
+
+
+class EventAugment:
+  """Per-row event augmentation of one `events_bin` batch of `rows` rows (snnqp_event_aug_t,
+  include/snnqp.h, which states the order the rules apply in).  Every argument is a host array with
+  one entry per row; an absent one is the identity:
+
+    flip_x, flip_y, swap_polarity   booleans
+    dx, dy          the shift in frame pixels, |.| <= 16384; what leaves the frame is dropped
+    cutout          [rows, 4] (x0, y0, x1, y1), half-open, in final frame pixels, int32; empty when
+                    x1 <= x0 or y1 <= y0
+    frames          [rows, 2] (f0, f1): frames [f0, f1) come out empty, 0 <= f0 <= f1 (<= T is
+                    checked where T is known, in `records`)
+    drop_below      event i of the row's sample is dropped when its hash under `seed` is below
+                    this: a drop probability p is floor(p * 2^32); both in 0 .. 2^32 - 1
+
+  Everything is validated here, on the host; the arrays are kept as int64 attributes of the same
+  names."""
+
+  def __init__(self, rows: int, *, flip_x=None, flip_y=None, swap_polarity=None, dx=None, dy=None,
+               cutout=None, frames=None, drop_below=None, seed=None):
+    import numpy as np
+    self.rows = B = int(rows)
+    if B < 0:
+      raise ValueError("rows must be >= 0, got %d" % B)
+
+    def field(v, name, lo, hi, width=None):
+      shape = (B,) if width is None else (B, width)
+      if v is None:
+        return np.zeros(shape, np.int64)
+      a = _host_array(v, name)
+      if a.dtype == np.uint64 and a.size and int(a.max()) > hi:
+        raise ValueError("%s must lie in %d..%d, got up to %d" % (name, lo, hi, int(a.max())))
+      a = a.astype(np.int64)
+      if a.shape != shape:
+        raise ValueError("%s must have shape %s, one entry per batch row, got %s" % (name, shape, a.shape))
+      if a.size and (int(a.min()) < lo or int(a.max()) > hi):
+        raise ValueError("%s must lie in %d..%d, got %d..%d" % (name, lo, hi, int(a.min()), int(a.max())))
+      return a
+
+    def flag(v, name):
+      if v is not None and not isinstance(v, torch.Tensor):
+        v = np.asarray(v)
+        v = v.astype(np.int64) if v.dtype == np.bool_ else v
+      elif v is not None:
+        v = v.to(torch.int64)
+      return field(v, name, 0, 1)
+
+    self.flip_x, self.flip_y = flag(flip_x, "flip_x"), flag(flip_y, "flip_y")
+    self.swap_polarity = flag(swap_polarity, "swap_polarity")
+    self.dx = field(dx, "dx", -EVENT_SHIFT_MAX, EVENT_SHIFT_MAX)
+    self.dy = field(dy, "dy", -EVENT_SHIFT_MAX, EVENT_SHIFT_MAX)
+    self.cutout = field(cutout, "cutout", -2 ** 31, 2 ** 31 - 1, 4)
+    self.frames = field(frames, "frames", 0, 2 ** 31 - 1, 2)
+    if np.any(self.frames[:, 0] > self.frames[:, 1]):
+      raise ValueError("frames must be (f0, f1) with 0 <= f0 <= f1, got %s" % self.frames.tolist())
+    self.drop_below = field(drop_below, "drop_below", 0, 2 ** 32 - 1)
+    self.seed = field(seed, "seed", 0, 2 ** 32 - 1)
+
+  def records(self, T: int):
+    """The rows as snnqp_event_aug_t records: numpy int32 [rows, 12] (the unsigned fields as their
+    bit patterns).  Refuses a frame range that ends beyond T."""
+    import numpy as np
+    if self.rows and int(self.frames[:, 1].max()) > int(T):
+      raise ValueError("frames must end at or before T = %d, got f1 up to %d" % (T, int(self.frames[:, 1].max())))
+    r = np.zeros((self.rows, 12), np.int64)
+    r[:, 0] = self.flip_x | (self.flip_y << 1) | (self.swap_polarity << 2)
+    r[:, 1], r[:, 2] = self.dx, self.dy
+    r[:, 3:7] = self.cutout
+    r[:, 7:9] = self.frames
+    r[:, 9], r[:, 10] = self.drop_below, self.seed
+    return (r & 0xFFFFFFFF).astype(np.uint32).view(np.int32)
+
+  def __repr__(self):
+    return "EventAugment(%d rows)" % self.rows
+
+
 def events_bin(events: EventSet, sample, T: int, H: int, W: int, *, mode, start=None, step_us=None,
                scale: float = 1.0, fmt: Optional[int] = None, flags: Optional[torch.Tensor] = None,
-               out: Optional[torch.Tensor] = None):
+               out: Optional[torch.Tensor] = None, augment: Optional[EventAugment] = None):
   """One launch (snnqp_events_bin): row b of the batch decodes sample[b] of `events` into T frames of
   H x W x 2 counts.  mode "number": equal-count slices (input_pipeline.py:142-219); mode "time":
   windows of step_us microseconds from start[b], both edges strict (:63-131).  Returns uint8
@@ -1626,7 +1704,10 @@ def events_bin(events: EventSet, sample, T: int, H: int, W: int, *, mode, start=
   15 / 1 with FLAG_GT_15 / FLAG_GT_ONE OR-ed into the int32 device word `flags` when one is
   given.  `sample` (each in [0, S)) and `start` (int32) are validated here, on the host.  `out`,
   when given, is the tensor the launch writes -- uint8 [B, T, H, W, 2] or the packed data
-  [B, T, units] --, every element of it."""
+  [B, T, units] --, every element of it.  `augment`, an EventAugment of B rows, makes it the
+  augmenting launch (snnqp_events_bin_aug): flips, shift, cutout, hashed drops, polarity swap and
+  emptied frames per row, its records in the same upload as `sample` and `start`; None is the
+  plain launch."""
   m = EVENT_MODES.get(mode, mode)
   if m not in (0, 1):
     raise ValueError("mode must be 'number' or 'time', got %r" % (mode,))
@@ -1646,6 +1727,12 @@ def events_bin(events: EventSet, sample, T: int, H: int, W: int, *, mode, start=
       raise ValueError("step_us must be a positive int32, got %r" % (step_us,))
   else:
     starts = None
+  if augment is not None:
+    if not isinstance(augment, EventAugment):
+      raise ValueError("augment must be an ops.EventAugment, got %r" % (type(augment).__name__,))
+    if augment.rows != B:
+      raise ValueError("augment must have one record per batch row (%d), got %d" % (B, augment.rows))
+    records = augment.records(T)
   _require_gpu(events.addr, flags, out)
   dev = events.device
   packed = fmt in (L.EV1, L.EV4)
@@ -1655,7 +1742,16 @@ def events_bin(events: EventSet, sample, T: int, H: int, W: int, *, mode, start=
     out = torch.empty(shape, dtype=dtype, device=dev)
   elif tuple(out.shape) != shape or out.dtype != dtype or not out.is_contiguous():
     raise ValueError("out must be a contiguous %s tensor of shape %s" % (dtype, shape))
-  if B and T:
+  if B and T and augment is not None:
+    host = torch.cat([rows] + ([] if starts is None else [starts]) + [torch.from_numpy(records).reshape(-1)])
+    both = host.to(dev)                                                          # one upload
+    rows_d, starts_d = both[:B], (None if starts is None else both[B:2 * B])
+    L.check(L.lib().snnqp_events_bin_aug(_ptr(events._addr_arg), _ptr(events._times_arg), _ptr(events.offsets),
+                                         events.num_samples, _ptr(rows_d), _ptr(starts_d), B, m, T,
+                                         int(step_us) if m == 1 else 0, H, W, float(scale),
+                                         _ptr(both[both.shape[0] - 12 * B:]), _ptr(out),
+                                         fmt if packed else L.U8, _ptr(flags), _stream()))
+  elif B and T:
     both = (rows if starts is None else torch.stack([rows, starts])).to(dev)     # one upload
     rows_d, starts_d = (both, None) if starts is None else (both[0], both[1])
     L.check(L.lib().snnqp_events_bin(_ptr(events._addr_arg), _ptr(events._times_arg), _ptr(events.offsets),

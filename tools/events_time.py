@@ -7,8 +7,14 @@ the loop and the launch give the same bytes.  Prints one JSON line: milliseconds
 a launch has to read and write, and that traffic over the CALL's time (host validation and upload
 included: a lower bound on the kernel's rate) as a fraction of --hbm-gbs.
 
+--augment times the augmenting launch (ops.events_bin(augment=...), snnqp_events_bin_aug) beside the
+plain one instead of the loop: every augmentation on, per-row records drawn once -- flips and
+polarity swap with probability 1/2, shifts of up to 8 pixels, a drop probability uniform on
+[0, 0.5], a cutout of up to a quarter of a side, up to two emptied frames.  Checks first that an
+identity record gives the plain launch's bytes.
+
   python tools/events_time.py [--batch 64] [--frames 20] [--hw 128] [--events 262144]
-                              [--steps 10] [--warmup 3] [--reps 3] [--hbm-gbs 8000]
+                              [--steps 10] [--warmup 3] [--reps 3] [--hbm-gbs 8000] [--augment]
 """
 import argparse
 import json
@@ -45,6 +51,7 @@ def main(argv=None):
   ap.add_argument("--warmup", type=int, default=3)
   ap.add_argument("--reps", type=int, default=3)
   ap.add_argument("--hbm-gbs", type=float, default=8000.0, help="HBM rate the traffic is set against")
+  ap.add_argument("--augment", action="store_true", help="time the augmenting launch beside the plain one")
   args = ap.parse_args(argv)
   assert torch.cuda.is_available(), "events_time.py needs the GPU"
   from snnquantprune_amd import _lib as L
@@ -68,15 +75,40 @@ def main(argv=None):
   def launch(fmt, mode):
     return ops.events_bin(es, rows, T, HW, HW, mode=mode, start=starts, step_us=1000, fmt=fmt)
 
+  def draw_augment():
+    w, h = rng.integers(0, HW // 4 + 1, B), rng.integers(0, HW // 4 + 1, B)
+    x0, y0 = rng.integers(0, HW - w + 1), rng.integers(0, HW - h + 1)
+    n = rng.integers(0, min(2, T) + 1, B)
+    f0 = rng.integers(0, T - n + 1)
+    return ops.EventAugment(B, flip_x=rng.integers(0, 2, B), flip_y=rng.integers(0, 2, B),
+                            swap_polarity=rng.integers(0, 2, B), dx=rng.integers(-8, 9, B), dy=rng.integers(-8, 9, B),
+                            cutout=np.stack([x0, y0, x0 + w, y0 + h], 1), frames=np.stack([f0, f0 + n], 1),
+                            drop_below=np.floor(rng.random(B) * 0.5 * 2.0 ** 32).astype(np.int64),
+                            seed=rng.integers(0, 1 << 32, B))
+
+  def launch_aug(fmt, mode, aug):
+    return ops.events_bin(es, rows, T, HW, HW, mode=mode, start=starts, step_us=1000, fmt=fmt, augment=aug)
+
   formats = (("u8", None), ("ev4", L.EV4), ("ev1", L.EV1))
-  for name, fmt in formats:                             # the same frames, before any timing
-    a, b = loop(fmt), launch(fmt, "number")
-    assert torch.equal(a.data if fmt else a, b.data if fmt else b), name
   cands = {}
-  for name, fmt in formats:
-    cands["loop_%s" % name] = lambda fmt=fmt: loop(fmt)
-    cands["bin_number_%s" % name] = lambda fmt=fmt: launch(fmt, "number")
-    cands["bin_time_%s" % name] = lambda fmt=fmt: launch(fmt, "time")
+  if args.augment:
+    aug, ident = draw_augment(), ops.EventAugment(B)
+    for name, fmt in formats:                           # an identity record: the plain launch's bytes
+      for mode in ("number", "time"):
+        a, b = launch_aug(fmt, mode, ident), launch(fmt, mode)
+        assert torch.equal(a.data if fmt else a, b.data if fmt else b), (name, mode)
+    for name, fmt in formats:
+      for mode in ("number", "time"):
+        cands["bin_%s_%s" % (mode, name)] = lambda fmt=fmt, mode=mode: launch(fmt, mode)
+        cands["aug_%s_%s" % (mode, name)] = lambda fmt=fmt, mode=mode: launch_aug(fmt, mode, aug)
+  else:
+    for name, fmt in formats:                           # the same frames, before any timing
+      a, b = loop(fmt), launch(fmt, "number")
+      assert torch.equal(a.data if fmt else a, b.data if fmt else b), name
+    for name, fmt in formats:
+      cands["loop_%s" % name] = lambda fmt=fmt: loop(fmt)
+      cands["bin_number_%s" % name] = lambda fmt=fmt: launch(fmt, "number")
+      cands["bin_time_%s" % name] = lambda fmt=fmt: launch(fmt, "time")
   ms = {k: [] for k in cands}
   for _ in range(args.reps):                            # alternating: every candidate once per round
     for k, fn in cands.items():
@@ -101,7 +133,12 @@ def main(argv=None):
                                "call_gb_per_s": round((rd + out_bytes[name]) / best / 1e6, 1),
                                "call_fraction_of_hbm": round((rd + out_bytes[name]) / best / 1e6 / args.hbm_gbs, 4),
                                "call_events_per_us": round(B * N / best / 1e3, 1)}
-    result.setdefault("speedup_over_loop", {})[name] = round(min(ms["loop_%s" % name]) / min(ms["bin_number_%s" % name]), 2)
+    if args.augment:
+      for mode in ("number", "time"):
+        result.setdefault("augmented_over_plain", {})["%s_%s" % (mode, name)] = round(
+            min(ms["aug_%s_%s" % (mode, name)]) / min(ms["bin_%s_%s" % (mode, name)]), 3)
+    else:
+      result.setdefault("speedup_over_loop", {})[name] = round(min(ms["loop_%s" % name]) / min(ms["bin_number_%s" % name]), 2)
   print(json.dumps(result))
 
 
