@@ -20,9 +20,7 @@
 //     MFMA from C = 0, then acc = fmaf(gate[c], result, acc) -- gate[c] is a scalar register;
 //  3. dequantise, store float32 currents [NB][H][W][Cout] (BatchNorm and the neuron follow as
 //     the stand-alone scan, as behind the float32 connection).
-#include <type_traits>
-
-#include "kernels.h"
+#include "gated_tile.h"
 
 namespace snnqp {
 
@@ -34,7 +32,7 @@ constexpr int CG_CMAX = 128;          // input channels (the LDS table is CMAX x
 struct ConvGatedArgs {
   const uint32_t *s;      // [NB][H][W][CW] spike words
   const float *gate;      // [NB][C]
-  const uint32_t *bp;     // packed codes [C][OT][64 lanes][2 dwords] (pack_codes_gated_kernel)
+  const uint32_t *bp;     // packed codes [C][OT][64 lanes][2 dwords] (ConvGatedCodes)
   float *y;               // [NB][H][W][Cout]
   int64_t NB, npatch;
   int32_t H, W, C, CW, Cout, OT, tiles_y, tiles_x;
@@ -42,77 +40,17 @@ struct ConvGatedArgs {
   float L, m;
 };
 
-// integer -7..7 -> e2m3 (runtime.hip enc6)
-__device__ __forceinline__ uint32_t enc6(int v) {
-  const uint32_t mag = (uint32_t)(v < 0 ? -v : v);
-  const uint32_t code = mag == 0 ? 0u : mag == 1 ? 8u : mag == 2 ? 16u : mag == 3 ? 20u : mag == 4 ? 24u
-                        : mag == 5 ? 26u : mag == 6 ? 28u : 30u;
-  return code | (v < 0 ? 32u : 0u);
-}
-
 }  // namespace
 
-// codes int8 HWIO [9][C][Cout] -> bp[c][ot][lane][2]: lane (n, h = 0) holds the fp6 values of taps
-// 0..7 at bits [6 j, 6 j + 6) and, lane (n, h = 1), tap 8 at bits [0, 6) -- k = 32 h + j of the
-// 64-deep matrix instruction; columns beyond Cout are zero.
-__global__ void __launch_bounds__(256)
-pack_codes_gated_kernel(const int8_t *w, int32_t C, int32_t Cout, int32_t OT, uint32_t *bp) {
-  const int64_t total = (int64_t)C * OT * 64;
-  for (int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x; i < total; i += (int64_t)gridDim.x * 256) {
-    const int lane = (int)(i & 63), n = lane & 31, h = lane >> 5;
-    const int ot = (int)((i >> 6) % OT), c = (int)((i >> 6) / OT);
-    const int o = ot * 32 + n;
-    unsigned long long bits = 0;
-    if (o < Cout) {
-      if (h == 0) {
-        for (int tap = 0; tap < 8; ++tap)
-          bits |= (unsigned long long)enc6(w[((int64_t)tap * C + c) * Cout + o]) << (6 * tap);
-      } else {
-        bits = enc6(w[((int64_t)8 * C + c) * Cout + o]);
-      }
-    }
-    bp[i * 2] = (uint32_t)bits;
-    bp[i * 2 + 1] = (uint32_t)(bits >> 32);
-  }
-}
-
-// integer -8..8 -> fp6 e3m2 (bias 3, three significant bits: every integer up to 8 is exact;
-// 1 = 0x0C, 2 = 0x10, 3 = 0x12, 4 = 0x14, 5 = 0x15, 6 = 0x16, 7 = 0x17, 8 = 0x18)
-__device__ __forceinline__ uint32_t enc6w(int v) {
-  const uint32_t mag = (uint32_t)(v < 0 ? -v : v);
-  const uint32_t tab[9] = {0x00u, 0x0Cu, 0x10u, 0x12u, 0x14u, 0x15u, 0x16u, 0x17u, 0x18u};
-  return tab[mag] | (v < 0 ? 0x20u : 0u);
-}
-// Codes beyond e2m3 (|code| <= 127: up to 8 bits) as TWO six-bit digits, code = 16 hi + lo with lo in
-// [-8, 7], hi in [-8, 8] -- exact in the OTHER fp6 format, e3m2 -- one digit per 32-deep K block of
-// the 64-deep instruction: the block scale of the second block is 2^4 (v_mfma_scale: an E8M0 scale
-// per lane half = per K block), so ONE instruction returns sum(lo s) + 16 sum(hi s): the exact
-// integer, at the fp6 rate and with not one vector instruction more than the narrow form.  (fp8
-// digits work too -- tools/ubench/mfma_fp8_kmap.hip, mfma_fp8_digits.hip: an 8-bit operand beside a
-// 4-bit one counts k differently, the digits then sit in bytes 0..8 / 16..24 of the lanes of half 0
-// -- and were the first version: twice the matrix-pipe time and eight operand dwords, 2.09 ms for
-// CextNet's 8-bit layer against 1.38 with e3m2.)  bp[c][ot][lane][2]: lane (n, h = 0) holds the lo digits
-// of the nine taps at bits [6 j, 6 j + 6), lane (n, h = 1) the hi digits; the spike operand holds
-// the nine taps in both lane halves.
-__global__ void __launch_bounds__(256)
-pack_codes_gated_wide_kernel(const int8_t *w, int32_t C, int32_t Cout, int32_t OT, uint32_t *bp) {
-  const int64_t total = (int64_t)C * OT * 64;
-  for (int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x; i < total; i += (int64_t)gridDim.x * 256) {
-    const int lane = (int)(i & 63), n = lane & 31, h = lane >> 5;
-    const int ot = (int)((i >> 6) % OT), c = (int)((i >> 6) / OT);
-    const int o = ot * 32 + n;
-    unsigned long long bits = 0;
-    if (o < Cout) {
-      for (int tap = 0; tap < 9; ++tap) {
-        const int code = w[((int64_t)tap * C + c) * Cout + o];
-        const int lo = ((code + 8) & 15) - 8, hi = (code - lo) / 16;
-        bits |= (unsigned long long)enc6w(h ? hi : lo) << (6 * tap);
-      }
-    }
-    bp[i * 2] = (uint32_t)bits;
-    bp[i * 2 + 1] = (uint32_t)(bits >> 32);
-  }
-}
+// The source of the code operand (gated_tile.h): codes int8 HWIO [9][C][Cout] -> bp[c][ot][lane][2].
+// Narrow: lane (n, h = 0) holds the fp6 values of taps 0..7 at bits [6 j, 6 j + 6) and, lane
+// (n, h = 1), tap 8 at bits [0, 6) -- k = 32 h + j of the 64-deep matrix instruction.
+struct ConvGatedCodes {
+  int32_t C, Cout;
+  __device__ int64_t at(int tap, int c, int o) const { return ((int64_t)tap * C + c) * Cout + o; }
+  __device__ static int half(int tap) { return tap >> 3; }
+  __device__ static int slot(int tap) { return tap & 7; }
+};
 
 // NT: output tiles (of 32) this launch's workgroups hold -- a template parameter, so that the four
 // matrix instructions of a channel and their 64 fmaf are one basic block the scheduler can
@@ -168,8 +106,7 @@ conv_gated_kernel(ConvGatedArgs a) {
   constexpr int nt = NT;
   v16f acc[4];
 #pragma unroll
-  for (int t = 0; t < 4; ++t) acc[t] = v16f{0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0};
-  const v16f zero16 = {0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0};
+  for (int t = 0; t < 4; ++t) acc[t] = gated_zero16();
   const float *grow = a.gate + img * a.C;             // wave-uniform: scalar loads
   // four channels per group; the codes of the next group are requested before this group's
   // matrix instructions (an L2 round trip per group would otherwise sit in front of every one)
@@ -187,8 +124,7 @@ conv_gated_kernel(ConvGatedArgs a) {
       for (int t = 0; t < 4; ++t) dst[j][t] = *(const u2 *)(bc + (t < nt ? t : 0) * 128);
     }
   };
-  // WIDE: the E8M0 scale of B's K block h comes from the lanes of half h: 2^0 (lo digits), 2^4 (hi)
-  const int sb = WIDE ? (h ? 131 : 127) : 127;
+  const int sb = gated_scale<WIDE>(h);
   load_group(bcur, 0);
   // the gates of a group are requested a group ahead as well (scalar loads: their latency would
   // otherwise sit in front of the group's first fmaf)
@@ -216,21 +152,12 @@ conv_gated_kernel(ConvGatedArgs a) {
 #pragma unroll
       for (int t = 0; t < 4; ++t) {
         if (t < nt) {
-          v8i B;
-          v16f I;
           // K elements 9.. of A are zero and no fp6 encoding is an infinity or a NaN: what the other
           // four dwords of the B tuple hold does not matter, so they are left undefined (sixteen
           // tuples per group otherwise cost 64 v_mov: 358 -> 310 vector instructions per 16 MFMAs)
           const v2i bxy = {(int)bcur[j][t].x, (int)bcur[j][t].y};
-          if constexpr (WIDE) {
-            B = __builtin_shufflevector(bxy, bxy, 0, 1, -1, -1, -1, -1, -1, -1);
-            I = __builtin_amdgcn_mfma_scale_f32_32x32x64_f8f6f4(A, B, zero16, 4 /* fp4 */, 3 /* fp6 e3m2 */,
-                                                                0, 127, 0, sb);
-          } else {
-            B = __builtin_shufflevector(bxy, bxy, 0, 1, -1, -1, -1, -1, -1, -1);
-            I = __builtin_amdgcn_mfma_scale_f32_32x32x64_f8f6f4(A, B, zero16, 4 /* fp4 */, 2 /* fp6 */,
-                                                                0, 127, 0, 127);
-          }
+          const v8i B = __builtin_shufflevector(bxy, bxy, 0, 1, -1, -1, -1, -1, -1, -1);
+          const v16f I = gated_mfma<WIDE, false>(A, B, sb);
 #pragma unroll
           for (int i = 0; i < 16; ++i) acc[t][i] = __builtin_fmaf(g[j], I[i], acc[t][i]);
         }
@@ -244,19 +171,17 @@ conv_gated_kernel(ConvGatedArgs a) {
     }
   }
 
-  // ---- 3. dequantise and store: lane = output, register i = pixel (i & 3) + 8 (i >> 2) + 4 h ----
+  // ---- 3. dequantise and store: lane = output, register i = pixel gated_acc_row(i, h) ------------
 #pragma unroll
   for (int t = 0; t < 4; ++t) {
     const int o = (ot0 + t) * 32 + n;
     if (t < nt && o < a.Cout) {
 #pragma unroll
       for (int i = 0; i < 16; ++i) {
-        const int row = (i & 3) + 8 * (i >> 2) + 4 * h;
+        const int row = gated_acc_row(i, h);
         const int gy = y0 + (row >> 3), gx = x0 + (row & 7);
-        if (gy < a.H && gx < a.W) {
-          const float q = acc[t][i] / a.L;
-          a.y[((img * a.H + gy) * a.W + gx) * a.Cout + o] = q * a.m;
-        }
+        if (gy < a.H && gx < a.W)
+          a.y[((img * a.H + gy) * a.W + gx) * a.Cout + o] = gated_current(acc[t][i], a.L, a.m);
       }
     }
   }
@@ -282,7 +207,15 @@ struct ConvGatedPlan { int full, rest; bool wide; };
 
 static ConvGatedPlan conv_gated_plan(int32_t Cout, int32_t code_max) {
   const int OT = (Cout + 31) / 32;
-  return ConvGatedPlan{OT / 4, OT % 4, code_max > 7};
+  return ConvGatedPlan{OT / 4, OT % 4, gated_wide(code_max)};
+}
+
+template <int NT>
+static void conv_gated_launch(bool wide, const ConvGatedArgs &a, int64_t gx, int gy, hipStream_t st) {
+  gated_form(wide, [&](auto w) {
+    hipLaunchKernelGGL((conv_gated_kernel<NT, decltype(w)::value>), dim3((unsigned)gx, (unsigned)gy),
+                       dim3(CG_WAVES * 64), 0, st, a);
+  });
 }
 
 }  // namespace snnqp
@@ -310,17 +243,8 @@ extern "C" int snnqp_pack_codes_gated_ex(const int8_t *w, int32_t Cin, int32_t C
   using namespace snnqp;
   SNNQP_REQUIRE(w && packed && Cin > 0 && Cout > 0 && code_max > 0 && code_max <= 127, SNNQP_EINVAL,
                 "pack_codes_gated: bad argument");
-  const int OT = (Cout + 31) / 32;
-  const int64_t total = (int64_t)Cin * OT * 64;
-  const int64_t blocks = (total + 255) / 256;
-  if (!conv_gated_plan(Cout, code_max).wide)
-    hipLaunchKernelGGL(pack_codes_gated_kernel, dim3((unsigned)(blocks < 4096 ? blocks : 4096)), dim3(256), 0,
-                       (hipStream_t)stream, w, Cin, Cout, OT, (uint32_t *)packed);
-  else
-    hipLaunchKernelGGL(pack_codes_gated_wide_kernel, dim3((unsigned)(blocks < 4096 ? blocks : 4096)), dim3(256), 0,
-                       (hipStream_t)stream, w, Cin, Cout, OT, (uint32_t *)packed);
-  SNNQP_CHECK_LAUNCH("pack_codes_gated_kernel");
-  return SNNQP_OK;
+  return pack_codes_gated<2>("pack_codes_gated_kernel", w, ConvGatedCodes{Cin, Cout}, Cin, 9, Cout, code_max, packed,
+                             (hipStream_t)stream);
 }
 extern "C" int snnqp_pack_codes_gated(const int8_t *w, int32_t Cin, int32_t Cout, void *packed,
                                       snnqp_stream_t stream) {
@@ -349,24 +273,15 @@ extern "C" int snnqp_conv_gated_forward(const uint32_t *s, const float *gate, in
   SNNQP_REQUIRE(gx < ((int64_t)1 << 31), SNNQP_EUNSUPPORTED, "conv_gated_forward: more than 2^31 workgroups");
   // full groups of four output tiles, then the remainder (its blockIdx.y = 0 is tile group OT / 4)
   const ConvGatedPlan plan = conv_gated_plan(g->Cout, w->code_max);
-  const int full = plan.full, rest = plan.rest;
-  const bool wide = plan.wide;
-#define SNNQP_CG_LAUNCH(NTV, ARGS, GY)                                                                  \
-  do {                                                                                                  \
-    if (wide) hipLaunchKernelGGL((conv_gated_kernel<NTV, true>), dim3((unsigned)gx, (unsigned)(GY)),     \
-                                 dim3(CG_WAVES * 64), 0, (hipStream_t)stream, ARGS);                    \
-    else hipLaunchKernelGGL((conv_gated_kernel<NTV, false>), dim3((unsigned)gx, (unsigned)(GY)),         \
-                            dim3(CG_WAVES * 64), 0, (hipStream_t)stream, ARGS);                         \
-  } while (0)
-  if (full > 0) SNNQP_CG_LAUNCH(4, a, full);
-  if (rest > 0) {
+  const hipStream_t st = (hipStream_t)stream;
+  if (plan.full > 0) conv_gated_launch<4>(plan.wide, a, gx, plan.full, st);
+  if (plan.rest > 0) {
     ConvGatedArgs b = a;
-    b.ot_base = full * 4;
-    if (rest == 1) SNNQP_CG_LAUNCH(1, b, 1);
-    else if (rest == 2) SNNQP_CG_LAUNCH(2, b, 1);
-    else SNNQP_CG_LAUNCH(3, b, 1);
+    b.ot_base = plan.full * 4;
+    if (plan.rest == 1) conv_gated_launch<1>(plan.wide, b, gx, 1, st);
+    else if (plan.rest == 2) conv_gated_launch<2>(plan.wide, b, gx, 1, st);
+    else conv_gated_launch<3>(plan.wide, b, gx, 1, st);
   }
-#undef SNNQP_CG_LAUNCH
   SNNQP_CHECK_LAUNCH("conv_gated_kernel");
   return SNNQP_OK;
 }

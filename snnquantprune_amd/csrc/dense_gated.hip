@@ -17,9 +17,7 @@
 // its images are transposed once into LDS as B-operand dwords (Bt[c][image] = the fp4 nibbles of
 // the positions of channel c) beside the gates (Gt[c][image]); the fp6 codes come pre-packed per
 // (channel, 32 outputs).
-#include <type_traits>
-
-#include "kernels.h"
+#include "gated_tile.h"
 
 namespace snnqp {
 
@@ -33,76 +31,25 @@ constexpr int DG_PMAX = 16;           // positions per channel (H W)
 struct DenseGatedArgs {
   const uint32_t *s;      // [NB][HW][CW] spike words
   const float *gate;      // [NB][C]
-  const uint32_t *ap;     // packed codes [C][OT][64 lanes][4 dwords] (pack_codes_dense_gated_kernel)
+  const uint32_t *ap;     // packed codes [C][OT][64 lanes][4 dwords] (DenseGatedCodes)
   float *y;               // [NB][N]
   int64_t NB;
   int32_t HW, C, CW, N, OT;
   float L, m;
 };
 
-__device__ __forceinline__ uint32_t dg_enc6(int v) {      // integer -7..7 -> e2m3 (runtime.hip enc6)
-  const uint32_t mag = (uint32_t)(v < 0 ? -v : v);
-  const uint32_t code = mag == 0 ? 0u : mag == 1 ? 8u : mag == 2 ? 16u : mag == 3 ? 20u : mag == 4 ? 24u
-                        : mag == 5 ? 26u : mag == 6 ? 28u : 30u;
-  return code | (v < 0 ? 32u : 0u);
-}
-
 }  // namespace
 
-// codes int8 [C * HW][N] (k = c HW + p) -> ap[c][ot][lane][4]: lane (o, h = 0) holds the fp6 values
-// of positions 0 .. HW - 1 at bits [6 p, 6 p + 6) of dwords 0..2; lanes of half 1 and outputs
-// beyond N are zero.
-__global__ void __launch_bounds__(256)
-pack_codes_dense_gated_kernel(const int8_t *w, int32_t C, int32_t HW, int32_t N, int32_t OT, uint32_t *ap) {
-  const int64_t total = (int64_t)C * OT * 64;
-  for (int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x; i < total; i += (int64_t)gridDim.x * 256) {
-    const int lane = (int)(i & 63), n = lane & 31, h = lane >> 5;
-    const int ot = (int)((i >> 6) % OT), c = (int)((i >> 6) / OT);
-    const int o = ot * 32 + n;
-    uint32_t d[4] = {0, 0, 0, 0};
-    if (o < N && h == 0) {
-      for (int p = 0; p < HW; ++p) {
-        const uint32_t e = dg_enc6(w[((int64_t)c * HW + p) * N + o]);
-        const int bit = 6 * p;
-        d[bit >> 5] |= e << (bit & 31);
-        if ((bit & 31) > 26) d[(bit >> 5) + 1] |= e >> (32 - (bit & 31));
-      }
-    }
-    for (int j = 0; j < 4; ++j) ap[i * 4 + j] = d[j];
-  }
-}
-
-// Codes beyond e2m3 (|code| <= 127) as two six-bit digits in the e3m2 format, code = 16 hi + lo
-// (conv_gated.hip: one digit per K block, the 2^4 block scale on the second): lane (o, h = 0) holds
-// the lo digits of the sixteen positions at bits [6 p, 6 p + 6) of dwords 0..2, lane (o, h = 1) the
-// hi digits; the spike operand holds the positions in both lane halves.  Same record as the narrow
-// form: ap[c][ot][lane][4 dwords].
-__device__ __forceinline__ uint32_t dg_enc6w(int v) {     // integer -8..8 -> fp6 e3m2
-  const uint32_t mag = (uint32_t)(v < 0 ? -v : v);
-  const uint32_t tab[9] = {0x00u, 0x0Cu, 0x10u, 0x12u, 0x14u, 0x15u, 0x16u, 0x17u, 0x18u};
-  return tab[mag] | (v < 0 ? 0x20u : 0u);
-}
-__global__ void __launch_bounds__(256)
-pack_codes_dense_gated_wide_kernel(const int8_t *w, int32_t C, int32_t HW, int32_t N, int32_t OT, uint32_t *ap) {
-  const int64_t total = (int64_t)C * OT * 64;
-  for (int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x; i < total; i += (int64_t)gridDim.x * 256) {
-    const int lane = (int)(i & 63), n = lane & 31, h = lane >> 5;
-    const int ot = (int)((i >> 6) % OT), c = (int)((i >> 6) / OT);
-    const int o = ot * 32 + n;
-    uint32_t d[4] = {0, 0, 0, 0};
-    if (o < N) {
-      for (int p = 0; p < HW; ++p) {
-        const int code = w[((int64_t)c * HW + p) * N + o];
-        const int lo = ((code + 8) & 15) - 8, hi = (code - lo) / 16;
-        const uint32_t e = dg_enc6w(h ? hi : lo);
-        const int bit = 6 * p;
-        d[bit >> 5] |= e << (bit & 31);
-        if ((bit & 31) > 26) d[(bit >> 5) + 1] |= e >> (32 - (bit & 31));
-      }
-    }
-    for (int j = 0; j < 4; ++j) ap[i * 4 + j] = d[j];
-  }
-}
+// The source of the code operand (gated_tile.h): codes int8 [C * HW][N] (k = c HW + p) ->
+// ap[c][ot][lane][4].  Narrow: lane (o, h = 0) holds the fp6 values of positions 0 .. HW - 1 at bits
+// [6 p, 6 p + 6) of dwords 0..2; lanes of half 1 are zero.  Wide: the same record, the lo digits
+// in half 0 and the hi digits in half 1.
+struct DenseGatedCodes {
+  int32_t HW, N;
+  __device__ int64_t at(int p, int c, int o) const { return ((int64_t)c * HW + p) * N + o; }
+  __device__ static int half(int) { return 0; }
+  __device__ static int slot(int p) { return p; }
+};
 
 template <bool WIDE>
 __global__ void __launch_bounds__(256, 2)
@@ -146,11 +93,10 @@ dense_gated_kernel(DenseGatedArgs a) {
   if (ot0 >= a.OT) return;
   v16f acc[4];
 #pragma unroll
-  for (int t = 0; t < 4; ++t) acc[t] = v16f{0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0};
-  const v16f zero16 = {0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0};
+  for (int t = 0; t < 4; ++t) acc[t] = gated_zero16();
   typedef v4i avec;
   const v4i *apl = (const v4i *)a.ap + (int64_t)ot0 * 64 + lane;
-  const int sa = WIDE ? (h ? 131 : 127) : 127;             // E8M0 scale of A's K block h: 2^0 / 2^4
+  const int sa = gated_scale<WIDE>(h);
   constexpr int GC = 4;
   avec acur[GC][4], anxt[GC][4];
   auto load_group = [&](avec (&dst)[GC][4], int c0) {
@@ -174,15 +120,8 @@ dense_gated_kernel(DenseGatedArgs a) {
                          : v8i{(int)(h ? 0u : bb.x), (int)(h ? 0u : bb.y), 0, 0, 0, 0, 0, 0};
 #pragma unroll
       for (int t = 0; t < 4; ++t) {
-        v16f I;
         const v8i A = {acur[j][t].x, acur[j][t].y, acur[j][t].z, 0, 0, 0, 0, 0};
-        if constexpr (WIDE) {
-          I = __builtin_amdgcn_mfma_scale_f32_32x32x64_f8f6f4(A, B, zero16, 3 /* A: fp6 e3m2 */, 4 /* B: fp4 */,
-                                                              0, sa, 0, 127);
-        } else {
-          I = __builtin_amdgcn_mfma_scale_f32_32x32x64_f8f6f4(A, B, zero16, 2 /* A: fp6 */, 4 /* B: fp4 */,
-                                                              0, 127, 0, 127);
-        }
+        const v16f I = gated_mfma<WIDE, true>(A, B, sa);
 #pragma unroll
         for (int i = 0; i < 16; ++i) acc[t][i] = __builtin_fmaf(g, I[i], acc[t][i]);
       }
@@ -193,7 +132,7 @@ dense_gated_kernel(DenseGatedArgs a) {
       for (int t = 0; t < 4; ++t) acur[j][t] = anxt[j][t];
   }
 
-  // ---- dequantise and store: lane = image, register i = output (i & 3) + 8 (i >> 2) + 4 h ----
+  // ---- dequantise and store: lane = image, register i = output gated_acc_row(i, h) ------------
   const int64_t gi = img0 + n;
   if (gi < a.NB) {
 #pragma unroll
@@ -201,11 +140,8 @@ dense_gated_kernel(DenseGatedArgs a) {
       if (ot0 + t < a.OT) {
 #pragma unroll
         for (int i = 0; i < 16; ++i) {
-          const int o = (ot0 + t) * 32 + (i & 3) + 8 * (i >> 2) + 4 * h;
-          if (o < a.N) {
-            const float q = acc[t][i] / a.L;
-            a.y[gi * a.N + o] = q * a.m;
-          }
+          const int o = gated_acc_row(i, h, (ot0 + t) * 32);
+          if (o < a.N) a.y[gi * a.N + o] = gated_current(acc[t][i], a.L, a.m);
         }
       }
     }
@@ -229,7 +165,7 @@ struct DenseGatedPlan { int gy; bool wide; };
 
 static DenseGatedPlan dense_gated_plan(int32_t N, int32_t code_max) {
   const int OT = (N + 31) / 32;
-  return DenseGatedPlan{(OT + 15) / 16, code_max > 7};
+  return DenseGatedPlan{(OT + 15) / 16, gated_wide(code_max)};
 }
 
 }  // namespace snnqp
@@ -256,17 +192,8 @@ extern "C" int snnqp_pack_codes_dense_gated_ex(const int8_t *w, int32_t C, int32
   using namespace snnqp;
   SNNQP_REQUIRE(w && packed && C > 0 && HW > 0 && HW <= DG_PMAX && N > 0 && code_max > 0 && code_max <= 127,
                 SNNQP_EINVAL, "pack_codes_dense_gated: bad argument");
-  const int OT = (N + 31) / 32;
-  const int64_t total = (int64_t)C * OT * 64;
-  const int64_t blocks = (total + 255) / 256;
-  if (!dense_gated_plan(N, code_max).wide)
-    hipLaunchKernelGGL(pack_codes_dense_gated_kernel, dim3((unsigned)(blocks < 4096 ? blocks : 4096)), dim3(256), 0,
-                       (hipStream_t)stream, w, C, HW, N, OT, (uint32_t *)packed);
-  else
-    hipLaunchKernelGGL(pack_codes_dense_gated_wide_kernel, dim3((unsigned)(blocks < 4096 ? blocks : 4096)), dim3(256),
-                       0, (hipStream_t)stream, w, C, HW, N, OT, (uint32_t *)packed);
-  SNNQP_CHECK_LAUNCH("pack_codes_dense_gated_kernel");
-  return SNNQP_OK;
+  return pack_codes_gated<4>("pack_codes_dense_gated_kernel", w, DenseGatedCodes{HW, N}, C, HW, N, code_max, packed,
+                             (hipStream_t)stream);
 }
 extern "C" int snnqp_pack_codes_dense_gated(const int8_t *w, int32_t C, int32_t HW, int32_t N, void *packed,
                                             snnqp_stream_t stream) {
@@ -290,12 +217,10 @@ extern "C" int snnqp_dense_gated_forward(const uint32_t *s, const float *gate, i
   const int64_t gx = (NB + 31) / 32;
   SNNQP_REQUIRE(gx < ((int64_t)1 << 31), SNNQP_EUNSUPPORTED, "dense_gated_forward: more than 2^31 workgroups");
   const DenseGatedPlan plan = dense_gated_plan(N, w->code_max);
-  if (plan.wide)
-    hipLaunchKernelGGL(dense_gated_kernel<true>, dim3((unsigned)gx, (unsigned)plan.gy), dim3(256), 0,
+  gated_form(plan.wide, [&](auto wide) {
+    hipLaunchKernelGGL(dense_gated_kernel<decltype(wide)::value>, dim3((unsigned)gx, (unsigned)plan.gy), dim3(256), 0,
                        (hipStream_t)stream, a);
-  else
-    hipLaunchKernelGGL(dense_gated_kernel<false>, dim3((unsigned)gx, (unsigned)plan.gy), dim3(256), 0,
-                       (hipStream_t)stream, a);
+  });
   SNNQP_CHECK_LAUNCH("dense_gated_kernel");
   return SNNQP_OK;
 }

@@ -26,7 +26,7 @@
 #include <tuple>
 #include <vector>
 
-#include "kernels.h"
+#include "gated_tile.h"
 
 namespace snnqp {
 
@@ -164,11 +164,6 @@ denorm_probe_kernel(const int *__restrict__ b6, uint32_t cinit_bits, uint32_t *_
   for (int i = 0; i < 16; ++i) out[lane * 16 + i] = __float_as_uint(acc[i]);
 }
 
-int enc6(int v) {                    // integer -7..7 -> e2m3
-  static const int mag[8] = {0, 8, 16, 20, 24, 26, 28, 30};
-  return (v < 0 ? 32 : 0) | mag[v < 0 ? -v : v];
-}
-
 // true iff every accumulator of every chain came out as 4 * (off + column sum) exactly
 bool run_denorm_probe() {
   // three code patterns: all +7 (the positive end: 18 * 64 * 7 = 8064 units), all -7 from an
@@ -192,7 +187,7 @@ bool run_denorm_probe() {
           else if (pattern == 1) v = -7;
           else { lcg = lcg * 1664525u + 1013904223u; v = ((lcg >> 24) % 10 == 0) ? (int)((lcg >> 8) % 15) - 7 : 0; }
           colsum[lane & 31] += v;
-          const int e = enc6(v), bit = 6 * j;
+          const int e = (int)fp6_e2m3(v), bit = 6 * j;
           for (int q = 0; q < 6; ++q)
             if ((e >> q) & 1) bytes[(bit + q) >> 3] |= (unsigned char)(1 << ((bit + q) & 7));
         }

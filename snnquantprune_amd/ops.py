@@ -925,17 +925,21 @@ def conv_forward_speculative(x: torch.Tensor, geom: ConvGeom, int_weight: Weight
   return y
 
 
+def _pack_gated(codes: torch.Tensor, code_max: int, bytes_fn, pack_fn, *dims) -> torch.Tensor:
+  """bytes_fn(C, N, code_max) bytes, filled by pack_fn(codes, *dims, code_max, out, stream); dims = (C, ..., N)"""
+  codes = codes.contiguous()
+  out = torch.empty(int(bytes_fn(dims[0], dims[-1], int(code_max))), dtype=torch.uint8, device=codes.device)
+  L.check(pack_fn(_ptr(codes), *dims, int(code_max), _ptr(out), _stream()))
+  return out
+
+
 def pack_codes_gated(codes: torch.Tensor, code_max: int = 7) -> torch.Tensor:
   """int8 HWIO codes [3, 3, Cin, Cout] -> the operand layout of conv_gated_forward
   (snnqp_pack_codes_gated_ex): e2m3 for code_max <= 7, two e3m2 digits per code up to 127."""
   _require_gpu(codes)
   assert codes.dtype == torch.int8 and codes.ndim == 4 and tuple(codes.shape[:2]) == (3, 3)
-  codes = codes.contiguous()
-  cin, cout = codes.shape[2], codes.shape[3]
-  out = torch.empty(int(L.lib().snnqp_conv_gated_packed_bytes_ex(cin, cout, int(code_max))), dtype=torch.uint8,
-                    device=codes.device)
-  L.check(L.lib().snnqp_pack_codes_gated_ex(_ptr(codes), cin, cout, int(code_max), _ptr(out), _stream()))
-  return out
+  return _pack_gated(codes, code_max, L.lib().snnqp_conv_gated_packed_bytes_ex, L.lib().snnqp_pack_codes_gated_ex,
+                     codes.shape[2], codes.shape[3])
 
 
 def conv_gated_forward(x: GatedSpikes, geom: ConvGeom, weight: Weight, packed: torch.Tensor) -> torch.Tensor:
@@ -958,12 +962,8 @@ def pack_codes_dense_gated(codes: torch.Tensor, C: int, HW: int, code_max: int =
   (snnqp_pack_codes_dense_gated_ex): e2m3 for code_max <= 7, two e3m2 digits per code up to 127."""
   _require_gpu(codes)
   assert codes.dtype == torch.int8 and codes.ndim == 2 and codes.shape[0] == C * HW
-  codes = codes.contiguous()
-  N = codes.shape[1]
-  out = torch.empty(int(L.lib().snnqp_dense_gated_packed_bytes_ex(C, N, int(code_max))), dtype=torch.uint8,
-                    device=codes.device)
-  L.check(L.lib().snnqp_pack_codes_dense_gated_ex(_ptr(codes), C, HW, N, int(code_max), _ptr(out), _stream()))
-  return out
+  return _pack_gated(codes, code_max, L.lib().snnqp_dense_gated_packed_bytes_ex,
+                     L.lib().snnqp_pack_codes_dense_gated_ex, C, HW, codes.shape[1])
 
 
 def dense_gated_forward(x: GatedSpikes, weight: Weight, packed: torch.Tensor) -> torch.Tensor:
