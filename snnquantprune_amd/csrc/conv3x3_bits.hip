@@ -15,9 +15,9 @@
 // K runs over (tap, 32-channel group) pairs: the codes are padded to 32 G input channels
 // (snnqp.h), 9 G pairs, two per fp6 k-step (5 / 9 / 14 / 18 k-steps for G = 1 .. 4), one per
 // int8 k-step.  A last group of which only the lower 16 channels can spike (CIN = 16, 48, 80, 112:
-// Cin mod 32 in 1 .. 16) is walked in (tap, 16-channel) units instead and the upper 16 rows of its
-// tiles are not read: fp6 three k-steps of three units (k16_tap; 3 / 8 / 12 / 17 k-steps), int8
-// the five k-steps of the pair walk, one unit per lane half (5 / 14 / 23 / 32).
+// Cin mod 32 in 1 .. 16) is walked in (tap, 16-channel) units instead: fp6 3 / 8 / 12 / 17
+// k-steps, int8 5 / 14 / 23 / 32.  The walk, the B operand, the halo image in LDS and how a lane
+// reads its A fragments from it: BitsTile, bits_tile.h.
 //
 // A workgroup is 4 waves on one 4x8-pixel tile (patch), two workgroups per CU = two waves
 // per SIMD: wave w owns output channels [32 w, +32) of the tile, its B fragments for
@@ -34,28 +34,15 @@
 // the previous one, so the A fragments of step s + 1 are requested during the last slots of
 // step s and the matrix pipe does not drain at a step boundary (with two buffers and the
 // barrier at the end of the step every step began with an LDS round trip).
-// LDS image: one plane per 64 fp4 / 32 byte channels (32 B per pixel), rows of 12 pixels, the
-// two 16-byte halves (fp4: channel groups 2 p, 2 p + 1) swapped on odd rows: every tap/half
-// offset is an instruction immediate and the reads are bank-conflict free.  An odd fp6 G leaves
-// group G - 1 alone in the first half of the last plane; its k-steps pair two taps instead
-// (pair_tap) and read it through lane bases of their own.  A 16-channel last group (fp6) is staged
-// with its 8 bytes in both halves of its 16-byte slot; the two 8-byte pieces of a lane (k16_tap)
-// come from the half that keeps the 32 lanes of a ds_read_b64 group on 64 different banks.
-#include <type_traits>
-
-#include "conv_tile.h"
+#include "bits_tile.h"
 
 namespace snnqp {
 
-// (halo image geometry F6_*, fp6_pack32, FMT_*, pair_tap: conv_tile.h, shared with the currents
-// form of this conv, conv3x3_currents.hip)
 constexpr int F6_NBUF = 3;                   // halo images in the ring
 // (DQT_MAXA = 2047, conv_tile.h: the |acc| bound DQ_TABLE's table is sized for)
 constexpr int DQT_BYTES = 16384;             // 4095 entries
 
-// FMT: the matrix instruction the contraction runs on
-//   FMT_FP6: v_mfma_scale_f32_32x32x64_f8f6f4, fp4 spikes x fp6 codes (|code| <= 7), K = 64
-//   FMT_I8 : v_mfma_i32_32x32x32_i8, byte spikes x int8 codes (any 8-bit code), K = 32
+// FMT (bits_tile.h): the matrix instruction the contraction runs on
 // DQ (conv_tile.h): how the accumulator becomes the current fl(fl(acc / L) * m)
 //   DQ_ARITH: three float32 instructions (the exact two-instruction division of common.h)
 //   DQ_ONE  : L == 1 (2-bit DuQ codes, the step quantisers): one multiply
@@ -83,11 +70,6 @@ constexpr int F6_WR_SLOT = 2;    // slot of a step after which the staged halo i
 constexpr int F6_BAR_SLOT = 4;   // slot of a step after which the step's barrier sits
 constexpr int F6_PF = 4;         // A fragments in flight (ring of 6 or 7); 2 with a ring of 3 or 5
 
-// fp6, 16-channel last group: the tap of piece i (k rows 32 h + 16 i .. + 15) of lane half h in
-// k-step q = 0 .. 2 of that group -- h = 0: taps q and 6 + q (two halo rows apart), h = 1: tap
-// 3 + q and nothing ("tap 9": zero codes; the piece re-reads tap 6 + q)
-__host__ __device__ constexpr int k16_tap(int q, int h, int i) { return i == 0 ? q + 3 * h : h == 0 ? 6 + q : 9; }
-
 // The A ring: the fragment of k-step k lives in entry k % ring, requested pf slots ahead.  True
 // when no request overwrites an entry that is still waiting for its MFMA (always so when the ring
 // divides ks; otherwise the wrap into the next timestep has to be checked)
@@ -102,27 +84,16 @@ constexpr bool ring_ok(int ks, int ring, int pf) {
 template <int FMT, int CIN, int NF, bool POOL, int DQ, bool FMA = false, bool BNF = false, bool BNU = false>
 __global__ void __launch_bounds__(F6_NT, 2)
 conv3x3_bits_kernel(ConvMfmaArgs a) {
-  static_assert(CIN % 16 == 0 && CIN >= 16 && CIN <= 128, "one to eight 16-channel half groups");
   static_assert(!BNU || (BNF && DQ == DQ_TABLE), "the uniform multiplier folds into the shared table");
   static_assert(DQ == DQ_ARITH || DQ == DQ_ONE || DQ == DQ_TABLE, "dequantisation mode");
-  constexpr bool I8 = FMT == FMT_I8;
+  typedef BitsTile<FMT, CIN> W;                  // the K walk and the operand layout
+  typedef typename W::Bases Bases;               // lane bases of one halo image
+  typedef typename W::acc_t acc_t;
+  constexpr bool I8 = W::I8;
   constexpr bool TABLE = DQ == DQ_TABLE;
   static_assert(!(TABLE && I8), "the table is addressed by a float32 accumulator");
-  typedef typename std::conditional<I8, v16i, v16f>::type acc_t;
-  constexpr int BR = I8 ? 4 : 6;                 // registers of one B fragment
-  constexpr int WPP = (CIN + 31) / 32;           // spike words (32-channel groups) per pixel
-  constexpr int GW = CIN / 32;                   // groups walked whole
-  constexpr bool HALF = CIN % 32 != 0;           // group GW: its lower 16 channels only
-  constexpr int NP = I8 ? WPP : (WPP + 1) / 2;   // planes of the halo image
-  constexpr int NPL = I8 ? GW : GW / 2;          // planes read whole: both lane halves at one tap
-  // k-steps of the pair walk (pair_tap) over the first half of plane NPL: fp6, the last whole
-  // group when their number is odd; int8, the lower 16 channels of a 16-channel last group
-  constexpr int PAIRS = (I8 ? HALF : GW % 2 == 1) ? 5 : 0;
-  constexpr int PGRP = I8 ? GW : GW - 1;         // the group the pair walk covers
-  constexpr int K16 = !I8 && HALF ? 3 : 0;       // fp6 k-steps over a 16-channel last group (k16_tap)
-  constexpr int KS = 9 * NPL + PAIRS + K16;      // MFMAs (slots) of one timestep
-  constexpr int NPD = NPL > 0 ? NPL : 1;         // (divisor of the whole-plane k-step index)
-  constexpr int HALO_B = NP * F6_PLANE;          // one halo image
+  constexpr int KS = W::KS;                      // MFMAs (slots) of one timestep
+  constexpr int HALO_B = W::HALO_B;              // one halo image
   constexpr int FL = POOL ? 16 : 4;              // timesteps per flush block
   constexpr int SLOTS = 2 * FL;                  // ring of staged spike words
   constexpr int NPIX = OutStage<POOL>::NPIX / 2;
@@ -145,44 +116,8 @@ conv3x3_bits_kernel(ConvMfmaArgs a) {
 
   // the byte -> 8 nibbles table (int8: bits -> bytes by arithmetic)
   if (!I8) fp4_table_fill((uint32_t *)(lds + TAB_OFF), tid, F6_NT);
-  // B operand: k-step ks = NPL tap + kk (< 9 NPL) covers channels 64 kk .. +63 of the tap; lane
-  // (n, h) holds k = 32 h + j, i.e. both 16-byte halves of int8 tile WPP tap + 2 kk + h; pair
-  // k-step 9 NPL + p: lane half h holds group WPP - 1 of tap pair_tap(p, h)
-  // k16 k-step 9 NPL + PAIRS + q: lane half h holds rows 0 .. 15 of group GW's tiles of taps
-  // k16_tap(q, h, 0) and k16_tap(q, h, 1)
-  // (int8: k-step ks = GW tap + kk is int8 tile WPP tap + kk as it is, lane (n, h) holds
-  // k = 16 h + j; pair k-step p: rows 0 .. 15 of group GW's tile of tap pair_tap(p, h))
-  int bf[KS][BR];
-  {
-    const v4i *wtile = (const v4i *)a.wt + (int64_t)(cout_base >> 5) * (9 * WPP) * 64;
-#pragma unroll
-    for (int ks = 0; ks < KS; ++ks) {
-      if constexpr (I8) {
-        const int ptap = pair_tap(ks - 9 * NPL, h);
-        const bool pair = ks >= 9 * NPL;
-        const int idx = pair ? (ptap * WPP + GW) * 64 + n : ((ks / NPD) * WPP + ks % NPD) * 64 + lane;
-        const v4i t = wave_on && !(pair && ptap >= 9) ? wtile[idx] : v4i{0, 0, 0, 0};
-        bf[ks][0] = t.x; bf[ks][1] = t.y; bf[ks][2] = t.z; bf[ks][3] = t.w;
-      } else if (ks >= 9 * NPL + PAIRS) {
-        const int q = ks - 9 * NPL - PAIRS;
-        const int t0 = k16_tap(q, h, 0), t1 = k16_tap(q, h, 1);
-        v4i lo = {0, 0, 0, 0}, hi = {0, 0, 0, 0};
-        if (wave_on) lo = wtile[(t0 * WPP + GW) * 64 + n];
-        if (wave_on && t1 < 9) hi = wtile[(t1 * WPP + GW) * 64 + n];
-        fp6_pack32(lo, hi, bf[ks]);
-      } else {
-        const int ptap = pair_tap(ks - 9 * NPL, h);
-        const bool pair = ks >= 9 * NPL;
-        const int ks8 = pair ? ptap * WPP + PGRP : (ks / NPD) * WPP + (ks % NPD) * 2 + h;
-        v4i lo = {0, 0, 0, 0}, hi = {0, 0, 0, 0};
-        if (wave_on && !(pair && ptap >= 9)) {
-          lo = wtile[ks8 * 64 + n];
-          hi = wtile[ks8 * 64 + 32 + n];
-        }
-        fp6_pack32(lo, hi, bf[ks]);
-      }
-    }
-  }
+  int bf[KS][W::BR];                             // the wave's B fragments, for the whole launch
+  W::load_b(bf, a.wt, cout_base, wave_on, n, h);
 
   // DQ_TABLE: entry i of the table is the current of acc = i - A (A = a.lut_bound), computed
   // with the instructions DQ_ARITH would run on the accumulator; the chain constant is the
@@ -208,43 +143,9 @@ conv3x3_bits_kernel(ConvMfmaArgs a) {
   constexpr int SCALE_A = TABLE ? 64 : 127;
   constexpr int SCALE_B = TABLE ? 43 : 127;
 
-  const int ty = ((n >> 2) & 1) | ((n >> 4) << 1);
-  const int tx = (n & 3) | (((n >> 3) & 1) << 2);
-  // A fragment of tap (dy, dx), half kk: pixel (ty + dy, tx + dx), 32 B per pixel, the two
-  // 16-byte lane halves swapped on odd halo rows.  With the 12-pixel row pitch this makes
-  // every ds_read_b128 of the wave bank-conflict free (tools/ubench/lds_conv_patterns.hip).
-  const uint32_t pixb = lds0 + (uint32_t)((ty * F6_PITCH + tx) * 32);
-  const uint32_t abase_even = pixb + (uint32_t)((h ^ (ty & 1)) * 16);       // dy = 0, 2
-  const uint32_t abase_odd = pixb + (uint32_t)((h ^ (ty & 1) ^ 1) * 16);    // dy = 1
-  // pair k-steps (first half of plane NPL): half h one halo row lower (taps p, p + 3) or one
-  // pixel to the right (taps 6 + 2q, 7 + 2q); the same swizzle, so still conflict free
-  const uint32_t abase_pv = pixb + (uint32_t)(h * F6_PITCH * 32 + ((ty ^ h) & 1) * 16);
-  const uint32_t abase_ph = pixb + (uint32_t)(h * 32 + (ty & 1) * 16);
-  // k16 k-steps (group GW: half GW & 1 of plane GW / 2, its 8 bytes in both halves of the 16-byte
-  // slot): piece 0 at taps q / 3 + q (half h one halo row lower), piece 1 at tap 6 + q for both
-  // halves.  The 8-byte half alternates every two halo rows, so that with the 16-byte swizzle the
-  // four rows of a 32-lane group sit in four different quarters of a pixel's 32 bytes: every
-  // ds_read_b64 is bank-conflict free (tests/test_conv_k16_cpu.py)
-  const uint32_t abase_ka = pixb + (uint32_t)(h * F6_PITCH * 32 + (((GW ^ ty ^ h) & 1) * 16) +
-                                              (((ty + h) >> 1) & 1) * 8);
-  const uint32_t abase_kb = pixb + (uint32_t)((((GW ^ ty) & 1) * 16) + (((ty >> 1) & 1) ^ 1) * 8);
-  struct Bases { uint32_t e, o, pv, ph, ka, kb; };   // lane bases of one halo image
-
-  // staging task of this thread: word wi of halo pixel pix
-  const int s_pix = tid / WPP, s_wi = tid % WPP;
-  const bool s_task = tid < F6_ROWS * HALO * WPP;
-  // a pixel has ceil(Cin / 32) spike words in memory; the groups beyond them (codes padded
-  // wider than that, snnqp_weight_t.wt_cin) are zero spikes against zero codes
-  const int wpm = (a.Cin + 31) >> 5;
-  const int s_hy = s_pix / HALO, s_hx = s_pix % HALO;
-  // fp4: word wi = half wi & 1 of plane wi >> 1; bytes: word wi = both halves of plane wi
-  const uint32_t s_dst = lds0 + (uint32_t)((I8 ? s_wi : s_wi >> 1) * F6_PLANE +
-                                           (s_hy * F6_PITCH + s_hx) * 32 +
-                                           ((((I8 ? 0 : s_wi) & 1) ^ (s_hy & 1)) * 16));
-  const uint32_t tabl = fp4_table_lane(lds0 + TAB_OFF, lane);
-  // fp6, 16-channel last group: its 8 bytes (channels 0 .. 15: bytes 0, 1 of the word) twice; the
-  // upper half of the word is not looked at
-  const uint32_t s_sh2 = K16 && s_wi == GW ? 0u : 16u, s_sh3 = K16 && s_wi == GW ? 8u : 24u;
+  const Bases img0 = W::bases(lds0, n, h);       // lane bases of the ring's first halo image
+  // staging task of this thread: spike word stg.wi of halo pixel (stg.hy, stg.hx)
+  const typename W::Stage stg = W::stage_task(lds0, lds0 + TAB_OFF, tid, a.Cin);
   const uint32_t *xb = (const uint32_t *)a.x;
 
   const int ob = out_pix<POOL>(0, lane) * 4 + cg;
@@ -279,9 +180,9 @@ conv3x3_bits_kernel(ConvMfmaArgs a) {
       for (int i = 0; i < 16; ++i) u[i] = 0.0f;
     }
 
-    const int gy = y0 + s_hy - 1, gx = x0 + s_hx - 1;
-    const bool s_valid = s_task && s_wi < wpm && gy >= 0 && gy < a.H && gx >= 0 && gx < a.W;
-    const int64_t s_goff = (int64_t)b * a.xs_b + ((int64_t)gy * a.W + gx) * wpm + s_wi;
+    const int gy = y0 + stg.hy - 1, gx = x0 + stg.hx - 1;
+    const bool s_valid = stg.task && stg.wi < stg.wpm && gy >= 0 && gy < a.H && gx >= 0 && gx < a.W;
+    const int64_t s_goff = (int64_t)b * a.xs_b + ((int64_t)gy * a.W + gx) * stg.wpm + stg.wi;
     // the spike word of halo(t) is requested two steps before it is expanded (a step is about a
     // microsecond, a loaded global round trip can be longer): two registers, by parity of t
     uint32_t stgq[2] = {0, 0}, stg_cur = 0;
@@ -289,65 +190,12 @@ conv3x3_bits_kernel(ConvMfmaArgs a) {
       stgq[par] = s_valid ? xb[(int64_t)t * a.xs_t + s_goff] : 0u;
     };
     v4i s_exp = {0, 0, 0, 0};
-    auto stage_expand = [&](int par) {           // table reads; consumed by stage_write
-      if (I8) {
-        stg_cur = stgq[par];
-      } else if (s_task) {
-        const uint32_t sw = stgq[par];
-        // byte k of the word -> entry (byte << 7) of this lane's copy: conflict-free whatever
-        // the bytes of the 32 lanes are
-        s_exp.x = (int)*(lds_cu32_t *)(uintptr_t)(((sw & 0xFFu) << 7) + tabl);
-        s_exp.y = (int)*(lds_cu32_t *)(uintptr_t)((((sw >> 8) & 0xFFu) << 7) + tabl);
-        if constexpr (K16 > 0) {
-          s_exp.z = (int)*(lds_cu32_t *)(uintptr_t)((((sw >> s_sh2) & 0xFFu) << 7) + tabl);
-          s_exp.w = (int)*(lds_cu32_t *)(uintptr_t)((((sw >> s_sh3) & 0xFFu) << 7) + tabl);
-        } else {
-          s_exp.z = (int)*(lds_cu32_t *)(uintptr_t)((((sw >> 16) & 0xFFu) << 7) + tabl);
-          s_exp.w = (int)*(lds_cu32_t *)(uintptr_t)(((sw >> 24) << 7) + tabl);
-        }
-      }
-    };
-    auto stage_write = [&](uint32_t bufoff) {
-      typedef __attribute__((address_space(3))) v4i lds_v4i_t;
-      if (I8) {
-        if (s_task) {
-          const uint32_t d = s_dst + bufoff;
-          *(lds_v4i_t *)(uintptr_t)d = expand16(stg_cur & 0xFFFFu);        // channels 0..15
-          *(lds_v4i_t *)(uintptr_t)(s_hy & 1 ? d - 16 : d + 16) = expand16(stg_cur >> 16);
-        }
-      } else if (s_task) {
-        *(lds_v4i_t *)(uintptr_t)(s_dst + bufoff) = s_exp;
-      }
-    };
-    // A fragment of k-step ks from the halo image whose lane bases are ib
-    auto a_read = [&](const Bases &ib, int ks) -> v4i {
-      if (ks >= 9 * NPL + PAIRS) {                // k16 k-step: two 8-byte pieces
-        typedef __attribute__((address_space(3))) const v2i lds_cv2i_t;
-        const int q = ks - 9 * NPL - PAIRS;
-        const uint32_t off = (uint32_t)((GW >> 1) * F6_PLANE + q * 32);
-        const v2i p0 = *(lds_cv2i_t *)(uintptr_t)(ib.ka + off);
-        const v2i p1 = *(lds_cv2i_t *)(uintptr_t)(ib.kb + off + 2 * F6_PITCH * 32);
-        return v4i{p0.x, p0.y, p1.x, p1.y};
-      }
-      if (ks >= 9 * NPL) {                        // pair k-step: the padding half ("tap 9")
-        const int p = ks - 9 * NPL;               // reads pixel (2, 3), inside the image
-        const uint32_t off = (uint32_t)(NPL * F6_PLANE + (p < 3 ? p : 2 * F6_PITCH + 2 * (p - 3)) * 32);
-        return *(lds_cv4i_t *)(uintptr_t)((p < 3 ? ib.pv : ib.ph) + off);
-      }
-      const int tap = ks / NPD;
-      const uint32_t off = (uint32_t)((ks % NPD) * F6_PLANE + ((tap / 3) * F6_PITCH + tap % 3) * 32);
-      return *(lds_cv4i_t *)(uintptr_t)(((tap / 3) & 1 ? ib.o : ib.e) + off);
-    };
+    // the two steps of BitsTile's expansion: the table reads at the start of a step (consumed by
+    // stage_write), the LDS write in slot WR_SLOT
+    auto stage_expand = [&](int par) { stg_cur = stgq[par]; W::expand(stg, stg_cur, s_exp); };
+    auto stage_write = [&](uint32_t bufoff) { W::write(stg, bufoff, stg_cur, s_exp); };
     auto mfma_acc = [&](int ks, const v4i &av, const acc_t &c) -> acc_t {
-      if constexpr (I8) {
-        return __builtin_amdgcn_mfma_i32_32x32x32_i8(
-            av, v4i{bf[ks][0], bf[ks][1], bf[ks][2], bf[ks][3]}, c, 0, 0, 0);
-      } else {
-        return __builtin_amdgcn_mfma_scale_f32_32x32x64_f8f6f4(
-            v8i{av.x, av.y, av.z, av.w, 0, 0, 0, 0},
-            v8i{bf[ks][0], bf[ks][1], bf[ks][2], bf[ks][3], bf[ks][4], bf[ks][5], 0, 0}, c,
-            4 /* A: fp4 */, 2 /* B: fp6 */, 0, SCALE_A, 0, SCALE_B);
-      }
+      return W::template mfma<SCALE_A, SCALE_B>(av, bf[ks], c);
     };
     const acc_t zero16 = {0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0};
     auto dequant1 = [&](auto a0) -> float {
@@ -514,8 +362,8 @@ conv3x3_bits_kernel(ConvMfmaArgs a) {
         else accN = mfma_acc(ks, A[ks % RING], accN);                   // the chain constants)
         __builtin_amdgcn_sched_barrier(0);
         // the slot's A read: PF slots ahead, wrapping into the next step's image
-        if (ks + PF < KS) A[(ks + PF) % RING] = a_read(rd, ks + PF);
-        else if (more) A[(ks + PF - KS) % RING] = a_read(rn, ks + PF - KS);
+        if (ks + PF < KS) A[(ks + PF) % RING] = W::a_read(rd, ks + PF);
+        else if (more) A[(ks + PF - KS) % RING] = W::a_read(rn, ks + PF - KS);
         // an even share of the epilogue stages
         {
           const int lo = ks * NSTAGES / KS, hi = (ks + 1) * NSTAGES / KS;
@@ -563,10 +411,7 @@ conv3x3_bits_kernel(ConvMfmaArgs a) {
     };
 
     // lane bases of the halo images: halo(t) lives in image t % 3 of the ring
-    auto img = [&](int k) {
-      const uint32_t d = (uint32_t)(k * HALO_B);
-      return Bases{abase_even + d, abase_odd + d, abase_pv + d, abase_ph + d, abase_ka + d, abase_kb + d};
-    };
+    auto img = [&](int k) { return img0.at((uint32_t)(k * HALO_B)); };
 
     // pipeline prologue: halo(0), halo(1) staged; MFMA(0) alone
     acc_t accA, accB;
@@ -586,13 +431,13 @@ conv3x3_bits_kernel(ConvMfmaArgs a) {
     {
       const Bases i0 = img(0), i1 = img(1);
 #pragma unroll
-      for (int i = 0; i < PF; ++i) A[i] = a_read(i0, i);
+      for (int i = 0; i < PF; ++i) A[i] = W::a_read(i0, i);
 #pragma unroll
       for (int ks = 0; ks < KS; ++ks) {
         if (ks == 0) accA = mfma_acc(0, A[0], TABLE ? cblk : zero16);
         else accA = mfma_acc(ks, A[ks % RING], accA);
-        if (ks + PF < KS) A[(ks + PF) % RING] = a_read(i0, ks + PF);
-        else if (a.T > 1) A[(ks + PF - KS) % RING] = a_read(i1, ks + PF - KS);
+        if (ks + PF < KS) A[(ks + PF) % RING] = W::a_read(i0, ks + PF);
+        else if (a.T > 1) A[(ks + PF - KS) % RING] = W::a_read(i1, ks + PF - KS);
         __builtin_amdgcn_sched_barrier(0);
       }
     }

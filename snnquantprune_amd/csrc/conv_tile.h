@@ -1,6 +1,7 @@
-// Device helpers shared by the fused conv3x3 MFMA kernels (conv3x3_u8c2.hip,
-// conv3x3_bits.hip): patch schedule, LDS tables, the neuron epilogue on the MFMA
-// C/D layout, spike-word staging.  gfx950 only.
+// Device helpers shared by the conv3x3 MFMA kernels, the event layer (conv3x3_u8c2.hip) as well
+// as the bit-input conv (conv3x3_bits.hip, conv3x3_currents.hip): launch arguments, patch schedule,
+// LDS tables, the neuron epilogue on the MFMA C/D layout, spike-word staging.  What only the
+// bit-input conv uses -- its halo image and operand layout -- is in bits_tile.h.  gfx950 only.
 #pragma once
 #include "kernels.h"
 
@@ -54,40 +55,6 @@ constexpr int HALO = 10;
 // B/clk/CU; the earlier pixel-major image with an XOR swizzle measured 63).
 constexpr int HPITCH = 12;
 constexpr int HPLANE = HALO * HPITCH * 32;      // one k-step plane
-
-// The bit-input 3x3 kernels (conv3x3_bits.hip and its currents form conv3x3_currents.hip): a
-// workgroup of four waves on one 4x8-pixel tile, the same halo image in LDS
-typedef __attribute__((address_space(3))) const v4i lds_cv4i_t;
-
-constexpr int F6_PITCH = HPITCH;             // pixels per LDS halo row (10 used)
-constexpr int F6_ROWS = 6;                   // halo rows of a 4x8 patch
-constexpr int F6_NT = 256;                   // threads of a workgroup: 4 waves
-constexpr int F6_PLANE = F6_ROWS * HPITCH * 32;   // one k-step plane of a halo image
-constexpr int F6_TAB = FP4_TAB_BYTES;        // byte -> 8 fp4 nibbles (tile_util.h)
-
-// 32 int8 codes in k order (lo = k 0..15, hi = k 16..31) -> 32 fp6 values, value j
-// at bits [6j, 6j + 6) of 6 dwords (the B fragment of one lane for one k-step)
-__device__ __forceinline__ void fp6_pack32(const v4i &lo, const v4i &hi, int (&d)[6]) {
-  uint32_t t[8];
-#pragma unroll
-  for (int i = 0; i < 4; ++i) {
-    t[i] = squeeze6(fp6_codes4((uint32_t)lo[i]));
-    t[4 + i] = squeeze6(fp6_codes4((uint32_t)hi[i]));
-  }
-#pragma unroll
-  for (int g = 0; g < 2; ++g) {
-    d[3 * g + 0] = (int)(t[4 * g] | (t[4 * g + 1] << 24));
-    d[3 * g + 1] = (int)((t[4 * g + 1] >> 8) | (t[4 * g + 2] << 16));
-    d[3 * g + 2] = (int)((t[4 * g + 2] >> 16) | (t[4 * g + 3] << 8));
-  }
-}
-
-// the matrix instruction the contraction runs on (conv3x3_bits.hip)
-enum { FMT_FP6 = 0, FMT_I8 = 1 };
-
-// fp6, odd G: the tap lane half h reads in pair k-step p of the last group -- (0, 3), (1, 4),
-// (2, 5) one halo row apart, (6, 7), (8, -) one pixel apart; "tap 9" has zero codes
-__host__ __device__ constexpr int pair_tap(int p, int h) { return p < 3 ? p + 3 * h : 2 * p + h; }
 
 struct ConvMfmaArgs {
   const void *x;

@@ -188,7 +188,7 @@ dense_fp6_kernel(DenseFp6Args a) {
     return w & rmask[k] & (uint32_t)((chunk_word(chunk, k) - a.KW) >> 31);
   };
   auto lookup = [&](uint32_t w, int d) -> int {
-    return (int)*(lds_cu32_t *)(uintptr_t)((((w >> (8 * d)) & 0xFFu) << 7) + tabl);
+    return (int)fp4_table_entry(tabl, (w >> (8 * d)) & 0xFFu);
   };
   int wr_off[TPT];
 #pragma unroll

@@ -17,6 +17,7 @@ typedef float v16f __attribute__((ext_vector_type(16)));
 typedef __attribute__((address_space(3))) const float lds_cfloat_t;
 typedef __attribute__((address_space(3))) const uint8_t lds_cu8_t;
 typedef __attribute__((address_space(3))) const uint32_t lds_cu32_t;
+typedef __attribute__((address_space(3))) v4i lds_v4i_t;
 __device__ __forceinline__ uint32_t lds_addr(const void *p) {
   return (uint32_t)(uintptr_t)(lds_cu8_t *)p;
 }
@@ -52,9 +53,13 @@ __device__ __forceinline__ void fp4_table_fill(uint32_t *tab, int tid, int nthre
     tab[i] = v;
   }
 }
-// this lane's copy of the table at LDS address `tab`; the entry of byte b is at (b << 7) + base
+// this lane's copy of the table at LDS address `tab`
 __device__ __forceinline__ uint32_t fp4_table_lane(uint32_t tab, int lane) {
   return tab + (uint32_t)(lane & 31) * 4;
+}
+// the entry of `byte` (< 256) in the copy `tabl` (fp4_table_lane): its 8 nibbles
+__device__ __forceinline__ uint32_t fp4_table_entry(uint32_t tabl, uint32_t byte) {
+  return *(lds_cu32_t *)(uintptr_t)((byte << 7) + tabl);
 }
 
 // 4 int8 codes (|c| <= 7) -> 4 e2m3 codes, one per byte

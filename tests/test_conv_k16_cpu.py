@@ -1,5 +1,5 @@
-"""CPU checks of the 16-channel K walk of the bit-input 3x3 conv kernel (conv3x3_bits.hip,
-DESIGN.md 4.3.1): the address model of test_conv_kpack_cpu.py extended to a last channel group of
+"""CPU checks of the 16-channel K walk of the bit-input 3x3 conv kernel (conv3x3_bits.hip on the
+layout of bits_tile.h): the address model of test_conv_kpack_cpu.py extended to a last channel group of
 which only the lower 16 channels are walked (CIN = 16, 48, 80, 112).  On a model of the LDS halo
 image as the kernel stages it and of its lane addressing: every A piece meets the code rows of its
 own (tap, 16-channel) unit, every (tap, channel) is covered exactly once, empty units meet zero
@@ -7,7 +7,7 @@ codes, the k-step counts are the ones DESIGN.md lists, the A ring never overwrit
 is still waiting for its MFMA, and the lanes of one LDS read group hit distinct banks."""
 import pytest
 
-# conv3x3_bits.hip / conv_tile.h
+# bits_tile.h (BitsTile: the layout conv3x3_bits.hip and conv3x3_currents.hip share); HALO: conv_tile.h
 F6_PITCH, F6_ROWS, HALO = 12, 6, 10
 F6_PLANE = F6_ROWS * F6_PITCH * 32
 KS_TABLE = {("fp6", 16): 3, ("fp6", 48): 8, ("fp6", 80): 12, ("fp6", 112): 17,

@@ -1,4 +1,4 @@
-"""CPU checks of the K packing of the bit-input 3x3 conv kernel (conv3x3_bits.hip):
+"""CPU checks of the K packing of the bit-input 3x3 conv kernels (bits_tile.h):
 the Cin padding rule of the packed codes, and -- on a model of the kernel's LDS halo image and
 lane addressing -- that the k-steps it walks pair every A fragment with the int8 tile of the same
 (tap, 32-channel group), each exactly once."""
@@ -6,7 +6,7 @@ import pytest
 
 from snnquantprune_amd import packing
 
-# conv3x3_bits.hip / conv_tile.h
+# bits_tile.h (BitsTile: the layout conv3x3_bits.hip and conv3x3_currents.hip share); HALO: conv_tile.h
 F6_PITCH, F6_ROWS, HALO = 12, 6, 10
 F6_PLANE = F6_ROWS * F6_PITCH * 32
 
