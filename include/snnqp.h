@@ -242,7 +242,8 @@ typedef struct {
  * snnqp_conv_grad_splits, snnqp_conv_weight_grad_workspace_bytes, snnqp_maxpool2x2_backward;
  * 507: snnqp_conv_forward_ex -- currents from the bit-input MFMA conv; within 507, layout-
  * compatible: snnqp_weight_t.cout_fire in the struct's former tail padding,
- * snnqp_set_event_half_group, snnqp_conv_event_half_group; training of CextNet's gated stages --
+ * snnqp_set_event_half_group, snnqp_conv_event_half_group, snnqp_set_event_wave_spread,
+ * snnqp_conv_event_wave_spread; training of CextNet's gated stages --
  * snnqp_gate_pool_grad_gate, snnqp_gate_pool_grad_input, snnqp_conv_weight_grad_f64,
  * snnqp_conv_weight_grad_f64_workspace_bytes; the batched event front end snnqp_events_bin and its augmenting
  * form snnqp_events_bin_aug with snnqp_event_aug_t; the host-side
@@ -279,6 +280,18 @@ int snnqp_set_event_half_group(int enabled);
  * given), a negative error for a null or malformed descriptor.  Launches nothing. */
 int snnqp_conv_event_half_group(int in_type, int32_t T, const snnqp_conv_geom_t *g, const snnqp_weight_t *w,
                                 const snnqp_neuron_t *nrn, int has_state, int pool, int x_max);
+/* The wave spread of the event layer.  1 (the default): among the launches of the half group's family
+ * (bit-packed frames, pool 1 or 2, no state carried, one staging chunk, per-channel tables, the
+ * v_reset = 0 neuron with a multiplied time constant) the two whose four waves would carry unequal
+ * work -- Cout = 96 on the half-group path, and Cout = 64 not on it -- give every wave one (channel
+ * group, 4x8 tile) unit of channels 0..63 and, at 96, a quarter of the half group's neuron updates.
+ * 0: wave w computes channel group w (the same results).  Process-wide, for the launches enqueued
+ * after the call; returns the previous setting.  A negative argument only queries. */
+int snnqp_set_event_wave_spread(int enabled);
+/* 1 when that launch would run on the spread path under the current settings (of this switch and of
+ * snnqp_set_event_half_group), 0 when not, a negative error: as snnqp_conv_event_half_group. */
+int snnqp_conv_event_wave_spread(int in_type, int32_t T, const snnqp_conv_geom_t *g, const snnqp_weight_t *w,
+                                 const snnqp_neuron_t *nrn, int has_state, int pool, int x_max);
 
 int snnqp_conv_out_shape(const snnqp_conv_geom_t *g, int32_t *OH, int32_t *OW);
 

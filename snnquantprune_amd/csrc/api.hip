@@ -9,6 +9,8 @@ static std::atomic<int> g_conv_k16{1};
 bool conv_k16_enabled() { return g_conv_k16.load(std::memory_order_relaxed) != 0; }
 static std::atomic<int> g_event_half_group{1};
 bool event_half_group_enabled() { return g_event_half_group.load(std::memory_order_relaxed) != 0; }
+static std::atomic<int> g_event_wave_spread{1};
+bool event_wave_spread_enabled() { return g_event_wave_spread.load(std::memory_order_relaxed) != 0; }
 
 static thread_local std::string g_last_error;
 
@@ -42,6 +44,11 @@ int snnqp_set_conv_k16(int enabled) {
 int snnqp_set_event_half_group(int enabled) {
   if (enabled < 0) return snnqp::event_half_group_enabled() ? 1 : 0;
   return snnqp::g_event_half_group.exchange(enabled ? 1 : 0, std::memory_order_relaxed);
+}
+
+int snnqp_set_event_wave_spread(int enabled) {
+  if (enabled < 0) return snnqp::event_wave_spread_enabled() ? 1 : 0;
+  return snnqp::g_event_wave_spread.exchange(enabled ? 1 : 0, std::memory_order_relaxed);
 }
 
 int snnqp_conv_out_shape(const snnqp_conv_geom_t *g, int32_t *OH, int32_t *OW) {

@@ -88,8 +88,13 @@ __host__ __device__ inline int u8c2_table_bytes(int lutm, int bound, int rows) {
 #ifndef SNNQP_U8C2_EV1_ONE_WPS
 #define SNNQP_U8C2_EV1_ONE_WPS 6
 #endif
-template <int NF, bool POOL, int LUTM, int IN, bool ONE>
+// The spread instances (below) with the fused pool: six, like the instance they stand in for.
+#ifndef SNNQP_U8C2_SPREAD_WPS
+#define SNNQP_U8C2_SPREAD_WPS 6
+#endif
+template <int NF, bool POOL, int LUTM, int IN, bool ONE, bool SPREAD = false>
 constexpr int u8c2_waves() {
+  if (SPREAD && POOL) return SNNQP_U8C2_SPREAD_WPS;
   if (IN == SNNQP_EV1 && ONE && LUTM == LUT_CHANNEL && NF == NF_MUL0 && POOL) return SNNQP_U8C2_EV1_ONE_WPS;
   if (IN == SNNQP_EV1) return SNNQP_U8C2_EV1_WPS;
   return ONE ? SNNQP_U8C2_ONE_WPS : U8C2_WPS;
@@ -104,13 +109,27 @@ constexpr int u8c2_waves() {
 // updates.  All 32 k rows carry taps, so the table address comes in as the C operand; lane n >= 16 builds
 // its twin's table (codes, BatchNorm) in its own slot.  The other waves, the staging, the barriers, the
 // flush and the queue are the full path's.
-template <int NF, bool POOL, int LUTM, int IN = SNNQP_U8, bool ONE = false, bool HALF = false>
-__global__ void __launch_bounds__(256, (u8c2_waves<NF, POOL, LUTM, IN, ONE>()))
+//
+// SPREAD (the wave spread): the launches of that family that would leave waves idle or
+// unevenly loaded -- 64 channels (two waves idle), and 96 channels with the half group (32 / 32 / 16 /
+// 0 registers of neuron updates per wave and timestep) -- with the same work on every wave.  The
+// four (channel group g, tile) units of channels 0..63 go one to a wave: wave w computes tile w & 1 of
+// group g = w >> 1, one MFMA and 16 potentials, and stores word g of that tile's pixels.  With HALF
+// every wave also issues the half group's MFMA (the operands of the HALF wave above) and runs the
+// epilogue on a quarter of its product: the columns 4 (w & 1) ..+3 of the image rows 4 g ..+3, which
+// the wave brings into registers 0..3 by permuting the rows of its A operand (lane n reads the pixel
+// of lane n ^ 8 w; tile_epilogue_quarter), and stores word 2 of those pixels.  The matrix pipe, nearly
+// idle in this kernel, computes that product four times; the vector work of a patch-step is the same
+// and every wave carries 16 (+ 4) potentials.  The tables are built as ever, wave = channel group
+// (wave 2: the half group's twins); a wave then takes the table addresses of the groups it computes
+// from the scratch.  Staging, barriers, flush, queue and LDS plan are the full path's.
+template <int NF, bool POOL, int LUTM, int IN = SNNQP_U8, bool ONE = false, bool HALF = false, bool SPREAD = false>
+__global__ void __launch_bounds__(256, (u8c2_waves<NF, POOL, LUTM, IN, ONE, SPREAD>()))
 conv3x3_u8c2_kernel(ConvMfmaArgs a) {
   constexpr int FL = OutStage<POOL>::FL;
   constexpr bool EV1 = IN == SNNQP_EV1;
-  static_assert(!HALF || (EV1 && ONE && LUTM == LUT_CHANNEL && NF == NF_MUL0),
-                "the half group: bit-packed frames, one chunk, per-channel tables, NF_MUL0");
+  static_assert(!(HALF || SPREAD) || (EV1 && ONE && LUTM == LUT_CHANNEL && NF == NF_MUL0),
+                "the half group, the wave spread: bit-packed frames, one chunk, per-channel tables, NF_MUL0");
   constexpr bool EV4 = IN == SNNQP_EV4;     // one byte per pixel: polarity 0 low nibble, 1 high
   // float32 frames as the reference hands them over (flax_qconv.py:101): eight bytes per pixel,
   // converted to the two count bytes and checked while they wait in registers (snnqp.h, x_flags)
@@ -134,7 +153,7 @@ conv3x3_u8c2_kernel(ConvMfmaArgs a) {
   const int cout = wave_on ? cout_base + n : n;
   const int cpar = cout < a.Cout ? cout : a.Cout - 1;      // parameter loads
   // (the channels from cout_fire on are the caller's silent ones: their bits are stored as zeros)
-  const uint32_t cmask = chan_mask(cout_base, a.cout_fire);
+  uint32_t cmask = chan_mask(cout_base, a.cout_fire);
   // the wave of the half group (a scalar), and the channel whose codes and table this lane holds
   const bool half_wave = HALF && cout_base + 32 == a.Cout;
   const int ctab = half_wave && n >= 16 ? cout - 16 : cout;
@@ -167,6 +186,7 @@ conv3x3_u8c2_kernel(ConvMfmaArgs a) {
     }
   }
   int ch_row0 = 0, ch_col = 0;      // LUT_CHANNEL: the table row and column of this lane's entry of acc = 0
+  int hg_row0 = 0, hg_col = 0;      // SPREAD: the same of this lane's channel of the half group
   if (LUTM == LUT_CHANNEL) {
     // what this lane's channel can accumulate: the sums of its positive and |negative| codes
     // (the lane halves hold k 0..15 and 16..23 of the same channel), times the largest input
@@ -198,6 +218,18 @@ conv3x3_u8c2_kernel(ConvMfmaArgs a) {
 #pragma unroll
     for (int k = 0; k < 4; ++k) total += (int)scr[(slot & ~3) + k];
     ch_row0 = start + neg * a.x_limit;
+    if constexpr (SPREAD) {
+      // the entries of acc = 0 this wave reads in the loop: channel n of its own group w >> 1, and of
+      // the half group (group 2), as the waves of those groups just wrote them down
+      auto entry_of = [&](int grp, int &row0, int &col) {
+        int s = 4 * n + grp;
+        if (a.ch_slots) s = a.ch_slots[blockIdx.y * 128 + grp * 32 + n] & 127;
+        row0 = lut_column_start(scr, s) + (int)scr[128 + grp * 32 + n];
+        col = s >> 2;
+      };
+      entry_of(wave >> 1, ch_row0, ch_col);
+      if (HALF) entry_of(2, hg_row0, hg_col);
+    }
     // a column taller than the launch reserved: snnqp_weight_t.ch_stack_max is below the codes it
     // came with.  Its entries are not written (reads beyond the allocation return zeros): wrong
     // currents, reported -- the next call fails until the status is reset (snnqp.h).
@@ -223,7 +255,46 @@ conv3x3_u8c2_kernel(ConvMfmaArgs a) {
   float acc_off = 0.0f;
   int tab0 = 0;
   v4i bf, bfg;
-  {
+  v4i bfh = {0, 0, 0, 0};           // SPREAD with HALF: the half group's B fragment (`bf`: the own group's)
+  if constexpr (SPREAD) {
+    // lane (n, h) holds k = 16 h .. 16 h + 15 of one channel: `shift` = 0, the address `bias` of its table
+    // entry of acc = 0 in the constant rows (own group), or every k row a tap, `shift` = 8 for the twin
+    // lanes n >= 16 (half group: the address is the C operand)
+    auto taps = [&](int chan, int shift, bool all_taps, int bias) {
+      int q = bias / 127;
+      const int r = bias - 127 * q;
+      int v[4];
+#pragma unroll
+      for (int d = 0; d < 4; ++d) {
+        uint32_t pk = 0;
+#pragma unroll
+        for (int j = 0; j < 4; ++j) {
+          const int k = 16 * h + 4 * d + j, kk = k - shift;
+          uint32_t bv = 0;
+          if (all_taps || k < 24) {
+            if (kk >= 0 && kk < 24 && (kk & 7) < 6)
+              bv = (uint8_t)(a.w[(int64_t)(6 * (kk >> 3) + (kk & 7)) * a.Cout + chan] * 8);
+          } else if (k < 28) {
+            const int part = q < 127 ? q : 127;
+            q -= part;
+            bv = (uint32_t)part;
+          } else if (k == 28) {
+            bv = (uint32_t)r;
+          }
+          pk |= bv << (8 * j);
+        }
+        v[d] = (int)pk;
+      }
+      return v4i{v[0], v[1], v[2], v[3]};
+    };
+    const int tbase = (int)lds_addr(lds) + lut_off;
+    bf = taps(blockIdx.y * 128 + (wave >> 1) * 32 + n, 0, false, tbase + 4 * (ch_row0 * 32 + ch_col));
+    bfg = bf;                       // (bit-packed frames within per-channel tables: no general path)
+    if (HALF) {
+      tab0 = tbase + 4 * (hg_row0 * 32 + hg_col);
+      bfh = taps(blockIdx.y * 128 + 64 + (n & 15), n >= 16 ? 8 : 0, true, 0);
+    }
+  } else {
     int bias = 0;
     if (LUTM == LUT_SHARED) bias = (int)lds_addr(lds) + lut_off + 4 * a.lut_bound;
     if (LUTM == LUT_CHANNEL)     // row of acc = 0 of this lane's channel, its column
@@ -281,7 +352,9 @@ conv3x3_u8c2_kernel(ConvMfmaArgs a) {
   const int cpy = tx & 1;
   const int px0 = (int)lds_addr(lds) + cpy * HCOPY2 + 2 * tx + 2 * cpy;
   // (the half-group wave: halo rows Y + 2 h and, at an immediate offset, Y + 2 h + 1 of image row Y = 2 ty)
-  const int tyh = half_wave ? 2 * ty : ty;
+  // (the wave that runs the half group's loop: under SPREAD every wave runs a quarter of it instead)
+  const bool half_loop = half_wave && !SPREAD;
+  const int tyh = half_loop ? 2 * ty : ty;
   int offA[2], offB[2];
 #pragma unroll
   for (int tl = 0; tl < 2; ++tl) {
@@ -289,12 +362,37 @@ conv3x3_u8c2_kernel(ConvMfmaArgs a) {
     offB[tl] = h ? (int)lds_addr(lds) + HCONST2 : px0 + (ty + 4 * tl + 1) * HROW2;
   }
   // (the half-group wave reads no second fragment: the register carries its table address, the C operand)
-  if (HALF && half_wave) offB[1] = tab0;
+  if (HALF && half_loop) offB[1] = tab0;
   const uint8_t *xb = (const uint8_t *)a.x;
   // (the half-group wave: lane = (pooled) pixel of the patch, sixteen or all sixty-four of them)
-  const int ob0 = (half_wave ? lane : out_pix<POOL>(0, lane)) * 4 + wave;
-  const int ob1 = out_pix<POOL>(1, lane) * 4 + wave;
-  const bool store_lane = POOL ? lane < (half_wave ? 16 : 8) : (half_wave || lane < 32);
+  int ob0 = (half_loop ? lane : out_pix<POOL>(0, lane)) * 4 + wave;
+  int ob1 = out_pix<POOL>(1, lane) * 4 + wave;
+  const bool store_lane = POOL ? lane < (half_loop ? 16 : 8) : (half_loop || lane < 32);
+  // SPREAD: the own unit is tile w & 1 of group g = w >> 1 (fragment: offA[0], offB[0]; word g of the
+  // tile's pixels: ob0, stored by `store_lane`, masked by `cmask`); the quarter of the half group reads
+  // the four halo rows of the pixel of lane n ^ 8 w (offA[1], + HROW2; C: offB[1]) and leaves word 2 of
+  // pixel (row 4 g + r, column 4 (w & 1) + i) in lane 4 r + i, pooled: of pixel (row 2 g + (lane >> 2),
+  // column 2 (w & 1) + (lane & 1)) in lanes 0, 1, 4, 5 (ob1, `quarter_lane`, `qmask`)
+  bool quarter_lane = false;
+  uint32_t qmask = 0u;
+  if constexpr (SPREAD) {
+    const int g = wave >> 1, q = wave & 1;
+    offA[0] = q ? offA[1] : offA[0];
+    offB[0] = q ? offB[1] : offB[0];
+    ob0 = out_pix<POOL>(q, lane) * 4 + g;
+    cmask = chan_mask(blockIdx.y * 128 + g * 32, a.cout_fire);
+    if (HALF) {
+      const int np = n ^ (8 * wave);
+      const int typ = ((np >> 2) & 1) | ((np >> 4) << 1), txp = (np & 3) | (((np >> 3) & 1) << 2);
+      offA[1] = (int)lds_addr(lds) + cpy * HCOPY2 + 2 * txp + 2 * cpy + (2 * typ + 2 * h) * HROW2;
+      offB[1] = tab0;
+      const int pix = POOL ? (2 * g + ((lane >> 2) & 1)) * 4 + 2 * q + (lane & 1)
+                           : (4 * g + ((lane >> 2) & 3)) * 8 + 4 * q + (lane & 3);
+      ob1 = pix * 4 + 2;
+      quarter_lane = POOL ? lane < 8 && (lane & 2) == 0 : lane < 16;
+      qmask = chan_mask(blockIdx.y * 128 + 64, a.cout_fire);
+    }
+  }
   uint32_t seen = 0;                       // largest input value this thread's waves met
   // staged chunks by their largest value: <= 1, <= 2, <= 7, <= 31, above (workgroup-uniform
   // counters; they reach x_seen[1..5] once, at the end of the launch)
@@ -500,11 +598,50 @@ conv3x3_u8c2_kernel(ConvMfmaArgs a) {
       constexpr bool FMA = decltype(fma_tag)::value;
       constexpr bool OFFS = MODE == LUT_NONE;
       const v4i bw = OFFS ? bfg : bf;
+      if constexpr (SPREAD) {
+        // every wave: its own (group, tile) unit, then its quarter of the half group's product
+        int ctab0 = offB[1];
+        asm volatile("" : "+v"(ctab0));
+        // (made per patch, like the half-group wave's; only registers 0..3 of the product are read, so only
+        // those of C are given a value: the other twelve need no register of their own)
+        const v4i c4 = {ctab0, ctab0, ctab0, ctab0};
+        const v16i c0 = __builtin_shufflevector(c4, c4, 0, 1, 2, 3, -1, -1, -1, -1, -1, -1, -1, -1, -1, -1, -1, -1);
+        for (int tf = 0; tf < nt; tf += FL) {
+          const int nf = min(FL, nt - tf);
+#pragma unroll 1
+          for (int tt = tf; tt < tf + nf; ++tt) {
+            const uint32_t img = (uint32_t)(tt * HIMG2);
+            uint32_t *o = obuf + ((t0 + tt) % FL) * (OutStage<POOL>::NPIX * 4);
+            {
+              const v2i_a4 lo = *(lds_cv2i_t *)(uintptr_t)(img + (uint32_t)offA[0]);
+              const v2i_a4 hi = *(lds_cv2i_t *)(uintptr_t)(img + (uint32_t)offB[0]);
+              v16i acc = splat16(0);
+              acc = __builtin_amdgcn_mfma_i32_32x32x32_i8(v4i{lo.x, lo.y, hi.x, hi.y}, bw, acc, 0, 0, 0);
+              const uint32_t word = tile_epilogue_halves<NF, POOL, MODE, FMA, OFFS>(acc, u[0], a.dq, lc, a.nrn,
+                                                                                    lane, acc_off);
+              if (store_lane) o[ob0] = word & cmask;
+            }
+            if constexpr (HALF) {
+              const v2i_a4 lo = *(lds_cv2i_t *)(uintptr_t)(img + (uint32_t)offA[1]);
+              const v2i_a4 hi = *(lds_cv2i_t *)(uintptr_t)(img + (uint32_t)offA[1] + (uint32_t)HROW2);
+              const v16i acc = __builtin_amdgcn_mfma_i32_32x32x32_i8(v4i{lo.x, lo.y, hi.x, hi.y}, bfh, c0,
+                                                                     0, 0, 0);
+              const uint32_t word = tile_epilogue_quarter<NF, POOL, MODE, FMA, OFFS>(acc, u[1], a.dq, lc, a.nrn,
+                                                                                     acc_off);
+              if (quarter_lane) o[ob1] = word & qmask;
+            }
+          }
+          lds_barrier();
+          flush_out<POOL>(obuf, a, t0 + tf, nf, b, y0, x0, tid);
+          lds_barrier();
+        }
+        return;
+      }
       if constexpr (HALF) {
         // the wave of the half group, on a scalar branch: one MFMA from C = the table address, 16
         // potentials, one word per (pooled) pixel of the patch; the barriers and the flush are the
         // other waves'
-        if (half_wave) {
+        if (half_loop) {
           // (sixteen registers, made per patch: as a loop invariant they would live through the staging code)
           int ctab0 = offB[1];
           asm volatile("" : "+v"(ctab0));
@@ -606,11 +743,12 @@ conv3x3_u8c2_kernel(ConvMfmaArgs a) {
 // ---------------------------------------------------------------------------
 
 // What an event-layer launch is made of -- table mode, staging chunk, LDS bytes, the ONE and HALF
-// variants -- decided in one place for the launch and for snnqp_conv_event_half_group.
+// and SPREAD variants -- decided in one place for the launch and for the predicates
+// snnqp_conv_event_half_group / snnqp_conv_event_wave_spread.
 namespace {
 struct U8c2Plan {
   int32_t x_limit, lut_bound, lut_rows, tchunk;
-  bool lut, lutc, one, half;
+  bool lut, lutc, one, half, spread;
   size_t ldsb;
 };
 U8c2Plan u8c2_plan(int in_type, int32_t T, int32_t Cout, const snnqp_weight_t *w, int nf, bool has_state,
@@ -663,22 +801,37 @@ U8c2Plan u8c2_plan(int in_type, int32_t T, int32_t Cout, const snnqp_weight_t *w
   // 32-channel group in a 16-channel half (template parameter HALF; snnqp_set_event_half_group)
   p.half = event_half_group_enabled() && ev1 && p.one && p.lutc && nf == NF_MUL0 && w->cout_fire > 0 &&
            w->cout_fire % 16 == 0 && w->cout_fire + 16 == Cout && Cout % 32 == 0;
+  // ... and of that family the two launches whose four waves would carry unequal work: 96 channels
+  // with the half group, and 64 channels (template parameter SPREAD; snnqp_set_event_wave_spread)
+  p.spread = event_wave_spread_enabled() && ev1 && p.one && p.lutc && nf == NF_MUL0 &&
+             (p.half ? Cout == 96 : Cout == 64);
   return p;
 }
 }  // namespace
 
-int conv3x3_event_half_group(int in_type, int32_t T, const snnqp_conv_geom_t *g, const snnqp_weight_t *w,
-                             const snnqp_neuron_t *nrn, bool has_state, int pool, int x_max) {
-  SNNQP_REQUIRE(g && w && nrn, SNNQP_EINVAL, "conv_event_half_group: null descriptor");
-  SNNQP_REQUIRE(pool == 1 || pool == 2, SNNQP_EINVAL, "conv_event_half_group: pool must be 1 or 2");
-  SNNQP_REQUIRE(T >= 0, SNNQP_EINVAL, "conv_event_half_group: negative T");
+// The two predicates: `who` opens the messages, `flag` is the plan's answer.
+static int event_plan_flag(const char *who, bool U8c2Plan::*flag, int in_type, int32_t T, const snnqp_conv_geom_t *g,
+                           const snnqp_weight_t *w, const snnqp_neuron_t *nrn, bool has_state, int pool, int x_max) {
+  SNNQP_REQUIRE(g && w && nrn, SNNQP_EINVAL, "%s: null descriptor", who);
+  SNNQP_REQUIRE(pool == 1 || pool == 2, SNNQP_EINVAL, "%s: pool must be 1 or 2", who);
+  SNNQP_REQUIRE(T >= 0, SNNQP_EINVAL, "%s: negative T", who);
   if (in_type != SNNQP_EV1 || T == 0) return 0;
   BlockCall c;
   c.in_type = in_type; c.g = g; c.w = w; c.nrn = nrn;
   if (conv3x3_mfma_unsupported(c)) return 0;
   SNNQP_REQUIRE(w->L >= 1.0f, SNNQP_EINVAL, "dequant L must be >= 1");
-  if (int rc = conv3x3_check_cout_fire("conv_event_half_group", w, g->Cout)) return rc;
-  return u8c2_plan(in_type, T, g->Cout, w, neuron_form(make_neuron(nrn)), has_state, pool == 2, x_max).half ? 1 : 0;
+  if (int rc = conv3x3_check_cout_fire(who, w, g->Cout)) return rc;
+  return u8c2_plan(in_type, T, g->Cout, w, neuron_form(make_neuron(nrn)), has_state, pool == 2, x_max).*flag ? 1 : 0;
+}
+
+int conv3x3_event_half_group(int in_type, int32_t T, const snnqp_conv_geom_t *g, const snnqp_weight_t *w,
+                             const snnqp_neuron_t *nrn, bool has_state, int pool, int x_max) {
+  return event_plan_flag("conv_event_half_group", &U8c2Plan::half, in_type, T, g, w, nrn, has_state, pool, x_max);
+}
+
+int conv3x3_event_wave_spread(int in_type, int32_t T, const snnqp_conv_geom_t *g, const snnqp_weight_t *w,
+                              const snnqp_neuron_t *nrn, bool has_state, int pool, int x_max) {
+  return event_plan_flag("conv_event_wave_spread", &U8c2Plan::spread, in_type, T, g, w, nrn, has_state, pool, x_max);
 }
 
 // The instance of a launch, one template parameter per step: table mode (launch_conv3x3_u8c2), neuron
@@ -732,7 +885,13 @@ int launch_conv3x3_u8c2(ConvMfmaArgs a, int in_type, const snnqp_weight_t *w, in
     a.x_flags = x_flags;
   }
   if (plan.lut) check_code_bound_once(stream_device(st), a.w, (int64_t)9 * a.Cin, a.Cout, w->abs_sum_max, st);
-  if (plan.half && pl)
+  if (plan.spread) {
+    constexpr int N0 = NF_MUL0, LC = LUT_CHANNEL, E1 = SNNQP_EV1;
+    if (plan.half && pl) launch_persistent(conv3x3_u8c2_kernel<N0, true, LC, E1, true, true, true>, a, gy, st, plan.ldsb);
+    else if (plan.half) launch_persistent(conv3x3_u8c2_kernel<N0, false, LC, E1, true, true, true>, a, gy, st, plan.ldsb);
+    else if (pl) launch_persistent(conv3x3_u8c2_kernel<N0, true, LC, E1, true, false, true>, a, gy, st, plan.ldsb);
+    else launch_persistent(conv3x3_u8c2_kernel<N0, false, LC, E1, true, false, true>, a, gy, st, plan.ldsb);
+  } else if (plan.half && pl)
     launch_persistent(conv3x3_u8c2_kernel<NF_MUL0, true, LUT_CHANNEL, SNNQP_EV1, true, true>, a, gy, st, plan.ldsb);
   else if (plan.half)
     launch_persistent(conv3x3_u8c2_kernel<NF_MUL0, false, LUT_CHANNEL, SNNQP_EV1, true, true>, a, gy, st, plan.ldsb);

@@ -481,6 +481,41 @@ __device__ __forceinline__ uint32_t tile_epilogue_halves(const v16i &acc, float 
   return myw;
 }
 
+// The HALFW form over a register sub-range (the spread launch, conv3x3_u8c2.hip): a wave that runs one
+// quarter of the half group's product.  The wave permutes the ROWS of its A operand so that its
+// quarter -- columns 4 q .. 4 q + 3 of image rows 4 g .. 4 g + 3 -- arrives in registers 0..3 whatever
+// (g, q) is: register i = column 4 q + i, and its 64-bit mask is the four 16-channel fields of rows
+// 4 g .. 4 g + 3 as above.  Four potentials, four table reads.  Returns, in bits 0..15,
+//   POOL : lanes j, 4 + j (j = 0, 1) = pooled pixel (row 2 g, 2 g + 1; column 2 q + j)
+//   !POOL: lanes 4 r + i (r, i = 0..3) = pixel (row 4 g + r, column 4 q + i)
+template <int NF, bool POOL, int LUTM, bool FMA = false, bool OFFS = false>
+__device__ __forceinline__ uint32_t tile_epilogue_quarter(const v16i &acc, float (&u)[16], const Dequant &dq,
+                                                          const LaneConsts &lc, const NeuronP &nrn,
+                                                          float off = 0.0f) {
+  uint32_t myw = 0;
+  v2f y[2];
+#pragma unroll
+  for (int j = 0; j < 2; ++j) y[j] = dequant_pair<LUTM, OFFS>(acc[2 * j], acc[2 * j + 1], dq, off);
+#pragma unroll
+  for (int j = 0; j < 2; ++j) {
+    unsigned long long m0, m1;
+    neuron_pair<NF, LUTM == LUT_CHANNEL, FMA>(y[j], u[2 * j], u[2 * j + 1], lc, nrn, m0, m1);
+    if (POOL) {
+      const unsigned long long o = m0 | m1;
+      const uint32_t lo = (uint32_t)o, hi = (uint32_t)(o >> 32);
+      myw = writelane_u32((lo | (lo >> 16)) & 0xFFFFu, j, myw);
+      myw = writelane_u32((hi | (hi >> 16)) & 0xFFFFu, 4 + j, myw);
+    } else {
+#pragma unroll
+      for (int r = 0; r < 4; ++r) {
+        myw = writelane_u32((uint32_t)(m0 >> (16 * r)) & 0xFFFFu, 4 * r + 2 * j, myw);
+        myw = writelane_u32((uint32_t)(m1 >> (16 * r)) & 0xFFFFu, 4 * r + 2 * j + 1, myw);
+      }
+    }
+  }
+  return myw;
+}
+
 // Spike words are staged in LDS, obuf[slot = t % FL][pixel][4 words of the 128-
 // channel block], and flushed with 16-byte stores: no global store sits in the
 // per-timestep loop (vmcnt stays a pure load counter there).
@@ -621,5 +656,7 @@ int launch_conv3x3_u8c2(ConvMfmaArgs a, int in_type, const snnqp_weight_t *w, in
 bool conv_k16_enabled();
 // snnqp_set_event_half_group (api.hip): whether launch_conv3x3_u8c2 picks the half-group instances
 bool event_half_group_enabled();
+// snnqp_set_event_wave_spread (api.hip): whether launch_conv3x3_u8c2 picks the spread instances
+bool event_wave_spread_enabled();
 
 }  // namespace snnqp

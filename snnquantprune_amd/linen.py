@@ -194,6 +194,23 @@ def event_half_group() -> bool:
   return bool(_lib.lib().snnqp_set_event_half_group(-1))
 
 
+# The wave spread of the event layer: on the 96-channel half-group launch (C3) and on
+# a 64-channel launch the four waves of a workgroup would carry 32 / 32 / 16 / 0 and 32 / 32 / 0 / 0
+# registers of neuron updates; spread, every wave carries 20 and 16.  On by default.
+def set_event_wave_spread(enabled: bool):
+  """True (default): those launches give every wave one (channel group, tile) unit and, at 96
+  channels, a quarter of the half group.  False: wave w computes channel group w (the A side of an
+  A/B on one build; the results are the same).  A switch of the library: applies to the launches after
+  it."""
+  from . import _lib
+  _lib.lib().snnqp_set_event_wave_spread(1 if enabled else 0)
+
+
+def event_wave_spread() -> bool:
+  from . import _lib
+  return bool(_lib.lib().snnqp_set_event_wave_spread(-1))
+
+
 # The connection alone over a bit-packed raster (DESIGN.md 4.3.2): the training forward of a conv
 # block (conv_train.conv_currents with mfma=True) and QuantConv called on its own hand ops.conv_forward the
 # MFMA-tiled codes, so a 3x3 / stride 1 / pad 1 connection with Cin <= 128 runs on the currents

@@ -1189,6 +1189,8 @@ def conv_lif_forward(x, geom: ConvGeom, weight: Weight, neuron: Neuron,
       ev1 = L.EV1 if (in_type == L.EV1 or (binary_first and in_type in (L.U8, L.F32))) else in_type
       PROFILE_NOTES[tag]["channels"]["half_group"] = conv_event_half_group(
           ev1, T, geom, weight, neuron, state=u0 is not None or want_u, pool=pool, x_max=1 if ev1 == L.EV1 else x_max)
+      PROFILE_NOTES[tag]["channels"]["wave_spread"] = conv_event_wave_spread(
+          ev1, T, geom, weight, neuron, state=u0 is not None or want_u, pool=pool, x_max=1 if ev1 == L.EV1 else x_max)
   # (the bit-packed variant writes bit-packed spikes only: float32 spikes take the frames as they are)
   speculate = (binary_first and packed_out and not isinstance(x, (PackedFrames, PackedSpikes))
                and in_type in (L.U8, L.F32) and geom.Cin == 2 and weight.is_int and impl != L.IMPL_GENERIC
@@ -1398,6 +1400,19 @@ def workqueue_capture_release(device, begin: int, end: int):
 
 
 DQ_FORMS = {1: "arith", 2: "one", 3: "table"}
+
+
+def conv_event_wave_spread(in_type: int, T: int, geom: ConvGeom, w: Weight, nrn: Neuron, state: bool = False,
+                           pool: int = 1, x_max: int = 0) -> bool:
+  """Whether snnqp_conv_lif_forward runs this event-layer launch on the spread path
+  (snnqp_conv_event_wave_spread): 96 channels on the half-group path or 64 channels off it, the
+  bit-packed single-chunk table variant, and nn.set_event_wave_spread is on."""
+  gs, ws, ns = geom.struct(), w.struct(), nrn.struct()
+  rc = L.lib().snnqp_conv_event_wave_spread(int(in_type), int(T), ctypes.byref(gs), ctypes.byref(ws),
+                                            ctypes.byref(ns), 1 if state else 0, int(pool), int(x_max))
+  if rc < 0:
+    L.check(rc)
+  return rc == 1
 
 
 def conv_event_half_group(in_type: int, T: int, geom: ConvGeom, w: Weight, nrn: Neuron, state: bool = False,

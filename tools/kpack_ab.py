@@ -6,9 +6,11 @@ the kernel walks whole 32-channel groups, on = it leaves the empty upper half of
 out), K packing on in both.  --ab half: the same A/B of nn.set_event_half_group (off =
 the event layer computes the whole last channel group and masks its silent half, on = it computes
 that group in a 16-channel half); the C5 and 8-bit legs run identical instances both ways, so their
-ratios are the session's noise.
+ratios are the session's noise.  --ab spread: the same A/B of nn.set_event_wave_spread (DESIGN.md 4.2:
+off = wave w of the event layer computes channel group w, on = every wave one (group, tile) unit and a
+quarter of the half group), the half group on in both.
 
-  python tools/kpack_ab.py [--ab kpack|k16|half] [--B 1024] [--T 20] [--reps 5] [--out FILE.json]
+  python tools/kpack_ab.py [--ab kpack|k16|half|spread] [--B 1024] [--T 20] [--reps 5] [--out FILE.json]
 """
 import argparse
 import json
@@ -86,10 +88,11 @@ def main():
   ap.add_argument("--T", type=int, default=20)
   ap.add_argument("--reps", type=int, default=5)
   ap.add_argument("--out", default=None)
-  ap.add_argument("--ab", choices=["kpack", "k16", "half"], default="kpack")
+  ap.add_argument("--ab", choices=["kpack", "k16", "half", "spread"], default="kpack")
   args = ap.parse_args()
   dev = torch.device("cuda:0")
-  switch = {"k16": nn.set_conv_k16, "half": nn.set_event_half_group}.get(args.ab, nn.set_conv_kpack)
+  switch = {"k16": nn.set_conv_k16, "half": nn.set_event_half_group,
+            "spread": nn.set_event_wave_spread}.get(args.ab, nn.set_conv_kpack)
   res = {"ab": args.ab, "B": args.B, "T": args.T, "reps": args.reps, "device": torch.cuda.get_device_name(0), "legs": {}}
   for name, bits, prune, lb, inp in LEGS:
     r = leg(name, bits, prune, lb, inp, args.B, args.T, args.reps, dev, switch)
