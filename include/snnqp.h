@@ -248,7 +248,9 @@ typedef struct {
  * snnqp_conv_weight_grad_f64_workspace_bytes; the batched event front end snnqp_events_bin and its augmenting
  * form snnqp_events_bin_aug with snnqp_event_aug_t; the host-side
  * query snnqp_conv_float_form; the host-side plan queries snnqp_conv_gated_plan,
- * snnqp_dense_gated_plan, snnqp_dense_wide_plan: new entry points, nothing else moves).
+ * snnqp_dense_gated_plan, snnqp_dense_wide_plan; streaming inference --
+ * snnqp_dense_head_forward_state, snnqp_vote_accumulate, snnqp_vote_counts: new entry points,
+ * nothing else moves).
  * A binding compares snnqp_version()
  * with the SNNQP_VERSION it was written against and refuses a library of another version (_lib.py does). */
 #define SNNQP_VERSION 507
@@ -746,7 +748,8 @@ int snnqp_dense_lif_forward_if(const int32_t *pred, const void *x, int in_type, 
  * s1_out / s2_out  nullable: the two spike rasters, SNNQP_BITS [T][B][ceil(N / 32)], as
  *       snnqp_dense_lif_forward writes them (the hidden raster otherwise never leaves the CU).
  * Membrane potentials start from zero (initialize_carry, spiking_learning.py:464-472) and are
- * not returned: a caller that carries state uses snnqp_dense_lif_forward per block.
+ * not returned: a caller that carries state uses snnqp_dense_head_forward_state (below), or
+ * snnqp_dense_lif_forward per block.
  * ws / ws_bytes  nullable workspace (device memory, 256-byte aligned, one launch at a time; its
  *       tickets are zeroed on `stream` by every call, as for snnqp_dense_lif_forward_ws;
  *       snnqp_dense_head_workspace_bytes says how much, 0 = it would not be used).  With it a batch that fills at most half the chip (config C2: B = 256) runs as two
@@ -773,6 +776,28 @@ int snnqp_dense_head_forward(const void *x, int in_type, int64_t x_stride_t,
                              const snnqp_neuron_t *nrn2, int32_t group,
                              uint32_t *s1_out, uint32_t *s2_out, float *logits,
                              int32_t *x_flags, void *ws, int64_t ws_bytes, snnqp_stream_t stream);
+/* The same launch for a recording that arrives window by window (T = the window's steps):
+ * u1 [B][N1], u2 [B][N2]  float32 membranes of the two blocks, read as the initial state and
+ *       written as the final one, IN PLACE: each potential is loaded and stored by the one lane
+ *       that owns its (sample, feature), the store behind the load.
+ * counts [B][N2]  int32: the window's spike counts of the second block are added in (plain load,
+ *       add, store by the owning lane; snnqp_vote_counts turns them into the running vote).
+ * logits stays the vote over THIS window.  Same inputs, same refusals, same workspace rule as
+ * snnqp_dense_head_forward; SNNQP_EINVAL for a null u1, u2 or counts.  The column split is served:
+ * the two workgroups of a tile own disjoint columns of u1, and u2 / counts are touched by the last
+ * arriver alone, so snnqp_dense_wide_plan and snnqp_dense_head_workspace_bytes answer for both
+ * entries.  Float32 rows: the launch has updated u1 / u2 / counts by the time x_flags is known, so a
+ * caller with a float32 stand-by hands this entry COPIES of the state and lets its predicated
+ * launches read the originals (ops.dense_head_forward_state). */
+int snnqp_dense_head_forward_state(const void *x, int in_type, int64_t x_stride_t,
+                                   int64_t x_stride_b, int32_t T, int32_t B, int32_t K,
+                                   int32_t N1, const snnqp_weight_t *w1, const int8_t *wt1,
+                                   const snnqp_neuron_t *nrn1, int32_t N2,
+                                   const snnqp_weight_t *w2, const int8_t *wt2,
+                                   const snnqp_neuron_t *nrn2, int32_t group,
+                                   float *u1, float *u2, int32_t *counts,
+                                   uint32_t *s1_out, uint32_t *s2_out, float *logits,
+                                   int32_t *x_flags, void *ws, int64_t ws_bytes, snnqp_stream_t stream);
 
 /* ---- element-wise pieces ----------------------------------------------------
  * replaces: neural_dynamics(u, x) scanned over T, spiking_learning.py:460
@@ -900,6 +925,18 @@ int snnqp_vote(const void *s, int type, int32_t T, int32_t B, int32_t N,
 /* executed only if *pred != 0 (snnqp_conv_lif_forward_if) */
 int snnqp_vote_if(const int32_t *pred, const void *s, int type, int32_t T, int32_t B, int32_t N,
                   int32_t group, float *logits, snnqp_stream_t stream);
+/* The vote of a raster that arrives window by window, kept as integer counts.
+ * snnqp_vote_accumulate: s [T][B][N] (F32 holding 0 / 1, or BITS; any N) -- each neuron's spike
+ *   count over the T steps is added into counts int32 [B][N] (one owner per (b, n), plain loads and
+ *   stores; T = 0 adds nothing).
+ * snnqp_vote_counts: counts [B][N] -> logits float32 [B][N / group] = snnqp_vote of the raster the
+ *   counts were taken from: (float)count / (float)steps, then the in-order mean over `group`
+ *   (exact while steps < 2^24).  steps_b int32 [B] on the device gives every row its own number of
+ *   steps (`steps` is then ignored); null: all rows share `steps`.  A row with 0 steps votes 0. */
+int snnqp_vote_accumulate(const void *s, int type, int32_t T, int32_t B, int32_t N, int32_t *counts,
+                          snnqp_stream_t stream);
+int snnqp_vote_counts(const int32_t *counts, int32_t steps, const int32_t *steps_b, int32_t B, int32_t N,
+                      int32_t group, float *logits, snnqp_stream_t stream);
 
 /* replaces: nothing in the reference (it computes every output channel); the blocks of a model
  * whose pruned channels cannot fire compute the others only, and this restores the

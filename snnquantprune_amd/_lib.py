@@ -156,6 +156,10 @@ _PROTOTYPES = {
         c_void_p, c_int, c_int64, c_int64, c_int32, c_int32, c_int32, c_int32, POINTER(WeightT),
         c_void_p, POINTER(NeuronT), c_int32, POINTER(WeightT), c_void_p, POINTER(NeuronT), c_int32,
         c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int64, c_void_p]),
+    "snnqp_dense_head_forward_state": (c_int, [
+        c_void_p, c_int, c_int64, c_int64, c_int32, c_int32, c_int32, c_int32, POINTER(WeightT),
+        c_void_p, POINTER(NeuronT), c_int32, POINTER(WeightT), c_void_p, POINTER(NeuronT), c_int32,
+        c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int64, c_void_p]),
     "snnqp_device_status": (c_int, [c_int, POINTER(c_uint32), c_int]),
     "snnqp_workqueue_capture_mark": (c_int, [c_int, POINTER(c_int64)]),
     "snnqp_workqueue_capture_release": (c_int, [c_int, c_int64, c_int64]),
@@ -189,6 +193,8 @@ _PROTOTYPES = {
                            c_void_p, c_void_p]),
     "snnqp_vote_if": (c_int, [c_void_p, c_void_p, c_int, c_int32, c_int32, c_int32, c_int32,
                               c_void_p, c_void_p]),
+    "snnqp_vote_accumulate": (c_int, [c_void_p, c_int, c_int32, c_int32, c_int32, c_void_p, c_void_p]),
+    "snnqp_vote_counts": (c_int, [c_void_p, c_int32, c_void_p, c_int32, c_int32, c_int32, c_void_p, c_void_p]),
     "snnqp_scatter_spike_channels": (c_int, [c_void_p, c_int64, c_int32, c_void_p, c_int32,
                                              c_void_p, c_void_p]),
     "snnqp_lif_forward_save": (c_int, [c_void_p, c_int32, c_int64, c_int32, POINTER(NeuronT),

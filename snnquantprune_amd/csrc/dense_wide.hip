@@ -29,7 +29,10 @@
 //    counts / T for the vote (models.py:253-255), which the workgroup finishes;
 //  * batches that fill at most half the chip run TWO workgroups per tile of samples, 256 hidden
 //    columns each, which hand their halves of the hidden raster over through a caller workspace
-//    (write-through stores, a ticket; the last arriver runs the second block and the vote).
+//    (write-through stores, a ticket; the last arriver runs the second block and the vote);
+//  * the head of a STREAM (snnqp_dense_head_forward_state, template parameter STATE) carries the
+//    membranes of both blocks and the output spike counts from window to window in the caller's
+//    buffers, read and written in place by the lane that owns each value.
 //
 // K loop as in dense_fp6.hip: chunks of 128 k, three LDS images (chunk c computes from image
 // c mod 3 while chunk c + 2 is staged, the barrier waits with a counted lgkmcnt so that the
@@ -87,6 +90,9 @@ struct DenseWideArgs {
   uint32_t *hs_raster;            // [tiles][2][ROWS][8 words]
   uint32_t *status;               // the device's status word (runtime.hip), or null
   int32_t *x_flags;               // float32 rows: OR-ed with SNNQP_FLAG_NOT_INTEGER (zeroed by the launcher)
+  // fused head with carried state (STATE; the first block's membranes are u0 == u_out above)
+  float *u2;                      // [B][N2] the second block's membranes, read at a sample's first row, written at its last
+  int32_t *counts;                // [B][N2] the window's spike counts are added in
 };
 
 // four float32 values -> the four bytes x - 128 of the int8 operand; `bad` collects what is not
@@ -271,9 +277,17 @@ __device__ __forceinline__ void mask_words(uint32_t (&words)[(16 * RT * CT * 2 +
 
 }  // namespace
 
-template <int RT, int CT, int IN, bool FUSE>
+// STATE (fused head only): the membranes of both blocks are read from and written back to the
+// caller's buffers and the second block's spike counts are added into a.counts.  Every potential
+// and every count is read and written by ONE lane -- neuron_walk loads u0 of (sample, column) at the
+// sample's first row and stores u_out of the same (sample, column) behind its last, and the lane
+// that owns (sample, column) is the same at both: reading and writing the same buffer is safe.
+// With the column split the two workgroups of a tile own disjoint hidden columns, and the second
+// block runs in the last arriver alone.
+template <int RT, int CT, int IN, bool FUSE, bool STATE = false>
 __global__ void __launch_bounds__(W_THREADS)
 dense_wide_kernel(DenseWideArgs a) {
+  static_assert(FUSE || !STATE, "carried state is the fused head's");
   constexpr bool F32IN = IN == SNNQP_F32;
   constexpr bool U8 = IN == SNNQP_U8 || F32IN;     // the operand bytes are x - 128
   constexpr int ROWS = RT * 32;
@@ -671,7 +685,7 @@ dense_wide_kernel(DenseWideArgs a) {
       const float Tf = (float)a.T;
       const bool fast2 = a.nrn2.kind != SNNQP_NEURON_LIF && a.nrn2.inv_k != 0.0f;
       BnP nobn; nobn.mean = nullptr; nobn.mul = nullptr; nobn.bias = nullptr; nobn.flags = 0;
-      if (fast2 && a.nrn2.vr == 0.0f) {
+      if (!STATE && fast2 && a.nrn2.vr == 0.0f) {
         // jnp.mean over T of 0/1 values: the exact count, one division (models.py:253)
         auto sample_done = [&](int, int cnt, int k) {
           const int j = k / a.T, s = 2 * j + h;
@@ -685,12 +699,20 @@ dense_wide_kernel(DenseWideArgs a) {
         auto count = [&](int, bool sp, int t, int s, bool slive) {
           cnt += sp ? 1 : 0;
           if (t == a.T - 1) {
-            if (slive && col2_live[0]) vbuf[s * 128 + col2[0]] = (float)cnt / Tf;
+            if (slive && col2_live[0]) {
+              vbuf[s * 128 + col2[0]] = (float)cnt / Tf;
+              if constexpr (STATE) {
+                // (the lane owns (sample, column): a plain load, add and store)
+                int32_t *c = a.counts + (int64_t)(b0 + s) * a.N2 + col2[0];
+                *c = *c + cnt;
+              }
+            }
             cnt = 0;
           }
         };
-        if (fast2) neuron_walk<RT, 1, true, false>(acc2, off, col2_live, col2, a.dq2, nobn, a.nrn2, a.T, a.SPH, nsamp, b0, a.N2, nullptr, nullptr, h, words, count);
-        else neuron_walk<RT, 1, false, false>(acc2, off, col2_live, col2, a.dq2, nobn, a.nrn2, a.T, a.SPH, nsamp, b0, a.N2, nullptr, nullptr, h, words, count);
+        float *const u2 = STATE ? a.u2 : nullptr;
+        if (fast2) neuron_walk<RT, 1, true, false>(acc2, off, col2_live, col2, a.dq2, nobn, a.nrn2, a.T, a.SPH, nsamp, b0, a.N2, u2, u2, h, words, count);
+        else neuron_walk<RT, 1, false, false>(acc2, off, col2_live, col2, a.dq2, nobn, a.nrn2, a.T, a.SPH, nsamp, b0, a.N2, u2, u2, h, words, count);
       }
       if (a.s2_out) {
 #pragma unroll
@@ -758,18 +780,18 @@ const char *dense_wide_unsupported(const BlockCall &c) {
   return wide_rows_unsupported(c, c.in_type == SNNQP_BITS ? (c.K + 31) / 32 : c.K);
 }
 
-template <int RT, int CT, int IN, bool FUSE>
+template <int RT, int CT, int IN, bool FUSE, bool STATE>
 static void launch_wide(const DenseWideArgs &a, unsigned gx, unsigned gy, hipStream_t st) {
-  hipLaunchKernelGGL((dense_wide_kernel<RT, CT, IN, FUSE>), dim3(gx, gy), dim3(W_THREADS), 0, st, a);
+  hipLaunchKernelGGL((dense_wide_kernel<RT, CT, IN, FUSE, STATE>), dim3(gx, gy), dim3(W_THREADS), 0, st, a);
 }
 
-template <int CT, int IN, bool FUSE>
+template <int CT, int IN, bool FUSE, bool STATE = false>
 static void launch_wide_rt(int rt, const DenseWideArgs &a, unsigned gx, unsigned gy, hipStream_t st) {
   switch (rt) {
-    case 4: launch_wide<4, CT, IN, FUSE>(a, gx, gy, st); break;
-    case 3: launch_wide<3, CT, IN, FUSE>(a, gx, gy, st); break;
-    case 2: launch_wide<2, CT, IN, FUSE>(a, gx, gy, st); break;
-    default: launch_wide<1, CT, IN, FUSE>(a, gx, gy, st); break;
+    case 4: launch_wide<4, CT, IN, FUSE, STATE>(a, gx, gy, st); break;
+    case 3: launch_wide<3, CT, IN, FUSE, STATE>(a, gx, gy, st); break;
+    case 2: launch_wide<2, CT, IN, FUSE, STATE>(a, gx, gy, st); break;
+    default: launch_wide<1, CT, IN, FUSE, STATE>(a, gx, gy, st); break;
   }
 }
 
@@ -816,8 +838,10 @@ static int64_t wide_workspace_bytes(const WidePlan &p) {
   return p.csplit ? W_TICKET_BYTES + (int64_t)p.gx * 2 * (p.rt * 32) * 8 * 4 : 0;
 }
 
+// state: the fused head with carried membranes and counts (a.u0 == a.u_out, a.u2, a.counts).  The
+// plan is the stateless one, column split included: see dense_wide_kernel on who owns what.
 static int fill_and_launch(DenseWideArgs &a, int in_type, bool fuse, void *ws, int64_t ws_bytes,
-                           hipStream_t st) {
+                           hipStream_t st, bool state = false) {
   WidePlan p = plan_wide(a, fuse, ws != nullptr);
   if (p.csplit && (wide_workspace_bytes(p) > ws_bytes || ((uintptr_t)ws & 255) != 0)) p = plan_wide(a, fuse, false);
   SNNQP_REQUIRE(p.rt > 0, SNNQP_EUNSUPPORTED, "dense wide: T too large");
@@ -836,13 +860,15 @@ static int fill_and_launch(DenseWideArgs &a, int in_type, bool fuse, void *ws, i
     SNNQP_REQUIRE(a.x_flags != nullptr, SNNQP_EINVAL, "dense wide: float32 rows need x_flags");
     if (int rc = zero_words_async((uint32_t *)a.x_flags, 1, st)) return rc;
   }
-#define SNNQP_WIDE_IN(CTV, FUSEV)                                                          \
-  do {                                                                                     \
-    if (in_type == SNNQP_U8) launch_wide_rt<CTV, SNNQP_U8, FUSEV>(rt, a, gx, gy, st);        \
-    else if (in_type == SNNQP_F32) launch_wide_rt<CTV, SNNQP_F32, FUSEV>(rt, a, gx, gy, st); \
-    else launch_wide_rt<CTV, SNNQP_BITS, FUSEV>(rt, a, gx, gy, st);                          \
+#define SNNQP_WIDE_IN(CTV, FUSEV, ...)                                                                  \
+  do {                                                                                                  \
+    if (in_type == SNNQP_U8) launch_wide_rt<CTV, SNNQP_U8, FUSEV, ##__VA_ARGS__>(rt, a, gx, gy, st);        \
+    else if (in_type == SNNQP_F32) launch_wide_rt<CTV, SNNQP_F32, FUSEV, ##__VA_ARGS__>(rt, a, gx, gy, st); \
+    else launch_wide_rt<CTV, SNNQP_BITS, FUSEV, ##__VA_ARGS__>(rt, a, gx, gy, st);                          \
   } while (0)
-  if (fuse) {
+  if (fuse && state) {
+    if (p.ct == 2) SNNQP_WIDE_IN(2, true, true); else SNNQP_WIDE_IN(1, true, true);
+  } else if (fuse) {
     if (p.ct == 2) SNNQP_WIDE_IN(2, true); else SNNQP_WIDE_IN(1, true);
   } else {
     if (p.ct == 2) SNNQP_WIDE_IN(2, false); else SNNQP_WIDE_IN(1, false);
@@ -868,16 +894,19 @@ int run_dense_wide(const BlockCall &c) {
 
 }  // namespace snnqp
 
-extern "C" int snnqp_dense_head_forward(const void *x, int in_type, int64_t x_stride_t,
-                                        int64_t x_stride_b, int32_t T, int32_t B, int32_t K,
-                                        int32_t N1, const snnqp_weight_t *w1, const int8_t *wt1,
-                                        const snnqp_neuron_t *nrn1, int32_t N2,
-                                        const snnqp_weight_t *w2, const int8_t *wt2,
-                                        const snnqp_neuron_t *nrn2, int32_t group,
-                                        uint32_t *s1_out, uint32_t *s2_out, float *logits,
-                                        int32_t *x_flags, void *ws, int64_t ws_bytes,
-                                        snnqp_stream_t stream) {
+// snnqp_dense_head_forward (state == false: u1, u2 and counts are null) and its stateful form
+static int dense_head(const void *x, int in_type, int64_t x_stride_t,
+                      int64_t x_stride_b, int32_t T, int32_t B, int32_t K,
+                      int32_t N1, const snnqp_weight_t *w1, const int8_t *wt1,
+                      const snnqp_neuron_t *nrn1, int32_t N2,
+                      const snnqp_weight_t *w2, const int8_t *wt2,
+                      const snnqp_neuron_t *nrn2, int32_t group,
+                      uint32_t *s1_out, uint32_t *s2_out, float *logits,
+                      int32_t *x_flags, void *ws, int64_t ws_bytes,
+                      snnqp_stream_t stream, bool state, float *u1, float *u2, int32_t *counts) {
   using namespace snnqp;
+  SNNQP_REQUIRE(!state || (u1 && u2 && counts) || B == 0, SNNQP_EINVAL,
+                "dense_head_forward_state: null u1, u2 or counts");
   SNNQP_REQUIRE(w1 && w2 && nrn1 && nrn2 && ((x && logits) || T == 0 || B == 0), SNNQP_EINVAL,
                 "dense_head_forward: null argument");
   if (int rc = refuse_after_device_report((hipStream_t)stream, "dense_head_forward")) return rc;
@@ -909,7 +938,35 @@ extern "C" int snnqp_dense_head_forward(const void *x, int in_type, int64_t x_st
   a.N2 = N2; a.KS2 = (N1 + 31) / 32; a.group = group;
   a.wt2 = wt2; a.dq2 = make_dequant(w2->L, w2->m); a.nrn2 = make_neuron(nrn2);
   a.s2_out = s2_out; a.logits = logits;
-  return fill_and_launch(a, in_type, true, ws, ws_bytes, (hipStream_t)stream);
+  if (state) { a.u0 = u1; a.u_out = u1; a.u2 = u2; a.counts = counts; }
+  return fill_and_launch(a, in_type, true, ws, ws_bytes, (hipStream_t)stream, state);
+}
+
+extern "C" int snnqp_dense_head_forward(const void *x, int in_type, int64_t x_stride_t,
+                                        int64_t x_stride_b, int32_t T, int32_t B, int32_t K,
+                                        int32_t N1, const snnqp_weight_t *w1, const int8_t *wt1,
+                                        const snnqp_neuron_t *nrn1, int32_t N2,
+                                        const snnqp_weight_t *w2, const int8_t *wt2,
+                                        const snnqp_neuron_t *nrn2, int32_t group,
+                                        uint32_t *s1_out, uint32_t *s2_out, float *logits,
+                                        int32_t *x_flags, void *ws, int64_t ws_bytes,
+                                        snnqp_stream_t stream) {
+  return dense_head(x, in_type, x_stride_t, x_stride_b, T, B, K, N1, w1, wt1, nrn1, N2, w2, wt2, nrn2, group,
+                    s1_out, s2_out, logits, x_flags, ws, ws_bytes, stream, false, nullptr, nullptr, nullptr);
+}
+
+extern "C" int snnqp_dense_head_forward_state(const void *x, int in_type, int64_t x_stride_t,
+                                              int64_t x_stride_b, int32_t T, int32_t B, int32_t K,
+                                              int32_t N1, const snnqp_weight_t *w1, const int8_t *wt1,
+                                              const snnqp_neuron_t *nrn1, int32_t N2,
+                                              const snnqp_weight_t *w2, const int8_t *wt2,
+                                              const snnqp_neuron_t *nrn2, int32_t group,
+                                              float *u1, float *u2, int32_t *counts,
+                                              uint32_t *s1_out, uint32_t *s2_out, float *logits,
+                                              int32_t *x_flags, void *ws, int64_t ws_bytes,
+                                              snnqp_stream_t stream) {
+  return dense_head(x, in_type, x_stride_t, x_stride_b, T, B, K, N1, w1, wt1, nrn1, N2, w2, wt2, nrn2, group,
+                    s1_out, s2_out, logits, x_flags, ws, ws_bytes, stream, true, u1, u2, counts);
 }
 
 extern "C" int snnqp_dense_wide_plan(int32_t T, int32_t B, int32_t N, int fused, int may_split, int32_t *rt,

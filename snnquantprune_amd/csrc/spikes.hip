@@ -244,6 +244,50 @@ vote_kernel(const void *__restrict__ s, int32_t T, int32_t B, int32_t N,
   }
 }
 
+// The vote kept as counts, for a raster that arrives window by window: one thread owns (b, n),
+// reads its count, adds the window's spikes and stores it -- plain loads and stores, no atomics.
+template <bool BITS>
+__global__ void __launch_bounds__(256)
+vote_accumulate_kernel(const void *__restrict__ s, int32_t T, int32_t B, int32_t N,
+                       int32_t *__restrict__ counts) {
+  const int32_t CW = (N + 31) / 32;
+  const int64_t n = (int64_t)B * N;
+  for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n;
+       i += (int64_t)gridDim.x * blockDim.x) {
+    const int32_t b = (int32_t)(i / N);
+    const int32_t nn = (int32_t)(i % N);
+    int32_t c = 0;
+    for (int32_t t = 0; t < T; ++t) {
+      if (BITS) {
+        const uint32_t w = ((const uint32_t *)s)[((int64_t)t * B + b) * CW + (nn >> 5)];
+        c += (int32_t)((w >> (nn & 31)) & 1u);
+      } else {
+        c += ((const float *)s)[((int64_t)t * B + b) * N + nn] != 0.0f ? 1 : 0;
+      }
+    }
+    counts[i] = counts[i] + c;
+  }
+}
+
+// counts -> logits with the two divisions of vote_kernel: (float)count is the sequential float32
+// sum of that many ones (exact below 2^24 steps).  A row that has seen no step votes 0.
+__global__ void __launch_bounds__(256)
+vote_counts_kernel(const int32_t *__restrict__ counts, int32_t steps, const int32_t *__restrict__ steps_b,
+                   int32_t B, int32_t N, int32_t group, float *__restrict__ logits) {
+  const int32_t NC = N / group;
+  const int64_t n = (int64_t)B * NC;
+  for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n;
+       i += (int64_t)gridDim.x * blockDim.x) {
+    const int32_t b = (int32_t)(i / NC);
+    const int32_t k = (int32_t)(i % NC);
+    const int32_t T = steps_b ? steps_b[b] : steps;
+    float acc2 = 0.0f;
+    for (int32_t j = 0; j < group; ++j)
+      acc2 = acc2 + (float)counts[(int64_t)b * N + k * group + j] / (float)T;
+    logits[i] = T > 0 ? acc2 / (float)group : 0.0f;
+  }
+}
+
 // TCJA pieces (examples/tcja/models.py:41-99) ---------------------------------
 // mean over the HW pixels of each (image, channel): one thread per (image, c),
 // sequential float32 sum over pixels (exact integer count for spikes) / HW.
@@ -603,6 +647,38 @@ int snnqp_vote_if(const int32_t *pred, const void *s, int type, int32_t T, int32
     hipLaunchKernelGGL(vote_kernel<false>, dim3(grid_for(n)), dim3(256), 0,
                        (hipStream_t)stream, s, T, B, N, group, logits, pred);
   SNNQP_CHECK_LAUNCH("vote_kernel");
+  return SNNQP_OK;
+}
+
+int snnqp_vote_accumulate(const void *s, int type, int32_t T, int32_t B, int32_t N, int32_t *counts,
+                          snnqp_stream_t stream) {
+  SNNQP_REQUIRE(((s && counts) || B == 0 || T == 0) && T >= 0 && B >= 0 && N > 0, SNNQP_EINVAL,
+                "vote_accumulate: bad argument");
+  SNNQP_REQUIRE(type == SNNQP_F32 || type == SNNQP_BITS, SNNQP_EINVAL,
+                "vote_accumulate: type must be F32 or BITS");
+  if (B == 0 || T == 0) return SNNQP_OK;
+  const int64_t n = (int64_t)B * N;
+  if (type == SNNQP_BITS)
+    hipLaunchKernelGGL(vote_accumulate_kernel<true>, dim3(grid_for(n)), dim3(256), 0,
+                       (hipStream_t)stream, s, T, B, N, counts);
+  else
+    hipLaunchKernelGGL(vote_accumulate_kernel<false>, dim3(grid_for(n)), dim3(256), 0,
+                       (hipStream_t)stream, s, T, B, N, counts);
+  SNNQP_CHECK_LAUNCH("vote_accumulate_kernel");
+  return SNNQP_OK;
+}
+
+int snnqp_vote_counts(const int32_t *counts, int32_t steps, const int32_t *steps_b, int32_t B, int32_t N,
+                      int32_t group, float *logits, snnqp_stream_t stream) {
+  SNNQP_REQUIRE(((counts && logits) || B == 0) && B >= 0 && N > 0 && group > 0 && (steps_b || steps >= 0),
+                SNNQP_EINVAL, "vote_counts: bad argument");
+  SNNQP_REQUIRE(N % group == 0, SNNQP_EINVAL,
+                "vote_counts: N=%d not divisible by group=%d", N, group);
+  if (B == 0) return SNNQP_OK;
+  const int64_t n = (int64_t)B * (N / group);
+  hipLaunchKernelGGL(vote_counts_kernel, dim3(grid_for(n)), dim3(256), 0, (hipStream_t)stream,
+                     counts, steps, steps_b, B, N, group, logits);
+  SNNQP_CHECK_LAUNCH("vote_counts_kernel");
   return SNNQP_OK;
 }
 

@@ -652,6 +652,12 @@ class CapturedApply:
   partial results over between workgroups get a workspace allocated INSIDE the capture (the
   graph's private pool: ops._dense_workspace), so the addresses baked into the graph live and
   die with it.
+
+  `u_state=state` (models.StreamState) records ONE WINDOW of a stream: every replay reads and
+  updates the state's tensors, whose addresses the graph holds -- one graph launch per window.  The
+  warm-up runs and the recording leave the state's values as they were.  Integer-typed windows only
+  (uint8, PackedFrames, PackedSpikes): a float32 window is a launch pair that swaps the state's
+  buffers (ops.dense_head_forward_state), which a recorded graph cannot follow.
   """
 
   def __init__(self, module, variables, example, **kwargs):
@@ -660,6 +666,16 @@ class CapturedApply:
     dev = example.device if not isinstance(example, torch.Tensor) else example.device
     if torch.device(dev).type != "cuda":
       raise RuntimeError("capture needs the inputs on the GPU")
+    self._state = state = kwargs.get("u_state")
+    self._slots = self._graph = None      # (close() runs from the destructor of a refused capture too)
+    snap = None
+    if state is not None:
+      if isinstance(example, torch.Tensor) and example.dtype not in (torch.uint8,):
+        raise NotImplementedError(
+            "capture with u_state takes integer-typed windows (uint8, PackedFrames, PackedSpikes): a %s "
+            "window runs as a launch pair that swaps the state's buffers" % example.dtype)
+      snap = state.clone()
+      self._window_steps = int(example.shape[1])
     self.static_input = self._clone(example)
     self._stream = torch.cuda.Stream(device=dev)
     self._graph = torch.cuda.CUDAGraph()
@@ -670,6 +686,7 @@ class CapturedApply:
     with torch.cuda.stream(self._stream):
       for _ in range(2):               # packs, caches and the allocator's pools, outside the capture
         module.apply(variables, self.static_input, **kwargs)
+      self._restore(snap)
       self._stream.synchronize()
       # the conv launches recorded below take a work-queue slot each (snnqp.h): remember which,
       # so that they go back to the pool with this object
@@ -680,6 +697,8 @@ class CapturedApply:
       try:
         with torch.cuda.graph(self._graph, stream=self._stream):
           self.static_output = module.apply(variables, self.static_input, **kwargs)
+        if state is not None:
+          state.steps = snap.steps           # (recording ran nothing: only the host's count moved)
       finally:
         ops._CAPTURE_KEEP = outer
         self._slots = (mark, ops.workqueue_capture_mark(self._device))
@@ -701,6 +720,18 @@ class CapturedApply:
 
   def __del__(self):
     self.close()
+
+  def _restore(self, snap):
+    """The stream state as it was before the warm-up runs (an empty one: sized, all zero)."""
+    state = self._state
+    if state is None:
+      return
+    if snap.counts is None:
+      state.reset()
+    else:
+      for dst, src in zip(state._tensors(), snap._tensors()):
+        dst.copy_(src)
+      state.steps = snap.steps
 
   def _clone(self, x):
     ops = self._ops
@@ -724,6 +755,8 @@ class CapturedApply:
     if self._graph is None:
       raise RuntimeError("this CapturedApply has been closed")
     self._graph.replay()
+    if self._state is not None:
+      self._state.steps += self._window_steps    # (row_steps is advanced by the graph)
     return self.static_output
 
 

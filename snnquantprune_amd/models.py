@@ -18,6 +18,9 @@ BatchNorm_i, QuantDense_i; tcja_load_pretrained_weights.py:19-36).
 
 All three train (`apply(..., train=True, rng=...)`): the training forward
 is each model's `_train_forward`, attached to torch autograd through the parameter leaves.
+
+DenseSNN and ConvDenseSNN stream (`apply(variables, window, u_state=StreamState())`):
+the membranes of every block and the read-out's spike counts survive between calls.
 """
 
 from __future__ import annotations
@@ -130,6 +133,132 @@ def _as_input(inputs):
   return x
 
 
+class StreamState:
+  """What a model carries from one window of a stream to the next:
+
+    membranes  the float32 potentials of every SpikingBlock, in model order: [B, OH, OW, C] at the
+               block's own, pre-pool resolution for a conv block, [B, N] for a dense block
+    counts     int32 [B, N_out]: the read-out's spike counts so far
+    row_steps  int32 [B]: the steps every batch row has seen since its last reset
+    steps      host int: the steps since the state was created or last reset as a whole
+
+  `StreamState()` is empty; the first `apply(..., u_state=state)` sizes it with zeros (the initial
+  potentials of initialize_carry).  Every later call updates the same tensors."""
+
+  def __init__(self):
+    self.membranes = []
+    self.counts = None
+    self.row_steps = None
+    self.steps = 0
+
+  @classmethod
+  def zeros(cls, shapes, n_out, device=None):
+    """A zero state for blocks whose membranes have `shapes` (each [B, ...]) and n_out read-out neurons."""
+    st = cls()
+    st._fit([tuple(int(d) for d in sh) for sh in shapes], int(n_out), device)
+    return st
+
+  def _fit(self, shapes, n_out, device):
+    """Sizes an empty state; ValueError when a sized one is not for these blocks / this batch / device."""
+    B = shapes[0][0]
+    if self.counts is None:
+      self.membranes = [torch.zeros(sh, dtype=torch.float32, device=device) for sh in shapes]
+      self.counts = torch.zeros((B, n_out), dtype=torch.int32, device=device)
+      self.row_steps = torch.zeros((B,), dtype=torch.int32, device=device)
+      self.steps = 0
+      return
+    have = [tuple(u.shape) for u in self.membranes]
+    if self.counts.shape[0] != B:
+      raise ValueError("u_state holds %d batch rows, the window has %d" % (self.counts.shape[0], B))
+    if have != list(shapes) or tuple(self.counts.shape) != (B, n_out):
+      raise ValueError("u_state was sized for membranes %s and %d outputs, this model and window need %s and %d"
+                       % (have, self.counts.shape[1], list(shapes), n_out))
+    if device is not None and self.counts.device != torch.device(device):
+      raise ValueError("u_state lives on %s, the window on %s" % (self.counts.device, device))
+
+  def _tensors(self):
+    return list(self.membranes) + [self.counts, self.row_steps]
+
+  def advance(self, steps: int):
+    """Books `steps` time steps for every row (the model does this once per window)."""
+    self.steps += int(steps)
+    self.row_steps += int(steps)
+
+  def logits(self, group: int = 10):
+    """float32 [B, num_classes]: the vote over every step so far -- counts / steps, then the in-order
+    mean over each class's `group` neurons: the operations and order of ops.vote, on the device
+    (snnqp_vote_counts).  A row that has seen no step votes 0."""
+    if self.counts is None:
+      raise ValueError("an empty StreamState has no vote")
+    if self.counts.is_cuda:
+      return ops.vote_counts(self.counts, self.row_steps, group)
+    B, N = self.counts.shape
+    if N % group:
+      raise ValueError("vote: %d features not divisible by group %d" % (N, group))
+    steps = self.row_steps.to(torch.float32)[:, None]
+    mean_t = (self.counts.to(torch.float32) / steps).reshape(B, N // group, group)
+    acc = torch.zeros((B, N // group), dtype=torch.float32)
+    for g in range(group):
+      acc = acc + mean_t[:, :, g]
+    return torch.where(steps > 0, acc / float(group), torch.zeros_like(acc))
+
+  def reset(self, rows=None):
+    """Zeroes the membranes, counts and step counts of the batch rows `rows` (all rows when None):
+    a new recording starts in those slots."""
+    if self.counts is None:
+      return self
+    if rows is None:
+      for t in self._tensors():
+        t.zero_()
+      self.steps = 0
+      return self
+    idx = torch.as_tensor(rows, dtype=torch.long).reshape(-1)
+    B = self.counts.shape[0]
+    if idx.numel() and (int(idx.min()) < 0 or int(idx.max()) >= B):
+      raise ValueError("reset: rows %s outside the state's %d batch rows" % (idx.tolist(), B))
+    idx = idx.to(self.counts.device)
+    for t in self._tensors():
+      t.index_fill_(0, idx, 0)
+    return self
+
+  def clone(self):
+    """A snapshot: new tensors with the same values."""
+    st = StreamState()
+    st.membranes = [u.clone() for u in self.membranes]
+    st.counts = None if self.counts is None else self.counts.clone()
+    st.row_steps = None if self.row_steps is None else self.row_steps.clone()
+    st.steps = self.steps
+    return st
+
+
+def _stream_state(mod, cfg, u_state):
+  """The StreamState of an eval call (None: the whole-run call), after the refusals every model shares."""
+  if u_state is None:
+    return None
+  if not isinstance(u_state, StreamState):
+    raise TypeError("u_state must be a models.StreamState, got %s" % type(u_state).__name__)
+  if _probing(mod, cfg):
+    raise NotImplementedError("density probes together with u_state: probe the whole-run call")
+  return u_state
+
+
+def _window_done(state, x, window_logits, steps):
+  """The read-out raster `x` of a window behind the per-block path: counted, voted, booked."""
+  ops.vote_accumulate(x, state.counts)
+  state.advance(steps)
+  return window_logits, state
+
+
+def _carry(state, i, layer, x):
+  """Block i of a stream on the per-block path.  A block there may be a launch pair (the float32 stand-by
+  of ops.FloatFallback, the event layer's binary-first launch and its redo), so it never updates a
+  potential in place: it reads the state's buffer, writes u_T to a buffer of its own, and that is
+  copied into the state's -- whose address stays what a captured window was recorded with."""
+  u_T, x = layer(state.membranes[i], x)
+  state.membranes[i].copy_(u_T)
+  return x
+
+
 # The dense head of a given set of parameters, prepared once: what `fused_dense_head` hands to
 # the kernel depends on the parameter tensors (identity and version), the two bit widths, the
 # quantiser and neuron factories of the config and the input's layout -- nothing else.  A step
@@ -179,37 +308,64 @@ class DenseSNN(nn.Module):
     x = _as_input(inputs)
     hidden = cfg.hidden if "hidden" in cfg else cfg.channels * 2 * 2
     probe = _probing(self, cfg)
+    state = _stream_state(self, cfg, u_state)
+    nout = self.num_classes * 10
+    if state is not None:
+      if x.ndim != 3:
+        raise ValueError("DenseSNN expects [B, T, K] inputs, got %s" % (tuple(x.shape),))
+      B, steps = x.shape[0], x.shape[1]
+      state._fit([(B, hidden), (B, nout)], nout, x.device)
+      if steps == 0:                                   # nothing to scan: the state stays as it is
+        return torch.zeros((B, self.num_classes), dtype=torch.float32, device=x.device), state
     global _head_plans
-    key = None if probe else _head_key(self, cfg, x, hidden, self.num_classes * 10)
+    key = None if probe else _head_key(self, cfg, x, hidden, nout)
     if key is not None:
+      if state is not None:
+        key = (key[0], key[1] + ("stream",))           # a stateless plan is never a stateful call's
       if _head_plans is None:
         from ._cache import TensorCache
         _head_plans = TensorCache(32)
       plan = _head_plans.get(*key)
       if plan is not None:
         w1, K, N1, nrn1, w2, N2, nrn2, group, tm, fb, _refs = plan
+        if state is not None:
+          return self._head_window(state, steps, ops.dense_head_forward_state(
+              x, w1, K, N1, nrn1, w2, N2, nrn2, state.membranes[0], state.membranes[1], state.counts,
+              group=group, time_major=tm, fallback=fb))
         return ops.dense_head_forward(x, w1, K, N1, nrn1, w2, N2, nrn2, group=group, time_major=tm,
                                       fallback=fb)[0], None
     layer = SpikingBlock(
         connection_fn=_qdense(cfg, self.dtype, _layer_bits(cfg, 0), hidden),
         neural_dynamics=cfg.neuron_dynamics(dtype=self.dtype),
-        return_state=False, batch_major_input=True)
+        return_state=state is not None, batch_major_input=True)
     layer2 = SpikingBlock(
-        connection_fn=_qdense(cfg, self.dtype, _layer_bits(cfg, 1), self.num_classes * 10),
+        connection_fn=_qdense(cfg, self.dtype, _layer_bits(cfg, 1), nout),
         neural_dynamics=cfg.neuron_dynamics(dtype=self.dtype),
-        return_state=False)
+        return_state=state is not None)
     if not probe:
       # both blocks and the vote as one launch when the head fits it (the hidden raster then
       # never leaves the CU); the output raster only when somebody collects the intermediates
       want_s2 = self.is_mutable_collection("intermediates")
-      head = fused_dense_head(layer, layer2, x, 10, want_s2=want_s2)
+      head = fused_dense_head(layer, layer2, x, 10, want_s1=want_s2 and state is not None, want_s2=want_s2,
+                              state=None if state is None else (state.membranes[0], state.membranes[1], state.counts))
       if head is not None:
         if want_s2:
+          if state is not None:
+            self.sow("intermediates", "dense1_out", head[1])
           self.sow("intermediates", "dense2_out", head[2])
         if key is not None and fused_dense_head.last_plan is not None:
           # (the factories are kept alive with the plan: their ids are part of its key)
           _head_plans.put(key[0], key[1], fused_dense_head.last_plan + ((cfg.quant.get("weight"), cfg.neuron_dynamics),))
+        if state is not None:
+          return self._head_window(state, steps, head)
         return head[0], None
+    if state is not None:
+      # the head does not fit the one launch: block by block with their carries, the counting vote
+      x = _carry(state, 0, layer, x)
+      self.sow("intermediates", "dense1_out", x)
+      x = _carry(state, 1, layer2, x)
+      self.sow("intermediates", "dense2_out", x)
+      return _window_done(state, x, ops.vote(x, 10), steps)
     if probe:
       _sow_density(self, "dense1_inpt", x)
     _, x = layer(None, x)
@@ -221,6 +377,14 @@ class DenseSNN(nn.Module):
     if probe:
       _sow_density(self, "dense2_out", x)
     return ops.vote(x, 10), None                       # models.py:253-255
+
+  @staticmethod
+  def _head_window(state, steps, head):
+    """Books a window the stateful head has run: it counted into state.counts itself; the membranes
+    are the tensors it hands back (the state's own, or -- float32 rows -- the copies it wrote)."""
+    state.membranes[0], state.membranes[1] = head[3], head[4]
+    state.advance(steps)
+    return head[0], state
 
   def _train_forward(self, inputs, rng, u_state, online):
     """The training forward of models.py:191-255 (dropout masks M0 on the input and M1 on the
@@ -258,19 +422,32 @@ class ConvDenseSNN(nn.Module):
     x = _as_input(inputs)
     nblocks = cfg.num_conv_blocks if "num_conv_blocks" in cfg else 3
     probe = _probing(self, cfg)
+    state = _stream_state(self, cfg, u_state)
     compact = _compacting(self, cfg, u_state)
+    nout = self.num_classes * 10
+    if state is not None:
+      if x.ndim != 5:
+        raise ValueError("ConvDenseSNN expects [B, T, H, W, 2] inputs, got %s" % (tuple(x.shape),))
+      B, steps, H, W = x.shape[:4]
+      # a conv block's membranes at its own resolution: the 2x2 pool halves what the next one sees
+      state._fit([(B, H >> i, W >> i, cfg.channels) for i in range(nblocks)] + [(B, nout)], nout, x.device)
+      if steps == 0:                                   # nothing to scan: the state stays as it is
+        return torch.zeros((B, self.num_classes), dtype=torch.float32, device=x.device), state
     for i in range(nblocks):
       layer = SpikingBlock(
           connection_fn=_qconv3x3(cfg, self.dtype, _layer_bits(cfg, i)),
           neural_dynamics=cfg.neuron_dynamics(dtype=self.dtype),
           norm_fn=_batchnorm(self.dtype),
           pool=1 if probe else 2,       # the reduce_window max of models.py:145-147
-          return_state=False,
+          return_state=state is not None,
           batch_major_input=(i == 0),   # models.py:109 swapaxes, done by strides
           compact=compact)
       if probe:
         _sow_density(self, "conv_%d_inpt" % i, x)
-      _, x = layer(None, x)
+      if state is not None:
+        x = _carry(state, i, layer, x)
+      else:
+        _, x = layer(None, x)
       if probe:
         _sow_density(self, "conv_%d_out" % i, x)
         x = ops.maxpool2x2(x)
@@ -279,9 +456,13 @@ class ConvDenseSNN(nn.Module):
     if probe:
       _sow_density(self, "dense1_inpt", x)
     layer = SpikingBlock(
-        connection_fn=_qdense(cfg, self.dtype, _layer_bits(cfg, nblocks), self.num_classes * 10),
+        connection_fn=_qdense(cfg, self.dtype, _layer_bits(cfg, nblocks), nout),
         neural_dynamics=cfg.neuron_dynamics(dtype=self.dtype),
-        return_state=False)
+        return_state=state is not None)
+    if state is not None:
+      x = _carry(state, nblocks, layer, x)
+      self.sow("intermediates", "dense_out", x)
+      return _window_done(state, x, ops.vote(x, 10), steps)
     _, x = layer(None, x)
     self.sow("intermediates", "dense_out", x)
     if probe:
@@ -324,6 +505,10 @@ class CextNet(nn.Module):
                u_state=None, online=False):
     if train:
       return self._train_forward(inputs, rng, u_state, online)
+    if u_state is not None:
+      raise NotImplementedError(
+          "CextNet does not stream: its TCJA gates are convolutions over the window's time axis with T "
+          "features, so a window shorter than the configured T has no defined gate (DESIGN.md 15)")
     cfg = self.config
 
     def qconv1d(features, x):

@@ -1305,6 +1305,38 @@ def dense_head_forward(x, w1: Weight, K: int, N1: int, nrn1: Neuron, w2: Weight,
                        nrn2: Neuron, group: int = 10, want_s1: bool = False,
                        want_s2: bool = False, time_major: bool = True,
                        fallback: Optional[FloatFallback] = None):
+  """See _dense_head: the head whose membranes start from zero and are not returned."""
+  return _dense_head(x, w1, K, N1, nrn1, w2, N2, nrn2, group, want_s1, want_s2, time_major, fallback, None)[:3]
+
+
+def dense_head_forward_state(x, w1: Weight, K: int, N1: int, nrn1: Neuron, w2: Weight, N2: int,
+                             nrn2: Neuron, u1: torch.Tensor, u2: torch.Tensor, counts: torch.Tensor,
+                             group: int = 10, want_s1: bool = False, want_s2: bool = False,
+                             time_major: bool = True, fallback: Optional[FloatFallback] = None,
+                             workspace: bool = True):
+  """The dense head as one launch over one WINDOW of a stream (snnqp_dense_head_forward_state):
+  u1 [B, N1], u2 [B, N2] float32 carry the membranes from window to window, counts int32 [B, N2]
+  the output spike counts; -> (logits of this window, hidden raster | None, output raster | None,
+  u1, u2) where u1 / u2 are the tensors that now hold the state.
+
+  uint8 and bit-packed rows: one launch, which updates u1, u2 and counts in place (each value is
+  read and written by the lane that owns it, snnqp.h) and returns the tensors it was given.
+  float32 rows are a launch PAIR -- the integer launch, then the predicated float32 redo -- and no
+  launch of a window may read a potential another launch of it has written: the integer launch runs
+  on copies of u1 / u2 (and counts into a scratch), the redo reads the ORIGINALS and writes the
+  copies, and the copies are returned for the caller to keep instead (a swap); counts then take
+  the window's output raster, whichever launch wrote it (snnqp_vote_accumulate).
+  workspace=False withholds the hand-over workspace: the launch then never splits its columns."""
+  for t, n, dt in ((u1, N1, torch.float32), (u2, N2, torch.float32), (counts, N2, torch.int32)):
+    if not (isinstance(t, torch.Tensor) and t.dtype == dt and t.is_contiguous() and t.ndim == 2 and t.shape[1] == n):
+      raise ValueError("dense_head_forward_state: state tensors are contiguous float32 [B, N1], float32 [B, N2], "
+                       "int32 [B, N2]")
+  return _dense_head(x, w1, K, N1, nrn1, w2, N2, nrn2, group, want_s1, want_s2, time_major, fallback,
+                     (u1, u2, counts), workspace)
+
+
+def _dense_head(x, w1, K, N1, nrn1, w2, N2, nrn2, group, want_s1, want_s2, time_major, fallback, state,
+                workspace=True):
   """The dense head as ONE launch (snnqp_dense_head_forward; examples/tcja/models.py:200-255):
   x [T, B, K] uint8, PackedSpikes or float32 (the rows as the reference holds them, staged in
   place; `fallback` = the float32 kernel of the FIRST block) -> (logits [B, N2 // group], hidden
@@ -1327,16 +1359,27 @@ def dense_head_forward(x, w1: Weight, K: int, N1: int, nrn1: Neuron, w2: Weight,
   s1 = torch.empty((T, B, (N1 + 31) // 32), dtype=torch.int32, device=dev) if (want_s1 or redo) else None
   s2 = torch.empty((T, B, (N2 + 31) // 32), dtype=torch.int32, device=dev) if (want_s2 or redo) else None
   a, b, n1, n2 = w1.struct(), w2.struct(), nrn1.struct(), nrn2.struct()
+  u1 = u2 = counts = None
+  if state is not None:
+    u1, u2, counts = state
+    _require_gpu(u1, u2, counts)
+    if u1.shape[0] != B or u2.shape[0] != B or counts.shape[0] != B:
+      raise ValueError("dense_head_forward_state: a state of %d rows for a window of %d" % (u1.shape[0], B))
+    if redo:
+      u1_0, u2_0, counts_0 = u1, u2, counts
+      u1, u2, counts = u1_0.clone(), u2_0.clone(), torch.zeros_like(counts_0)
   # a batch that fills at most half the chip: two workgroups per tile through a workspace
   nws = _head_ws_bytes.get((T, B, N1))
   if nws is None:
     nws = _head_ws_bytes[(T, B, N1)] = int(L.lib().snnqp_dense_head_workspace_bytes(T, B, N1))
-  ws = _dense_workspace(dev, nws)
-  with _timed("dense_head[%d->%d->%d]" % (K, N1, N2)):
-    L.check(L.lib().snnqp_dense_head_forward(
+  ws = _dense_workspace(dev, nws) if workspace else None
+  rasters = (_ptr(s1) if (want_s1 or redo) else None, _ptr(s2) if (want_s2 or redo) else None)
+  carried = () if state is None else (_ptr(u1), _ptr(u2), _ptr(counts))
+  entry = L.lib().snnqp_dense_head_forward if state is None else L.lib().snnqp_dense_head_forward_state
+  with _timed("dense_head%s[%d->%d->%d]" % ("" if state is None else "_state", K, N1, N2)):
+    L.check(entry(
         _ptr(xt), in_type, xs_t, xs_b, T, B, K, N1, ctypes.byref(a), _ptr(w1.wt), ctypes.byref(n1),
-        N2, ctypes.byref(b), _ptr(w2.wt), ctypes.byref(n2), int(group),
-        _ptr(s1) if (want_s1 or redo) else None, _ptr(s2) if (want_s2 or redo) else None,
+        N2, ctypes.byref(b), _ptr(w2.wt), ctypes.byref(n2), int(group), *carried, *rasters,
         _ptr(logits), _ptr(x_flags), _ptr(ws), 0 if ws is None else ws.numel(), _stream()))
   if redo:
     # not integer-valued after all: the first block on the float32 kernel, the second (its input
@@ -1344,16 +1387,20 @@ def dense_head_forward(x, w1: Weight, K: int, N1: int, nrn1: Neuron, w2: Weight,
     # executed only if the word says so
     fw = fallback.weight.struct()
     lib = L.lib()
+    # (with a carried state: from the potentials the integer launch has NOT touched, into its copies)
+    u1_in, u2_in = (None, None) if state is None else (u1_0, u2_0)
     L.check(lib.snnqp_dense_lif_forward_if(_ptr(x_flags), _ptr(xt), L.F32, xs_t, xs_b, T, B, K, N1,
-                                           ctypes.byref(fw), None, ctypes.byref(n1), None, None, _ptr(s1),
+                                           ctypes.byref(fw), None, ctypes.byref(n1), _ptr(u1_in), _ptr(u1), _ptr(s1),
                                            L.BITS, _stream()))
     cw1 = (N1 + 31) // 32
     L.check(lib.snnqp_dense_lif_forward_if(_ptr(x_flags), _ptr(s1), L.BITS, B * cw1, cw1, T, B, N1, N2,
-                                           ctypes.byref(b), None, ctypes.byref(n2), None, None, _ptr(s2),
+                                           ctypes.byref(b), None, ctypes.byref(n2), _ptr(u2_in), _ptr(u2), _ptr(s2),
                                            L.BITS, _stream()))
     L.check(lib.snnqp_vote_if(_ptr(x_flags), _ptr(s2), L.BITS, T, B, N2, int(group), _ptr(logits), _stream()))
+    if state is not None:
+      counts = vote_accumulate(PackedSpikes(s2, N2), counts_0)
   return (logits, PackedSpikes(s1, N1) if want_s1 else None,
-          PackedSpikes(s2, N2) if want_s2 else None)
+          PackedSpikes(s2, N2) if want_s2 else None, u1, u2)
 
 
 _head_ws_bytes = {}
@@ -1812,6 +1859,40 @@ def vote(s, group: int = 10) -> torch.Tensor:
     raise ValueError("vote: %d features not divisible by group %d" % (N, group))
   out = torch.empty((B, N // group), dtype=torch.float32, device=t.device)
   L.check(L.lib().snnqp_vote(_ptr(t), typ, T, B, N, group, _ptr(out), _stream()))
+  return out
+
+
+def vote_accumulate(s, counts: torch.Tensor) -> torch.Tensor:
+  """spikes [T, B, N] of one window: each neuron's spike count is added into counts int32 [B, N],
+  in place (snnqp_vote_accumulate); returns counts."""
+  t, typ, N = _bits_or_f32(s)
+  _require_gpu(t, counts)
+  T, B = t.shape[0], t.shape[1]
+  if not (counts.dtype == torch.int32 and counts.is_contiguous() and tuple(counts.shape) == (B, N)):
+    raise ValueError("vote_accumulate: counts must be contiguous int32 [%d, %d], got %s %s"
+                     % (B, N, counts.dtype, tuple(counts.shape)))
+  L.check(L.lib().snnqp_vote_accumulate(_ptr(t), typ, T, B, N, _ptr(counts), _stream()))
+  return counts
+
+
+def vote_counts(counts: torch.Tensor, steps, group: int = 10) -> torch.Tensor:
+  """counts int32 [B, N] over `steps` time steps -> logits float32 [B, N // group], the bits ops.vote
+  gives for the raster the counts were taken from (snnqp_vote_counts).  steps: an int, or an int32
+  device tensor [B] with every row's own number of steps (a row with none votes 0)."""
+  _require_gpu(counts)
+  B, N = counts.shape
+  if N % group:
+    raise ValueError("vote: %d features not divisible by group %d" % (N, group))
+  if not (counts.dtype == torch.int32 and counts.is_contiguous()):
+    raise ValueError("vote_counts: counts must be contiguous int32")
+  per_row = isinstance(steps, torch.Tensor)
+  if per_row:
+    _require_gpu(steps)
+    if not (steps.dtype == torch.int32 and steps.is_contiguous() and tuple(steps.shape) == (B,)):
+      raise ValueError("vote_counts: per-row steps must be contiguous int32 [%d]" % B)
+  out = torch.empty((B, N // group), dtype=torch.float32, device=counts.device)
+  L.check(L.lib().snnqp_vote_counts(_ptr(counts), 0 if per_row else int(steps), _ptr(steps) if per_row else None,
+                                    B, N, group, _ptr(out), _stream()))
   return out
 
 

@@ -227,15 +227,18 @@ def _flat_perm(c, h, w, device):
 
 
 def fused_dense_head(block1, block2, inputs, group: int = 10, want_s1: bool = False,
-                     want_s2: bool = False):
+                     want_s2: bool = False, state=None):
   """SpikingBlock(QuantDense) -> SpikingBlock(QuantDense) -> vote of examples/tcja/models.py:
   200-255 as ONE launch (snnqp_dense_head_forward) when both blocks are plain fusable dense blocks
   over integer inputs with int8 codes; returns (logits, s1 | None, s2 | None), or None when the
   head does not fit (the caller then runs the blocks one by one: same numbers).  The parameters
-  are created in the order the two blocks would create them."""
+  are created in the order the two blocks would create them.
+  state = (u1 [B, N1], u2 [B, N2], counts int32 [B, N2]): one window of a stream
+  (snnqp_dense_head_forward_state, ops.dense_head_forward_state); the result is then
+  (logits, s1 | None, s2 | None, u1, u2) with the tensors that hold the membranes now."""
   for blk in (block1, block2):
     if (not blk._fusable() or not isinstance(blk.connection_fn, QuantDense) or blk.norm_fn is not None
-        or blk.pool != 1 or blk.impl != L.IMPL_AUTO or blk.return_state):
+        or blk.pool != 1 or blk.impl != L.IMPL_AUTO or (blk.return_state and state is None)):
       return None
   if block2.batch_major_input or getattr(inputs, "flat_perm", None) is not None:
     return None
@@ -268,8 +271,12 @@ def fused_dense_head(block1, block2, inputs, group: int = 10, want_s1: bool = Fa
   # the float32 kernel of the first block stands by (ops.FloatFallback)
   fb = ops.FloatFallback(pk1.float_weight()) if f32 else None
   try:
-    out = ops.dense_head_forward(x, w1, K, N1, nrn1, w2, N2, nrn2, group=group, want_s1=want_s1,
-                                 want_s2=want_s2, time_major=tm, fallback=fb)
+    if state is not None:
+      out = ops.dense_head_forward_state(x, w1, K, N1, nrn1, w2, N2, nrn2, *state, group=group,
+                                         want_s1=want_s1, want_s2=want_s2, time_major=tm, fallback=fb)
+    else:
+      out = ops.dense_head_forward(x, w1, K, N1, nrn1, w2, N2, nrn2, group=group, want_s1=want_s1,
+                                   want_s2=want_s2, time_major=tm, fallback=fb)
   except L.SnnqpError as e:
     if e.code != L.EUNSUPPORTED:
       raise
