@@ -82,7 +82,7 @@ __host__ __device__ inline int u8c2_table_bytes(int lutm, int bound, int rows) {
 #endif
 // SIX waves for the one variant that fits 80 registers without a spill -- bit-packed frames, ONE,
 // per-channel tables, the tau = 2^j neuron with reset to 0, fused pool: the headline's -- with its
-// table entries read in two halves (tile_epilogue_halves), tile 1's fragment and output word at
+// table entries read in two halves (tile_epilogue_parts), tile 1's fragment and output word at
 // immediate offsets from tile 0's and the wave index a scalar: 4.82-4.83 ms against 4.96-4.98 at
 // five waves on the same box.  Its siblings would spill 2-6 dwords per patch at six: five.
 #ifndef SNNQP_U8C2_EV1_ONE_WPS
@@ -118,11 +118,19 @@ constexpr int u8c2_waves() {
 // every wave also issues the half group's MFMA (the operands of the HALF wave above) and runs the
 // epilogue on a quarter of its product: the columns 4 (w & 1) ..+3 of the image rows 4 g ..+3, which
 // the wave brings into registers 0..3 by permuting the rows of its A operand (lane n reads the pixel
-// of lane n ^ 8 w; tile_epilogue_quarter), and stores word 2 of those pixels.  The matrix pipe, nearly
+// of lane n ^ 8 w; EP_QUARTER, conv_tile.h), and stores word 2 of those pixels.  The matrix pipe, nearly
 // idle in this kernel, computes that product four times; the vector work of a patch-step is the same
 // and every wave carries 16 (+ 4) potentials.  The tables are built as ever, wave = channel group
 // (wave 2: the half group's twins); a wave then takes the table addresses of the groups it computes
 // from the scratch.  Staging, barriers, flush, queue and LDS plan are the full path's.
+// The tap rule of the B operand: k row kk = 8 dy + b carries byte b = 2 dx + cin of halo row dy (b < 6:
+// bytes 6, 7 of a row read belong to the next pixel), which meets weight row (3 dy + dx) * 2 + cin =
+// 6 dy + b of HWIO with Cin = 2.  Whether kk is a tap, and its weight row.
+__device__ __forceinline__ bool tap_row(int kk, int &row) {
+  row = 6 * (kk >> 3) + (kk & 7);
+  return kk >= 0 && kk < 24 && (kk & 7) < 6;
+}
+
 template <int NF, bool POOL, int LUTM, int IN = SNNQP_U8, bool ONE = false, bool HALF = false, bool SPREAD = false>
 __global__ void __launch_bounds__(256, (u8c2_waves<NF, POOL, LUTM, IN, ONE, SPREAD>()))
 conv3x3_u8c2_kernel(ConvMfmaArgs a) {
@@ -193,9 +201,9 @@ conv3x3_u8c2_kernel(ConvMfmaArgs a) {
     int pos = 0, neg = 0;
 #pragma unroll
     for (int j = 0; j < 16; ++j) {
-      const int k = 16 * h + j, dy = k >> 3, b = k & 7;
-      if (k < 24 && b < 6 && wave_on && cout < a.Cout) {      // (a wave beyond Cout: one row per lane)
-        const int code = a.w[(int64_t)(6 * dy + b) * a.Cout + ctab];
+      int row;
+      if (tap_row(16 * h + j, row) && wave_on && cout < a.Cout) {      // (a wave beyond Cout: one row per lane)
+        const int code = a.w[(int64_t)row * a.Cout + ctab];
         pos += code > 0 ? code : 0;
         neg += code < 0 ? -code : 0;
       }
@@ -271,9 +279,9 @@ conv3x3_u8c2_kernel(ConvMfmaArgs a) {
         for (int j = 0; j < 4; ++j) {
           const int k = 16 * h + 4 * d + j, kk = k - shift;
           uint32_t bv = 0;
+          int row;
           if (all_taps || k < 24) {
-            if (kk >= 0 && kk < 24 && (kk & 7) < 6)
-              bv = (uint8_t)(a.w[(int64_t)(6 * (kk >> 3) + (kk & 7)) * a.Cout + chan] * 8);
+            if (tap_row(kk, row)) bv = (uint8_t)(a.w[(int64_t)row * a.Cout + chan] * 8);
           } else if (k < 28) {
             const int part = q < 127 ? q : 127;
             q -= part;
@@ -311,14 +319,12 @@ conv3x3_u8c2_kernel(ConvMfmaArgs a) {
       for (int j = 0; j < 4; ++j) {
         const int k = 16 * h + 4 * d + j;
         uint32_t bv = 0, bg = 0;
+        int row;
         if (HALF && half_wave) {
-          const int kk = n >= 16 ? k - 8 : k;
-          if (kk >= 0 && kk < 24 && (kk & 7) < 6)
-            bv = (uint8_t)(a.w[(int64_t)(6 * (kk >> 3) + (kk & 7)) * a.Cout + ctab] * 8);
+          if (tap_row(n >= 16 ? k - 8 : k, row)) bv = (uint8_t)(a.w[(int64_t)row * a.Cout + ctab] * 8);
         } else if (k < 24) {
-          const int dy = k >> 3, b = k & 7;
-          if (b < 6 && cout < a.Cout) {   // HWIO with Cin = 2: row (3 dy + dx) * 2 + cin = 6 dy + b
-            const int code = a.w[(int64_t)(6 * dy + b) * a.Cout + cout];
+          if (tap_row(k, row) && cout < a.Cout) {
+            const int code = a.w[(int64_t)row * a.Cout + cout];
             wsum += code;
             bg = (uint8_t)code;
             bv = (uint8_t)(LUTM == LUT_CHANNEL ? code * 8 : code);   // see build_lut_channel
@@ -617,8 +623,8 @@ conv3x3_u8c2_kernel(ConvMfmaArgs a) {
               const v2i_a4 hi = *(lds_cv2i_t *)(uintptr_t)(img + (uint32_t)offB[0]);
               v16i acc = splat16(0);
               acc = __builtin_amdgcn_mfma_i32_32x32x32_i8(v4i{lo.x, lo.y, hi.x, hi.y}, bw, acc, 0, 0, 0);
-              const uint32_t word = tile_epilogue_halves<NF, POOL, MODE, FMA, OFFS>(acc, u[0], a.dq, lc, a.nrn,
-                                                                                    lane, acc_off);
+              const uint32_t word = tile_epilogue_parts<NF, POOL, MODE, FMA, OFFS, EP_TILE, 4, 2>(
+                  acc, u[0], a.dq, lc, a.nrn, lane, acc_off);
               if (store_lane) o[ob0] = word & cmask;
             }
             if constexpr (HALF) {
@@ -626,8 +632,8 @@ conv3x3_u8c2_kernel(ConvMfmaArgs a) {
               const v2i_a4 hi = *(lds_cv2i_t *)(uintptr_t)(img + (uint32_t)offA[1] + (uint32_t)HROW2);
               const v16i acc = __builtin_amdgcn_mfma_i32_32x32x32_i8(v4i{lo.x, lo.y, hi.x, hi.y}, bfh, c0,
                                                                      0, 0, 0);
-              const uint32_t word = tile_epilogue_quarter<NF, POOL, MODE, FMA, OFFS>(acc, u[1], a.dq, lc, a.nrn,
-                                                                                     acc_off);
+              const uint32_t word = tile_epilogue_parts<NF, POOL, MODE, FMA, OFFS, EP_QUARTER, 2, 1>(
+                  acc, u[1], a.dq, lc, a.nrn, lane, acc_off);
               if (quarter_lane) o[ob1] = word & qmask;
             }
           }
@@ -655,7 +661,7 @@ conv3x3_u8c2_kernel(ConvMfmaArgs a) {
               const v2i_a4 hi = *(lds_cv2i_t *)(uintptr_t)(img + (uint32_t)offA[0] + (uint32_t)HROW2);
               const v16i acc = __builtin_amdgcn_mfma_i32_32x32x32_i8(v4i{lo.x, lo.y, hi.x, hi.y}, bw, c0,
                                                                      0, 0, 0);
-              const uint32_t word = tile_epilogue_halves<NF, POOL, MODE, FMA, OFFS, true>(
+              const uint32_t word = tile_epilogue_parts<NF, POOL, MODE, FMA, OFFS, EP_HALFW, 4, 2>(
                   acc, u[0], a.dq, lc, a.nrn, lane, acc_off);
               if (store_lane) {
                 uint32_t *o = obuf + ((t0 + tt) % FL) * (OutStage<POOL>::NPIX * 4);
@@ -689,8 +695,8 @@ conv3x3_u8c2_kernel(ConvMfmaArgs a) {
                                                         0, 0, 0);
             // (the six-wave build reads its table entries in two halves: eight in flight, not sixteen)
             if constexpr (u8c2_waves<NF, POOL, LUTM, IN, ONE>() >= 6)
-              words[tl] = tile_epilogue_halves<NF, POOL, MODE, FMA, OFFS>(acc, u[tl], a.dq, lc, a.nrn,
-                                                                            lane, acc_off);
+              words[tl] = tile_epilogue_parts<NF, POOL, MODE, FMA, OFFS, EP_TILE, 4, 2>(acc, u[tl], a.dq, lc, a.nrn,
+                                                                                        lane, acc_off);
             else
               words[tl] = tile_epilogue<NF, POOL, MODE, FMA, OFFS>(acc, u[tl], a.dq, lc, a.nrn,
                                                                      lane, acc_off);
@@ -862,6 +868,13 @@ static void launch_u8c2_nf(const ConvMfmaArgs &a, int nf, int in_type, bool pool
   else launch_u8c2_in<NF_DECAY, LUTM>(a, in_type, pool, one, gy, st, lds);
 }
 
+// The half-group and spread instances: bit-packed frames, ONE, per-channel tables, NF_MUL0 (u8c2_plan)
+template <bool HALF, bool SPREAD>
+static void launch_u8c2_event(const ConvMfmaArgs &a, bool pool, unsigned gy, hipStream_t st, size_t lds) {
+  if (pool) launch_persistent(conv3x3_u8c2_kernel<NF_MUL0, true, LUT_CHANNEL, SNNQP_EV1, true, HALF, SPREAD>, a, gy, st, lds);
+  else launch_persistent(conv3x3_u8c2_kernel<NF_MUL0, false, LUT_CHANNEL, SNNQP_EV1, true, HALF, SPREAD>, a, gy, st, lds);
+}
+
 int launch_conv3x3_u8c2(ConvMfmaArgs a, int in_type, const snnqp_weight_t *w, int x_max, int32_t *x_flags,
                         hipStream_t st) {
   a.patch_h = 8;                             // this kernel's patch: two tiles of 4x8 pixels
@@ -885,16 +898,9 @@ int launch_conv3x3_u8c2(ConvMfmaArgs a, int in_type, const snnqp_weight_t *w, in
     a.x_flags = x_flags;
   }
   if (plan.lut) check_code_bound_once(stream_device(st), a.w, (int64_t)9 * a.Cin, a.Cout, w->abs_sum_max, st);
-  if (plan.spread) {
-    constexpr int N0 = NF_MUL0, LC = LUT_CHANNEL, E1 = SNNQP_EV1;
-    if (plan.half && pl) launch_persistent(conv3x3_u8c2_kernel<N0, true, LC, E1, true, true, true>, a, gy, st, plan.ldsb);
-    else if (plan.half) launch_persistent(conv3x3_u8c2_kernel<N0, false, LC, E1, true, true, true>, a, gy, st, plan.ldsb);
-    else if (pl) launch_persistent(conv3x3_u8c2_kernel<N0, true, LC, E1, true, false, true>, a, gy, st, plan.ldsb);
-    else launch_persistent(conv3x3_u8c2_kernel<N0, false, LC, E1, true, false, true>, a, gy, st, plan.ldsb);
-  } else if (plan.half && pl)
-    launch_persistent(conv3x3_u8c2_kernel<NF_MUL0, true, LUT_CHANNEL, SNNQP_EV1, true, true>, a, gy, st, plan.ldsb);
-  else if (plan.half)
-    launch_persistent(conv3x3_u8c2_kernel<NF_MUL0, false, LUT_CHANNEL, SNNQP_EV1, true, true>, a, gy, st, plan.ldsb);
+  if (plan.half && plan.spread) launch_u8c2_event<true, true>(a, pl, gy, st, plan.ldsb);
+  else if (plan.spread) launch_u8c2_event<false, true>(a, pl, gy, st, plan.ldsb);
+  else if (plan.half) launch_u8c2_event<true, false>(a, pl, gy, st, plan.ldsb);
   else if (plan.lutc) launch_u8c2_nf<LUT_CHANNEL>(a, nf, in_type, pl, plan.one, gy, st, plan.ldsb);
   else if (plan.lut) launch_u8c2_nf<LUT_SHARED>(a, nf, in_type, pl, plan.one, gy, st, plan.ldsb);
   else launch_u8c2_nf<LUT_NONE>(a, nf, in_type, pl, plan.one, gy, st, plan.ldsb);

@@ -385,11 +385,98 @@ __device__ __forceinline__ void neuron_pair(v2f y, float &u0, float &u1,
   u1 = neuron_reset<NF>(uu.y, m1, lc);
 }
 
-// BatchNorm + neuron + spike words of one 32x32 tile from its 8 dequantised pairs.
-// The lane mask of register i holds pixel (ty = 2*(i>>3), tx = i&7) in its low half
-// and (ty + 1, tx) in its high half.  Returns the word this lane stores:
-//   POOL : lanes 0..7  = pooled pixel (pty = lane >> 2, ptx = lane & 3)
-//   !POOL: lanes 0..31 = pixel row `lane` of the tile
+// Where the two compare masks of register pair p (registers 2 p, 2 p + 1) go: the masks are
+// wave-uniform, so v_writelane drops each word into the lane that stores it (no per-lane compare
+// masks to keep in SGPRs).  `myw` in, `myw` out.  Three forms of the product exist:
+//   EP_TILE   : one 32x32 tile.  The lane mask of register i holds pixel (ty = 2*(i>>3), tx = i&7) in
+//               its low half and (ty + 1, tx) in its high half.  The word a lane stores:
+//                 POOL : lanes 0..7  = pooled pixel (pty = lane >> 2, ptx = lane & 3)
+//                 !POOL: lanes 0..31 = pixel row `lane` of the tile
+//   EP_HALFW  : the half-group wave (conv3x3_u8c2.hip).  Lanes n and n + 16 hold ONE channel at the
+//               pixels (Y, tx) and (Y + 1, tx), Y = 2 ty the even image rows of the 8x8 patch, so the
+//               64-bit mask of register i (tx = i & 7, g = i >> 3) is four 16-channel fields: image rows
+//               4 g .. 4 g + 3.  The 2x2 pool's row pair lies inside a lane half.  In bits 0..15 (bits
+//               16..31 are zero):
+//                 POOL : lanes 0..15 = pooled pixel `lane` of the patch (4 x 4)
+//                 !POOL: lanes 0..63 = pixel `lane` of the patch (8 x 8)
+//   EP_QUARTER: the same fields over registers 0..3 (the spread launch, conv3x3_u8c2.hip): a wave that
+//               runs one quarter of the half group's product.  The wave permutes the ROWS of its A
+//               operand so that its quarter -- columns 4 q .. 4 q + 3 of image rows 4 g .. 4 g + 3 --
+//               arrives in registers 0..3 whatever (g, q) is: register i = column 4 q + i.
+//                 POOL : lanes j, 4 + j (j = 0, 1) = pooled pixel (row 2 g, 2 g + 1; column 2 q + j)
+//                 !POOL: lanes 4 r + i (r, i = 0..3) = pixel (row 4 g + r, column 4 q + i)
+// The two field forms are one placement: pooled words in lane rows of 4 (the quarter fills two of
+// a row), the others in rows of PW pixels -- the patch's 8, the quarter's 4.
+enum { EP_TILE = 0, EP_HALFW = 1, EP_QUARTER = 2 };
+template <int FORM, bool POOL>
+__device__ __forceinline__ uint32_t place_words(unsigned long long m0, unsigned long long m1, int p, uint32_t myw) {
+  if (FORM == EP_TILE && POOL) {
+    const unsigned long long o = m0 | m1;
+    const uint32_t pw = (uint32_t)o | (uint32_t)(o >> 32);
+    myw = writelane_u32(pw, p, myw);
+  } else if (FORM == EP_TILE) {
+    const int r0 = (2 * p & 3) + 8 * (p >> 1);      // row of register 2 p, low half
+    myw = writelane_u32((uint32_t)m0, r0, myw);
+    myw = writelane_u32((uint32_t)(m0 >> 32), r0 + 4, myw);
+    myw = writelane_u32((uint32_t)m1, r0 + 1, myw);
+    myw = writelane_u32((uint32_t)(m1 >> 32), r0 + 5, myw);
+  } else {
+    constexpr int PW = FORM == EP_HALFW ? 8 : 4;
+    const int g = p >> 2, j = p & 3;                // (the quarter: g = 0)
+    if (POOL) {
+      const unsigned long long o = m0 | m1;
+      const uint32_t lo = (uint32_t)o, hi = (uint32_t)(o >> 32);
+      myw = writelane_u32((lo | (lo >> 16)) & 0xFFFFu, 8 * g + j, myw);          // pooled row 2 g
+      myw = writelane_u32((hi | (hi >> 16)) & 0xFFFFu, 8 * g + 4 + j, myw);      // pooled row 2 g + 1
+    } else {
+#pragma unroll
+      for (int r = 0; r < 4; ++r) {
+        myw = writelane_u32((uint32_t)(m0 >> (16 * r)) & 0xFFFFu, (4 * g + r) * PW + 2 * j, myw);
+        myw = writelane_u32((uint32_t)(m1 >> (16 * r)) & 0xFFFFu, (4 * g + r) * PW + 2 * j + 1, myw);
+      }
+    }
+  }
+  return myw;
+}
+
+// BatchNorm + neuron + spike words of PARTS x PAIRS register pairs of a product, from register 0 on.
+// The table reads (dequant_pair) of a part are issued first, then its pairs are processed; the
+// scheduling barrier keeps the parts apart.  Returns the word this lane stores (place_words).
+//   <EP_TILE, 4, 2>   : a tile in two halves of four pairs: eight table reads in flight instead of
+//                       sixteen -- fewer registers alive, for the build that buys a sixth wave per
+//                       SIMD with them (conv3x3_u8c2.hip)
+//   <EP_HALFW, 4, 2>  : the product of the half-group wave, the same way
+//   <EP_QUARTER, 2, 1>: a quarter of it: four potentials, four table reads
+// (`lane` is not read.  It stays a parameter, here and in tile_epilogue: without it the no-pool
+// half-group instances come out of the register allocator with other register numbers, and the
+// assembly of this kernel is what its refactors are compared by: DESIGN.md 4.2.)
+template <int NF, bool POOL, int LUTM, bool FMA, bool OFFS, int FORM, int PAIRS, int PARTS>
+__device__ __forceinline__ uint32_t tile_epilogue_parts(const v16i &acc, float (&u)[16], const Dequant &dq, const LaneConsts &lc,
+                                                        const NeuronP &nrn, int lane, float off = 0.0f) {
+  uint32_t myw = 0;
+#pragma unroll
+  for (int g = 0; g < PARTS; ++g) {
+    v2f y[PAIRS];
+#pragma unroll
+    for (int j = 0; j < PAIRS; ++j) {
+      const int i = 2 * PAIRS * g + 2 * j;
+      y[j] = dequant_pair<LUTM, OFFS>(acc[i], acc[i + 1], dq, off);
+    }
+#pragma unroll
+    for (int j = 0; j < PAIRS; ++j) {     // masks are consumed pair by pair
+      const int i = 2 * PAIRS * g + 2 * j;
+      unsigned long long m0, m1;
+      neuron_pair<NF, LUTM == LUT_CHANNEL, FMA>(y[j], u[i], u[i + 1], lc, nrn, m0, m1);
+      myw = place_words<FORM, POOL>(m0, m1, i >> 1, myw);
+    }
+    if (PARTS > 1) __builtin_amdgcn_sched_barrier(0);
+  }
+  return myw;
+}
+
+// The neurons of a whole tile from its 8 dequantised pairs (tile_epilogue below; a function of its
+// own: folded into tile_epilogue_parts<EP_TILE, 8, 1> the bit-packed instance with carried potentials
+// allocates its registers differently)
 template <int NF, bool POOL, bool BNDONE, bool FMA = false>
 __device__ __forceinline__ uint32_t tile_neurons(const v2f (&y)[8], float (&u)[16],
                                                  const LaneConsts &lc, const NeuronP &nrn) {
@@ -398,19 +485,7 @@ __device__ __forceinline__ uint32_t tile_neurons(const v2f (&y)[8], float (&u)[1
   for (int i = 0; i < 16; i += 2) {     // masks are consumed pair by pair
     unsigned long long m0, m1;
     neuron_pair<NF, BNDONE, FMA>(y[i >> 1], u[i], u[i + 1], lc, nrn, m0, m1);
-    // the masks are wave-uniform: v_writelane drops each word into the lane that
-    // stores it (no per-lane compare masks to keep in SGPRs)
-    if (POOL) {
-      const unsigned long long o = m0 | m1;
-      const uint32_t pw = (uint32_t)o | (uint32_t)(o >> 32);
-      myw = writelane_u32(pw, i >> 1, myw);
-    } else {
-      const int r0 = (i & 3) + 8 * (i >> 2);          // row of element i, low half
-      myw = writelane_u32((uint32_t)m0, r0, myw);
-      myw = writelane_u32((uint32_t)(m0 >> 32), r0 + 4, myw);
-      myw = writelane_u32((uint32_t)m1, r0 + 1, myw);
-      myw = writelane_u32((uint32_t)(m1 >> 32), r0 + 5, myw);
-    }
+    myw = place_words<EP_TILE, POOL>(m0, m1, i >> 1, myw);
   }
   return myw;
 }
@@ -421,99 +496,11 @@ template <int NF, bool POOL, int LUTM, bool FMA = false, bool OFFS = false>
 __device__ __forceinline__ uint32_t tile_epilogue(const v16i &acc, float (&u)[16],
                                                   const Dequant &dq,
                                                   const LaneConsts &lc,
-                                                  const NeuronP &nrn, int lane,
-                                                  float off = 0.0f) {
+                                                  const NeuronP &nrn, int lane, float off = 0.0f) {
   v2f y[8];
 #pragma unroll
   for (int j = 0; j < 8; ++j) y[j] = dequant_pair<LUTM, OFFS>(acc[2 * j], acc[2 * j + 1], dq, off);
   return tile_neurons<NF, POOL, LUTM == LUT_CHANNEL, FMA>(y, u, lc, nrn);
-}
-
-// The same in two halves of four pairs: eight table reads in flight instead of sixteen -- fewer
-// registers alive, for the build that buys a sixth wave per SIMD with them (conv3x3_u8c2.hip)
-// HALFW (the half-group wave, conv3x3_u8c2.hip): lanes n and n + 16 hold ONE channel at the pixels
-// (Y, tx) and (Y + 1, tx), Y = 2 ty the even image rows of the 8x8 patch, so the 64-bit mask of
-// register i (tx = i & 7, g = i >> 3) is four 16-channel fields: image rows 4 g .. 4 g + 3.  The
-// 2x2 pool's row pair lies inside a lane half.  Returns
-//   POOL : lanes 0..15 = pooled pixel `lane` of the patch (4 x 4)
-//   !POOL: lanes 0..63 = pixel `lane` of the patch (8 x 8)
-// in bits 0..15; bits 16..31 are zero.
-template <int NF, bool POOL, int LUTM, bool FMA = false, bool OFFS = false, bool HALFW = false>
-__device__ __forceinline__ uint32_t tile_epilogue_halves(const v16i &acc, float (&u)[16],
-                                                         const Dequant &dq, const LaneConsts &lc,
-                                                         const NeuronP &nrn, int lane, float off = 0.0f) {
-  uint32_t myw = 0;
-#pragma unroll
-  for (int g = 0; g < 2; ++g) {
-    v2f y[4];
-#pragma unroll
-    for (int j = 0; j < 4; ++j) y[j] = dequant_pair<LUTM, OFFS>(acc[8 * g + 2 * j], acc[8 * g + 2 * j + 1], dq, off);
-#pragma unroll
-    for (int j = 0; j < 4; ++j) {
-      const int i = 8 * g + 2 * j;
-      unsigned long long m0, m1;
-      neuron_pair<NF, LUTM == LUT_CHANNEL, FMA>(y[j], u[i], u[i + 1], lc, nrn, m0, m1);
-      if (HALFW && POOL) {
-        const unsigned long long o = m0 | m1;
-        const uint32_t lo = (uint32_t)o, hi = (uint32_t)(o >> 32);
-        myw = writelane_u32((lo | (lo >> 16)) & 0xFFFFu, 8 * g + j, myw);          // pooled row 2 g
-        myw = writelane_u32((hi | (hi >> 16)) & 0xFFFFu, 8 * g + 4 + j, myw);      // pooled row 2 g + 1
-      } else if (HALFW) {
-#pragma unroll
-        for (int r = 0; r < 4; ++r) {
-          myw = writelane_u32((uint32_t)(m0 >> (16 * r)) & 0xFFFFu, (4 * g + r) * 8 + 2 * j, myw);
-          myw = writelane_u32((uint32_t)(m1 >> (16 * r)) & 0xFFFFu, (4 * g + r) * 8 + 2 * j + 1, myw);
-        }
-      } else if (POOL) {
-        const unsigned long long o = m0 | m1;
-        const uint32_t pw = (uint32_t)o | (uint32_t)(o >> 32);
-        myw = writelane_u32(pw, i >> 1, myw);
-      } else {
-        const int r0 = (i & 3) + 8 * (i >> 2);
-        myw = writelane_u32((uint32_t)m0, r0, myw);
-        myw = writelane_u32((uint32_t)(m0 >> 32), r0 + 4, myw);
-        myw = writelane_u32((uint32_t)m1, r0 + 1, myw);
-        myw = writelane_u32((uint32_t)(m1 >> 32), r0 + 5, myw);
-      }
-    }
-    __builtin_amdgcn_sched_barrier(0);
-  }
-  return myw;
-}
-
-// The HALFW form over a register sub-range (the spread launch, conv3x3_u8c2.hip): a wave that runs one
-// quarter of the half group's product.  The wave permutes the ROWS of its A operand so that its
-// quarter -- columns 4 q .. 4 q + 3 of image rows 4 g .. 4 g + 3 -- arrives in registers 0..3 whatever
-// (g, q) is: register i = column 4 q + i, and its 64-bit mask is the four 16-channel fields of rows
-// 4 g .. 4 g + 3 as above.  Four potentials, four table reads.  Returns, in bits 0..15,
-//   POOL : lanes j, 4 + j (j = 0, 1) = pooled pixel (row 2 g, 2 g + 1; column 2 q + j)
-//   !POOL: lanes 4 r + i (r, i = 0..3) = pixel (row 4 g + r, column 4 q + i)
-template <int NF, bool POOL, int LUTM, bool FMA = false, bool OFFS = false>
-__device__ __forceinline__ uint32_t tile_epilogue_quarter(const v16i &acc, float (&u)[16], const Dequant &dq,
-                                                          const LaneConsts &lc, const NeuronP &nrn,
-                                                          float off = 0.0f) {
-  uint32_t myw = 0;
-  v2f y[2];
-#pragma unroll
-  for (int j = 0; j < 2; ++j) y[j] = dequant_pair<LUTM, OFFS>(acc[2 * j], acc[2 * j + 1], dq, off);
-#pragma unroll
-  for (int j = 0; j < 2; ++j) {
-    unsigned long long m0, m1;
-    neuron_pair<NF, LUTM == LUT_CHANNEL, FMA>(y[j], u[2 * j], u[2 * j + 1], lc, nrn, m0, m1);
-    if (POOL) {
-      const unsigned long long o = m0 | m1;
-      const uint32_t lo = (uint32_t)o, hi = (uint32_t)(o >> 32);
-      myw = writelane_u32((lo | (lo >> 16)) & 0xFFFFu, j, myw);
-      myw = writelane_u32((hi | (hi >> 16)) & 0xFFFFu, 4 + j, myw);
-    } else {
-#pragma unroll
-      for (int r = 0; r < 4; ++r) {
-        myw = writelane_u32((uint32_t)(m0 >> (16 * r)) & 0xFFFFu, 4 * r + 2 * j, myw);
-        myw = writelane_u32((uint32_t)(m1 >> (16 * r)) & 0xFFFFu, 4 * r + 2 * j + 1, myw);
-      }
-    }
-  }
-  return myw;
 }
 
 // Spike words are staged in LDS, obuf[slot = t % FL][pixel][4 words of the 128-

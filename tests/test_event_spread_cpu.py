@@ -127,8 +127,8 @@ def _mask(spikes, where):
 
 @pytest.mark.parametrize("pool", [False, True])
 def test_stored_words_are_the_spikes_of_their_pixels(pool):
-  """The words as tile_epilogue_halves (own unit) and tile_epilogue_quarter (shared unit) drop them into
-  lanes, stored by the plan above, against the raster read directly."""
+  """The words as place_words (conv_tile.h) drops them into lanes -- EP_TILE for the own unit, EP_QUARTER
+  for the shared unit -- stored by the plan above, against the raster read directly."""
   r = np.random.Generator(np.random.PCG64(11))
   s = r.random((8, 8, 80)) < 0.3
   ring = {}
