@@ -249,8 +249,8 @@ typedef struct {
  * form snnqp_events_bin_aug with snnqp_event_aug_t; the host-side
  * query snnqp_conv_float_form; the host-side plan queries snnqp_conv_gated_plan,
  * snnqp_dense_gated_plan, snnqp_dense_wide_plan; streaming inference --
- * snnqp_dense_head_forward_state, snnqp_vote_accumulate, snnqp_vote_counts: new entry points,
- * nothing else moves).
+ * snnqp_dense_head_forward_state, snnqp_vote_accumulate, snnqp_vote_counts; the rate encoder
+ * snnqp_rate_encode with SNNQP_ENCODE_*: new entry points, nothing else moves).
  * A binding compares snnqp_version()
  * with the SNNQP_VERSION it was written against and refuses a library of another version (_lib.py does). */
 #define SNNQP_VERSION 507
@@ -911,6 +911,41 @@ int snnqp_events_bin_aug(const uint32_t *addr, const int32_t *times, const int64
                          const int32_t *sample, const int32_t *start, int32_t B, int mode, int32_t T,
                          int32_t step_us, int32_t H, int32_t W, float scale, const snnqp_event_aug_t *aug,
                          void *out, int out_type, int32_t *flags, snnqp_stream_t stream);
+/* replaces: the `mnist` branch of examples/input_pipeline.py:286-296 (static images, Poisson-
+ *           encoded into num_frames count frames) over a whole batch, in one launch: B rows of a
+ *           device-resident uint8 image set -> [B][T][K] counts or spikes.
+ * images    uint8 [S][K]
+ * sample    int32 [B]: which row of `images` each batch row encodes (any order, repeats allowed); a
+ *           value outside [0, S) encodes as an image of zeros
+ * sample_id uint32 [B]: the id of each row in the key below -- the sample's index in the whole
+ *           source, not in the slice that happens to be resident
+ * table     uint32 [256][16], 4-byte aligned: the thresholds of each pixel value.  An entry of
+ *           2^32 - 1 stands for 2^32: no hash reaches it
+ * kind      SNNQP_ENCODE_BERNOULLI or SNNQP_ENCODE_POISSON
+ * out       element (b, t, k) at os_b * b + os_t * t + k, out_type SNNQP_U8: bytes, strides in
+ *           bytes; SNNQP_BITS (Bernoulli only): int32 words, element k in bit (k & 31) of word
+ *           (k >> 5), the unused high bits of a row's last word 0, strides in words, 4-byte
+ *           aligned.  os_b = T * row, os_t = row is batch-major [B][T][K]; os_b = row, os_t = B * row
+ *           time-major [T][B][K] (row = K bytes or (K + 31) / 32 words).  Every element of every
+ *           (b, t) row is written and nothing else; the strides are the caller's to get right.
+ * For row b, step t and element k, in 32-bit unsigned arithmetic (fmix32: snnqp_events_bin_aug):
+ *   e = t * K + k
+ *   c = fmix32(fmix32(seed ^ fmix32(draw)) ^ sample_id[b])
+ *   u = fmix32(c ^ e)
+ *   v = images[sample[b]][k]
+ *   Bernoulli: 1 iff u < table[v][0], else 0
+ *   Poisson:   the number of j in 0..14 with u >= table[v][j] (0..15; entry 15 is unused
+ *              padding and must be 0)
+ * The value at (sample_id, t, k) depends on nothing else: not on B, the row's place in the batch,
+ * the strides or out_type.  Two launches give the same bytes.
+ * SNNQP_EINVAL, checked on the host before anything is launched: T * K >= 2^32, K < 1, negative
+ * S, B or T, an unknown kind or out_type, Poisson with SNNQP_BITS, and -- with B * T > 0 -- a null
+ * or misaligned pointer.  B == 0 or T == 0 returns SNNQP_OK without a launch. */
+#define SNNQP_ENCODE_BERNOULLI 0
+#define SNNQP_ENCODE_POISSON 1
+int snnqp_rate_encode(const uint8_t *images, int32_t S, const int32_t *sample, const uint32_t *sample_id,
+                      int32_t B, int32_t T, int32_t K, uint32_t seed, uint32_t draw, const uint32_t *table,
+                      int kind, void *out, int out_type, int64_t os_b, int64_t os_t, snnqp_stream_t stream);
 /* replaces: the activation-density probes sown at examples/tcja/models.py:128-142
  *           (consumed by examples/sparsity.py:143-170): non-zero count of each of
  *           NB slices of n elements (C innermost; F32, U8 or BITS). */

@@ -29,6 +29,7 @@ FLAG_CODE_OVERFLOW, FLAG_MASK_NOT_BINARY = 1, 2
 FLAG_NOT_INTEGER, FLAG_GT_ONE, FLAG_GT_127, FLAG_GT_15 = 4, 8, 16, 32
 OK, EINVAL, EUNSUPPORTED, EHIP = 0, -1, -2, -3
 STATUS_QUEUE_CORRUPT, STATUS_TICKET, STATUS_BOUND = 1, 2, 4
+ENCODE_BERNOULLI, ENCODE_POISSON = 0, 1
 
 
 class WeightT(Structure):
@@ -188,6 +189,8 @@ _PROTOTYPES = {
     "snnqp_events_bin_aug": (c_int, [c_void_p, c_void_p, c_void_p, c_int32, c_void_p, c_void_p, c_int32, c_int,
                                      c_int32, c_int32, c_int32, c_int32, c_float, c_void_p, c_void_p, c_int,
                                      c_void_p, c_void_p]),
+    "snnqp_rate_encode": (c_int, [c_void_p, c_int32, c_void_p, c_void_p, c_int32, c_int32, c_int32, c_uint32,
+                                  c_uint32, c_void_p, c_int, c_void_p, c_int, c_int64, c_int64, c_void_p]),
     "snnqp_density": (c_int, [c_void_p, c_int, c_int64, c_int64, c_int32, c_void_p, c_void_p]),
     "snnqp_vote": (c_int, [c_void_p, c_int, c_int32, c_int32, c_int32, c_int32,
                            c_void_p, c_void_p]),

@@ -9,7 +9,7 @@ import sys
 from concurrent.futures import ThreadPoolExecutor
 
 HERE = os.path.dirname(os.path.abspath(__file__))
-SOURCES = ["api.hip", "runtime.hip", "quantize.hip", "spikes.hip", "frames.hip", "events.hip", "elementwise.hip",
+SOURCES = ["api.hip", "runtime.hip", "quantize.hip", "spikes.hip", "frames.hip", "events.hip", "encode.hip", "elementwise.hip",
            "generic_block.hip", "blocks.hip", "workqueue.hip", "conv3x3_mfma.hip", "conv3x3_u8c2.hip",
            "conv3x3_bits.hip", "conv3x3_currents.hip",
            "dense_mfma.hip", "dense_wide.hip", "dense_fp6.hip", "fseq_gemm.hip", "conv_gated.hip", "dense_gated.hip",

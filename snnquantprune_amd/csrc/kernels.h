@@ -134,6 +134,11 @@ FseqForm fseq_gemm_form(const void *x, int in_type, int64_t NB, const snnqp_conv
 int run_fseq_gemm(const void *x, int in_type, int64_t NB, const snnqp_conv_geom_t *g,
                   const snnqp_weight_t *w, float *y, hipStream_t st);
 
+// snnqp_rate_encode: the checks, the geometry and the launch of the rate encoder (encode.hip)
+int run_rate_encode(const uint8_t *images, int32_t S, const int32_t *sample, const uint32_t *sample_id,
+                    int32_t B, int32_t T, int32_t K, uint32_t seed, uint32_t draw, const uint32_t *table,
+                    int kind, void *out, int out_type, int64_t os_b, int64_t os_t, hipStream_t st);
+
 // The row rules of the dense MFMA kernels, as a mask of the broken ones: strides not negative; uint8 /
 // float32 rows 16-byte aligned; the offsets of one workgroup (`steps` timestep and `samples` sample
 // strides, a row of `extent` units; float32: in bytes) below 2^31.  The caller words the refusal.

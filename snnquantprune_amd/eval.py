@@ -8,7 +8,8 @@ Differences forced by the platform, none in the numbers:
     metrics that pmap stacks on the host (eval.py:125-129) are all-gathered;
   * the dataset is a `.npz` of event-count frames (`config.dataset`), see
     input_pipeline.py; batches are prefetched two deep over PCIe (feed.DeviceFeeder),
-    in the wire format `config.feed_format`;
+    in the wire format `config.feed_format`; an event or image source (input_pipeline.py) is
+    decoded / rate-encoded on the device instead, one launch per batch;
   * `config.prepare_params = True` re-derives the prune masks and DuQ (a, c) from the
     restored kernels the way train_inpt_spikingjelly.py:206-230 does before training
     (a freshly converted TCJA checkpoint has none).
@@ -50,19 +51,23 @@ def latest_checkpoint(workdir: str, prefix: str = "checkpoint_") -> Optional[str
   return best
 
 
-def initialized(key, image_size, model, t, device):
-  """train_utils.py:137-158: variables of a model from a dummy [1, T, S, S, 2] batch."""
+def initialized(key, image_size, model, t, device, *, input_shape=None):
+  """train_utils.py:137-158: variables of a model from a dummy [1, T, S, S, 2] batch, or from one
+  of `input_shape` when that is given (an image source: input_pipeline.image_input_shape)."""
   shape = (1, image_size, image_size, 2) if t == -1 else (1, t, image_size, image_size, 2)
+  if input_shape is not None:
+    shape = tuple(int(d) for d in input_shape)
   variables = model.init({"params": key, "dropout": key},
                          torch.zeros(shape, dtype=torch.float32, device=device), rng=key,
                          trgt=torch.ones((1,)), online=t == -1, train=False)
   return variables["params"], variables.get("batch_stats", {})
 
 
-def create_eval_state(rng, config, model, image_size, device) -> EvalState:
+def create_eval_state(rng, config, model, image_size, device, *, input_shape=None) -> EvalState:
   """create_train_state (train_utils.py:161-192) without the optimiser."""
   params, batch_stats = initialized(rng, image_size, model,
-                                    -1 if "online" in config else config.num_frames, device)
+                                    -1 if "online" in config else config.num_frames, device,
+                                    input_shape=input_shape)
   return EvalState(apply_fn=model.apply, params={"params": params}, batch_stats=batch_stats)
 
 
@@ -125,15 +130,18 @@ def evaluate_metrics(config, workdir: str, *, model=None, source=None, device=No
     from . import models
     model = create_model(model_cls=getattr(models, config.model),
                          num_classes=config.num_classes, config=config)
+  input_shape = None
   if input_pipeline.is_event_source(source):                       # the scaled sensor (input_pipeline.py:87)
     image_size = int(int(source["sensor_size"][-1]) // config.get("resolution_scale", 1))
+  elif input_pipeline.is_image_source(source):                     # [1, T, K] or [1, T, H, W, 2]
+    image_size, input_shape = None, input_pipeline.image_input_shape(source, config)
   else:
     image_size = source["dvs_matrix"].shape[-2]                    # eval.py:98
   state = restore_checkpoint(None, workdir, model.apply, device)   # eval.py:104
   if state is None:
     key = torch.Generator()
     key.manual_seed(int(config.seed))
-    state = create_eval_state(key, config, model, image_size, device)
+    state = create_eval_state(key, config, model, image_size, device, input_shape=input_shape)
   if config.get("prepare_params", False):
     from . import prune_utils
     state = EvalState(state.apply_fn, {"params": prune_utils.prepare_params(state.params["params"], config)},

@@ -1,4 +1,4 @@
-"""Input pipeline -- mirror of examples/input_pipeline.py for two kinds of source (there is no
+"""Input pipeline -- mirror of examples/input_pipeline.py for three kinds of source (there is no
 tfds and no network on the boxes this runs on):
 
   * a FRAME source: event-count frames in host memory (a `.npz` with `dvs_matrix`
@@ -8,7 +8,12 @@ tfds and no network on the boxes this runs on):
     microseconds; `offsets` [N + 1]; `label` [N]; `sensor_size`), eval and training.  The
     rank's slice goes resident on the device as an `ops.EventSet` and every batch is one
     `ops.events_bin` launch (preprocess_data_number, :142-219, or preprocess_data_time,
-    :63-139): nothing crosses PCIe per batch, so there is no host ring.
+    :63-139): nothing crosses PCIe per batch, so there is no host ring;
+  * an IMAGE source: static images (`image` [N, ...] uint8 and `label` [N], no `dvs_matrix`),
+    eval and training -- the `mnist` branch of :286-296, which Poisson-encodes each image into
+    `num_frames` count frames.  The rank's slice goes resident as an `ops.ImageSet` and every
+    batch is one `ops.rate_encode` launch into [B, T, K] (`config.encoding`, `feed_format`
+    "u8" | "bits", `image_layout` "flat" | "frames": ImagePlan); no host ring either.
 
 What is kept from the reference:
   * every PROCESS takes a contiguous slice of the split, `split_size = N // processes`,
@@ -39,6 +44,10 @@ def is_event_source(source) -> bool:
   return all(k in source for k in EVENT_KEYS)
 
 
+def is_image_source(source) -> bool:
+  return "image" in source and "label" in source and "dvs_matrix" not in source and not is_event_source(source)
+
+
 def _open_source(source):
   """The arrays of a source as a dict, unvalidated (a `.npz` path is read)."""
   if isinstance(source, str):
@@ -58,7 +67,14 @@ def load_source(source) -> Dict[str, np.ndarray]:
     return {"addrs": np.asarray(source["addrs"]), "times": np.asarray(source["times"]),
             "offsets": off.astype(np.int64), "label": y.astype(np.int8),
             "sensor_size": np.array([int(hw[0]), int(hw[-1])], np.int64)}
-  x, y = np.asarray(source["dvs_matrix"]), np.asarray(source["label"])
+  if is_image_source(source):
+    x, y = np.asarray(source["image"]), np.asarray(source["label"]).reshape(-1)
+    if x.dtype != np.uint8:
+      raise ValueError("an image source holds uint8 images, got %s" % (x.dtype,))
+    if x.ndim < 1 or x.shape[0] != y.shape[0]:
+      raise ValueError("image must be [N, ...] with one label per image, got %s / %s" % (x.shape, y.shape))
+    return {"image": x, "label": y.astype(np.int8)}
+  x, y =np.asarray(source["dvs_matrix"]), np.asarray(source["label"])
   if x.ndim != 5 or x.shape[-1] != 2 or x.shape[0] != y.shape[0]:
     raise ValueError("dvs_matrix must be [N, T, H, W, 2] with one label per sample, got %s / %s"
                      % (x.shape, y.shape))
@@ -284,13 +300,144 @@ def create_event_split(data, config, train: bool, rank: int = 0, world: int = 1,
   return gen()
 
 
+class ImagePlan:
+  """Everything about an image split that is decided on the host, without a device: the encoder,
+  the batch's format and layout and, per batch, which images are encoded, under which ids and with
+  which draw.  Config keys: num_frames (T), seed, batch_size / eval_batch_size, encoding (a mapping
+  of kind, gain, mean, std: ops.RateTable; default kind "poisson", the reference's encoder),
+  feed_format ("u8" | "bits"), image_layout ("flat" | "frames").
+
+    * eval: the batches in order, remainder dropped, repeated; draw = 0 always, so every
+      evaluation of a sample sees the same spikes;
+    * train: a fresh permutation of the rank's slice per epoch from a torch.Generator seeded
+      `seed + rank`, as EventPlan draws it; draw = 1 + the epoch's index, so every epoch sees fresh
+      spikes and never the evaluation's;
+    * the id that goes into the hash is `lo + index`, the sample's index in the whole source
+      (lo = rank * counts_per_rank): what a sample is encoded as does not depend on the world size.
+
+  The reference encodes with tf.random.poisson under TensorFlow's global generator (and shuffles
+  through a buffer with seed 0), which cannot be reproduced; see DESIGN.md 16."""
+
+  FORMATS = ("u8", "bits")
+  LAYOUTS = ("flat", "frames")
+  ENCODING_KEYS = ("kind", "gain", "mean", "std")
+
+  def __init__(self, config, item_shape, counts_per_rank: int, train: bool, rank: int = 0, world: int = 1):
+    self.train = bool(train)
+    self.T = int(_cfg(config, "num_frames"))
+    self.item_shape = tuple(int(d) for d in item_shape)
+    self.K = int(np.prod(self.item_shape, dtype=np.int64)) if self.item_shape else 1
+    enc = _cfg(config, "encoding")
+    if enc is None:
+      enc = {}
+    if not hasattr(enc, "keys"):
+      raise ValueError("encoding must be a mapping of %s, got %r" % (list(self.ENCODING_KEYS), enc))
+    unknown = sorted(set(enc.keys()) - set(self.ENCODING_KEYS))
+    if unknown:
+      raise ValueError("encoding has unknown keys %s (known: %s)" % (unknown, list(self.ENCODING_KEYS)))
+    self.table = ops.RateTable(enc.get("kind", "poisson"), gain=enc.get("gain", 1.0), mean=enc.get("mean", 0.0),
+                               std=enc.get("std", 1.0))
+    self.fmt = _cfg(config, "feed_format", "u8")
+    if self.fmt not in self.FORMATS:
+      raise ValueError("feed_format must be one of %s, got %r" % (sorted(self.FORMATS), self.fmt))
+    if self.fmt == "bits" and (self.table.kind != "bernoulli" or train):
+      raise ValueError("feed_format %r holds spikes: %s needs feed_format 'u8'"
+                       % (self.fmt, "the training split" if train else "encoding kind %r" % (self.table.kind,)))
+    self.layout = _cfg(config, "image_layout", "flat")
+    if self.layout not in self.LAYOUTS:
+      raise ValueError("image_layout must be one of %s, got %r" % (sorted(self.LAYOUTS), self.layout))
+    if self.layout == "frames":
+      if len(self.item_shape) != 3 or self.item_shape[-1] != 2:
+        raise ValueError("image_layout 'frames' needs images of [N, H, W, 2], got items of %s" % (self.item_shape,))
+      if self.fmt != "u8":
+        raise ValueError("image_layout 'frames' yields uint8 [B, T, H, W, 2] batches: it needs feed_format 'u8'")
+    aug = _cfg(config, "augment")
+    if aug is not None and not (hasattr(aug, "keys") and len(aug.keys()) == 0):
+      raise ValueError("augment is for event sources: an image source has no event to flip, shift or drop")
+    total = int(_cfg(config, "batch_size" if train else "eval_batch_size"))
+    self.per = total // world
+    self.n = int(counts_per_rank)
+    if self.per < 1 or self.n < self.per:
+      raise ValueError("%s %d over %d processes needs at least %d samples per process, the split has %d"
+                       % ("batch_size" if train else "eval_batch_size", total, world, max(self.per, 1), self.n))
+    self.nb = self.n // self.per                                   # drop_remainder=True
+    self.lo = int(rank) * self.n
+    self.seed = int(_cfg(config, "seed", 0))                       # the encoder's: the same on every rank
+    self.gen = torch.Generator()
+    self.gen.manual_seed(self.seed + int(rank))
+
+  @property
+  def batch_shape(self):
+    """The shape of a yielded batch (PackedSpikes: the logical one)."""
+    return (self.per, self.T) + (self.item_shape if self.layout == "frames" else (self.K,))
+
+  def batches(self, skip: int = 0):
+    """Endless (indices, ids, draw) triples: int64 sample indices within the rank's slice, their
+    ids in the whole source and the batch's draw.  `skip`: the first `skip` triples are drawn --
+    the permutations, so the generator ends up where a consumer of them leaves it -- and not
+    yielded: what follows is what a fresh plan yields from its skip-th triple on.  (An eval pass
+    draws nothing, so only skip modulo the pass counts there.)"""
+    skip = int(skip)
+    if skip < 0:
+      raise ValueError("skip must be >= 0, got %d" % skip)
+    if not self.train:
+      skip %= self.nb
+    epoch = 0
+    while True:
+      order = torch.randperm(self.n, generator=self.gen).numpy() if self.train else np.arange(self.n)
+      draw = 1 + epoch if self.train else 0
+      for i in range(self.nb):
+        if skip > 0:
+          skip -= 1
+          continue
+        idx = order[i * self.per:(i + 1) * self.per].astype(np.int64)
+        yield idx, self.lo + idx, draw
+      epoch += 1
+
+
+def create_image_split(data, config, train: bool, rank: int = 0, world: int = 1,
+                       device=None, skip: int = 0) -> Iterator[Dict[str, Any]]:
+  """The batches of an image source, rate-encoded on `device` (see ImagePlan for the rules), from
+  the `skip`-th on: the plan is advanced on the host and nothing is launched for a skipped batch.
+  The rank's slice goes resident as an ops.ImageSet and every batch is one ops.rate_encode launch:
+  uint8 [B, T, K] ("flat"), the same memory seen as [B, T, H, W, 2] ("frames"), or batch-major
+  PackedSpikes [B, T, K] (feed_format "bits": the layout DenseSNN's packed input takes)."""
+  device = torch.device("cuda" if device is None else device)
+  x = data["image"]
+  n = data["label"].shape[0]
+  split = n // world                                               # :245-254
+  lo = rank * split
+  plan = ImagePlan(config, x.shape[1:], split, train, rank, world)
+  images = ops.ImageSet(x[lo:lo + split], device=device)
+  labels = torch.from_numpy(np.ascontiguousarray(data["label"][lo:lo + split])).to(device)
+
+  def gen():
+    for idx, ids, draw in plan.batches(skip):
+      b = ops.rate_encode(images, idx, plan.T, plan.table, seed=plan.seed, draw=draw, sample_id=ids, fmt=plan.fmt)
+      if plan.layout == "frames":
+        b = b.view(plan.batch_shape)
+      yield {"dvs_matrix": b, "label": labels[torch.from_numpy(idx).to(device)]}
+  return gen()
+
+
+def image_input_shape(data, config):
+  """The dummy input a model is initialised from for an image source: [1, T, K] ("flat") or
+  [1, T, H, W, 2] ("frames")."""
+  item = tuple(int(d) for d in data["image"].shape[1:])
+  if _cfg(config, "image_layout", "flat") == "frames":
+    return (1, int(_cfg(config, "num_frames"))) + item
+  return (1, int(_cfg(config, "num_frames")), int(np.prod(item, dtype=np.int64)) if item else 1)
+
+
 def create_split(source, config, train: bool, cache: bool, rank: int = 0, world: int = 1,
                  pin: bool = False, device=None, skip: int = 0) -> Iterator[Dict[str, Any]]:
   """Iterator of this process's batches (input_pipeline.py:222-345), from the `skip`-th on: host
-  batches of a frame source, device batches of an event source."""
+  batches of a frame source, device batches of an event or image source."""
   source = _open_source(source)
   if is_event_source(source):
     return create_event_split(load_source(source), config, train, rank, world, device, skip)
+  if is_image_source(source):
+    return create_image_split(load_source(source), config, train, rank, world, device, skip)
   if train:
     raise NotImplementedError("the training split (shuffle, augmentation) is out of scope")
   data = load_source(source)
@@ -339,6 +486,8 @@ def create_input_iter(source, config, train: bool, cache: bool, rank: int = 0, w
   source = _open_source(source)
   if is_event_source(source):       # decoded on the device: nothing to prefetch
     return create_event_split(load_source(source), config, train, rank, world, device, skip)
+  if is_image_source(source):       # encoded on the device, one launch per batch: the same
+    return create_image_split(load_source(source), config, train, rank, world, device, skip)
   ds = create_split(source, config, train=train, cache=cache, rank=rank, world=world,
                     pin=torch.device(device).type == "cuda", skip=skip)
   return feed.DeviceFeeder(ds, device, 2)

@@ -1823,6 +1823,151 @@ def events_bin(events: EventSet, sample, T: int, H: int, W: int, *, mode, start=
   return PackedFrames(out, H, W, fmt) if packed else out
 
 
+class ImageSet:
+  """The static images of a split, resident on `device` for `rate_encode`: uint8 [N, ...] (a numpy
+  array or a tensor), kept as [N, K] with K the product of the other axes; `item_shape` remembers
+  them.  Anything but uint8 is refused; N = 0 is allowed."""
+
+  def __init__(self, images, device=None):
+    import numpy as np
+    if isinstance(images, torch.Tensor):
+      if device is None:
+        device = images.device
+      x = images.detach()
+    else:
+      x = np.asarray(images)
+      if x.dtype != np.uint8:
+        raise ValueError("images must be uint8, got %s" % (x.dtype,))
+      x = torch.from_numpy(np.ascontiguousarray(x))
+      if device is None:
+        device = torch.device("cpu")
+    if x.dtype != torch.uint8:
+      raise ValueError("images must be uint8, got %s" % (x.dtype,))
+    if x.ndim < 1:
+      raise ValueError("images must be [N, ...], got a scalar")
+    self.item_shape = tuple(int(d) for d in x.shape[1:])
+    self.num_samples = int(x.shape[0])
+    self.K = int(math.prod(self.item_shape))
+    self.data = x.reshape(self.num_samples, self.K).contiguous().to(device)
+
+  @property
+  def device(self):
+    return self.data.device
+
+  def __repr__(self):
+    return "ImageSet(%d images of %s, device=%s)" % (self.num_samples, self.item_shape, self.device)
+
+
+ENCODE_KINDS = {"bernoulli": L.ENCODE_BERNOULLI, "poisson": L.ENCODE_POISSON}
+ENCODE_COUNT_MAX = 15
+
+
+class RateTable:
+  """The 256 x 16 thresholds `rate_encode` compares its hashes with (include/snnqp.h), built on the
+  host in float64.  A pixel value v has the rate r(v) = max(0, gain * ((v / 255 - mean) / std)): a
+  negative rate encodes as 0.
+    bernoulli  entry 0 = min(floor(min(r, 1) * 2^32), 2^32 - 1): a spike iff the hash is below it
+               (2^32 - 1 stands for 2^32, always); the other entries are 0
+    poisson    entry j < 15 = min(floor(P(X <= j; r) * 2^32), 2^32 - 1), P accumulated in ascending j
+               from exp(-r), each term the previous one times r / j; the count is the number of
+               entries the hash is at or above, so it saturates at 15; entry 15 is 0
+  `entries` is the numpy uint32 [256, 16] table, `rates` the float64 [256] rates, and
+  `truncated_mass` the largest P(X > 15) over the 256 values: what the cap at 15 costs (0.0 for
+  bernoulli).  `on(device)` is the table on a device, uploaded once per device."""
+
+  def __init__(self, kind, gain: float = 1.0, mean: float = 0.0, std: float = 1.0):
+    import numpy as np
+    if kind not in ENCODE_KINDS:
+      raise ValueError("kind must be one of %s, got %r" % (sorted(ENCODE_KINDS), kind))
+    gain, mean, std = float(gain), float(mean), float(std)
+    if not (math.isfinite(gain) and math.isfinite(mean) and math.isfinite(std)):
+      raise ValueError("gain, mean and std must be finite, got %r, %r, %r" % (gain, mean, std))
+    if std <= 0.0:
+      raise ValueError("std must be positive, got %r" % (std,))
+    self.kind, self.gain, self.mean, self.std = kind, gain, mean, std
+    self.code = ENCODE_KINDS[kind]
+    r = np.maximum(0.0, gain * ((np.arange(256, dtype=np.float64) / 255.0 - mean) / std))
+    top = 2.0 ** 32
+    e = np.zeros((256, 16), np.float64)
+    self.truncated_mass = 0.0
+    if kind == "bernoulli":
+      e[:, 0] = np.floor(np.minimum(r, 1.0) * top)
+    else:
+      term = np.exp(-r)
+      cdf = term.copy()
+      e[:, 0] = np.floor(cdf * top)
+      for j in range(1, ENCODE_COUNT_MAX + 1):
+        term = term * (r / j)
+        cdf = cdf + term
+        if j < ENCODE_COUNT_MAX:
+          e[:, j] = np.floor(cdf * top)
+      self.truncated_mass = float(np.max(np.clip(1.0 - cdf, 0.0, 1.0)))      # cdf: P(X <= 15)
+    self.rates = r
+    self.entries = np.minimum(e, top - 1.0).astype(np.uint32)
+    self._on = {}
+
+  def on(self, device) -> torch.Tensor:
+    """The table as an int32 [256, 16] tensor (the uint32 bit patterns) on `device`."""
+    import numpy as np
+    device = torch.device(device)
+    if device.type == "cuda" and device.index is None:
+      device = torch.device("cuda", torch.cuda.current_device())
+    t = self._on.get(device)
+    if t is None:
+      t = self._on[device] = torch.from_numpy(self.entries.view(np.int32).copy()).to(device)
+    return t
+
+  def __repr__(self):
+    return "RateTable(%r, gain=%r, mean=%r, std=%r)" % (self.kind, self.gain, self.mean, self.std)
+
+
+def rate_encode(images: ImageSet, sample, T: int, table: RateTable, *, seed, draw=0, sample_id=None,
+                fmt: str = "u8", time_major: bool = False):
+  """One launch (snnqp_rate_encode): row b of the batch encodes image sample[b] of `images` into T
+  steps of K rate-coded elements under `table`.  Returns uint8 [B, T, K] (0 / 1 for a bernoulli
+  table, counts 0..15 for a poisson one) or, fmt "bits" (bernoulli only), PackedSpikes of that
+  shape; time_major=True gives [T, B, K].  `sample` is a host integer array, each entry in [0, N),
+  validated here; `sample_id` (default: `sample`) are the ids that go into the hash -- the samples'
+  indices in the whole source when `images` is one rank's slice --, taken modulo 2^32 as `seed`
+  and `draw` are.  The value at (sample_id, t, k) depends on seed, draw and the pixel alone."""
+  import numpy as np
+  if not isinstance(images, ImageSet):
+    raise ValueError("images must be an ops.ImageSet, got %r" % (type(images).__name__,))
+  if not isinstance(table, RateTable):
+    raise ValueError("table must be an ops.RateTable, got %r" % (type(table).__name__,))
+  if fmt not in ("u8", "bits"):
+    raise ValueError("fmt must be 'u8' or 'bits', got %r" % (fmt,))
+  if fmt == "bits" and table.kind != "bernoulli":
+    raise ValueError("fmt 'bits' holds spikes: it needs a bernoulli table, got %r" % (table.kind,))
+  T, K = int(T), images.K
+  if T < 0:
+    raise ValueError("T must be >= 0, got %d" % T)
+  if K < 1 or T * K >= 2 ** 32:
+    raise ValueError("rate_encode needs K >= 1 and T * K < 2^32, got T = %d, K = %d" % (T, K))
+  rows = _event_rows(sample, "sample", lo=0, hi=images.num_samples - 1)
+  B = rows.shape[0]
+  if sample_id is None:
+    ids = rows
+  else:
+    ids = _host_array(sample_id, "sample_id").reshape(-1)
+    if ids.shape[0] != B:
+      raise ValueError("sample_id must have one entry per batch row (%d), got %d" % (B, ids.shape[0]))
+    ids = np.array([int(i) % 2 ** 32 for i in ids.tolist()], np.int64)          # (uint64 ids too)
+    ids = torch.from_numpy(ids.astype(np.uint32).view(np.int32))
+  _require_gpu(images.data)
+  dev = images.device
+  unit = (K + 31) // 32 if fmt == "bits" else K
+  shape = (T, B, unit) if time_major else (B, T, unit)
+  out = torch.empty(shape, dtype=torch.int32 if fmt == "bits" else torch.uint8, device=dev)
+  if B and T:
+    os_t, os_b = _tb_strides(out, T, B, time_major, unit)
+    both = torch.stack([rows, ids]).to(dev)                                        # one upload
+    L.check(L.lib().snnqp_rate_encode(_ptr(images.data), images.num_samples, _ptr(both[0]), _ptr(both[1]), B, T, K,
+                                      int(seed) % 2 ** 32, int(draw) % 2 ** 32, _ptr(table.on(dev)), table.code,
+                                      _ptr(out), L.BITS if fmt == "bits" else L.U8, os_b, os_t, _stream()))
+  return PackedSpikes(out, K) if fmt == "bits" else out
+
+
 def density(x, lead_dims: int = 2, counts: bool = False) -> torch.Tensor:
   """Fraction of non-zero activations of each leading slice (default per [T, B]),
   the probe of examples/tcja/models.py:128-142; float32 of shape x.shape[:lead_dims]

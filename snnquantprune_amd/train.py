@@ -16,7 +16,7 @@ epoch, keep the best checkpoint.  DESIGN.md 14 has the rules; in short:
   python -m snnquantprune_amd.train --config CONFIG.py --workdir DIR
   python -m snnquantprune_amd.eval --config CONFIG.py --workdir DIR
 CONFIG.py defines get_config() as for eval.py, with the reference's training keys: dataset,
-eval_dataset (event sources, input_pipeline.py), batch_size, eval_batch_size, num_epochs,
+eval_dataset (event or image sources, input_pipeline.py; images: encoding, image_layout), batch_size, eval_batch_size, num_epochs,
 num_train_steps, steps_per_eval, learning_rate, warmup_epochs, optimizer, weight_decay,
 smoothing, log_every_steps, checkpoint_every_epochs, pretrained, quant.start_epoch.
 """
@@ -111,7 +111,7 @@ def _run(config, workdir: str, model, source, eval_source, device):
       raise ValueError("Batch size (" + str(size) + ") must be divisible by "
                        "the number of devices (" + str(world) + ").")
   source = input_pipeline.load_source(config.dataset if source is None else source)
-  if not input_pipeline.is_event_source(source):
+  if not (input_pipeline.is_event_source(source) or input_pipeline.is_image_source(source)):
     raise NotImplementedError("the training split needs an event source (addrs, times, offsets, "
                               "label, sensor_size); frame sources are eval only")
   if eval_source is None:
@@ -146,8 +146,12 @@ def _run(config, workdir: str, model, source, eval_source, device):
   else:
     key = torch.Generator()
     key.manual_seed(int(config.seed))
-    image_size = int(int(source["sensor_size"][-1]) // config.get("resolution_scale", 1))
-    params, batch_stats = initialized(key, image_size, model, config.num_frames, device)
+    if input_pipeline.is_image_source(source):                    # [1, T, K] or [1, T, H, W, 2]
+      params, batch_stats = initialized(key, None, model, config.num_frames, device,
+                                        input_shape=input_pipeline.image_input_shape(source, config))
+    else:
+      image_size = int(int(source["sensor_size"][-1]) // config.get("resolution_scale", 1))
+      params, batch_stats = initialized(key, image_size, model, config.num_frames, device)
     variables = {"params": params, "batch_stats": batch_stats}
   state = create_train_state(variables, config, model)
   state = restore_checkpoint(state, workdir)
@@ -250,7 +254,7 @@ def _run(config, workdir: str, model, source, eval_source, device):
 
 def train_and_evaluate(config, workdir: str, *, model=None, source=None, eval_source=None,
                        device=None) -> TrainState:
-  """examples/train.py:70-338: trains `config.model` on the event source `config.dataset` (or
+  """examples/train.py:70-338: trains `config.model` on the event or image source `config.dataset` (or
   `source`, an in-memory dict), evaluates on `config.eval_dataset` (or `eval_source`; default: the
   training source) before training and after every epoch, writes checkpoints and records under
   `workdir`, and continues from the newest checkpoint found there.  Returns the final state."""
