@@ -248,7 +248,7 @@ typedef struct {
  * snnqp_conv_weight_grad_f64_workspace_bytes; the batched event front end snnqp_events_bin and its augmenting
  * form snnqp_events_bin_aug with snnqp_event_aug_t; the host-side
  * query snnqp_conv_float_form; the host-side plan queries snnqp_conv_gated_plan,
- * snnqp_dense_gated_plan, snnqp_dense_wide_plan; streaming inference --
+ * snnqp_dense_gated_plan, snnqp_dense_wide_plan, snnqp_dense_fp6_plan; streaming inference --
  * snnqp_dense_head_forward_state, snnqp_vote_accumulate, snnqp_vote_counts; the rate encoder
  * snnqp_rate_encode with SNNQP_ENCODE_*: new entry points, nothing else moves).
  * A binding compares snnqp_version()
@@ -720,6 +720,22 @@ int snnqp_dense_lif_forward_ws(const void *x, int in_type, int64_t x_stride_t,
                                const snnqp_neuron_t *nrn, const float *u0,
                                float *u_out, void *s_out, int s_type, int impl,
                                int32_t *x_flags, void *ws, int64_t ws_bytes, snnqp_stream_t stream);
+/* The launch snnqp_dense_lif_forward_ws makes on the fp4 x fp6 kernel for T steps, B samples, K
+ * inputs and N features with this workspace (`ws` is looked at for its address only and never
+ * dereferenced; NULL: none).  Launches nothing, makes no GPU call.  The answer is the launch's own
+ * decision: the cost model, then the measurement knob SNNQP_DENSE_FP6_PLAN="rt,ks" (read when a
+ * workspace is given; a value that is malformed, has rt * 32 < T, or splits more tiles than the
+ * 4096-byte ticket head has words -- 1024 -- is ignored), then the workspace: a split plan that
+ * needs more than ws_bytes, or a `ws` not 256-byte aligned, gives way to the best unsplit plan.
+ *   rt   1..5 row tiles of 32 rows per workgroup: a workgroup owns floor(32 rt / T) samples
+ *   ks   1, 2 or 4 workgroups per tile of rows along K
+ *   gx   workgroups along the batch; the grid is gx x ceil(N / 128) x ks, tiles = gx ceil(N / 128)
+ *   gcz  0 when unsplit; else the 512-deep pieces of K (two chunks of 256, one per wave group) that
+ *        workgroup z of a tile walks from piece z * gcz on -- the last may get fewer, or none.
+ * A split launch needs 4096 + tiles * ks * rt * 32 * 128 * 4 bytes of workspace.
+ * SNNQP_EINVAL for sizes below 1 or a null pointer; SNNQP_EUNSUPPORTED for T > 160, as the launch. */
+int snnqp_dense_fp6_plan(int32_t T, int32_t B, int32_t K, int32_t N, const void *ws, int64_t ws_bytes,
+                         int32_t *rt, int32_t *ks, int32_t *gx, int32_t *gcz);
 /* the dense block on the direct-form kernel, executed only if *pred != 0 (snnqp_conv_lif_forward_if) */
 int snnqp_dense_lif_forward_if(const int32_t *pred, const void *x, int in_type, int64_t x_stride_t,
                                int64_t x_stride_b, int32_t T, int32_t B, int32_t K, int32_t N,

@@ -424,6 +424,44 @@ const char *dense_fp6_unsupported(const BlockCall &c) {
   return nullptr;
 }
 
+// The launch of T x B rows, K deep, N wide with this workspace: what run_dense_fp6 launches and
+// what snnqp_dense_fp6_plan reports.  No GPU call.
+struct Fp6Launch {
+  int rt, ks;        // row tiles of a workgroup; workgroups per tile along K
+  int sb;            // samples of a workgroup
+  unsigned gx, gy;   // the grid (z: ks)
+  int gcz;           // group-chunks of one workgroup of a split tile; 0: unsplit
+};
+static int plan_dense_fp6(int32_t T, int32_t B, int32_t K, int32_t N, const void *ws, int64_t ws_bytes,
+                          Fp6Launch *out) {
+  const unsigned gy = (unsigned)((N + 127) / 128);
+  // the workspace decides: the plan with a K split when the caller brought enough of it
+  // (snnqp_dense_workspace_bytes, zero-filled once), else the best plan without
+  Fp6Plan plan = pick_fp6_plan(T, B, K, gy, ws != nullptr);
+  if (const char *e = ws ? std::getenv("SNNQP_DENSE_FP6_PLAN") : nullptr) {     // "rt,ks": measurement knob
+    int r = 0, k = 0;
+    if (std::sscanf(e, "%d,%d", &r, &k) == 2 && r >= 1 && r <= 5 && r * 32 >= T && (k == 1 || k == 2 || k == 4)) {
+      // a ticket per tile in the fixed head, as in the planner: a forced split of more tiles is not a plan
+      const int sb = r * 32 / T;
+      if (k == 1 || (int64_t)((B + sb - 1) / sb) * gy <= F6_TICKET_BYTES / 4) plan = Fp6Plan{r, k};
+    }
+  }
+  if (plan.ks > 1 && (fp6_workspace_bytes(plan, T, B, gy) > ws_bytes || ((uintptr_t)ws & 255) != 0))
+    plan = pick_fp6_plan(T, B, K, gy, false);
+  SNNQP_REQUIRE(plan.rt > 0, SNNQP_EUNSUPPORTED, "dense fp6: T too large");
+  out->rt = plan.rt; out->ks = plan.ks;
+  out->sb = plan.rt * 32 / T;
+  out->gx = (unsigned)((B + out->sb - 1) / out->sb);
+  out->gy = gy;
+  out->gcz = 0;
+  if (plan.ks > 1) {
+    const int nchunks = ((K + 63) / 64 + F6_KSC - 1) / F6_KSC;
+    const int ngc_all = (nchunks + F6_KGROUPS - 1) / F6_KGROUPS;
+    out->gcz = (ngc_all + plan.ks - 1) / plan.ks;
+  }
+  return SNNQP_OK;
+}
+
 int run_dense_fp6(const BlockCall &c) {
   if (int rc = block_entry("dense fp6", c, c.w->wt_fp6 != nullptr)) return rc < 0 ? rc : SNNQP_OK;
   const int32_t T = c.T, B = c.B, K = c.K, N = c.N;
@@ -431,26 +469,14 @@ int run_dense_fp6(const BlockCall &c) {
   fill_block_args(a, c);
   a.K = K; a.N = N; a.KW = (K + 31) / 32; a.KS = (K + 63) / 64;
   a.wt6 = (const uint8_t *)c.w->wt_fp6;
-  const unsigned gy = (unsigned)((N + 127) / 128);
-  // the workspace decides: the plan with a K split when the caller brought enough of it
-  // (snnqp_dense_workspace_bytes, zero-filled once), else the best plan without
-  Fp6Plan plan = pick_fp6_plan(T, B, K, gy, c.ws != nullptr);
-  if (const char *e = c.ws ? std::getenv("SNNQP_DENSE_FP6_PLAN") : nullptr) {     // "rt,ks": measurement knob
-    int r = 0, k = 0;
-    if (std::sscanf(e, "%d,%d", &r, &k) == 2 && r >= 1 && r <= 5 && r * 32 >= T && (k == 1 || k == 2 || k == 4))
-      plan = Fp6Plan{r, k};
-  }
-  if (plan.ks > 1 && (fp6_workspace_bytes(plan, T, B, gy) > c.ws_bytes || ((uintptr_t)c.ws & 255) != 0))
-    plan = pick_fp6_plan(T, B, K, gy, false);
-  const int rt = plan.rt;
-  SNNQP_REQUIRE(rt > 0, SNNQP_EUNSUPPORTED, "dense fp6: T too large");
-  a.SB = rt * 32 / T;
-  const unsigned gx = (unsigned)((B + a.SB - 1) / a.SB);
-  a.ksplit = plan.ks;
-  if (plan.ks > 1) {
-    const int nchunks = (a.KS + F6_KSC - 1) / F6_KSC;
-    const int ngc_all = (nchunks + F6_KGROUPS - 1) / F6_KGROUPS;
-    a.gcz = (ngc_all + plan.ks - 1) / plan.ks;
+  Fp6Launch p;
+  if (int rc = plan_dense_fp6(T, B, K, N, c.ws, c.ws_bytes, &p)) return rc;
+  const int rt = p.rt;
+  const unsigned gx = p.gx, gy = p.gy;
+  a.SB = p.sb;
+  a.ksplit = p.ks;
+  if (p.ks > 1) {
+    a.gcz = p.gcz;
     const int64_t tiles = (int64_t)gx * gy;
     a.tickets = (uint32_t *)c.ws;
     a.slabs = (float *)((uint8_t *)c.ws + F6_TICKET_BYTES);
@@ -473,6 +499,17 @@ int run_dense_fp6(const BlockCall &c) {
 }
 
 }  // namespace snnqp
+
+extern "C" int snnqp_dense_fp6_plan(int32_t T, int32_t B, int32_t K, int32_t N, const void *ws,
+                                    int64_t ws_bytes, int32_t *rt, int32_t *ks, int32_t *gx, int32_t *gcz) {
+  using namespace snnqp;
+  SNNQP_REQUIRE(rt && ks && gx && gcz, SNNQP_EINVAL, "dense_fp6_plan: null argument");
+  SNNQP_REQUIRE(T >= 1 && B >= 1 && K >= 1 && N >= 1, SNNQP_EINVAL, "dense_fp6_plan: bad sizes");
+  Fp6Launch p;
+  if (int rc = plan_dense_fp6(T, B, K, N, ws, ws_bytes, &p)) return rc;
+  *rt = p.rt; *ks = p.ks; *gx = (int32_t)p.gx; *gcz = p.gcz;
+  return SNNQP_OK;
+}
 
 extern "C" int snnqp_pack_codes_fp6(const int8_t *w, int64_t K, int32_t N, int32_t Npad,
                                     void *wt6, snnqp_stream_t stream) {

@@ -1012,6 +1012,17 @@ def dense_wide_plan(T: int, B: int, N: int, fused: bool = True, may_split: bool 
   return rt.value, ct.value, sph.value, cs.value
 
 
+def dense_fp6_plan(T: int, B: int, K: int, N: int, ws: Optional[int] = None,
+                   ws_bytes: int = 0) -> Tuple[int, int, int, int]:
+  """(rt, ks, gx, gcz) of the fp4 x fp6 dense launch with the workspace at ADDRESS `ws` (None: no
+  workspace) of `ws_bytes` bytes (snnqp_dense_fp6_plan; no device work, the address is not read)."""
+  rt, ks, gx, gcz = ctypes.c_int32(), ctypes.c_int32(), ctypes.c_int32(), ctypes.c_int32()
+  L.check(L.lib().snnqp_dense_fp6_plan(int(T), int(B), int(K), int(N), None if ws is None else ctypes.c_void_p(ws),
+                                       int(ws_bytes), ctypes.byref(rt), ctypes.byref(ks), ctypes.byref(gx),
+                                       ctypes.byref(gcz)))
+  return rt.value, ks.value, gx.value, gcz.value
+
+
 # ---------------------------------------------------------------------------
 # per-launch timing with HIP events on the launch stream (bench.py roofline)
 # ---------------------------------------------------------------------------
