@@ -51,17 +51,12 @@ struct DenseFp6Args {
   uint32_t *s_out;
   // K split over workgroups (blockIdx.z): partial tiles and tickets in a caller-owned workspace
   int32_t ksplit, gcz;           // workgroups per tile; group-chunks of one of them
-  uint32_t *tickets;             // [tiles], zeroed on the stream in front of every launch (run_dense_fp6)
+  uint32_t *tickets;             // [tiles], zeroed on the stream in front of every launch (handoff_arm)
   float *slabs;                  // [tiles][ksplit][ROWS * 128]
   uint32_t *status;              // the device's status word (runtime.hip), or null
 };
 
-// 16-byte piece c (of 8) of row `row`: pieces swizzled by (row >> 1) & 7, so that the 16 lanes
-// a ds_read_b128 serves per cycle ({0-3, 12-15, 20-27}, ...) hit 16 different bank quads
-// (quad = 8 (row & 1) + (c ^ (row >> 1) & 7))
-__device__ __forceinline__ int a6_addr(int row, int c) {
-  return row * F6_ROWB + ((c ^ ((row >> 1) & 7)) << 4);
-}
+static_assert(F6_ROWB == 128, "the A images are swz128_addr's rows (dense_tile.h)");
 
 }  // namespace
 
@@ -169,15 +164,8 @@ dense_fp6_kernel(DenseFp6Args a) {
   const uint32_t *xw = a.x + (int64_t)b0 * a.xs_b;
 #pragma unroll
   for (int k = 0; k < TPT; ++k) {
-    const int task = tid + k * 256;
-    const int row = task / WPR;
-    const bool live = row < rows;
-    rmask[k] = live ? 0xFFFFFFFFu : 0u;
-    roff[k] = 0;
-    if (live) {
-      const int bl = row / a.T, t = row - bl * a.T;
-      roff[k] = (uint32_t)((int64_t)t * a.xs_t + (int64_t)bl * a.xs_b);   // < 2^31: launch check
-    }
+    const RowTask rt = row_task<WPR>(tid + k * 256, true, rows, a.T, a.xs_t, a.xs_b);   // NTASK = 256 TPT
+    roff[k] = rt.off; rmask[k] = rt.mask;
   }
   // word `chunk_word` of the row; words beyond K re-read the row's last one and are masked
   auto chunk_word = [&](int chunk, int k) { return (chunk * F6_KGROUPS + grp) * WPR + (tid + k * 256) % WPR; };
@@ -185,7 +173,7 @@ dense_fp6_kernel(DenseFp6Args a) {
     return xw[roff[k] + (uint32_t)min(chunk_word(chunk, k), a.KW - 1)];
   };
   auto masked = [&](uint32_t w, int chunk, int k) -> uint32_t {
-    return w & rmask[k] & (uint32_t)((chunk_word(chunk, k) - a.KW) >> 31);
+    return bit_word_masked(w, rmask[k], chunk_word(chunk, k), a.KW);
   };
   auto lookup = [&](uint32_t w, int d) -> int {
     return (int)fp4_table_entry(tabl, (w >> (8 * d)) & 0xFFu);
@@ -194,7 +182,7 @@ dense_fp6_kernel(DenseFp6Args a) {
 #pragma unroll
   for (int k = 0; k < TPT; ++k) {
     const int task = tid + k * 256;
-    wr_off[k] = a6_addr(task / WPR, task % WPR);
+    wr_off[k] = swz128_addr(task / WPR, task % WPR);
   }
 
   const uint8_t *wtile = a.wt6 + ((int64_t)(wave_on ? nb : 0) * a.KS) * F6_TILE;   // wave-uniform
@@ -212,7 +200,7 @@ dense_fp6_kernel(DenseFp6Args a) {
   constexpr int PF = 3;                               // A fragments in flight
   int rd_off[F6_KSC];
 #pragma unroll
-  for (int ks = 0; ks < F6_KSC; ++ks) rd_off[ks] = a6_addr(n, ks * 2 + h);
+  for (int ks = 0; ks < F6_KSC; ++ks) rd_off[ks] = swz128_addr(n, ks * 2 + h);
   auto frag = [&](int rbuf, int s) -> v4i {
     // row tile s % RT: 32 rows further (the swizzle repeats every 16 rows)
     return *(const v4i *)(abuf + rbuf * ABYTES + (s % RT) * 32 * F6_ROWB + rd_off[s / RT]);
@@ -258,11 +246,7 @@ dense_fp6_kernel(DenseFp6Args a) {
       }
       __builtin_amdgcn_sched_barrier(0);
     }
-    // The barrier publishes buffer wbuf, which nobody reads before the chunk after next.  LDS
-    // operations of a wave complete in order and the PF youngest are the fragment reads of the
-    // next chunk: waiting until only those are outstanding retires every write of this chunk
-    // without draining the fragments (no scalar load is in flight: the loop issues none).
-    asm volatile("s_waitcnt lgkmcnt(%0)\n\ts_barrier" : : "n"(PF) : "memory");
+    chunk_barrier<PF>();                            // publishes buffer wbuf
   };
 
   lds_barrier();                                  // the table is visible
@@ -308,30 +292,16 @@ dense_fp6_kernel(DenseFp6Args a) {
   dense_tile_merge<RT, F6_KGROUPS>(et, acc, grp, wave, n, h, wave_on);
 
   // K split over workgroups: every workgroup of a tile leaves its partial tile (exact integers
-  // in float32) in its slab and draws a ticket; the one that draws the last adds the others'
-  // slabs to its own tile and goes on to the neuron, the others are done.  The hand-off recipe of
-  // cdna_hip_programming.md (R1): the slab by agent-scope relaxed stores (write-through), every
-  // storing wave drains, one relaxed agent-scope ticket, the last arriver reads with agent-scope
-  // loads -- no release / acquire fence: on this part a fence pair writes back / invalidates an
-  // L2 and cost ~ 20 us per launch (round 4's first version: 0.075 ms against 0.066 unsplit).
+  // in float32) in its slab; the last arriver adds the others' slabs to its own tile and goes on
+  // to the neuron (the hand-over of dense_tile.h)
   if (a.ksplit > 1) {
     typedef unsigned long long u64;
     const int tile = blockIdx.y * gridDim.x + blockIdx.x;
     u64 *mine = (u64 *)(a.slabs + ((int64_t)tile * a.ksplit + blockIdx.z) * (ROWS * 128));
     const u64 *et64 = (const u64 *)et;
-    for (int i = threadIdx.x; i < ROWS * 64; i += 256 * F6_KGROUPS)
-      __hip_atomic_store(mine + i, et64[i], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-    __syncthreads();
-    uint32_t *flag = (uint32_t *)lds;               // (the byte -> nibble table is no longer needed)
-    if (threadIdx.x == 0) {
-      const uint32_t ticket = __hip_atomic_fetch_add(a.tickets + tile, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-      if (ticket >= (uint32_t)a.ksplit && a.status) *(volatile uint32_t *)a.status = SNNQP_STATUS_TICKET;
-      const bool last = ticket + 1u == (uint32_t)a.ksplit;
-      *flag = last ? 1u : 0u;
-    }
-    __syncthreads();
-    if (*flag == 0u) return;
+    handoff_publish(mine, ROWS * 64, 256 * F6_KGROUPS, [&](int i) { return et64[i]; });
+    // (the flag: the byte -> nibble table is no longer needed)
+    if (!handoff_last_arriver(a.tickets + tile, (uint32_t)a.ksplit, a.status, (uint32_t *)lds)) return;
     for (int z = 0; z < a.ksplit; ++z) {
       if (z == (int)blockIdx.z) continue;
       const u64 *other = (const u64 *)(a.slabs + ((int64_t)tile * a.ksplit + z) * (ROWS * 128));
@@ -367,9 +337,7 @@ static void launch_dense_fp6(const DenseFp6Args &a, unsigned gx, unsigned gy, hi
 // (5, 4) 0.096 against 0.066 unsplit -- with more rows per workgroup the per-k cost of a workgroup
 // (fragment reads, expansion, MFMAs per row tile) grows as fast as the stream shrinks -- so the
 // headline stays unsplit.  (SNNQP_DENSE_FP6_PLAN="rt,ks" forces a plan: a measurement knob.)
-// workspace = F6_TICKET_BYTES of tickets (a fixed head, whatever the plan: a workspace that
-// served another shape before still has zeros there), then the slabs
-constexpr int64_t F6_TICKET_BYTES = 4096;
+// workspace = the ticket head of kernels.h, then the slabs
 struct Fp6Plan { int rt, ks; };
 static Fp6Plan pick_fp6_plan(int T, int B, int K, unsigned gy, bool may_split) {
   const int nchunks = ((K + 63) / 64 + F6_KSC - 1) / F6_KSC;
@@ -381,7 +349,7 @@ static Fp6Plan pick_fp6_plan(int T, int B, int K, unsigned gy, bool may_split) {
       const int sb = rt * 32 / T;
       if (sb < 1) continue;
       const int64_t wgs = (int64_t)((B + sb - 1) / sb) * gy * ks;
-      if (ks > 1 && wgs / ks > F6_TICKET_BYTES / 4) continue;      // a ticket per tile
+      if (ks > 1 && wgs / ks > HANDOFF_TICKET_BYTES / 4) continue;      // a ticket per tile
       const double kscale = (double)K / 32768.0;
       const double cost = (double)((wgs + 255) / 256) * (11.0 + kscale * (9.5 + 15.5 * rt) / ks) +
                           (ks > 1 ? 6.0 + 0.09 * (rt * 16 * ks) : 0.0);
@@ -398,7 +366,7 @@ static int64_t fp6_workspace_bytes(const Fp6Plan &p, int T, int B, unsigned gy) 
   if (p.ks <= 1) return 0;
   const int sb = p.rt * 32 / T;
   const int64_t tiles = (int64_t)((B + sb - 1) / sb) * gy;
-  return F6_TICKET_BYTES + tiles * p.ks * (int64_t)(p.rt * 32 * 128) * 4;
+  return HANDOFF_TICKET_BYTES + tiles * p.ks * (int64_t)(p.rt * 32 * 128) * 4;
 }
 
 int64_t dense_fp6_workspace_bytes(int32_t T, int32_t B, int32_t K, int32_t N) {
@@ -443,10 +411,10 @@ static int plan_dense_fp6(int32_t T, int32_t B, int32_t K, int32_t N, const void
     if (std::sscanf(e, "%d,%d", &r, &k) == 2 && r >= 1 && r <= 5 && r * 32 >= T && (k == 1 || k == 2 || k == 4)) {
       // a ticket per tile in the fixed head, as in the planner: a forced split of more tiles is not a plan
       const int sb = r * 32 / T;
-      if (k == 1 || (int64_t)((B + sb - 1) / sb) * gy <= F6_TICKET_BYTES / 4) plan = Fp6Plan{r, k};
+      if (k == 1 || (int64_t)((B + sb - 1) / sb) * gy <= HANDOFF_TICKET_BYTES / 4) plan = Fp6Plan{r, k};
     }
   }
-  if (plan.ks > 1 && (fp6_workspace_bytes(plan, T, B, gy) > ws_bytes || ((uintptr_t)ws & 255) != 0))
+  if (plan.ks > 1 && !handoff_ws_usable(ws, ws_bytes, fp6_workspace_bytes(plan, T, B, gy)))
     plan = pick_fp6_plan(T, B, K, gy, false);
   SNNQP_REQUIRE(plan.rt > 0, SNNQP_EUNSUPPORTED, "dense fp6: T too large");
   out->rt = plan.rt; out->ks = plan.ks;
@@ -477,15 +445,9 @@ int run_dense_fp6(const BlockCall &c) {
   a.ksplit = p.ks;
   if (p.ks > 1) {
     a.gcz = p.gcz;
-    const int64_t tiles = (int64_t)gx * gy;
-    a.tickets = (uint32_t *)c.ws;
-    a.slabs = (float *)((uint8_t *)c.ws + F6_TICKET_BYTES);
-    a.status = device_status_word(stream_device(c.st));
-    // the tickets are zeroed on the stream in front of EVERY launch (a kernel node when the stream
-    // is being captured: zero_words_async, kernels.h): whatever an earlier launch, an aborted replay or a stray store left in
-    // them, this launch starts from zero (cdna_hip_programming.md, hand-off recipe: "zero the
-    // counter per call; a reset by the last arriver alone fails the first, poisoned launch")
-    if (int rc = zero_words_async((uint32_t *)c.ws, tiles, c.st)) return rc;
+    void *slabs;
+    if (int rc = handoff_arm(c.ws, (int64_t)gx * gy, c.st, &a.tickets, &slabs, &a.status)) return rc;
+    a.slabs = (float *)slabs;
   }
   switch (rt) {
     case 5: launch_dense_fp6<5>(a, gx, gy, c.st); break;

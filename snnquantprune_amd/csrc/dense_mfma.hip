@@ -99,24 +99,16 @@ dense_mfma_kernel(DenseMfmaArgs a) {
   constexpr int D = U8 ? 3 : 4;
   constexpr int U = D % 2 ? 2 * D : D;             // unroll: ring slot i % D, LDS buffer i & 1
   stg_t stgr[D][TPT];
-  // staging tasks: word wi of row `row`, the same (row, wi) for every chunk.  The loads of the
-  // K loop are unconditional (clamped addresses, the value dropped afterwards): with loads
-  // under lane masks the compiler falls back to s_waitcnt vmcnt(0), which drains the ring.
+  // staging tasks: word wi of row `row`, the same (row, wi) for every chunk; the loads of the K
+  // loop are unconditional, clamped addresses and the value dropped afterwards (dense_tile.h)
   uint32_t roff[TPT];                              // word / byte offset within this workgroup's samples
   uint32_t rmask[TPT];
   const uint32_t *xw = a.x + (U8 ? 0 : (int64_t)b0 * a.xs_b);
   const uint8_t *xbytes = (const uint8_t *)a.x + (U8 ? (int64_t)b0 * a.xs_b : 0);
 #pragma unroll
   for (int k = 0; k < TPT; ++k) {
-    const int task = tid + k * 256;
-    const int row = task / WPR;
-    const bool live = task < NTASK && row < rows;
-    rmask[k] = live ? 0xFFFFFFFFu : 0u;
-    roff[k] = 0;
-    if (live) {
-      const int bl = row / a.T, t = row - bl * a.T;
-      roff[k] = (uint32_t)((int64_t)t * a.xs_t + (int64_t)bl * a.xs_b);   // < 2^31: launch check
-    }
+    const RowTask rt = row_task<WPR>(tid + k * 256, tid + k * 256 < NTASK, rows, a.T, a.xs_t, a.xs_b);
+    roff[k] = rt.off; rmask[k] = rt.mask;
   }
   auto chunk_word = [&](int chunk, int k) { return (chunk * KGROUPS + grp) * WPR + (tid + k * 256) % WPR; };
   // uint8: 16-byte piece `chunk_word` of the row; K is a multiple of 16 (launch check).  Pieces
@@ -151,7 +143,7 @@ dense_mfma_kernel(DenseMfmaArgs a) {
               v4i{(v.x ^ (int)0x80808080) & m, (v.y ^ (int)0x80808080) & m,
                   (v.z ^ (int)0x80808080) & m, (v.w ^ (int)0x80808080) & m};
         } else {
-          const uint32_t wv = stg[k] & rmask[k] & (uint32_t)((chunk_word(chunk, k) - a.KS) >> 31);
+          const uint32_t wv = bit_word_masked(stg[k], rmask[k], chunk_word(chunk, k), a.KS);   // KS = words of a row
           *(v4i *)(base + a_addr(row, wi * 2)) = expand16(wv & 0xFFFFu);
           *(v4i *)(base + a_addr(row, wi * 2 + 1)) = expand16(wv >> 16);
         }
@@ -215,7 +207,7 @@ dense_mfma_kernel(DenseMfmaArgs a) {
         wv[k] = st_stg[k];
         inK[k] = chunk_word(st_chunk, k) * 16 < a.K ? -1 : 0;
       } else {
-        wv[k] = st_stg[k] & rmask[k] & (uint32_t)((chunk_word(st_chunk, k) - a.KS) >> 31);
+        wv[k] = bit_word_masked(st_stg[k], rmask[k], chunk_word(st_chunk, k), a.KS);
       }
     }
     v4i ex = {0, 0, 0, 0};

@@ -1,12 +1,83 @@
-// What the two K-group dense kernels (dense_mfma.hip: int32 sums, dense_fp6.hip: the same
-// integers in float32) run behind their K loops: the merge of the groups' accumulator tiles
-// into one LDS tile, and the neuron over that tile.
+// What the MFMA dense kernels share (who uses which, and what stayed in the kernels):
+// the staging task of row-major rows and the spike-word mask, the swizzle of 128-byte LDS rows and the
+// counted-wait barrier of a chunk, the hand-over between the workgroups of a tile (host half: kernels.h),
+// and for the two K-group kernels the merge of the groups' tiles and the neuron over the merged tile.
 #pragma once
 #include <type_traits>
 
 #include "kernels.h"
 
 namespace snnqp {
+
+// Staging task `task` of a workgroup is unit task % WPR of tile row task / WPR, the same for every chunk;
+// tile row = sample * T + t.  off: the row's offset from the workgroup's first sample in units of the
+// strides (< 2^31: launch check); mask: all ones for a live row (in_tile: the task exists at all).  The
+// loads of a K loop are unconditional (a dead row reads row 0) and the mask is applied when the word is
+// expanded: a load under a lane mask makes the compiler wait with vmcnt(0), which drains the ring.
+struct RowTask { uint32_t off, mask; };
+template <int WPR>
+__device__ __forceinline__ RowTask row_task(int task, bool in_tile, int rows, int T, int64_t xs_t, int64_t xs_b) {
+  const int row = task / WPR;
+  const bool live = in_tile && row < rows;
+  RowTask r = {0u, live ? 0xFFFFFFFFu : 0u};
+  if (live) {
+    const int bl = row / T, t = row - bl * T;
+    r.off = (uint32_t)((int64_t)t * xs_t + (int64_t)bl * xs_b);
+  }
+  return r;
+}
+
+// a staged spike word as it enters LDS: zero for a dead row and for word `chunk_word` >= KW (the load
+// re-read the row's last word there); the sign of the difference as a mask, no select
+__device__ __forceinline__ uint32_t bit_word_masked(uint32_t word, uint32_t rmask, int chunk_word, int KW) {
+  return word & rmask & (uint32_t)((chunk_word - KW) >> 31);
+}
+
+// Byte address of 16-byte piece `piece` (of 8) of row `row` in an image of 128-byte rows: pieces swizzled
+// by (row >> 1) & 7, so that the 16 lanes a ds_read_b128 serves per cycle ({0-3, 12-15, 20-27}, ...) hit
+// 16 different bank quads (quad = 8 (row & 1) + (piece ^ (row >> 1) & 7)): the read of an A fragment and
+// the ds_write_b128 of the staging are conflict-free.  The swizzle repeats every 16 rows; flipping bit 0
+// of `piece` flips bit 4 of the address only.
+__device__ __forceinline__ int swz128_addr(int row, int piece) {
+  return row * 128 + ((piece ^ ((row >> 1) & 7)) << 4);
+}
+
+// The barrier that ends a chunk and publishes the image staged during it, which nobody reads before the
+// chunk after next.  LDS operations of a wave complete in order and the PF youngest are the fragment
+// reads of the NEXT chunk: waiting until only those are outstanding retires every write of this chunk
+// without draining the fragments (no scalar load is in flight: the loops issue none).
+template <int PF>
+__device__ __forceinline__ void chunk_barrier() {
+  asm volatile("s_waitcnt lgkmcnt(%0)\n\ts_barrier" : : "n"(PF) : "memory");
+}
+
+// The hand-over, the only cross-workgroup protocol of the library: `parts` workgroups each leave a payload
+// in a caller workspace and draw a ticket; the one that draws the last reads the others' payloads (in its
+// kernel) and goes on, the others are done.  Recipe R1 of cdna_hip_programming.md: the payload by agent-scope
+// relaxed stores (write-through), every storing wave drains, one relaxed agent-scope ticket, agent-scope
+// relaxed loads by the last arriver -- NO release / acquire fence: on this part a pair writes back /
+// invalidates an L2, ~ 20 us per launch (0.075 ms against 0.066 unsplit).  The host zeroes the tickets in
+// front of every launch (handoff_arm, kernels.h); nobody resets one.
+// handoff_publish: dst[i] = load(i), i < n, by the workgroup's `nthreads` threads, every store drained.
+template <typename V, typename F>
+__device__ __forceinline__ void handoff_publish(V *dst, int n, int nthreads, F &&load) {
+  for (int i = threadIdx.x; i < n; i += nthreads)
+    __hip_atomic_store(dst + i, load(i), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+  asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+  __syncthreads();
+}
+// Behind the publication: true in every thread of the workgroup that drew the last of `parts` tickets; a
+// ticket too many goes to the device's status word.  lds_flag: a word of LDS free until the call returns.
+__device__ __forceinline__ bool handoff_last_arriver(uint32_t *ticket_word, uint32_t parts, uint32_t *status,
+                                                     uint32_t *lds_flag) {
+  if (threadIdx.x == 0) {
+    const uint32_t ticket = __hip_atomic_fetch_add(ticket_word, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    if (ticket >= parts && status) *(volatile uint32_t *)status = SNNQP_STATUS_TICKET;
+    *lds_flag = ticket + 1u == parts ? 1u : 0u;
+  }
+  __syncthreads();
+  return *lds_flag != 0u;
+}
 
 // Accumulator tiles of the KG wave groups -> one LDS tile et[row][128]: group KG - 1 stores its
 // partial sums, the others add theirs on top, a barrier after each (exact: integers).

@@ -34,15 +34,15 @@
 //    membranes of both blocks and the output spike counts from window to window in the caller's
 //    buffers, read and written in place by the lane that owns each value.
 //
-// K loop as in dense_fp6.hip: chunks of 128 k, three LDS images (chunk c computes from image
-// c mod 3 while chunk c + 2 is staged, the barrier waits with a counted lgkmcnt so that the
-// next chunk's first fragments stay in flight), staged rows requested four chunks ahead, B
-// fragments in a ring of RB k-steps, every wave interleaving its MFMAs with its share of the
-// loads and of the staging slot by slot.
+// K loop as in dense_fp6.hip, from the same pieces (dense_tile.h): chunks of 128 k, three LDS
+// images (chunk c computes from image c mod 3 while chunk c + 2 is staged, chunk_barrier keeps the
+// next chunk's first fragments in flight), staged rows requested four chunks ahead, B fragments in
+// a ring of RB k-steps, every wave interleaving its MFMAs with its share of the loads and of the
+// staging slot by slot.
 #include <cstdlib>
 #include <type_traits>
 
-#include "kernels.h"
+#include "dense_tile.h"
 
 namespace snnqp {
 
@@ -109,16 +109,36 @@ __device__ __forceinline__ uint32_t f32x4_to_i8x4(const v4f &f, uint32_t &bad) {
   return (u0 | (u1 << 8) | (u2 << 16) | (u3 << 24)) ^ 0x80808080u;
 }
 
-// 16-byte piece c (of 8) of row `row` (dense_fp6.hip: the ds_read_b128 of an A fragment and
-// the ds_write_b128 of the staging are conflict-free)
-__device__ __forceinline__ int wa_addr(int row, int c) {
-  return row * W_BK + ((c ^ ((row >> 1) & 7)) << 4);
-}
+static_assert(W_BK == 128, "the A images are swz128_addr's rows (dense_tile.h)");
 
-// row of the MFMA tile set <-> (lane half h, the half's row k)
-__device__ __forceinline__ int rho_of(int k, int h) {
+// The row map: row rho of the MFMA tile set <-> (lane half h, the half's row k); the half's row
+// k = j T + t is timestep t of the half's sample j, which is sample s = 2 j + h of the workgroup
+constexpr int rho_of(int k, int h) {
   return (k >> 4) * 32 + ((k >> 2) & 3) * 8 + h * 4 + (k & 3);
 }
+// (live when j < SPH && s < nsamp)
+struct WideRow { int h, k, j, t, s; };
+struct WideHalf { int h, k; };                  // what does not depend on T
+constexpr WideHalf wide_row_half(int rho) {
+  const int wv = rho & 31;
+  return WideHalf{(wv >> 2) & 1, (rho >> 5) * 16 + (wv >> 3) * 4 + (wv & 3)};
+}
+__device__ __forceinline__ WideRow wide_row_of(int h, int k, int T) {
+  const int j = k / T;
+  return WideRow{h, k, j, k - j * T, 2 * j + h};
+}
+__device__ __forceinline__ WideRow wide_row(int rho, int T) {
+  const WideHalf r = wide_row_half(rho);
+  return wide_row_of(r.h, r.k, T);
+}
+constexpr bool wide_rows_invert() {             // over the 64 half rows x 2 halves of RT = 4
+  for (int i = 0; i < 128; ++i) {
+    const WideHalf r = wide_row_half(rho_of(i >> 1, i & 1));
+    if (r.h != (i & 1) || r.k != (i >> 1) || rho_of(wide_row_half(i).k, wide_row_half(i).h) != i) return false;
+  }
+  return true;
+}
+static_assert(wide_rows_invert(), "rho_of and wide_row_half are inverses");
 
 // u += (x - (u - v_reset)) * m ; s = (u - v_th) >= 0 ; hard reset  (spiking_learning.py:410-414,
 // :381-385) when FASTN, else the neuron of common.h
@@ -338,7 +358,8 @@ dense_wide_kernel(DenseWideArgs a) {
   const int nchunks = (a.KS + W_KSC - 1) / W_KSC;
   const int nsteps = (nchunks + W_NBUF - 1) / W_NBUF * W_NBUF;
   // every workgroup streams the same code tiles; the walk over K starts at another chunk on
-  // every XCD (exact integer sums may be taken in any order; dense_fp6.hip)
+  // every XCD (exact integer sums may be taken in any order; measured in dense_fp6.hip, and why
+  // the two walks are not one: DESIGN.md 4.4.1)
   const int rot = (int)(((blockIdx.x & 7u) * (unsigned)nchunks) >> 3);
   auto phys = [&](int lc) -> int {
     const int pc = lc + rot >= nchunks ? lc + rot - nchunks : lc + rot;
@@ -380,29 +401,24 @@ dense_wide_kernel(DenseWideArgs a) {
     rmask[0] = 0u;
 #pragma unroll
     for (int j = 0; j < NU; ++j) {
-      const int rho = 16 * j + 2 * wave + h;
-      const int wv = rho & 31;
-      const int hh = (wv >> 2) & 1, kk = (rho >> 5) * 16 + (wv >> 3) * 4 + (wv & 3);
-      const int jj = kk / a.T, tt = kk - jj * a.T, ss = 2 * jj + hh;
-      const bool live = jj < a.SPH && ss < nsamp;
+      const WideRow r = wide_row(16 * j + 2 * wave + h, a.T);
+      const bool live = r.j < a.SPH && r.s < nsamp;
       rmask[0] |= live ? 1u << j : 0u;
       // byte offset of the row (< 2^31: launch check)
-      roff[j] = live ? (uint32_t)(((int64_t)tt * a.xs_t + (int64_t)ss * a.xs_b) * 4) : 0u;
+      roff[j] = live ? (uint32_t)(((int64_t)r.t * a.xs_t + (int64_t)r.s * a.xs_b) * 4) : 0u;
     }
-    // rho >> 1 = 8 j + wave: the swizzle of wa_addr does not depend on j, a row pair is 2 KiB on
-    wr_off[0] = wa_addr(2 * wave + h, n >> 2) + (n & 3) * 4;
+    // rho >> 1 = 8 j + wave: the swizzle does not depend on j, a row pair is 2 KiB on
+    wr_off[0] = swz128_addr(2 * wave + h, n >> 2) + (n & 3) * 4;
   }
 #pragma unroll
   for (int q = 0; q < (F32IN ? 0 : TPT); ++q) {
     const int task = tid + q * W_THREADS;
     const int rho = (task / WPR) % ROWS, wi = task % WPR;
-    const int wv = rho & 31;
-    const int hh = (wv >> 2) & 1, kk = (rho >> 5) * 16 + (wv >> 3) * 4 + (wv & 3);
-    const int jj = kk / a.T, tt = kk - jj * a.T, ss = 2 * jj + hh;
-    const bool live = task < NTASK && jj < a.SPH && ss < nsamp;
+    const WideRow r = wide_row(rho, a.T);
+    const bool live = task < NTASK && r.j < a.SPH && r.s < nsamp;
     rmask[q] = live ? 0xFFFFFFFFu : 0u;
-    roff[q] = live ? (uint32_t)((int64_t)tt * a.xs_t + (int64_t)ss * a.xs_b) : 0u;   // < 2^31: launch check
-    wr_off[q] = wa_addr(rho, U8 ? wi : wi * 2);
+    roff[q] = live ? (uint32_t)((int64_t)r.t * a.xs_t + (int64_t)r.s * a.xs_b) : 0u;   // < 2^31: launch check
+    wr_off[q] = swz128_addr(rho, U8 ? wi : wi * 2);
   }
   auto chunk_word = [&](int chunk, int q) { return chunk * WPR + (tid + q * W_THREADS) % WPR; };
   auto stage_load1 = [&](int chunk, int q) -> stg_t {
@@ -422,7 +438,7 @@ dense_wide_kernel(DenseWideArgs a) {
       *(v4i *)(base + wr_off[q]) = v4i{(v.x ^ (int)0x80808080) & m, (v.y ^ (int)0x80808080) & m,
                                        (v.z ^ (int)0x80808080) & m, (v.w ^ (int)0x80808080) & m};
     } else {
-      const uint32_t w = v & rmask[q] & (uint32_t)((chunk_word(chunk, q) - a.KW) >> 31);
+      const uint32_t w = bit_word_masked(v, rmask[q], chunk_word(chunk, q), a.KW);
       *(v4i *)(base + wr_off[q]) = expand16(w & 0xFFFFu);
       *(v4i *)(base + (wr_off[q] ^ 16)) = expand16(w >> 16);     // piece 2 wi + 1: the swizzle flips bit 4 only
     }
@@ -458,7 +474,7 @@ dense_wide_kernel(DenseWideArgs a) {
 
   int rd_off[W_KSC];
 #pragma unroll
-  for (int ks = 0; ks < W_KSC; ++ks) rd_off[ks] = wa_addr(n, ks * 2 + h);
+  for (int ks = 0; ks < W_KSC; ++ks) rd_off[ks] = swz128_addr(n, ks * 2 + h);
   // fragment f of a chunk: k-step f / RT, row tile f % RT
   auto frag = [&](int buf, int f) -> v4i {
     return *(const v4i *)(lds + buf * ABYTES + (f % RT) * 32 * W_BK + rd_off[f / RT]);
@@ -512,9 +528,7 @@ dense_wide_kernel(DenseWideArgs a) {
       }
       __builtin_amdgcn_sched_barrier(0);
     }
-    // LDS operations of a wave complete in order and the W_PF youngest are the next chunk's
-    // fragment reads: this retires every write of the chunk without draining those
-    asm volatile("s_waitcnt lgkmcnt(%0)\n\ts_barrier" : : "n"(W_PF) : "memory");
+    chunk_barrier<W_PF>();                          // publishes image wbuf
   };
 
   // ---- prologue ------------------------------------------------------------------------------
@@ -617,19 +631,15 @@ dense_wide_kernel(DenseWideArgs a) {
     const int CW = (a.N + 31) >> 5;
     for (int q = tid; q < ROWS * 16; q += W_THREADS) {
       const int rho = q >> 4, w = q & 15;
-      const int wv = rho & 31;
-      const int hh = (wv >> 2) & 1, kk = (rho >> 5) * 16 + (wv >> 3) * 4 + (wv & 3);
-      const int jj = kk / a.T, tt = kk - jj * a.T, ss = 2 * jj + hh;
+      const WideRow r = wide_row(rho, a.T);
       const int gw = blockIdx.y * 8 * CT + w;
-      if (w < 8 * CT && jj < a.SPH && ss < nsamp && gw < CW)
-        a.s_out[((int64_t)tt * a.B + (b0 + ss)) * CW + gw] = s1[rho * W_S1P + wofs + w];
+      if (w < 8 * CT && r.j < a.SPH && r.s < nsamp && gw < CW)
+        a.s_out[((int64_t)r.t * a.B + (b0 + r.s)) * CW + gw] = s1[rho * W_S1P + wofs + w];
     }
   }
   // ---- column split: hand the half raster over, the last arriver of the tile goes on ----------
-  // (cdna_hip_programming.md, hand-off recipe R1: the payload by agent-scope relaxed stores --
-  // write-through --, every storing wave drains, one relaxed agent-scope ticket; the last
-  // arriver reads the other half with agent-scope loads: no release / acquire fence, which on
-  // this part would write back / invalidate an L2)
+  // (the hand-over of dense_tile.h; the publication is handoff_publish written out: as a call it
+  // moved registers in this kernel)
   if constexpr (FUSE) {
     if (a.csplit) {
       const int tile = blockIdx.x, half = blockIdx.y;
@@ -639,14 +649,7 @@ dense_wide_kernel(DenseWideArgs a) {
       asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
       __syncthreads();
       uint32_t *flag = (uint32_t *)(lds + ROWS * W_S1P * 4 + W_VOTE_SB * 512);
-      if (tid == 0) {
-        const uint32_t ticket = __hip_atomic_fetch_add(a.hs_tickets + tile, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-        if (ticket >= 2u && a.status) *(volatile uint32_t *)a.status = SNNQP_STATUS_TICKET;
-        const bool last = ticket == 1u;
-        *flag = last ? 1u : 0u;
-      }
-      __syncthreads();
-      if (*flag == 0u) return;
+      if (!handoff_last_arriver(a.hs_tickets + tile, 2u, a.status, flag)) return;
       const uint32_t *other = a.hs_raster + ((int64_t)(tile * 2 + (1 - half)) * ROWS) * 8;
       for (int q = tid; q < ROWS * 8; q += W_THREADS)
         s1[(q >> 3) * W_S1P + (8 - wofs) + (q & 7)] =
@@ -688,8 +691,8 @@ dense_wide_kernel(DenseWideArgs a) {
       if (!STATE && fast2 && a.nrn2.vr == 0.0f) {
         // jnp.mean over T of 0/1 values: the exact count, one division (models.py:253)
         auto sample_done = [&](int, int cnt, int k) {
-          const int j = k / a.T, s = 2 * j + h;
-          if (j < a.SPH && s < nsamp && col2_live[0]) vbuf[s * 128 + col2[0]] = (float)cnt / Tf;
+          const WideRow r = wide_row_of(h, k, a.T);
+          if (r.j < a.SPH && r.s < nsamp && col2_live[0]) vbuf[r.s * 128 + col2[0]] = (float)cnt / Tf;
         };
         const unsigned long long colmask2[1] = {__ballot(col2_live[0])};
         neuron_walk_fast<RT, 1, false, true>(acc2, colmask2, col2, a.dq2, nobn, a.nrn2.inv_k, a.nrn2.vth, a.T, a.SPH * a.T, words, sample_done);
@@ -719,10 +722,9 @@ dense_wide_kernel(DenseWideArgs a) {
         for (int v = 0; v < (16 * RT * 2 + 63) / 64; ++v) {
           const int idx = v * 64 + lane;
           if (idx < 16 * RT * 2) {
-            const int hh = idx & 1, k = idx >> 1;
-            const int jj = k / a.T, tt = k - jj * a.T, ss = 2 * jj + hh;
-            if (jj < a.SPH && ss < nsamp)
-              a.s2_out[((int64_t)tt * a.B + (b0 + ss)) * CW2 + wave] = words[v];
+            const WideRow r = wide_row_of(idx & 1, idx >> 1, a.T);     // word (k, half) of the one column tile
+            if (r.j < a.SPH && r.s < nsamp)
+              a.s2_out[((int64_t)r.t * a.B + (b0 + r.s)) * CW2 + wave] = words[v];
           }
         }
       }
@@ -807,7 +809,6 @@ static int wide_row_tiles_override() {
 // the chip at most half a grid (config C2: B = 256 is 128 tiles of two samples), two workgroups of
 // 256 columns each pull half of the first block's codes through their CU's L1 -- the bound of the
 // unsplit launch -- and hand their half of the hidden raster over through the workspace.
-constexpr int64_t W_TICKET_BYTES = 4096;         // a fixed head of the workspace: a ticket per tile
 struct WidePlan { int rt, sph, ct, csplit; unsigned gx, gy; };
 
 static WidePlan plan_wide(const DenseWideArgs &a, bool fuse, bool may_split) {
@@ -825,7 +826,7 @@ static WidePlan plan_wide(const DenseWideArgs &a, bool fuse, bool may_split) {
   if (p.rt > 0) {
     p.gx = (unsigned)((a.B + 2 * p.sph - 1) / (2 * p.sph));
     static const bool no_split = std::getenv("SNNQP_DENSE_HEAD_NOSPLIT") != nullptr;
-    if (fuse && may_split && !no_split && a.N > 256 && p.gx * 2u <= 256u && p.gx <= W_TICKET_BYTES / 4) {
+    if (fuse && may_split && !no_split && a.N > 256 && p.gx * 2u <= 256u && p.gx <= HANDOFF_TICKET_BYTES / 4) {
       p.csplit = 1;
       p.ct = 1;
       p.gy = 2;
@@ -835,7 +836,7 @@ static WidePlan plan_wide(const DenseWideArgs &a, bool fuse, bool may_split) {
 }
 
 static int64_t wide_workspace_bytes(const WidePlan &p) {
-  return p.csplit ? W_TICKET_BYTES + (int64_t)p.gx * 2 * (p.rt * 32) * 8 * 4 : 0;
+  return p.csplit ? HANDOFF_TICKET_BYTES + (int64_t)p.gx * 2 * (p.rt * 32) * 8 * 4 : 0;
 }
 
 // state: the fused head with carried membranes and counts (a.u0 == a.u_out, a.u2, a.counts).  The
@@ -843,16 +844,14 @@ static int64_t wide_workspace_bytes(const WidePlan &p) {
 static int fill_and_launch(DenseWideArgs &a, int in_type, bool fuse, void *ws, int64_t ws_bytes,
                            hipStream_t st, bool state = false) {
   WidePlan p = plan_wide(a, fuse, ws != nullptr);
-  if (p.csplit && (wide_workspace_bytes(p) > ws_bytes || ((uintptr_t)ws & 255) != 0)) p = plan_wide(a, fuse, false);
+  if (p.csplit && !handoff_ws_usable(ws, ws_bytes, wide_workspace_bytes(p))) p = plan_wide(a, fuse, false);
   SNNQP_REQUIRE(p.rt > 0, SNNQP_EUNSUPPORTED, "dense wide: T too large");
   a.SPH = p.sph;
   a.csplit = p.csplit;
   if (p.csplit) {
-    a.hs_tickets = (uint32_t *)ws;
-    a.hs_raster = (uint32_t *)((uint8_t *)ws + W_TICKET_BYTES);
-    a.status = device_status_word(stream_device(st));
-    // zeroed on the stream in front of every launch (dense_fp6.hip: a kernel node under capture)
-    if (int rc = zero_words_async((uint32_t *)ws, (int64_t)p.gx, st)) return rc;
+    void *raster;
+    if (int rc = handoff_arm(ws, (int64_t)p.gx, st, &a.hs_tickets, &raster, &a.status)) return rc;
+    a.hs_raster = (uint32_t *)raster;
   }
   const int rt = p.rt;
   const unsigned gx = p.gx, gy = p.gy;

@@ -58,6 +58,17 @@ int zero_words_async(uint32_t *p, int64_t nwords, hipStream_t st) {
   return SNNQP_OK;
 }
 
+bool handoff_ws_usable(const void *ws, int64_t ws_bytes, int64_t need) {
+  return ws != nullptr && need <= ws_bytes && ((uintptr_t)ws & 255) == 0;
+}
+
+int handoff_arm(void *ws, int64_t tiles, hipStream_t st, uint32_t **tickets, void **payload, uint32_t **status) {
+  *tickets = (uint32_t *)ws;
+  *payload = (uint8_t *)ws + HANDOFF_TICKET_BYTES;
+  *status = device_status_word(stream_device(st));
+  return zero_words_async(*tickets, tiles, st);
+}
+
 int stream_device(hipStream_t st) {
   int dev = 0;
   hipDevice_t sdev;

@@ -289,6 +289,22 @@ def test_head_shapes_reach_all_seven_fused_forms():
   assert both == gc.ALL_HEAD_FORMS
 
 
+def test_head_workspace_is_a_ticket_head_and_two_raster_halves_per_tile():
+  """snnqp_dense_head_workspace_bytes as a contract, restated here and not read from the library:
+  a column-split launch hands over, per tile of 2 sph samples, two halves of the hidden raster of
+  32 rt rows x 8 words of 4 bytes, behind a fixed head of 4096 bytes of tickets; a launch that does
+  not split needs no workspace."""
+  L, ops = _ops()
+  split = 0
+  for (T, B, K, N1, N2) in gc.HEAD_SHAPES:
+    rt, ct, sph, cs = ops.dense_wide_plan(T, B, N1, fused=True, may_split=True)
+    tiles = -(-B // (2 * sph))
+    expected = 4096 + tiles * 2 * (32 * rt) * 8 * 4 if cs else 0
+    assert int(L.lib().snnqp_dense_head_workspace_bytes(T, B, N1)) == expected, (T, B, K, N1, N2)
+    split += cs
+  assert 0 < split < len(gc.HEAD_SHAPES)
+
+
 def test_no_shape_takes_another_head_form():
   L, ops = _ops()
   seen = set()
