@@ -250,7 +250,9 @@ typedef struct {
  * query snnqp_conv_float_form; the host-side plan queries snnqp_conv_gated_plan,
  * snnqp_dense_gated_plan, snnqp_dense_wide_plan, snnqp_dense_fp6_plan; streaming inference --
  * snnqp_dense_head_forward_state, snnqp_vote_accumulate, snnqp_vote_counts; the rate encoder
- * snnqp_rate_encode with SNNQP_ENCODE_*: new entry points, nothing else moves).
+ * snnqp_rate_encode with SNNQP_ENCODE_*; training of the PLIF and LIF neurons --
+ * snnqp_neuron_forward_save, snnqp_neuron_backward, snnqp_neuron_backward_splits,
+ * snnqp_neuron_backward_workspace_bytes: new entry points, nothing else moves).
  * A binding compares snnqp_version()
  * with the SNNQP_VERSION it was written against and refuses a library of another version (_lib.py does). */
 #define SNNQP_VERSION 507
@@ -1024,6 +1026,48 @@ int snnqp_dense_weight_grad(const float *x, const float *gI, int64_t M, int32_t 
  * optional (the dropout mask of the block's input). */
 int snnqp_dense_input_grad(const float *gI, const float *w, const float *mask, int64_t M,
                            int32_t K, int32_t N, float *gx, snnqp_stream_t stream);
+
+/* ---- training of the neurons with parameters (csrc/train_neuron.hip) -------------------------
+ * parametric_leaky_IF (k = m = sigmoid(tau), one scalar) and LIF (decay[c] = sigmoid(tau[c])),
+ * spiking_learning.py:357-387 and :419-438.  multi_step_LIF has no parameter: its scans are the
+ * two entry points above, and these answer SNNQP_EUNSUPPORTED for it, naming them.  LIF without
+ * `decay` is SNNQP_EINVAL.  All tensors float32, time-major; 64-bit index arithmetic; grids beyond
+ * the launch limits are SNNQP_EINVAL; every refusal is decided on the host before any launch.
+ *
+ * replaces: the scan in train mode, keeping its residual: x [T][R][C] currents, zero initial
+ *           state -> h_out the potential before the reset, s_out the spikes 0.0 / 1.0 -- the
+ *           arithmetic of snnqp_lif_forward for the same neuron, bit for bit:
+ *             PLIF  h = u + fl(fl(x - fl(u - v_reset)) m)      LIF  h = fl(fl(u decay[c]) + x) */
+int snnqp_neuron_forward_save(const float *x, int32_t T, int64_t R, int32_t C,
+                              const snnqp_neuron_t *nrn, float *h_out, float *s_out,
+                              snnqp_stream_t stream);
+/* the backward of that scan, t = T-1 .. 0, gu_T = 0, no gradient through the reset condition:
+ *   gh_t = g_t sigma'(h_t - v_th) + gu_t (1 - s_t),  u_{t-1} = s_{t-1} ? v_reset : h_{t-1},  u_{-1} = 0
+ *   PLIF  gI_t = gh_t m,  gu_{t-1} = gh_t fl(1 - m),   gparam[0] = sum_{t,r,c} gh_t d_t,
+ *         d_t = fl(x_t - fl(u_{t-1} - v_reset)) recomputed from x (the tensor the scan consumed)
+ *   LIF   gI_t = gh_t,    gu_{t-1} = gh_t decay[c],    gparam[c] = sum_{t,r} gh_t u_{t-1};  x unused
+ * Upstream gs [T][R][C] or glogits [R][C / group] (the fused vote), exactly one, as
+ * snnqp_lif_backward.  gparam is float64, [1] for PLIF and [C] for LIF: every product is formed in
+ * float64 from its two float32 factors (exact) and added in float64 in a fixed order -- the rows
+ * are cut into `splits` (1..max(R, 1)) contiguous ranges whose lengths differ by at most one, a
+ * range is walked r ascending and t descending within a row, the ranges of a feature are added in
+ * order (more than 32 of them: in groups of 32 consecutive ranges, then the groups in order) and,
+ * for PLIF, the features in order.  No atomics: bitwise reproducible for a given
+ * `splits`.  `workspace` holds the partials (snnqp_neuron_backward_workspace_bytes).  T == 0 or
+ * R == 0 writes zero sums and launches nothing. */
+int snnqp_neuron_backward(const float *h, const float *x, const float *gs, const float *glogits,
+                          int32_t group, int32_t T, int64_t R, int32_t C,
+                          const snnqp_neuron_t *nrn, int surrogate, int32_t splits, float *gI,
+                          double *gparam, void *workspace, int64_t workspace_bytes,
+                          snnqp_stream_t stream);
+/* Host only.  The default `splits`: min(max(R, 1), ceil(LANES / C)) -- a function of the shapes
+ * alone (the device is not asked); LANES is a constant of the build, DESIGN.md 17.  A negative
+ * SNNQP_E* on a bad shape. */
+int snnqp_neuron_backward_splits(int32_t T, int64_t R, int32_t C);
+/* Host only.  Bytes of `workspace` for `splits` ranges and neuron `kind` (SNNQP_NEURON_*), or a
+ * negative SNNQP_E*. */
+int64_t snnqp_neuron_backward_workspace_bytes(int32_t T, int64_t R, int32_t C, int32_t splits,
+                                              int kind);
 
 /* ---- training of the conv blocks (csrc/train_conv.hip) ---------------------------------------
  * The two gradient products of a 2-D convolution (flax_qconv.py:158-168 differentiated) and the

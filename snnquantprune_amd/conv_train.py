@@ -27,6 +27,7 @@ from __future__ import annotations
 
 import torch
 
+from . import _lib as _L
 from . import linen as _nn
 from . import ops
 from . import packing
@@ -119,6 +120,34 @@ def conv_currents(x, pk: packing.PackedKernel, geom: ops.ConvGeom, real: bool = 
   return ops.conv_forward(x, geom, w)
 
 
+# ---- the scan of a training block, conv or dense ------------------------------------------------
+# (here, beside conv_currents, and not in dense_train: dense_train imports this module for the
+# connection, so what both kinds of block share lives on this side of that import)
+
+
+def neuron_param_grad(gparam: torch.Tensor, tau: torch.Tensor) -> torch.Tensor:
+  """The `tau` leaf's gradient from the scan's float64 sum: Gm m (1 - m) for PLIF's scalar,
+  Gd_c d_c (1 - d_c) for LIF's decays, m / d = sigmoid(tau) in float64 on the device; in the
+  leaf's dtype and shape."""
+  sg = torch.sigmoid(tau.detach().to(torch.float64))
+  return (gparam.reshape(tau.shape) * sg * (1.0 - sg)).to(tau.dtype)
+
+
+def scan_forward(cur, nrn, tau):
+  """(h, s) of a training block's scan, conv or dense: the multi_step_LIF kernel, or with a `tau`
+  leaf (dense_train.neuron_train_form) the PLIF / LIF one."""
+  return ops.lif_forward_save(cur, nrn) if tau is None else ops.neuron_forward_save(cur, nrn)
+
+
+def scan_backward(h, cur, nrn, surrogate, tau, **upstream):
+  """(gI, gtau) of that scan; gtau None without a `tau` leaf.  cur: the currents the scan consumed
+  (read for PLIF only).  upstream: gs=, or glogits= and group=."""
+  if tau is None:
+    return ops.lif_backward(h, nrn, surrogate, **upstream), None
+  gI, gparam = ops.neuron_backward(h, cur, nrn, surrogate, **upstream)
+  return gI, neuron_param_grad(gparam, tau)
+
+
 class ConvBlock(torch.autograd.Function):
   """x [T, B, H, W, Cin] -> pooled spikes float32 [T, B, OH/2, OW/2, C], and without gradient the
   unpooled h, s [T, B, OH, OW, C] and the per-step statistics mean, var [T, C].  Gradients to x
@@ -130,19 +159,29 @@ class ConvBlock(torch.autograd.Function):
   (what a gate leaves), not spikes: it is not bit-packed and the currents come from the float32
   connection on it.  wgrad_f64: the weight gradient's chain runs in float64
   (ops.conv_weight_grad_f64) -- CextNet's first block, whose 64 x 64 and larger count frames make
-  the sum cancel further than a float32 chain resolves."""
+  the sum cancel further than a float32 chain resolves.
+
+  tau: the neuron's parameter leaf when it is learnt (dense_train.neuron_train_form: PLIF or LIF)
+  -- a further input that receives its gradient.  PLIF's backward reads the scan's input again:
+  it is recomputed from the saved currents and statistics (scan_input), the forward's bits."""
 
   @classmethod
   def apply(cls, x, wq, scale, bias, pk, geom, nrn, surrogate, eps, first, pool=2,
-            real_input=False, wgrad_f64=False):
+            real_input=False, wgrad_f64=False, tau=None):
     if pool not in (1, 2):
       raise ValueError("ConvBlock: pool must be 1 or 2, got %r" % (pool,))
     return super().apply(x, wq, scale, bias, pk, geom, nrn, surrogate, eps, first, pool,
-                         real_input, wgrad_f64)
+                         real_input, wgrad_f64, tau)
+
+  @staticmethod
+  def scan_input(cur, mean, var, scale, bias, eps):
+    """The normalised currents the scan consumes, from what the block saves: one sequence of
+    float32 operations, so the backward's recomputation is the forward's tensor bit for bit."""
+    return bn_normalise(cur.clone(), mean, bn_multiplier(var, scale, eps), bias)
 
   @staticmethod
   def forward(ctx, x, wq, scale, bias, pk, geom, nrn, surrogate, eps, first, pool, real_input,
-              wgrad_f64):
+              wgrad_f64, tau):
     T, B = x.shape[0], x.shape[1]
     C = geom.Cout
     if first or real_input or pk.int_weight() is None:
@@ -153,13 +192,14 @@ class ConvBlock(torch.autograd.Function):
     OH, OW = cur.shape[1], cur.shape[2]
     cur = cur.reshape(T, B * OH * OW, C)
     mean, var = batch_stats(cur)
-    y = bn_normalise(cur.clone(), mean, bn_multiplier(var, scale, eps), bias)
-    h, s = ops.lif_forward_save(y, nrn)
+    y = ConvBlock.scan_input(cur, mean, var, scale, bias, eps)
+    h, s = scan_forward(y, nrn, tau)
     del y
     h = h.reshape(T, B, OH, OW, C)
     s = s.reshape(T, B, OH, OW, C)
     pooled = ops.maxpool2x2(s) if pool == 2 else s.clone()
-    ctx.save_for_backward(x, wq, scale, cur, mean, var, h)
+    plif = tau is not None and nrn.kind == _L.NEURON_PARAMETRIC_LEAKY_IF
+    ctx.save_for_backward(x, wq, scale, cur, mean, var, h, tau, bias.detach() if plif else None)
     ctx.geom, ctx.nrn, ctx.surrogate, ctx.eps, ctx.first = geom, nrn, surrogate, eps, first
     ctx.pool, ctx.wgrad_f64 = pool, wgrad_f64
     ctx.mark_non_differentiable(h, s, mean, var)
@@ -167,7 +207,7 @@ class ConvBlock(torch.autograd.Function):
 
   @staticmethod
   def backward(ctx, gp, _gh, _gs, _gmean, _gvar):
-    x, wq, scale, cur, mean, var, h = ctx.saved_tensors
+    x, wq, scale, cur, mean, var, h, tau, bias = ctx.saved_tensors
     geom, nrn = ctx.geom, ctx.nrn
     T, B, OH, OW, C = h.shape
     if ctx.pool == 2:
@@ -176,9 +216,10 @@ class ConvBlock(torch.autograd.Function):
       del s
     else:
       gs = gp.contiguous()
-    gy = ops.lif_backward(h.reshape(T, B * OH * OW, C), nrn, ctx.surrogate,
-                          gs=gs.reshape(T, B * OH * OW, C))
-    del gs
+    y = None if bias is None else ConvBlock.scan_input(cur, mean, var, scale.detach(), bias, ctx.eps)
+    gy, gtau = scan_backward(h.reshape(T, B * OH * OW, C), y, nrn, ctx.surrogate, tau,
+                             gs=gs.reshape(T, B * OH * OW, C))
+    del gs, y
     gcur, gscale, gbias = bn_backward(gy, cur, mean, var, scale, ctx.eps)
     del gy
     gcur = gcur.reshape(T * B, OH, OW, C)
@@ -187,4 +228,4 @@ class ConvBlock(torch.autograd.Function):
     gx = None
     if not ctx.first and ctx.needs_input_grad[0]:
       gx = ops.conv_input_grad(gcur, wq.detach(), geom).reshape(x.shape)
-    return gx, gw, gscale, gbias, None, None, None, None, None, None, None, None, None
+    return gx, gw, gscale, gbias, None, None, None, None, None, None, None, None, None, gtau

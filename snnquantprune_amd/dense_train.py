@@ -25,7 +25,7 @@ import torch
 from . import _lib as L
 from . import ops
 from . import packing
-from .conv_train import conv_currents
+from .conv_train import conv_currents, neuron_param_grad, scan_backward, scan_forward  # noqa: F401
 
 SURROGATES = {
     "fast_sigmoid": L.SURR_FAST_SIGMOID,
@@ -61,6 +61,24 @@ def surrogate_of(neuron_module) -> int:
   if name not in SURROGATES:
     raise NotImplementedError("no surrogate gradient for spike function %r" % (name,))
   return SURROGATES[name]
+
+
+def neuron_train_form(neuron_module, cfg):
+  """(SURR_*, kind) of a block's neuron in training: what the training forwards ask.
+
+  Without config.learn_neuron_params this is surrogate_of -- multi_step_LIF or a refusal -- and
+  the kind is NEURON_MULTI_STEP_LIF.  With it, parametric_leaky_IF and LIF are taken too
+  (NEURON_PARAMETRIC_LEAKY_IF / NEURON_LIF): their scans are ops.neuron_forward_save and
+  ops.neuron_backward, and the block hands the `tau` leaf its gradient (neuron_param_grad)."""
+  from .spiking_learning import LIF, parametric_leaky_IF
+  kinds = {parametric_leaky_IF: L.NEURON_PARAMETRIC_LEAKY_IF, LIF: L.NEURON_LIF}
+  learn = cfg is not None and "learn_neuron_params" in cfg and bool(cfg["learn_neuron_params"])
+  if not learn or type(neuron_module) not in kinds:
+    return surrogate_of(neuron_module), L.NEURON_MULTI_STEP_LIF
+  name = getattr(neuron_module.spike_fn, "__name__", None)
+  if name not in SURROGATES:
+    raise NotImplementedError("no surrogate gradient for spike function %r" % (name,))
+  return SURROGATES[name], kinds[type(neuron_module)]
 
 
 # ---------------------------------------------------------------------------
@@ -156,21 +174,28 @@ class DenseBlock(torch.autograd.Function):
   the float32 connection without looking at the values.
 
   group None: a hidden block -- no vote; -> (s, None, h), and the spikes' gradient drives the
-  scan."""
+  scan.
+
+  tau: the neuron's parameter leaf when it is learnt (neuron_train_form: PLIF or LIF) -- a further
+  input that receives its gradient.  PLIF's backward reads the scan's currents again, so the block
+  keeps them ([T, B, N] float32 more than a multi_step_LIF or LIF block saves)."""
 
   @classmethod
-  def apply(cls, x, wq, m, pk, nrn, surrogate, group, first=False, real_input=False):
-    return super().apply(x, wq, m, pk, nrn, surrogate, group, first, real_input)
+  def apply(cls, x, wq, m, pk, nrn, surrogate, group, first=False, real_input=False, tau=None):
+    return super().apply(x, wq, m, pk, nrn, surrogate, group, first, real_input, tau)
 
   @staticmethod
-  def forward(ctx, x, wq, m, pk, nrn, surrogate, group, first, real_input):
+  def forward(ctx, x, wq, m, pk, nrn, surrogate, group, first, real_input, tau):
     x1 = x * m if m is not None else x
     if first or real_input or pk.int_weight() is None:
       xin = x1
     else:
       xin = ops.pack_bits(x1.contiguous())
-    h, s = ops.lif_forward_save(_currents(xin, pk, wq.shape[1], real_input), nrn)
-    ctx.save_for_backward(h, wq, m, x1)
+    cur = _currents(xin, pk, wq.shape[1], real_input)
+    h, s = scan_forward(cur, nrn, tau)
+    if tau is None or nrn.kind != L.NEURON_PARAMETRIC_LEAKY_IF:
+      cur = None
+    ctx.save_for_backward(h, wq, m, x1, tau, cur)
     ctx.nrn, ctx.surrogate, ctx.group, ctx.first = nrn, surrogate, group, first
     if group is None:
       ctx.mark_non_differentiable(h)
@@ -181,20 +206,20 @@ class DenseBlock(torch.autograd.Function):
 
   @staticmethod
   def backward(ctx, gout, _gs, _gh):
-    h, wq, m, x1 = ctx.saved_tensors
+    h, wq, m, x1, tau, cur = ctx.saved_tensors
     T, B, K = x1.shape
     N = h.shape[-1]
     if ctx.group is None:
-      gI = ops.lif_backward(h, ctx.nrn, ctx.surrogate, gs=gout.contiguous())
+      gI, gtau = scan_backward(h, cur, ctx.nrn, ctx.surrogate, tau, gs=gout.contiguous())
     else:
-      gI = ops.lif_backward(h, ctx.nrn, ctx.surrogate, glogits=gout, group=ctx.group)
+      gI, gtau = scan_backward(h, cur, ctx.nrn, ctx.surrogate, tau, glogits=gout, group=ctx.group)
     gI2 = gI.reshape(T * B, N)
     gw = ops.dense_weight_grad(x1.reshape(T * B, K).to(torch.float32), gI2)
     gx = None
     if not ctx.first and ctx.needs_input_grad[0]:
       gx = ops.dense_input_grad(gI2, wq.detach(), None if m is None else m.reshape(T * B, K))
       gx = gx.reshape(T, B, K)
-    return gx, gw, None, None, None, None, None, None, None
+    return gx, gw, None, None, None, None, None, None, None, gtau
 
 
 def dropout_mask(shape, keep: float, generator: torch.Generator, device) -> torch.Tensor:

@@ -288,6 +288,9 @@ def _head_key(mod, cfg, x, hidden, nout):
           l1["kernel"], l1["DuQ_0"]["a"], l1["DuQ_0"]["c"], l1["prune_0"]["mask"])
   except (KeyError, TypeError):
     return None
+  # the neurons' own parameters (PLIF / LIF `tau`): a training step moves them too
+  ts += tuple(v["tau"] for _, v in sorted(p.items())
+              if isinstance(v, dict) and isinstance(v.get("tau"), torch.Tensor))
   q = cfg.quant
   extra = (type(x).__name__, str(getattr(x, "dtype", "")), tuple(x.shape), hidden, nout, _layer_bits(cfg, 0), _layer_bits(cfg, 1), id(q.get("weight")),
            float(q.prune_percentage) >= 0.0, id(cfg.neuron_dynamics))

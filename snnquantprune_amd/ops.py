@@ -2091,6 +2091,69 @@ def lif_backward(h: torch.Tensor, neuron: Neuron, surrogate: int, gs: Optional[t
   return gI
 
 
+def neuron_forward_save(x: torch.Tensor, neuron: Neuron):
+  """lif_forward_save for the neurons with a parameter (PLIF, LIF; csrc/train_neuron.hip):
+  currents float32 [T, ..., C] -> (h, s), the arithmetic of lif_forward for the same neuron."""
+  x = _f32c(x)
+  _require_gpu(x)
+  T, C = x.shape[0], x.shape[-1]
+  R = (x.numel() // (T * C)) if T * C else 0
+  h = torch.empty_like(x)
+  s = torch.empty_like(x)
+  L.check(L.lib().snnqp_neuron_forward_save(_ptr(x), T, R, C, ctypes.byref(neuron.struct()),
+                                            _ptr(h), _ptr(s), _stream()))
+  return h, s
+
+
+def neuron_backward_splits(T: int, R: int, C: int) -> int:
+  """The default number of row ranges of neuron_backward: shapes only."""
+  rc = L.lib().snnqp_neuron_backward_splits(int(T), int(R), int(C))
+  if rc < 0:
+    L.check(rc)
+  return rc
+
+
+def neuron_backward_workspace_bytes(T: int, R: int, C: int, splits: int, kind: int) -> int:
+  rc = L.lib().snnqp_neuron_backward_workspace_bytes(int(T), int(R), int(C), int(splits), int(kind))
+  if rc < 0:
+    L.check(rc)
+  return rc
+
+
+def neuron_backward(h: torch.Tensor, x: Optional[torch.Tensor], neuron: Neuron, surrogate: int,
+                    gs: Optional[torch.Tensor] = None, glogits: Optional[torch.Tensor] = None,
+                    group: int = 10, splits: Optional[int] = None):
+  """BPTT of the PLIF / LIF scan: h [T, R, C] and, for PLIF, the currents x the scan consumed ->
+  (gI [T, R, C], gparam float64): gparam [1] = sum gh d for PLIF (the gradient of m), [C] =
+  sum_{t,r} gh u_{t-1} for LIF (of the decays).  Upstream gs or glogits as lif_backward; the rows
+  are cut into `splits` ranges summed in order (None: neuron_backward_splits)."""
+  h = _f32c(h)
+  x = None if x is None or neuron.kind == L.NEURON_LIF else _f32c(x)
+  gs = None if gs is None else _f32c(gs)
+  glogits = None if glogits is None else _f32c(glogits)
+  _require_gpu(h, x, gs, glogits)
+  T, C = h.shape[0], h.shape[-1]
+  R = (h.numel() // (T * C)) if T * C else 0
+  if neuron.kind == L.NEURON_PARAMETRIC_LEAKY_IF and h.numel():
+    if x is None or tuple(x.shape) != tuple(h.shape):
+      raise ValueError("neuron_backward: PLIF needs the scan's currents x, shaped like h")
+  if splits is None:
+    splits = neuron_backward_splits(T, R, C)
+  # (another kind has no workspace to size: the call below refuses it, naming its own entry point)
+  known = neuron.kind in (L.NEURON_PARAMETRIC_LEAKY_IF, L.NEURON_LIF)
+  nbytes = neuron_backward_workspace_bytes(T, R, C, splits, neuron.kind) if known else 0
+  gI = torch.empty_like(h)
+  gparam = torch.empty((C if neuron.kind == L.NEURON_LIF else 1,), dtype=torch.float64, device=h.device)
+  if h.numel() == 0 and (gs is None) != (glogits is None) and (
+      glogits is None or (group > 0 and C % group == 0)):
+    return gI, gparam.zero_()   # an empty upstream has no pointer to tell gs from glogits by
+  ws = torch.empty(nbytes // 8, dtype=torch.float64, device=h.device)
+  L.check(L.lib().snnqp_neuron_backward(_ptr(h), _ptr(x), _ptr(gs), _ptr(glogits), int(group), T, R, C,
+                                        ctypes.byref(neuron.struct()), int(surrogate), int(splits),
+                                        _ptr(gI), _ptr(gparam), _ptr(ws), nbytes, _stream()))
+  return gI, gparam
+
+
 def dense_weight_grad(x: torch.Tensor, gI: torch.Tensor) -> torch.Tensor:
   """x [M, K], gI [M, N] -> x^T gI [K, N] (float32 MFMA, one fixed reduction order)."""
   x, gI = _f32c(x), _f32c(gI)

@@ -371,6 +371,7 @@ class SpikingBlock(nn.Module):
       live_in = np.zeros(full_in, bool)
       live_in[cmap_in.index[cmap_in.live]] = True
     key = (w.w,) + ((bn.mean, bn.mul, bn.bias) if bn is not None else (None, None, None))
+    key += (nrn.decay,)                          # LIF: a trained tau brings a new decay tensor
     extra = (int(x_max), None if live_in is None else live_in.tobytes(), nrn.kind, float(nrn.k),
              float(nrn.v_threshold), float(nrn.v_reset))
     plan = _plan_cache.get(key, extra)

@@ -68,6 +68,18 @@ def _transformed_kernel(mod, layer, pk):
   return dt.transformed_kernel(leaf, pk)
 
 
+def _tau_leaf(mod, dyn, kind):
+  """The block's own `tau` leaf when its neuron's parameter is learnt (dt.neuron_train_form gave
+  PLIF or LIF), found as _transformed_kernel finds the kernel's: the tensor dyn.neuron() read, so
+  the gradient reaches the leaf the caller holds.  None for multi_step_LIF."""
+  if kind == dt.L.NEURON_MULTI_STEP_LIF:
+    return None
+  leaf = mod._root.variables["params"]
+  for name in dyn._path:
+    leaf = leaf[name]
+  return leaf["tau"]
+
+
 def conv_block(mod, x, i, bits, pool=2, first=False, real_input=False, wgrad_f64=False):
   """Conv block i on x [T, B, H, W, Cin]: QuantConv 3x3, BatchNorm on batch statistics, LIF, the
   2x2 max pool (conv_train.ConvBlock, whose arguments the last four are) -> the pooled spikes.
@@ -76,14 +88,15 @@ def conv_block(mod, x, i, bits, pool=2, first=False, real_input=False, wgrad_f64
   conv = _qconv3x3(cfg, mod.dtype, bits)
   dyn = cfg.neuron_dynamics(dtype=mod.dtype)
   norm = _batchnorm(mod.dtype, train=True)
-  surr = dt.surrogate_of(dyn)
+  surr, kind = dt.neuron_train_form(dyn, cfg)
   cin = x.shape[4]
   geom = conv.geometry((x.shape[2], x.shape[3]), cin)
   pk = conv.packed_kernel(cin)
   wq = _transformed_kernel(mod, conv, pk)
+  nrn = dyn.neuron(C)
   y, h, s, mean, var = ct.ConvBlock.apply(
-      x, wq, norm.scale_param(C), norm.bias_param(C), pk, geom, dyn.neuron(C), surr,
-      float(norm.epsilon), first, pool, real_input, wgrad_f64)
+      x, wq, norm.scale_param(C), norm.bias_param(C), pk, geom, nrn, surr,
+      float(norm.epsilon), first, pool, real_input, wgrad_f64, _tau_leaf(mod, dyn, kind))
   norm.update_running(mean, var)
   if mod.is_mutable_collection("intermediates"):
     mod.sow("intermediates", "conv%d_h" % i, h)
@@ -115,7 +128,7 @@ def dense_layer(mod, features, bits, K):
   layers before it enqueues any work, so that no read-back waits for block 1's kernels."""
   dense = _qdense(mod.config, mod.dtype, bits, features)
   dyn = mod.config.neuron_dynamics(dtype=mod.dtype)
-  return dense, dyn, dt.surrogate_of(dyn), dense.packed_kernel(K)
+  return dense, dyn, dt.neuron_train_form(dyn, mod.config), dense.packed_kernel(K)
 
 
 def dense_block(mod, x, name, layer, group, mask=None, first=False, real_input=False):
@@ -123,11 +136,12 @@ def dense_block(mod, x, name, layer, group, mask=None, first=False, real_input=F
   (dense_train.DenseBlock, whose arguments the last three are) -> the logits, or the spikes of a
   hidden block (group None).  mask (generator, n): draws the block's dropout mask, shaped like
   x, and sows it as dropout_<n>; None: no mask.  Sows <name>_out and <name>_h."""
-  dense, dyn, surr, pk = layer
+  dense, dyn, (surr, kind), pk = layer
   m = None if mask is None else dt.dropout_mask(x.shape, mod.config.dropout, mask[0], x.device)
   wq = _transformed_kernel(mod, dense, pk)
-  out, s, h = dt.DenseBlock.apply(x, wq, m, pk, dyn.neuron(dense.features), surr, group, first,
-                                  real_input)
+  nrn = dyn.neuron(dense.features)
+  out, s, h = dt.DenseBlock.apply(x, wq, m, pk, nrn, surr, group, first, real_input,
+                                  _tau_leaf(mod, dyn, kind))
   if mod.is_mutable_collection("intermediates"):
     if m is not None:
       mod.sow("intermediates", "dropout_%d" % mask[1], m)

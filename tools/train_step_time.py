@@ -15,6 +15,12 @@ timings each), and conv0's direct-form connection.
 
   python tools/train_step_time.py --conv [--steps 5] [--warmup 2] [--batch 2] [--frames 20] [--hw 128] [--reps 3]
 
+--conv --neuron multi_step_LIF|plif|lif times that step with the given neuron only (PLIF and LIF
+learn their `tau` under config.learn_neuron_params), --reps timings in one process, and the BPTT
+scan alone on conv1's shape, for PLIF / LIF at each --lanes target of its row split.
+
+  python tools/train_step_time.py --conv --neuron plif [--lanes 0 65536 262144 1048576]
+
 --cext times one CextNet train_step on the reference's geometry (128 x 128 x 2 frames, 128 channels,
 4-bit DuQ, 90 % pruned, default B = 2, T = 20, atan, Adam), the two kernels of csrc/train_gate.hip
 alone on both gated stages' shapes, block 0's weight gradient on the float64 and the float32 chain, and the same step in PyTorch eager float32 autograd; --reps
@@ -251,7 +257,62 @@ def cext_main(args):
                     **{k: [round(t, 4) for t in val] for k, val in kern.items()}}))
 
 
+def neuron_main(args):
+  """--conv --neuron {multi_step_LIF, plif, lif}: the ConvDenseSNN step of --conv with that neuron
+  (PLIF / LIF under config.learn_neuron_params, a `tau` leaf per block), --reps timings in one
+  process, and the BPTT scan of conv1's shape alone for several `splits` (0: the default)."""
+  from functools import partial
+  import numpy as np
+  from snnquantprune_amd import _lib as L
+  from snnquantprune_amd import linen as nn
+  from snnquantprune_amd import models, ops, spiking_learning as sl, synthetic as syn, train_utils as tu
+  dev = torch.device("cuda:0")
+  B, T, HW, C, NB = args.batch, args.frames, args.hw, 128, 3
+  cfg = syn.make_config(bits=4, prune_percentage=0.9, channels=C, dropout=0.9)
+  cfg.optimizer = "adam"
+  v = syn.conv_net_variables(C, 2, NB, HW, 110, True, 0.9)
+  if args.neuron != "multi_step_LIF":
+    cls = sl.parametric_leaky_IF if args.neuron == "plif" else sl.LIF
+    cfg.neuron_dynamics = partial(cls, init_tau=2.0, spike_fn=sl.atan)
+    cfg.learn_neuron_params = True
+    for i, width in enumerate((C,) * NB + (110,)):
+      v["params"]["%s_%d" % (cls.__name__, i)] = {
+          "tau": np.zeros(1 if args.neuron == "plif" else width, np.float32)}     # m = d = 0.5: tau 2
+  model = models.ConvDenseSNN(num_classes=11, config=cfg)
+  variables = nn.tree_from_numpy(v, dev)
+  x = torch.from_numpy(syn.poisson_counts((B, T, HW, HW, 2), 0.3, seed=941)).to(dev)
+  batch = {"dvs_matrix": x, "label": torch.arange(B, device=dev) % 11}
+  box = [tu.create_train_state(variables, cfg, model)]
+
+  def hip_step():
+    box[0], _ = tu.train_step(box[0], batch, 0, lambda s: 1e-4, 0.0, 0.0, tu.mse_loss)
+
+  _time(hip_step, 1, args.warmup)
+  out = {"workload": "conv_dense_snn_c3_train_step", "neuron": args.neuron, "batch": B, "frames": T, "hw": HW,
+         "hip_train_step_ms": [round(_time(hip_step, args.steps, 0), 3) for _ in range(args.reps)]}
+  # the scan's backward alone on conv1's shape [T, B (HW/2)^2, C]
+  R = B * (HW // 2) ** 2
+  h = torch.randn((T, R, C), device=dev) + 0.5
+  g = torch.randn((T, R, C), device=dev)
+  if args.neuron == "multi_step_LIF":
+    nrn = ops.Neuron(L.NEURON_MULTI_STEP_LIF, 2.0, 1.0, 0.0)
+    out["lif_backward_ms"] = [round(_time(lambda: ops.lif_backward(h, nrn, L.SURR_ATAN, gs=g), 20, 3), 4)
+                              for _ in range(args.reps)]
+  else:
+    nrn = ops.Neuron(L.NEURON_PARAMETRIC_LEAKY_IF, 0.5, 1.0, 0.0) if args.neuron == "plif" else \
+        ops.Neuron(L.NEURON_LIF, 0.0, 1.0, 0.0, decay=torch.full((C,), 0.5, device=dev))
+    out["neuron_backward_default_splits"] = ops.neuron_backward_splits(T, R, C)
+    for lanes in args.lanes:
+      splits = None if lanes == 0 else max(1, min(R, -(-lanes // C)))
+      out["neuron_backward_ms_lanes_%d" % lanes] = [
+          round(_time(lambda: ops.neuron_backward(h, g, nrn, L.SURR_ATAN, gs=g, splits=splits), 20, 3), 4)
+          for _ in range(args.reps)]
+  print(json.dumps(out))
+
+
 def conv_main(args):
+  if args.neuron is not None:
+    return neuron_main(args)
   from snnquantprune_amd import linen as nn
   from snnquantprune_amd import models, ops, synthetic as syn, train_utils as tu
   dev = torch.device("cuda:0")
@@ -355,6 +416,10 @@ def main():
   ap.add_argument("--frames", type=int, default=20)
   ap.add_argument("--hw", type=int, default=128)
   ap.add_argument("--reps", type=int, default=3, help="--conv: timings of each side of the A/B; --cext: timings of each figure")
+  ap.add_argument("--neuron", choices=["multi_step_LIF", "plif", "lif"], default=None,
+                  help="--conv: the step with this neuron, --reps timings, and its BPTT scan alone")
+  ap.add_argument("--lanes", type=int, nargs="*", default=[0],
+                  help="--conv --neuron plif|lif: lanes the scan's `splits` aims at (0: the default)")
   args = ap.parse_args()
   dflt = (5, 2, 2) if args.conv or args.cext else (20, 5, 256)
   args.steps = dflt[0] if args.steps is None else args.steps
