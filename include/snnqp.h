@@ -11,10 +11,11 @@
  * Conventions
  *  - every pointer named x/w/y/u/s/... is a DEVICE pointer owned by the caller
  *    (torch); the library allocates nothing that outlives a call, with one exception:
- *    the fused conv kernels keep 512 KiB of work-queue counters per device (the device of
- *    `stream`): 64 round-robin slots for eager launches -- a slot is zeroed on `stream`
- *    right before its launch and guarded by an event; a launch that finds its slot still in
- *    flight (more than 64 conv launches outstanding on the device) walks its patches
+ *    the fused conv kernels keep 736 KiB of work-queue counters per device (the device of
+ *    `stream`): 512 round-robin slots for eager launches -- a slot is zeroed on `stream`
+ *    right before its launch and guarded by an event, so launches that run at the same time,
+ *    on whatever streams, never share a counter; a launch that finds its slot still in
+ *    flight (more than 512 conv launches outstanding on the device) walks its patches
  *    statically instead: same results, no queue -- and 960 slots that launches captured into
  *    a graph take one each until snnqp_workqueue_capture_release hands them back (the pool
  *    must exist before the capture: one eager launch on the device); 64 bytes of page-locked

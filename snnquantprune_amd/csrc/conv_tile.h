@@ -90,7 +90,10 @@ struct ConvMfmaArgs {
 // of finished workgroups (the last one zeroes the words for the slot's next user).
 constexpr int SCHED_Y = 8;                  // blockIdx.y values a slot serves (Cout <= 1024)
 constexpr int SCHED_WORDS = SCHED_Y * 16;   // words of one slot
-constexpr int SCHED_SLOTS = 64;             // launches in flight per device
+// Sized by launches outstanding, not by launches per step: a caller that enqueues 20 steps
+// without a fence, each step's first two conv blocks cut into 8 batch chunks (tools/corun_ab.py),
+// has 20 x (8 + 8 + 1) = 340 launches behind the one that runs.  512 slots are 256 KiB of words.
+constexpr int SCHED_SLOTS = 512;            // launches in flight per device
 constexpr int SCHED_CAPTURE_SLOTS = 960;    // launches captured into graphs per device (never reused)
 
 // Patch schedule of a persistent workgroup.  With xcd_split the workgroups that

@@ -11,6 +11,15 @@
 //    flight across streams / threads), the launch takes the static walk instead (sched =
 //    nullptr), which is always correct, only less well balanced (C3 under a graph without
 //    queues: 13.6 ms against 12.3).
+// Which word belongs to which launch: slot s owns words [s * SCHED_WORDS, (s + 1) * SCHED_WORDS) --
+// per blockIdx.y sixteen of them, eight patch counters (one per XCD queue), the count of finished
+// workgroups and the patch tally (PatchWalk, conv_tile.h) -- and nothing outside a slot is shared
+// between launches.  The round-robin pointer moves under g_sched_mu and a slot whose event has not
+// completed is never handed out, so two launches that can run at the same time -- on two streams,
+// as the batch chunks of two blocks side by side do (tools/corun_ab.py) -- never hold the same
+// slot, counter or tally: the second asker walks statically (busy_static in snnqp_workqueue_stats).
+// SCHED_SLOTS is therefore sized by the launches a caller may have outstanding, not by the launches
+// of one step (conv_tile.h).
 // A launch that is being CAPTURED into a graph (events cannot be queried there) gets a slot of
 // its own out of SCHED_CAPTURE_SLOTS further ones, handed back when the caller says the graph is
 // gone (snnqp_workqueue_capture_release; linen.CapturedApply does).  Nothing is added to
