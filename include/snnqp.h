@@ -244,7 +244,8 @@ typedef struct {
  * 507: snnqp_conv_forward_ex -- currents from the bit-input MFMA conv; within 507, layout-
  * compatible: snnqp_weight_t.cout_fire in the struct's former tail padding,
  * snnqp_set_event_half_group, snnqp_conv_event_half_group, snnqp_set_event_wave_spread,
- * snnqp_conv_event_wave_spread; training of CextNet's gated stages --
+ * snnqp_conv_event_wave_spread, snnqp_set_event_quarter16, snnqp_conv_event_quarter16; training of
+ * CextNet's gated stages --
  * snnqp_gate_pool_grad_gate, snnqp_gate_pool_grad_input, snnqp_conv_weight_grad_f64,
  * snnqp_conv_weight_grad_f64_workspace_bytes; the batched event front end snnqp_events_bin and its augmenting
  * form snnqp_events_bin_aug with snnqp_event_aug_t; the host-side
@@ -297,6 +298,17 @@ int snnqp_set_event_wave_spread(int enabled);
  * snnqp_set_event_half_group), 0 when not, a negative error: as snnqp_conv_event_half_group. */
 int snnqp_conv_event_wave_spread(int in_type, int32_t T, const snnqp_conv_geom_t *g, const snnqp_weight_t *w,
                                  const snnqp_neuron_t *nrn, int has_state, int pool, int x_max);
+/* The quarter of the half group in the spread launch of Cout = 96.  1 (the default): a wave takes its
+ * quarter -- 16 channels x 16 pixels -- from one 16x16x64 int8 matrix instruction with a four-register
+ * product.  0: it issues the half group's whole 32x32x32 product and reads four registers of it (the
+ * same results).  Process-wide, for the launches enqueued after the call; returns the previous setting.
+ * A negative argument only queries. */
+int snnqp_set_event_quarter16(int enabled);
+/* 1 when that launch would take its quarters that way under the current settings (of this switch, of
+ * snnqp_set_event_wave_spread and of snnqp_set_event_half_group), 0 when not, a negative error: as
+ * snnqp_conv_event_half_group. */
+int snnqp_conv_event_quarter16(int in_type, int32_t T, const snnqp_conv_geom_t *g, const snnqp_weight_t *w,
+                               const snnqp_neuron_t *nrn, int has_state, int pool, int x_max);
 
 int snnqp_conv_out_shape(const snnqp_conv_geom_t *g, int32_t *OH, int32_t *OW);
 

@@ -75,6 +75,9 @@ _PROTOTYPES = {
     "snnqp_set_event_wave_spread": (c_int, [c_int]),
     "snnqp_conv_event_wave_spread": (c_int, [c_int, c_int32, POINTER(ConvGeomT), POINTER(WeightT),
                                              POINTER(NeuronT), c_int, c_int, c_int]),
+    "snnqp_set_event_quarter16": (c_int, [c_int]),
+    "snnqp_conv_event_quarter16": (c_int, [c_int, c_int32, POINTER(ConvGeomT), POINTER(WeightT),
+                                           POINTER(NeuronT), c_int, c_int, c_int]),
     "snnqp_conv_out_shape": (c_int, [POINTER(ConvGeomT), POINTER(c_int32),
                                      POINTER(c_int32)]),
     "snnqp_quantize": (c_int, [c_int, c_void_p, c_void_p, c_int64, c_int, c_float,

@@ -11,6 +11,8 @@ static std::atomic<int> g_event_half_group{1};
 bool event_half_group_enabled() { return g_event_half_group.load(std::memory_order_relaxed) != 0; }
 static std::atomic<int> g_event_wave_spread{1};
 bool event_wave_spread_enabled() { return g_event_wave_spread.load(std::memory_order_relaxed) != 0; }
+static std::atomic<int> g_event_quarter16{1};
+bool event_quarter16_enabled() { return g_event_quarter16.load(std::memory_order_relaxed) != 0; }
 
 static thread_local std::string g_last_error;
 
@@ -49,6 +51,11 @@ int snnqp_set_event_half_group(int enabled) {
 int snnqp_set_event_wave_spread(int enabled) {
   if (enabled < 0) return snnqp::event_wave_spread_enabled() ? 1 : 0;
   return snnqp::g_event_wave_spread.exchange(enabled ? 1 : 0, std::memory_order_relaxed);
+}
+
+int snnqp_set_event_quarter16(int enabled) {
+  if (enabled < 0) return snnqp::event_quarter16_enabled() ? 1 : 0;
+  return snnqp::g_event_quarter16.exchange(enabled ? 1 : 0, std::memory_order_relaxed);
 }
 
 int snnqp_conv_out_shape(const snnqp_conv_geom_t *g, int32_t *OH, int32_t *OW) {

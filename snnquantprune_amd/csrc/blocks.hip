@@ -119,6 +119,13 @@ int snnqp_conv_event_wave_spread(int in_type, int32_t T, const snnqp_conv_geom_t
   return conv3x3_event_wave_spread(in_type, T, g, w, nrn, has_state != 0, pool, x_max);
 }
 
+int snnqp_conv_event_quarter16(int in_type, int32_t T, const snnqp_conv_geom_t *g, const snnqp_weight_t *w,
+                               const snnqp_neuron_t *nrn, int has_state, int pool, int x_max) {
+  SNNQP_REQUIRE(g && w && nrn, SNNQP_EINVAL, "conv_event_quarter16: null descriptor");
+  SNNQP_CHECK_NEURON_KIND(nrn, "conv_event_quarter16");
+  return conv3x3_event_quarter16(in_type, T, g, w, nrn, has_state != 0, pool, x_max);
+}
+
 int snnqp_conv_lif_forward(const void *x, int in_type, int64_t x_stride_t,
                            int64_t x_stride_b, int32_t T, int32_t B,
                            const snnqp_conv_geom_t *g, const snnqp_weight_t *w,

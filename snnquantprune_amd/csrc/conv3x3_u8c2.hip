@@ -123,6 +123,13 @@ constexpr int u8c2_waves() {
 // and every wave carries 16 (+ 4) potentials.  The tables are built as ever, wave = channel group
 // (wave 2: the half group's twins); a wave then takes the table addresses of the groups it computes
 // from the scratch.  Staging, barriers, flush, queue and LDS plan are the full path's.
+//
+// Q16 (the quarter on a 16x16x64 matrix instruction; SPREAD with HALF): a wave's quarter
+// IS the product of one v_mfma_i32_16x16x64_i8 -- 16 channels x 16 pixels in four registers -- so the wave
+// issues that instead of the half group's whole 32x32x32 product: A row r = pixel r of its 4x4 quarter, B
+// column c = channel 64 + c with the taps in lane groups 0 and 1, C = four registers of the table address
+// (lane groups 1 and 3 read the twin's copy of the channel's table: 32 distinct banks per 32 lanes), and
+// EP_QUARTER16 (conv_tile.h) places the words where EP_QUARTER does.
 // The tap rule of the B operand: k row kk = 8 dy + b carries byte b = 2 dx + cin of halo row dy (b < 6:
 // bytes 6, 7 of a row read belong to the next pixel), which meets weight row (3 dy + dx) * 2 + cin =
 // 6 dy + b of HWIO with Cin = 2.  Whether kk is a tap, and its weight row.
@@ -131,13 +138,15 @@ __device__ __forceinline__ bool tap_row(int kk, int &row) {
   return kk >= 0 && kk < 24 && (kk & 7) < 6;
 }
 
-template <int NF, bool POOL, int LUTM, int IN = SNNQP_U8, bool ONE = false, bool HALF = false, bool SPREAD = false>
+template <int NF, bool POOL, int LUTM, int IN = SNNQP_U8, bool ONE = false, bool HALF = false, bool SPREAD = false,
+          bool Q16 = false>
 __global__ void __launch_bounds__(256, (u8c2_waves<NF, POOL, LUTM, IN, ONE, SPREAD>()))
 conv3x3_u8c2_kernel(ConvMfmaArgs a) {
   constexpr int FL = OutStage<POOL>::FL;
   constexpr bool EV1 = IN == SNNQP_EV1;
   static_assert(!(HALF || SPREAD) || (EV1 && ONE && LUTM == LUT_CHANNEL && NF == NF_MUL0),
                 "the half group, the wave spread: bit-packed frames, one chunk, per-channel tables, NF_MUL0");
+  static_assert(!Q16 || (HALF && SPREAD), "the 16x16x64 quarter: the spread launch with the half group");
   constexpr bool EV4 = IN == SNNQP_EV4;     // one byte per pixel: polarity 0 low nibble, 1 high
   // float32 frames as the reference hands them over (flax_qconv.py:101): eight bytes per pixel,
   // converted to the two count bytes and checked while they wait in registers (snnqp.h, x_flags)
@@ -300,7 +309,26 @@ conv3x3_u8c2_kernel(ConvMfmaArgs a) {
     bfg = bf;                       // (bit-packed frames within per-channel tables: no general path)
     if (HALF) {
       tab0 = tbase + 4 * (hg_row0 * 32 + hg_col);
-      bfh = taps(blockIdx.y * 128 + 64 + (n & 15), n >= 16 ? 8 : 0, true, 0);
+      if constexpr (Q16) {
+        // lane (c = lane & 15, kb = lane >> 4) holds bytes 16 kb ..+15 of channel 64 + c: byte j of group kb
+        // meets byte j of group kb of A -- k rows 0..7, 8..15 (kb 0) and 16..23 (kb 1) are the halo rows dy 0,
+        // 1, 2, every other byte is zero.  No twin lanes, no shifted taps.
+        const int chan = blockIdx.y * 128 + 64 + (lane & 15), kb = lane >> 4;
+        int v[4];
+#pragma unroll
+        for (int d = 0; d < 4; ++d) {
+          uint32_t pk = 0;
+#pragma unroll
+          for (int j = 0; j < 4; ++j) {
+            int row;
+            if (tap_row(16 * kb + 4 * d + j, row)) pk |= (uint32_t)(uint8_t)(a.w[(int64_t)row * a.Cout + chan] * 8) << (8 * j);
+          }
+          v[d] = (int)pk;
+        }
+        bfh = v4i{v[0], v[1], v[2], v[3]};
+      } else {
+        bfh = taps(blockIdx.y * 128 + 64 + (n & 15), n >= 16 ? 8 : 0, true, 0);
+      }
     }
   } else {
     int bias = 0;
@@ -391,6 +419,17 @@ conv3x3_u8c2_kernel(ConvMfmaArgs a) {
       const int np = n ^ (8 * wave);
       const int typ = ((np >> 2) & 1) | ((np >> 4) << 1), txp = (np & 3) | (((np >> 3) & 1) << 2);
       offA[1] = (int)lds_addr(lds) + cpy * HCOPY2 + 2 * txp + 2 * cpy + (2 * typ + 2 * h) * HROW2;
+      if constexpr (Q16) {
+        // row r = lane & 15 of A is pixel r of the quarter, block r >> 2 of its 2x2 pool blocks and place
+        // r & 3 inside it (EP_QUARTER16, conv_tile.h); lane group kb reads halo rows 2 (kb & 1) and, an
+        // immediate HROW2 further, 2 (kb & 1) + 1 below the pixel's: dy 0, 1 (kb 0) and dy 2 with the row
+        // under it (kb 1; LDS of this image or the next bytes of the allocation, met by zeros of B, as are
+        // all bytes of kb 2, 3)
+        const int rq = lane & 15, kb = lane >> 4;
+        const int py = 4 * g + 2 * (rq >> 3) + ((rq >> 1) & 1), px = 4 * q + 2 * ((rq >> 2) & 1) + (rq & 1);
+        const int cq = px & 1;
+        offA[1] = (int)lds_addr(lds) + cq * HCOPY2 + 2 * px + 2 * cq + (py + 2 * (kb & 1)) * HROW2;
+      }
       offB[1] = tab0;
       const int pix = POOL ? (2 * g + ((lane >> 2) & 1)) * 4 + 2 * q + (lane & 1)
                            : (4 * g + ((lane >> 2) & 3)) * 8 + 4 * q + (lane & 3);
@@ -627,7 +666,13 @@ conv3x3_u8c2_kernel(ConvMfmaArgs a) {
                   acc, u[0], a.dq, lc, a.nrn, lane, acc_off);
               if (store_lane) o[ob0] = word & cmask;
             }
-            if constexpr (HALF) {
+            if constexpr (Q16) {
+              const v2i_a4 lo = *(lds_cv2i_t *)(uintptr_t)(img + (uint32_t)offA[1]);
+              const v2i_a4 hi = *(lds_cv2i_t *)(uintptr_t)(img + (uint32_t)offA[1] + (uint32_t)HROW2);
+              const v4i acc = __builtin_amdgcn_mfma_i32_16x16x64_i8(v4i{lo.x, lo.y, hi.x, hi.y}, bfh, c4, 0, 0, 0);
+              const uint32_t word = quarter16_epilogue<NF, POOL, MODE, FMA, OFFS>(acc, u[1], a.dq, lc, a.nrn, acc_off);
+              if (quarter_lane) o[ob1] = word & qmask;
+            } else if constexpr (HALF) {
               const v2i_a4 lo = *(lds_cv2i_t *)(uintptr_t)(img + (uint32_t)offA[1]);
               const v2i_a4 hi = *(lds_cv2i_t *)(uintptr_t)(img + (uint32_t)offA[1] + (uint32_t)HROW2);
               const v16i acc = __builtin_amdgcn_mfma_i32_32x32x32_i8(v4i{lo.x, lo.y, hi.x, hi.y}, bfh, c0,
@@ -748,13 +793,13 @@ conv3x3_u8c2_kernel(ConvMfmaArgs a) {
 // host side: the plan of a launch and the launcher run_conv3x3_mfma (conv3x3_mfma.hip) hands over to
 // ---------------------------------------------------------------------------
 
-// What an event-layer launch is made of -- table mode, staging chunk, LDS bytes, the ONE and HALF
-// and SPREAD variants -- decided in one place for the launch and for the predicates
-// snnqp_conv_event_half_group / snnqp_conv_event_wave_spread.
+// What an event-layer launch is made of -- table mode, staging chunk, LDS bytes, the ONE, HALF,
+// SPREAD and Q16 variants -- decided in one place for the launch and for the predicates
+// snnqp_conv_event_half_group / snnqp_conv_event_wave_spread / snnqp_conv_event_quarter16.
 namespace {
 struct U8c2Plan {
   int32_t x_limit, lut_bound, lut_rows, tchunk;
-  bool lut, lutc, one, half, spread;
+  bool lut, lutc, one, half, spread, quarter16;
   size_t ldsb;
 };
 U8c2Plan u8c2_plan(int in_type, int32_t T, int32_t Cout, const snnqp_weight_t *w, int nf, bool has_state,
@@ -811,6 +856,9 @@ U8c2Plan u8c2_plan(int in_type, int32_t T, int32_t Cout, const snnqp_weight_t *w
   // with the half group, and 64 channels (template parameter SPREAD; snnqp_set_event_wave_spread)
   p.spread = event_wave_spread_enabled() && ev1 && p.one && p.lutc && nf == NF_MUL0 &&
              (p.half ? Cout == 96 : Cout == 64);
+  // ... and of those the one that runs quarters of the half group: each from a 16x16x64 product (template
+  // parameter Q16; snnqp_set_event_quarter16)
+  p.quarter16 = event_quarter16_enabled() && p.half && p.spread;
   return p;
 }
 }  // namespace
@@ -838,6 +886,11 @@ int conv3x3_event_half_group(int in_type, int32_t T, const snnqp_conv_geom_t *g,
 int conv3x3_event_wave_spread(int in_type, int32_t T, const snnqp_conv_geom_t *g, const snnqp_weight_t *w,
                               const snnqp_neuron_t *nrn, bool has_state, int pool, int x_max) {
   return event_plan_flag("conv_event_wave_spread", &U8c2Plan::spread, in_type, T, g, w, nrn, has_state, pool, x_max);
+}
+
+int conv3x3_event_quarter16(int in_type, int32_t T, const snnqp_conv_geom_t *g, const snnqp_weight_t *w,
+                            const snnqp_neuron_t *nrn, bool has_state, int pool, int x_max) {
+  return event_plan_flag("conv_event_quarter16", &U8c2Plan::quarter16, in_type, T, g, w, nrn, has_state, pool, x_max);
 }
 
 // The instance of a launch, one template parameter per step: table mode (launch_conv3x3_u8c2), neuron
@@ -869,10 +922,10 @@ static void launch_u8c2_nf(const ConvMfmaArgs &a, int nf, int in_type, bool pool
 }
 
 // The half-group and spread instances: bit-packed frames, ONE, per-channel tables, NF_MUL0 (u8c2_plan)
-template <bool HALF, bool SPREAD>
+template <bool HALF, bool SPREAD, bool Q16 = false>
 static void launch_u8c2_event(const ConvMfmaArgs &a, bool pool, unsigned gy, hipStream_t st, size_t lds) {
-  if (pool) launch_persistent(conv3x3_u8c2_kernel<NF_MUL0, true, LUT_CHANNEL, SNNQP_EV1, true, HALF, SPREAD>, a, gy, st, lds);
-  else launch_persistent(conv3x3_u8c2_kernel<NF_MUL0, false, LUT_CHANNEL, SNNQP_EV1, true, HALF, SPREAD>, a, gy, st, lds);
+  if (pool) launch_persistent(conv3x3_u8c2_kernel<NF_MUL0, true, LUT_CHANNEL, SNNQP_EV1, true, HALF, SPREAD, Q16>, a, gy, st, lds);
+  else launch_persistent(conv3x3_u8c2_kernel<NF_MUL0, false, LUT_CHANNEL, SNNQP_EV1, true, HALF, SPREAD, Q16>, a, gy, st, lds);
 }
 
 int launch_conv3x3_u8c2(ConvMfmaArgs a, int in_type, const snnqp_weight_t *w, int x_max, int32_t *x_flags,
@@ -898,7 +951,8 @@ int launch_conv3x3_u8c2(ConvMfmaArgs a, int in_type, const snnqp_weight_t *w, in
     a.x_flags = x_flags;
   }
   if (plan.lut) check_code_bound_once(stream_device(st), a.w, (int64_t)9 * a.Cin, a.Cout, w->abs_sum_max, st);
-  if (plan.half && plan.spread) launch_u8c2_event<true, true>(a, pl, gy, st, plan.ldsb);
+  if (plan.quarter16) launch_u8c2_event<true, true, true>(a, pl, gy, st, plan.ldsb);
+  else if (plan.half && plan.spread) launch_u8c2_event<true, true>(a, pl, gy, st, plan.ldsb);
   else if (plan.spread) launch_u8c2_event<false, true>(a, pl, gy, st, plan.ldsb);
   else if (plan.half) launch_u8c2_event<true, false>(a, pl, gy, st, plan.ldsb);
   else if (plan.lutc) launch_u8c2_nf<LUT_CHANNEL>(a, nf, in_type, pl, plan.one, gy, st, plan.ldsb);

@@ -477,6 +477,49 @@ __device__ __forceinline__ uint32_t tile_epilogue_parts(const v16i &acc, float (
   return myw;
 }
 
+// EP_QUARTER16: the quarter as the product of a 16x16x64 matrix instruction (the spread launch with
+// the quarter16 switch, conv3x3_u8c2.hip): lane = (channel c = lane & 15, lane group gq = lane >> 4),
+// register i = pixel 4 gq + i of the wave's 4x4 quarter, and the pixels are ordered so that a lane
+// group's four registers are ONE 2x2 pool block: block gq at rows 2 (gq >> 1) ..+1, columns 2 (gq & 1)
+// ..+1 of the quarter, register i at (i >> 1, i & 1) inside it.  The 64-bit mask of register i is then
+// four 16-channel fields, one pixel each, and the words land in the lanes EP_QUARTER puts them in:
+//   POOL : the OR of the four masks, field gq -> lane 4 (gq >> 1) + (gq & 1)
+//   !POOL: field gq of register i -> lane 4 r + x, (r, x) the pixel's row and column in the quarter
+constexpr int EP_QUARTER16 = 3;
+template <bool POOL>
+__device__ __forceinline__ uint32_t place_words_quarter16(const unsigned long long (&m)[4]) {
+  uint32_t myw = 0;
+  if (POOL) {
+    const unsigned long long o = (m[0] | m[1]) | (m[2] | m[3]);
+#pragma unroll
+    for (int gq = 0; gq < 4; ++gq)
+      myw = writelane_u32((uint32_t)(o >> (16 * gq)) & 0xFFFFu, 4 * (gq >> 1) + (gq & 1), myw);
+  } else {
+#pragma unroll
+    for (int i = 0; i < 4; ++i)
+#pragma unroll
+      for (int gq = 0; gq < 4; ++gq)
+        myw = writelane_u32((uint32_t)(m[i] >> (16 * gq)) & 0xFFFFu,
+                            4 * (2 * (gq >> 1) + (i >> 1)) + 2 * (gq & 1) + (i & 1), myw);
+  }
+  return myw;
+}
+
+// BatchNorm + neuron + spike word of the four registers of that product: four table reads, two pairs
+// (tile_epilogue_parts' sequence on a 4-register tuple; u[0..3] are the quarter's potentials).
+template <int NF, bool POOL, int LUTM, bool FMA, bool OFFS>
+__device__ __forceinline__ uint32_t quarter16_epilogue(const v4i &acc, float (&u)[16], const Dequant &dq,
+                                                       const LaneConsts &lc, const NeuronP &nrn, float off = 0.0f) {
+  v2f y[2];
+#pragma unroll
+  for (int j = 0; j < 2; ++j) y[j] = dequant_pair<LUTM, OFFS>(acc[2 * j], acc[2 * j + 1], dq, off);
+  unsigned long long m[4];
+#pragma unroll
+  for (int j = 0; j < 2; ++j)
+    neuron_pair<NF, LUTM == LUT_CHANNEL, FMA>(y[j], u[2 * j], u[2 * j + 1], lc, nrn, m[2 * j], m[2 * j + 1]);
+  return place_words_quarter16<POOL>(m);
+}
+
 // The neurons of a whole tile from its 8 dequantised pairs (tile_epilogue below; a function of its
 // own: folded into tile_epilogue_parts<EP_TILE, 8, 1> the bit-packed instance with carried potentials
 // allocates its registers differently)
@@ -648,5 +691,8 @@ bool conv_k16_enabled();
 bool event_half_group_enabled();
 // snnqp_set_event_wave_spread (api.hip): whether launch_conv3x3_u8c2 picks the spread instances
 bool event_wave_spread_enabled();
+// snnqp_set_event_quarter16 (api.hip): whether the 96 / 80 spread launch takes its quarter of the half
+// group from a 16x16x64 matrix instruction
+bool event_quarter16_enabled();
 
 }  // namespace snnqp

@@ -76,6 +76,9 @@ int conv3x3_event_half_group(int in_type, int32_t T, const snnqp_conv_geom_t *g,
 // snnqp_conv_event_wave_spread: the same
 int conv3x3_event_wave_spread(int in_type, int32_t T, const snnqp_conv_geom_t *g, const snnqp_weight_t *w,
                               const snnqp_neuron_t *nrn, bool has_state, int pool, int x_max);
+// snnqp_conv_event_quarter16: the same
+int conv3x3_event_quarter16(int in_type, int32_t T, const snnqp_conv_geom_t *g, const snnqp_weight_t *w,
+                            const snnqp_neuron_t *nrn, bool has_state, int pool, int x_max);
 int run_conv3x3_mfma(const BlockCall &c);
 
 // per-device state and helpers (runtime.hip): the status word kernels report broken invariants

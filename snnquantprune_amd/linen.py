@@ -211,6 +211,22 @@ def event_wave_spread() -> bool:
   return bool(_lib.lib().snnqp_set_event_wave_spread(-1))
 
 
+# The quarter of the half group in the 96-channel spread launch: each wave's 16 channels
+# x 16 pixels are one 16x16x64 matrix instruction with a four-register product, not four registers of
+# the half group's whole 32x32x32 product computed in every wave.  On by default.
+def set_event_quarter16(enabled: bool):
+  """True (default): the 16x16x64 form.  False: the 32x32x32 product in all four waves (the A side of
+  an A/B on one build; the results are the same).  A switch of the library: applies to the launches
+  after it."""
+  from . import _lib
+  _lib.lib().snnqp_set_event_quarter16(1 if enabled else 0)
+
+
+def event_quarter16() -> bool:
+  from . import _lib
+  return bool(_lib.lib().snnqp_set_event_quarter16(-1))
+
+
 # The connection alone over a bit-packed raster (DESIGN.md 4.3.2): the training forward of a conv
 # block (conv_train.conv_currents with mfma=True) and QuantConv called on its own hand ops.conv_forward the
 # MFMA-tiled codes, so a 3x3 / stride 1 / pad 1 connection with Cin <= 128 runs on the currents

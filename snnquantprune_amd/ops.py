@@ -1202,6 +1202,8 @@ def conv_lif_forward(x, geom: ConvGeom, weight: Weight, neuron: Neuron,
           ev1, T, geom, weight, neuron, state=u0 is not None or want_u, pool=pool, x_max=1 if ev1 == L.EV1 else x_max)
       PROFILE_NOTES[tag]["channels"]["wave_spread"] = conv_event_wave_spread(
           ev1, T, geom, weight, neuron, state=u0 is not None or want_u, pool=pool, x_max=1 if ev1 == L.EV1 else x_max)
+      PROFILE_NOTES[tag]["channels"]["quarter16"] = conv_event_quarter16(
+          ev1, T, geom, weight, neuron, state=u0 is not None or want_u, pool=pool, x_max=1 if ev1 == L.EV1 else x_max)
   # (the bit-packed variant writes bit-packed spikes only: float32 spikes take the frames as they are)
   speculate = (binary_first and packed_out and not isinstance(x, (PackedFrames, PackedSpikes))
                and in_type in (L.U8, L.F32) and geom.Cin == 2 and weight.is_int and impl != L.IMPL_GENERIC
@@ -1468,6 +1470,19 @@ def conv_event_wave_spread(in_type: int, T: int, geom: ConvGeom, w: Weight, nrn:
   gs, ws, ns = geom.struct(), w.struct(), nrn.struct()
   rc = L.lib().snnqp_conv_event_wave_spread(int(in_type), int(T), ctypes.byref(gs), ctypes.byref(ws),
                                             ctypes.byref(ns), 1 if state else 0, int(pool), int(x_max))
+  if rc < 0:
+    L.check(rc)
+  return rc == 1
+
+
+def conv_event_quarter16(in_type: int, T: int, geom: ConvGeom, w: Weight, nrn: Neuron, state: bool = False,
+                         pool: int = 1, x_max: int = 0) -> bool:
+  """Whether snnqp_conv_lif_forward runs this event-layer launch with the half group's quarters on the
+  16x16x64 matrix instruction (snnqp_conv_event_quarter16): the 96-channel spread launch, and
+  nn.set_event_quarter16 is on."""
+  gs, ws, ns = geom.struct(), w.struct(), nrn.struct()
+  rc = L.lib().snnqp_conv_event_quarter16(int(in_type), int(T), ctypes.byref(gs), ctypes.byref(ws),
+                                          ctypes.byref(ns), 1 if state else 0, int(pool), int(x_max))
   if rc < 0:
     L.check(rc)
   return rc == 1

@@ -16,6 +16,6 @@ for m in re.finditer(r"\.amdhsa_kernel (\S+)(.*?)\.end_amdhsa_kernel", s, re.S):
   g = lambda k: (re.search(r"\.amdhsa_" + k + r"\s+(\S+)", body) or [None, None])[1]
   dn = subprocess.run(["c++filt", name], capture_output=True, text=True).stdout.strip()
   dn = re.sub(r"\(.*", "", dn).replace("snnqp::", "").replace("void ", "")
-  print("%-60s vgpr+agpr %4s (acc at %4s) sgpr %3s scratch %5s lds %6s" % (
-      dn[:60], g("next_free_vgpr"), g("accum_offset"), g("next_free_sgpr"),
+  print("%-68s vgpr+agpr %4s (acc at %4s) sgpr %3s scratch %5s lds %6s" % (
+      dn[:68], g("next_free_vgpr"), g("accum_offset"), g("next_free_sgpr"),
       g("private_segment_fixed_size"), g("group_segment_fixed_size")))

@@ -8,9 +8,12 @@ the event layer computes the whole last channel group and masks its silent half,
 that group in a 16-channel half); the C5 and 8-bit legs run identical instances both ways, so their
 ratios are the session's noise.  --ab spread: the same A/B of nn.set_event_wave_spread (DESIGN.md 4.2:
 off = wave w of the event layer computes channel group w, on = every wave one (group, tile) unit and a
-quarter of the half group), the half group on in both.
+quarter of the half group), the half group on in both.  --ab quarter: the same A/B of
+nn.set_event_quarter16 (off = a spread wave takes its quarter out of the half group's whole
+32x32x32 product, on = from one 16x16x64 product), half group and spread on in both; here the C5 leg
+(64 channels: no quarter) and the 8-bit leg run identical instances both ways.
 
-  python tools/kpack_ab.py [--ab kpack|k16|half|spread] [--B 1024] [--T 20] [--reps 5] [--out FILE.json]
+  python tools/kpack_ab.py [--ab kpack|k16|half|spread|quarter] [--B 1024] [--T 20] [--reps 5] [--out FILE.json]
 """
 import argparse
 import json
@@ -88,11 +91,11 @@ def main():
   ap.add_argument("--T", type=int, default=20)
   ap.add_argument("--reps", type=int, default=5)
   ap.add_argument("--out", default=None)
-  ap.add_argument("--ab", choices=["kpack", "k16", "half", "spread"], default="kpack")
+  ap.add_argument("--ab", choices=["kpack", "k16", "half", "spread", "quarter"], default="kpack")
   args = ap.parse_args()
   dev = torch.device("cuda:0")
   switch = {"k16": nn.set_conv_k16, "half": nn.set_event_half_group,
-            "spread": nn.set_event_wave_spread}.get(args.ab, nn.set_conv_kpack)
+            "spread": nn.set_event_wave_spread, "quarter": nn.set_event_quarter16}.get(args.ab, nn.set_conv_kpack)
   res = {"ab": args.ab, "B": args.B, "T": args.T, "reps": args.reps, "device": torch.cuda.get_device_name(0), "legs": {}}
   for name, bits, prune, lb, inp in LEGS:
     r = leg(name, bits, prune, lb, inp, args.B, args.T, args.reps, dev, switch)
@@ -104,6 +107,7 @@ def main():
         r["logits_bit_equal"]), flush=True)
     torch.cuda.empty_cache()
   res["fallback_counts"] = ops.fallback_counts()
+  res["workqueue_stats"] = ops.workqueue_stats()
   res["device_status"] = ops.device_status()
   if args.out:
     with open(args.out, "w") as f:
