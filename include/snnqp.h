@@ -250,7 +250,8 @@ typedef struct {
  * snnqp_conv_weight_grad_f64_workspace_bytes; the batched event front end snnqp_events_bin and its augmenting
  * form snnqp_events_bin_aug with snnqp_event_aug_t; the host-side
  * query snnqp_conv_float_form; the host-side plan queries snnqp_conv_gated_plan,
- * snnqp_dense_gated_plan, snnqp_dense_wide_plan, snnqp_dense_fp6_plan; streaming inference --
+ * snnqp_dense_gated_plan, snnqp_dense_wide_plan, snnqp_dense_fp6_plan, snnqp_dense_mfma_plan;
+ * streaming inference --
  * snnqp_dense_head_forward_state, snnqp_vote_accumulate, snnqp_vote_counts; the rate encoder
  * snnqp_rate_encode with SNNQP_ENCODE_*; training of the PLIF and LIF neurons --
  * snnqp_neuron_forward_save, snnqp_neuron_backward, snnqp_neuron_backward_splits,
@@ -751,6 +752,19 @@ int snnqp_dense_lif_forward_ws(const void *x, int in_type, int64_t x_stride_t,
  * SNNQP_EINVAL for sizes below 1 or a null pointer; SNNQP_EUNSUPPORTED for T > 160, as the launch. */
 int snnqp_dense_fp6_plan(int32_t T, int32_t B, int32_t K, int32_t N, const void *ws, int64_t ws_bytes,
                          int32_t *rt, int32_t *ks, int32_t *gx, int32_t *gcz);
+/* The launch snnqp_dense_lif_forward makes on the int8 128-column kernel (SNNQP_IMPL_MFMA, at most
+ * 128 features or more than 64 timesteps) for rows of `in_type` (SNNQP_BITS or SNNQP_U8), T steps,
+ * B samples and N features.  Launches nothing, makes no GPU call.  The answer is the launch's own
+ * decision: the largest row tile that still gives 200 workgroups, else the smallest that holds a
+ * sample, then the measurement knob SNNQP_DENSE_MFMA_RT=1..3 (read on every call; a value with
+ * 32 rt < T, or above 2 for uint8 rows, is ignored).
+ *   rt  1..3 row tiles of 32 rows per workgroup (uint8 rows: 1..2)
+ *   sb  floor(32 rt / T) samples per workgroup
+ *   gx  ceil(B / sb) workgroups along the batch      gy  ceil(N / 128) along the features
+ * SNNQP_EINVAL for sizes below 1, another in_type or a null pointer; SNNQP_EUNSUPPORTED for T > 96
+ * (uint8 rows: T > 64), as the launch. */
+int snnqp_dense_mfma_plan(int in_type, int32_t T, int32_t B, int32_t N, int32_t *rt, int32_t *sb,
+                          int32_t *gx, int32_t *gy);
 /* the dense block on the direct-form kernel, executed only if *pred != 0 (snnqp_conv_lif_forward_if) */
 int snnqp_dense_lif_forward_if(const int32_t *pred, const void *x, int in_type, int64_t x_stride_t,
                                int64_t x_stride_b, int32_t T, int32_t B, int32_t K, int32_t N,

@@ -157,6 +157,8 @@ _PROTOTYPES = {
         c_void_p, c_void_p, c_int, c_int, c_void_p, c_void_p, c_int64, c_void_p]),
     "snnqp_dense_fp6_plan": (c_int, [c_int32, c_int32, c_int32, c_int32, c_void_p, c_int64, POINTER(c_int32),
                                      POINTER(c_int32), POINTER(c_int32), POINTER(c_int32)]),
+    "snnqp_dense_mfma_plan": (c_int, [c_int, c_int32, c_int32, c_int32, POINTER(c_int32), POINTER(c_int32),
+                                      POINTER(c_int32), POINTER(c_int32)]),
     "snnqp_dense_head_workspace_bytes": (c_int64, [c_int32, c_int32, c_int32]),
     "snnqp_dense_head_forward": (c_int, [
         c_void_p, c_int, c_int64, c_int64, c_int32, c_int32, c_int32, c_int32, POINTER(WeightT),

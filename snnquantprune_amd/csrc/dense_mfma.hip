@@ -25,6 +25,7 @@
 //  * after the K loop the int32 tile goes through LDS once so that each thread
 //    gets the T currents of one (sample, feature) pair in order, runs the
 //    neuron with u in a register and ballots the spikes into 32-bit words.
+#include <cstdlib>
 #include <type_traits>
 
 #include "dense_tile.h"
@@ -314,6 +315,33 @@ static void launch_dense(const DenseMfmaArgs &a, unsigned gx, unsigned gy, hipSt
   hipLaunchKernelGGL((dense_mfma_kernel<RT, IN>), dim3(gx, gy), dim3(256 * KGROUPS), 0, st, a);
 }
 
+// The launch of T x B rows, N wide: what run_dense_mfma launches and what snnqp_dense_mfma_plan
+// reports.  No GPU call.  The largest row tile that still gives the chip enough workgroups, else the
+// smallest one that holds a whole sample (most workgroups); uint8 rows: at most 64 rows (their
+// staging ring takes the registers of the third row tile).  SNNQP_DENSE_MFMA_RT=1..3 forces the
+// row tiles where they hold a sample: a measurement knob, read on every call.
+struct DenseMfmaPlan { int rt, sb; unsigned gx, gy; };
+static DenseMfmaPlan plan_dense_mfma(bool u8, int32_t T, int32_t B, int32_t N) {
+  DenseMfmaPlan p = {};
+  p.gy = (unsigned)((N + 127) / 128);
+  static const int rts[3] = {3, 2, 1};
+  for (int i = u8 ? 1 : 0; i < 3; ++i) {
+    const int sb = rts[i] * 32 / T;
+    if (sb < 1) continue;
+    p.rt = rts[i];
+    if ((int64_t)((B + sb - 1) / sb) * p.gy >= 200) break;
+  }
+  if (const char *e = std::getenv("SNNQP_DENSE_MFMA_RT")) {
+    const int forced = std::atoi(e);
+    if (forced >= 1 && forced <= (u8 ? 2 : 3) && 32 * forced >= T) p.rt = forced;
+  }
+  if (p.rt > 0) {
+    p.sb = p.rt * 32 / T;
+    p.gx = (unsigned)((B + p.sb - 1) / p.sb);
+  }
+  return p;
+}
+
 int run_dense_mfma(const BlockCall &c) {
   if (int rc = block_entry("dense mfma", c, true)) return rc < 0 ? rc : SNNQP_OK;
   const int32_t T = c.T, B = c.B, N = c.N;
@@ -325,21 +353,11 @@ int run_dense_mfma(const BlockCall &c) {
   fill_block_args(a, c);
   a.K = c.K; a.N = N; a.KS = (c.K + 31) / 32;
   a.wt = c.wt; a.col_sum = c.w->col_sum;
-  const unsigned gy = (unsigned)((N + 127) / 128);
-  // largest row tile that still gives the chip enough workgroups, else the
-  // smallest one that holds a whole sample (most workgroups); uint8 rows: at most 64 rows
-  // (their staging ring takes the registers of the third row tile)
-  static const int rts[3] = {3, 2, 1};
-  int rt = 0;
-  for (int i = u8 ? 1 : 0; i < 3; ++i) {
-    const int sb = rts[i] * 32 / T;
-    if (sb < 1) continue;
-    rt = rts[i];
-    if ((int64_t)((B + sb - 1) / sb) * gy >= 200) break;
-  }
-  SNNQP_REQUIRE(rt > 0, SNNQP_EUNSUPPORTED, "dense mfma: T too large");
-  a.SB = rt * 32 / T;
-  const unsigned gx = (unsigned)((B + a.SB - 1) / a.SB);
+  const DenseMfmaPlan p = plan_dense_mfma(u8, T, B, N);
+  SNNQP_REQUIRE(p.rt > 0, SNNQP_EUNSUPPORTED, "dense mfma: T too large");
+  const int rt = p.rt;
+  const unsigned gx = p.gx, gy = p.gy;
+  a.SB = p.sb;
   if (u8) {
     if (rt == 2) launch_dense<2, SNNQP_U8>(a, gx, gy, c.st);
     else launch_dense<1, SNNQP_U8>(a, gx, gy, c.st);
@@ -355,3 +373,18 @@ int run_dense_mfma(const BlockCall &c) {
 }
 
 }  // namespace snnqp
+
+extern "C" int snnqp_dense_mfma_plan(int in_type, int32_t T, int32_t B, int32_t N, int32_t *rt, int32_t *sb,
+                                     int32_t *gx, int32_t *gy) {
+  using namespace snnqp;
+  SNNQP_REQUIRE(rt && sb && gx && gy, SNNQP_EINVAL, "dense_mfma_plan: null argument");
+  SNNQP_REQUIRE(in_type == SNNQP_BITS || in_type == SNNQP_U8, SNNQP_EINVAL,
+                "dense_mfma_plan: input must be bit-packed or uint8");
+  SNNQP_REQUIRE(T >= 1 && B >= 1 && N >= 1, SNNQP_EINVAL, "dense_mfma_plan: bad sizes");
+  const bool u8 = in_type == SNNQP_U8;
+  SNNQP_REQUIRE(T <= (u8 ? 64 : 96), SNNQP_EUNSUPPORTED,
+                "dense_mfma_plan: more than 96 (uint8 input: 64) timesteps (one sample must fit a row tile)");
+  const DenseMfmaPlan p = plan_dense_mfma(u8, T, B, N);
+  *rt = p.rt; *sb = p.sb; *gx = (int32_t)p.gx; *gy = (int32_t)p.gy;
+  return SNNQP_OK;
+}

@@ -797,12 +797,10 @@ static void launch_wide_rt(int rt, const DenseWideArgs &a, unsigned gx, unsigned
   }
 }
 
+// (measurement knobs, read on every call: a process can force and query one plan after another)
 static int wide_row_tiles_override() {
-  static const int v = [] {
-    const char *e = std::getenv("SNNQP_DENSE_WIDE_RT");
-    return e ? std::atoi(e) : 0;
-  }();
-  return v;
+  const char *e = std::getenv("SNNQP_DENSE_WIDE_RT");
+  return e ? std::atoi(e) : 0;
 }
 
 // The fused head with its hidden columns split over two workgroups per tile: when the batch gives
@@ -825,7 +823,7 @@ static WidePlan plan_wide(const DenseWideArgs &a, bool fuse, bool may_split) {
   }
   if (p.rt > 0) {
     p.gx = (unsigned)((a.B + 2 * p.sph - 1) / (2 * p.sph));
-    static const bool no_split = std::getenv("SNNQP_DENSE_HEAD_NOSPLIT") != nullptr;
+    const bool no_split = std::getenv("SNNQP_DENSE_HEAD_NOSPLIT") != nullptr;
     if (fuse && may_split && !no_split && a.N > 256 && p.gx * 2u <= 256u && p.gx <= HANDOFF_TICKET_BYTES / 4) {
       p.csplit = 1;
       p.ct = 1;

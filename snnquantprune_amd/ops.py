@@ -1023,6 +1023,15 @@ def dense_fp6_plan(T: int, B: int, K: int, N: int, ws: Optional[int] = None,
   return rt.value, ks.value, gx.value, gcz.value
 
 
+def dense_mfma_plan(in_type: int, T: int, B: int, N: int) -> Tuple[int, int, int, int]:
+  """(rt, sb, gx, gy) of the int8 128-column dense launch on rows of `in_type` (L.BITS or L.U8):
+  snnqp_dense_mfma_plan, the SNNQP_DENSE_MFMA_RT knob included; no device work."""
+  rt, sb, gx, gy = ctypes.c_int32(), ctypes.c_int32(), ctypes.c_int32(), ctypes.c_int32()
+  L.check(L.lib().snnqp_dense_mfma_plan(int(in_type), int(T), int(B), int(N), ctypes.byref(rt), ctypes.byref(sb),
+                                        ctypes.byref(gx), ctypes.byref(gy)))
+  return rt.value, sb.value, gx.value, gy.value
+
+
 # ---------------------------------------------------------------------------
 # per-launch timing with HIP events on the launch stream (bench.py roofline)
 # ---------------------------------------------------------------------------

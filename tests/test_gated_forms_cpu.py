@@ -266,8 +266,9 @@ def test_head_shapes_reach_all_seven_fused_forms():
   test_dense_head_as_one_launch / test_dense_head_on_float32_rows.  RT = 1 is chosen by no shape
   at all: below four MFMAs per k-step a choice costs (rounds of workgroups) x 4 whatever RT is, RT =
   2 never needs more rounds than RT = 1, and cost ties go to the larger tile -- only the
-  SNNQP_DENSE_WIDE_RT override gets there (not exercised here: the variable is read once per
-  process)."""
+  SNNQP_DENSE_WIDE_RT override gets there (the variable is read on every call:
+  tests/test_dense_int8_plans_cpu.py queries the forced forms, tests/test_dense_int8_plans_gpu.py
+  launches them)."""
   _, ops = _ops()
   reached = {}
   for (T, B, K, N1, N2), form in gc.HEAD_SHAPES.items():
