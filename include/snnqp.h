@@ -255,7 +255,9 @@ typedef struct {
  * snnqp_dense_head_forward_state, snnqp_vote_accumulate, snnqp_vote_counts; the rate encoder
  * snnqp_rate_encode with SNNQP_ENCODE_*; training of the PLIF and LIF neurons --
  * snnqp_neuron_forward_save, snnqp_neuron_backward, snnqp_neuron_backward_splits,
- * snnqp_neuron_backward_workspace_bytes: new entry points, nothing else moves).
+ * snnqp_neuron_backward_workspace_bytes; training over windows of a recording --
+ * snnqp_lif_forward_save_state, snnqp_lif_backward_state, snnqp_neuron_forward_save_state,
+ * snnqp_neuron_backward_state: new entry points, nothing else moves).
  * A binding compares snnqp_version()
  * with the SNNQP_VERSION it was written against and refuses a library of another version (_lib.py does). */
 #define SNNQP_VERSION 507
@@ -1045,6 +1047,24 @@ int snnqp_lif_forward_save(const float *x, int32_t T, int64_t R, int32_t C,
 int snnqp_lif_backward(const float *h, const float *gs, const float *glogits, int32_t group,
                        int32_t T, int64_t R, int32_t C, const snnqp_neuron_t *nrn,
                        int surrogate, float *gI, snnqp_stream_t stream);
+/* The two scans over one window of a recording (truncated BPTT): the arithmetic
+ * of the two entries above, step for step, from and to a carried membrane.
+ *   u0     float32 [R][C], nullable (zeros): the membrane the window starts from
+ *   u_out  float32 [R][C], nullable: receives u_T = s_{T-1} ? v_reset : h_{T-1}; may be u0's buffer
+ *          (one lane owns one element).  T == 0 writes u_out = u0 and nothing else.
+ *   gu_T   float32 [R][C], nullable (zeros): the gradient arriving at u_T; it enters step T-1 as
+ *          gu_t (1 - s_t) does for every other step (no gradient through the reset condition)
+ *   gu0    float32 [R][C], nullable: receives the recurrence's last gu, gh_0 (1 - 1/tau) = dL/du0;
+ *          T == 0 writes gu0 = gu_T
+ * With glogits, T in glogits / (group T) is the window's own length: a window's logits are the
+ * vote over that window. */
+int snnqp_lif_forward_save_state(const float *x, int32_t T, int64_t R, int32_t C,
+                                 const snnqp_neuron_t *nrn, const float *u0, float *u_out,
+                                 float *h_out, float *s_out, snnqp_stream_t stream);
+int snnqp_lif_backward_state(const float *h, const float *gs, const float *glogits, int32_t group,
+                             int32_t T, int64_t R, int32_t C, const snnqp_neuron_t *nrn,
+                             int surrogate, const float *gu_T, float *gI, float *gu0,
+                             snnqp_stream_t stream);
 /* gw [K][N] = sum_m x[m][k] gI[m][n] over x [M][K], gI [M][N], m ascending (exact f32 MFMA,
  * one fixed order: bitwise reproducible). */
 int snnqp_dense_weight_grad(const float *x, const float *gI, int64_t M, int32_t K, int32_t N,
@@ -1087,6 +1107,20 @@ int snnqp_neuron_backward(const float *h, const float *x, const float *gs, const
                           const snnqp_neuron_t *nrn, int surrogate, int32_t splits, float *gI,
                           double *gparam, void *workspace, int64_t workspace_bytes,
                           snnqp_stream_t stream);
+/* The PLIF / LIF scans over one window of a recording: u0, u_out, gu_T and gu0 as in
+ * snnqp_lif_forward_save_state / snnqp_lif_backward_state (gu0 = gh_0 fl(1 - m) for PLIF,
+ * gh_0 decay[c] for LIF).  The backward reads u0 (nullable: zeros) as u_{-1} in the t = 0 term of
+ * both sums: d_0 = fl(x_0 - fl(u0 - v_reset)) for PLIF, gh_0 u0 for LIF.  The range split, the
+ * float64 partials, the reduction order and the workspace are snnqp_neuron_backward's.  T == 0 or
+ * R == 0 writes zero sums, gu0 = gu_T, and launches no kernel. */
+int snnqp_neuron_forward_save_state(const float *x, int32_t T, int64_t R, int32_t C,
+                                    const snnqp_neuron_t *nrn, const float *u0, float *u_out,
+                                    float *h_out, float *s_out, snnqp_stream_t stream);
+int snnqp_neuron_backward_state(const float *h, const float *x, const float *u0, const float *gs,
+                                const float *glogits, int32_t group, int32_t T, int64_t R,
+                                int32_t C, const snnqp_neuron_t *nrn, int surrogate, int32_t splits,
+                                const float *gu_T, float *gI, float *gu0, double *gparam,
+                                void *workspace, int64_t workspace_bytes, snnqp_stream_t stream);
 /* Host only.  The default `splits`: min(max(R, 1), ceil(LANES / C)) -- a function of the shapes
  * alone (the device is not asked); LANES is a constant of the build, DESIGN.md 17.  A negative
  * SNNQP_E* on a bad shape. */

@@ -216,6 +216,17 @@ _PROTOTYPES = {
     "snnqp_neuron_backward": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_int32, c_int32,
                                       c_int64, c_int32, POINTER(NeuronT), c_int, c_int32, c_void_p,
                                       c_void_p, c_void_p, c_int64, c_void_p]),
+    "snnqp_lif_forward_save_state": (c_int, [c_void_p, c_int32, c_int64, c_int32, POINTER(NeuronT),
+                                             c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]),
+    "snnqp_lif_backward_state": (c_int, [c_void_p, c_void_p, c_void_p, c_int32, c_int32, c_int64,
+                                         c_int32, POINTER(NeuronT), c_int, c_void_p, c_void_p,
+                                         c_void_p, c_void_p]),
+    "snnqp_neuron_forward_save_state": (c_int, [c_void_p, c_int32, c_int64, c_int32, POINTER(NeuronT),
+                                                c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]),
+    "snnqp_neuron_backward_state": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int32,
+                                            c_int32, c_int64, c_int32, POINTER(NeuronT), c_int, c_int32,
+                                            c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int64,
+                                            c_void_p]),
     "snnqp_neuron_backward_splits": (c_int, [c_int32, c_int64, c_int32]),
     "snnqp_neuron_backward_workspace_bytes": (c_int64, [c_int32, c_int64, c_int32, c_int32, c_int]),
     "snnqp_dense_weight_grad": (c_int, [c_void_p, c_void_p, c_int64, c_int32, c_int32, c_void_p,

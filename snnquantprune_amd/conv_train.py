@@ -133,19 +133,38 @@ def neuron_param_grad(gparam: torch.Tensor, tau: torch.Tensor) -> torch.Tensor:
   return (gparam.reshape(tau.shape) * sg * (1.0 - sg)).to(tau.dtype)
 
 
-def scan_forward(cur, nrn, tau):
+def scan_forward(cur, nrn, tau, u0=None):
   """(h, s) of a training block's scan, conv or dense: the multi_step_LIF kernel, or with a `tau`
-  leaf (dense_train.neuron_train_form) the PLIF / LIF one."""
-  return ops.lif_forward_save(cur, nrn) if tau is None else ops.neuron_forward_save(cur, nrn)
+  leaf (dense_train.neuron_train_form) the PLIF / LIF one.  u0 (a window of a recording, DESIGN.md
+  18): the membrane the scan starts from, shaped like one step -> (h, s, u_T)."""
+  scan = ops.lif_forward_save if tau is None else ops.neuron_forward_save
+  return scan(cur, nrn) if u0 is None else scan(cur, nrn, u0=u0, return_state=True)
 
 
-def scan_backward(h, cur, nrn, surrogate, tau, **upstream):
+def scan_backward(h, cur, nrn, surrogate, tau, state=None, **upstream):
   """(gI, gtau) of that scan; gtau None without a `tau` leaf.  cur: the currents the scan consumed
-  (read for PLIF only).  upstream: gs=, or glogits= and group=."""
+  (read for PLIF only).  upstream: gs=, or glogits= and group=.  state (u0, gu_T, want_gu0) of a
+  window's scan: the block's own copy of the membrane it started from (read for PLIF and LIF only,
+  else None), the gradient arriving at u_T or None -> (gI, gtau, gu0), gu0 None unless wanted."""
+  if state is None:
+    if tau is None:
+      return ops.lif_backward(h, nrn, surrogate, **upstream), None
+    gI, gparam = ops.neuron_backward(h, cur, nrn, surrogate, **upstream)
+    return gI, neuron_param_grad(gparam, tau)
+  u0, gu_T, want = state
   if tau is None:
-    return ops.lif_backward(h, nrn, surrogate, **upstream), None
-  gI, gparam = ops.neuron_backward(h, cur, nrn, surrogate, **upstream)
-  return gI, neuron_param_grad(gparam, tau)
+    out = ops.lif_backward(h, nrn, surrogate, gu_T=gu_T, return_gu0=True, **upstream)
+    return out[0], None, (out[1] if want else None)
+  gI, gparam, gu0 = ops.neuron_backward(h, cur, nrn, surrogate, u0=u0, gu_T=gu_T, return_gu0=True,
+                                        **upstream)
+  return gI, neuron_param_grad(gparam, tau), (gu0 if want else None)
+
+
+def saved_membrane(u0, tau):
+  """What a window's block keeps of u0 for its backward: its own copy where the backward reads it
+  (PLIF, LIF: u_{-1} of the parameter sums) -- the caller overwrites the state's buffer with u_T
+  before the backward runs --, nothing for multi_step_LIF."""
+  return None if u0 is None or tau is None else u0.detach().clone()
 
 
 class ConvBlock(torch.autograd.Function):
@@ -163,15 +182,19 @@ class ConvBlock(torch.autograd.Function):
 
   tau: the neuron's parameter leaf when it is learnt (dense_train.neuron_train_form: PLIF or LIF)
   -- a further input that receives its gradient.  PLIF's backward reads the scan's input again:
-  it is recomputed from the saved currents and statistics (scan_input), the forward's bits."""
+  it is recomputed from the saved currents and statistics (scan_input), the forward's bits.
+
+  u0 [B, OH, OW, C]: the membranes the scan starts from, a window of a recording --
+  a further input that receives dL/du0, and a sixth output u_T [B, OH, OW, C], differentiable: the
+  gradient arriving at it enters the backward scan.  The block never writes into u0."""
 
   @classmethod
   def apply(cls, x, wq, scale, bias, pk, geom, nrn, surrogate, eps, first, pool=2,
-            real_input=False, wgrad_f64=False, tau=None):
+            real_input=False, wgrad_f64=False, tau=None, u0=None):
     if pool not in (1, 2):
       raise ValueError("ConvBlock: pool must be 1 or 2, got %r" % (pool,))
     return super().apply(x, wq, scale, bias, pk, geom, nrn, surrogate, eps, first, pool,
-                         real_input, wgrad_f64, tau)
+                         real_input, wgrad_f64, tau, u0)
 
   @staticmethod
   def scan_input(cur, mean, var, scale, bias, eps):
@@ -181,7 +204,7 @@ class ConvBlock(torch.autograd.Function):
 
   @staticmethod
   def forward(ctx, x, wq, scale, bias, pk, geom, nrn, surrogate, eps, first, pool, real_input,
-              wgrad_f64, tau):
+              wgrad_f64, tau, u0):
     T, B = x.shape[0], x.shape[1]
     C = geom.Cout
     if first or real_input or pk.int_weight() is None:
@@ -193,21 +216,29 @@ class ConvBlock(torch.autograd.Function):
     cur = cur.reshape(T, B * OH * OW, C)
     mean, var = batch_stats(cur)
     y = ConvBlock.scan_input(cur, mean, var, scale, bias, eps)
-    h, s = scan_forward(y, nrn, tau)
+    u_T = None
+    if u0 is None:
+      h, s = scan_forward(y, nrn, tau)
+    else:
+      if tuple(u0.shape) != (B, OH, OW, C):
+        raise ValueError("ConvBlock: u0 %s, the block's membranes are %s" % (tuple(u0.shape), (B, OH, OW, C)))
+      h, s, u_T = scan_forward(y, nrn, tau, u0.detach().reshape(B * OH * OW, C))
+      u_T = u_T.reshape(B, OH, OW, C)
     del y
     h = h.reshape(T, B, OH, OW, C)
     s = s.reshape(T, B, OH, OW, C)
     pooled = ops.maxpool2x2(s) if pool == 2 else s.clone()
     plif = tau is not None and nrn.kind == _L.NEURON_PARAMETRIC_LEAKY_IF
-    ctx.save_for_backward(x, wq, scale, cur, mean, var, h, tau, bias.detach() if plif else None)
+    ctx.save_for_backward(x, wq, scale, cur, mean, var, h, tau, bias.detach() if plif else None,
+                          saved_membrane(u0, tau))
     ctx.geom, ctx.nrn, ctx.surrogate, ctx.eps, ctx.first = geom, nrn, surrogate, eps, first
-    ctx.pool, ctx.wgrad_f64 = pool, wgrad_f64
+    ctx.pool, ctx.wgrad_f64, ctx.window = pool, wgrad_f64, u0 is not None
     ctx.mark_non_differentiable(h, s, mean, var)
-    return pooled, h, s, mean, var
+    return (pooled, h, s, mean, var) if u0 is None else (pooled, h, s, mean, var, u_T)
 
   @staticmethod
-  def backward(ctx, gp, _gh, _gs, _gmean, _gvar):
-    x, wq, scale, cur, mean, var, h, tau, bias = ctx.saved_tensors
+  def backward(ctx, gp, _gh, _gs, _gmean, _gvar, gu_T=None):
+    x, wq, scale, cur, mean, var, h, tau, bias, u0 = ctx.saved_tensors
     geom, nrn = ctx.geom, ctx.nrn
     T, B, OH, OW, C = h.shape
     if ctx.pool == 2:
@@ -217,8 +248,15 @@ class ConvBlock(torch.autograd.Function):
     else:
       gs = gp.contiguous()
     y = None if bias is None else ConvBlock.scan_input(cur, mean, var, scale.detach(), bias, ctx.eps)
-    gy, gtau = scan_backward(h.reshape(T, B * OH * OW, C), y, nrn, ctx.surrogate, tau,
-                             gs=gs.reshape(T, B * OH * OW, C))
+    gu0 = None
+    if ctx.window:
+      gy, gtau, gu0 = scan_backward(h.reshape(T, B * OH * OW, C), y, nrn, ctx.surrogate, tau,
+                                    state=(u0, gu_T, ctx.needs_input_grad[14]),
+                                    gs=gs.reshape(T, B * OH * OW, C))
+      gu0 = None if gu0 is None else gu0.reshape(B, OH, OW, C)
+    else:
+      gy, gtau = scan_backward(h.reshape(T, B * OH * OW, C), y, nrn, ctx.surrogate, tau,
+                               gs=gs.reshape(T, B * OH * OW, C))
     del gs, y
     gcur, gscale, gbias = bn_backward(gy, cur, mean, var, scale, ctx.eps)
     del gy
@@ -228,4 +266,4 @@ class ConvBlock(torch.autograd.Function):
     gx = None
     if not ctx.first and ctx.needs_input_grad[0]:
       gx = ops.conv_input_grad(gcur, wq.detach(), geom).reshape(x.shape)
-    return gx, gw, gscale, gbias, None, None, None, None, None, None, None, None, None, gtau
+    return gx, gw, gscale, gbias, None, None, None, None, None, None, None, None, None, gtau, gu0

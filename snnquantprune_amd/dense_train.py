@@ -25,7 +25,8 @@ import torch
 from . import _lib as L
 from . import ops
 from . import packing
-from .conv_train import conv_currents, neuron_param_grad, scan_backward, scan_forward  # noqa: F401
+from .conv_train import (conv_currents, neuron_param_grad, saved_membrane, scan_backward,  # noqa: F401
+                         scan_forward)
 
 SURROGATES = {
     "fast_sigmoid": L.SURR_FAST_SIGMOID,
@@ -178,48 +179,66 @@ class DenseBlock(torch.autograd.Function):
 
   tau: the neuron's parameter leaf when it is learnt (neuron_train_form: PLIF or LIF) -- a further
   input that receives its gradient.  PLIF's backward reads the scan's currents again, so the block
-  keeps them ([T, B, N] float32 more than a multi_step_LIF or LIF block saves)."""
+  keeps them ([T, B, N] float32 more than a multi_step_LIF or LIF block saves).
+
+  u0 [B, N]: the membranes the scan starts from, a window of a recording -- a
+  further input that receives dL/du0, and a fourth output u_T [B, N], differentiable: the gradient
+  arriving at it enters the backward scan.  The block never writes into u0.  With the vote, the
+  logits and their gradient are the window's own (T is the window's length)."""
 
   @classmethod
-  def apply(cls, x, wq, m, pk, nrn, surrogate, group, first=False, real_input=False, tau=None):
-    return super().apply(x, wq, m, pk, nrn, surrogate, group, first, real_input, tau)
+  def apply(cls, x, wq, m, pk, nrn, surrogate, group, first=False, real_input=False, tau=None,
+            u0=None):
+    return super().apply(x, wq, m, pk, nrn, surrogate, group, first, real_input, tau, u0)
 
   @staticmethod
-  def forward(ctx, x, wq, m, pk, nrn, surrogate, group, first, real_input, tau):
+  def forward(ctx, x, wq, m, pk, nrn, surrogate, group, first, real_input, tau, u0):
     x1 = x * m if m is not None else x
     if first or real_input or pk.int_weight() is None:
       xin = x1
     else:
       xin = ops.pack_bits(x1.contiguous())
     cur = _currents(xin, pk, wq.shape[1], real_input)
-    h, s = scan_forward(cur, nrn, tau)
+    if u0 is None:
+      h, s = scan_forward(cur, nrn, tau)
+      tail = ()
+    else:
+      if tuple(u0.shape) != tuple(cur.shape[1:]):
+        raise ValueError("DenseBlock: u0 %s, the block's membranes are %s"
+                         % (tuple(u0.shape), tuple(cur.shape[1:])))
+      h, s, u_T = scan_forward(cur, nrn, tau, u0.detach())
+      tail = (u_T,)
     if tau is None or nrn.kind != L.NEURON_PARAMETRIC_LEAKY_IF:
       cur = None
-    ctx.save_for_backward(h, wq, m, x1, tau, cur)
+    ctx.save_for_backward(h, wq, m, x1, tau, cur, saved_membrane(u0, tau))
     ctx.nrn, ctx.surrogate, ctx.group, ctx.first = nrn, surrogate, group, first
+    ctx.window = u0 is not None
     if group is None:
       ctx.mark_non_differentiable(h)
-      return s, None, h
+      return (s, None, h) + tail
     logits = ops.vote(s, group)
     ctx.mark_non_differentiable(s, h)
-    return logits, s, h
+    return (logits, s, h) + tail
 
   @staticmethod
-  def backward(ctx, gout, _gs, _gh):
-    h, wq, m, x1, tau, cur = ctx.saved_tensors
+  def backward(ctx, gout, _gs, _gh, gu_T=None):
+    h, wq, m, x1, tau, cur, u0 = ctx.saved_tensors
     T, B, K = x1.shape
     N = h.shape[-1]
-    if ctx.group is None:
-      gI, gtau = scan_backward(h, cur, ctx.nrn, ctx.surrogate, tau, gs=gout.contiguous())
+    upstream = dict(gs=gout.contiguous()) if ctx.group is None else dict(glogits=gout, group=ctx.group)
+    gu0 = None
+    if ctx.window:
+      gI, gtau, gu0 = scan_backward(h, cur, ctx.nrn, ctx.surrogate, tau,
+                                    state=(u0, gu_T, ctx.needs_input_grad[10]), **upstream)
     else:
-      gI, gtau = scan_backward(h, cur, ctx.nrn, ctx.surrogate, tau, glogits=gout, group=ctx.group)
+      gI, gtau = scan_backward(h, cur, ctx.nrn, ctx.surrogate, tau, **upstream)
     gI2 = gI.reshape(T * B, N)
     gw = ops.dense_weight_grad(x1.reshape(T * B, K).to(torch.float32), gI2)
     gx = None
     if not ctx.first and ctx.needs_input_grad[0]:
       gx = ops.dense_input_grad(gI2, wq.detach(), None if m is None else m.reshape(T * B, K))
       gx = gx.reshape(T, B, K)
-    return gx, gw, None, None, None, None, None, None, None, gtau
+    return gx, gw, None, None, None, None, None, None, None, gtau, gu0
 
 
 def dropout_mask(shape, keep: float, generator: torch.Generator, device) -> torch.Tensor:

@@ -397,8 +397,13 @@ class DenseSNN(nn.Module):
     from . import dense_train as dt
     from . import train_forward as fw
     cfg = self.config
-    x = fw.check_call(self, inputs, rng, u_state, online, frames=False)
+    x = fw.check_call(self, inputs, rng, u_state, online, frames=False, carries=True)
     hidden = cfg.hidden if "hidden" in cfg else cfg.channels * 2 * 2
+    nout = self.num_classes * 10
+    B, steps = x.shape[0], x.shape[1]
+    state, empty = fw.window_state(self, u_state, [(B, hidden), (B, nout)], nout, B, x.device)
+    if state is not None and steps == 0:               # nothing to scan: the state stays as it is
+      return empty, state
     dense1 = fw.dense_layer(self, hidden, _layer_bits(cfg, 0), x.shape[-1])
     dense2 = fw.dense_layer(self, self.num_classes * 10, _layer_bits(cfg, 1), hidden)
     gen = dt.generator_of(rng, x.device)
@@ -406,6 +411,10 @@ class DenseSNN(nn.Module):
     if self.is_mutable_collection("intermediates"):
       self.sow("intermediates", "dropout_0", m0)
     x = dt.input_time_major(dt.apply_input_mask(x, m0))                 # [T, B, K], in x's own dtype
+    if state is not None:                              # a window of a recording, DESIGN.md 18
+      x = fw.dense_block(self, x, "dense1", dense1, None, first=True, state=(state, 0))
+      logits, s = fw.dense_block(self, x, "dense2", dense2, 10, mask=(gen, 1), state=(state, 1))
+      return fw.window_done(state, s, logits, steps)
     x = fw.dense_block(self, x, "dense1", dense1, None, first=True)     # models.py:200-216
     logits = fw.dense_block(self, x, "dense2", dense2, 10, mask=(gen, 1))   # models.py:219-255
     return logits, None
@@ -479,16 +488,27 @@ class ConvDenseSNN(nn.Module):
     dense_train.py).  Channel compaction and the fused kernels are not used."""
     from . import dense_train as dt
     from . import train_forward as fw
-    x = fw.check_call(self, inputs, rng, u_state, online, frames=True)
+    x = fw.check_call(self, inputs, rng, u_state, online, frames=True, carries=True)
     cfg = self.config
-    x = x.transpose(0, 1).contiguous()                    # models.py:109, [T, B, H, W, C]
     nblocks = cfg.num_conv_blocks if "num_conv_blocks" in cfg else 3
+    nout = self.num_classes * 10
+    B, steps, H, W = x.shape[:4]
+    # (a conv block's membranes at its own resolution, as the eval path sizes them)
+    state, empty = fw.window_state(
+        self, u_state, [(B, H >> i, W >> i, cfg.channels) for i in range(nblocks)] + [(B, nout)],
+        nout, B, x.device)
+    if state is not None and steps == 0:               # nothing to scan: the state stays as it is
+      return empty, state
+    x = x.transpose(0, 1).contiguous()                    # models.py:109, [T, B, H, W, C]
     for i in range(nblocks):                              # models.py:111-147
-      x = fw.conv_block(self, x, i, _layer_bits(cfg, i), first=(i == 0))
+      x = fw.conv_block(self, x, i, _layer_bits(cfg, i), first=(i == 0), state=state)
     x = flatten_channel_major(x)                          # models.py:189-190
-    dense = fw.dense_layer(self, self.num_classes * 10, _layer_bits(cfg, nblocks), x.shape[-1])
-    logits = fw.dense_block(self, x, "dense", dense, 10,
-                            mask=(dt.generator_of(rng, x.device), 0))   # models.py:219-255
+    dense = fw.dense_layer(self, nout, _layer_bits(cfg, nblocks), x.shape[-1])
+    mask = (dt.generator_of(rng, x.device), 0)
+    if state is not None:                              # a window of a recording, DESIGN.md 18
+      logits, s = fw.dense_block(self, x, "dense", dense, 10, mask=mask, state=(state, nblocks))
+      return fw.window_done(state, s, logits, steps)
+    logits = fw.dense_block(self, x, "dense", dense, 10, mask=mask)     # models.py:219-255
     return logits, None
 
 

@@ -2081,52 +2081,102 @@ def vote_counts(counts: torch.Tensor, steps, group: int = 10) -> torch.Tensor:
 # ---------------------------------------------------------------------------
 
 
-def lif_forward_save(x: torch.Tensor, neuron: Neuron):
-  """currents float32 [T, ..., C] -> (h, s) float32 [T, ..., C]: the multi_step_LIF potential
-  before the reset and the spikes, from a zero state (the arithmetic of lif_forward)."""
+def _window_state(who, name, u, shape, device):
+  """A window's membrane-shaped operand (u0, gu_T): float32, contiguous, [R, C] in any leading
+  shape; None stays None (the kernels read zeros)."""
+  if u is None:
+    return None
+  if not isinstance(u, torch.Tensor) or u.numel() != math.prod(shape):
+    raise ValueError("%s: %s must hold the %d membranes of one step %s, got %s"
+                     % (who, name, math.prod(shape), tuple(shape),
+                        tuple(u.shape) if isinstance(u, torch.Tensor) else type(u).__name__))
+  u = _f32c(u)
+  _require_gpu(u)
+  return u
+
+
+def _forward_save(who, entry, entry_state, x, neuron, u0, return_state):
   x = _f32c(x)
   _require_gpu(x)
   T, C = x.shape[0], x.shape[-1]
-  R = (x.numel() // (T * C)) if T * C else 0
+  step = tuple(x.shape[1:])
+  R = (math.prod(step) // C) if C else 0
   h = torch.empty_like(x)
   s = torch.empty_like(x)
-  L.check(L.lib().snnqp_lif_forward_save(_ptr(x), T, R, C, ctypes.byref(neuron.struct()),
-                                         _ptr(h), _ptr(s), _stream()))
-  return h, s
+  if u0 is None and not return_state:
+    L.check(entry(_ptr(x), T, R if T else 0, C, ctypes.byref(neuron.struct()), _ptr(h), _ptr(s), _stream()))
+    return h, s
+  u0 = _window_state(who, "u0", u0, step, x.device)
+  u_out = torch.empty(step, dtype=torch.float32, device=x.device) if return_state else None
+  L.check(entry_state(_ptr(x), T, R, C, ctypes.byref(neuron.struct()), _ptr(u0), _ptr(u_out),
+                      _ptr(h), _ptr(s), _stream()))
+  return (h, s, u_out) if return_state else (h, s)
+
+
+def lif_forward_save(x: torch.Tensor, neuron: Neuron, u0: Optional[torch.Tensor] = None,
+                     return_state: bool = False):
+  """currents float32 [T, ..., C] -> (h, s) float32 [T, ..., C]: the multi_step_LIF potential
+  before the reset and the spikes, from a zero state (the arithmetic of lif_forward).
+
+  u0 float32 [..., C]: the membrane the scan starts from (a window of a recording, DESIGN.md 18);
+  return_state: -> (h, s, u_T) with u_T [..., C] the membrane after the last step (u0 itself for
+  T == 0).  With neither, the call is the one it was (snnqp_lif_forward_save)."""
+  lib = L.lib()
+  return _forward_save("lif_forward_save", lib.snnqp_lif_forward_save, lib.snnqp_lif_forward_save_state,
+                       x, neuron, u0, return_state)
 
 
 def lif_backward(h: torch.Tensor, neuron: Neuron, surrogate: int, gs: Optional[torch.Tensor] = None,
-                 glogits: Optional[torch.Tensor] = None, group: int = 10) -> torch.Tensor:
+                 glogits: Optional[torch.Tensor] = None, group: int = 10,
+                 u0: Optional[torch.Tensor] = None, gu_T: Optional[torch.Tensor] = None,
+                 return_gu0: bool = False):
   """BPTT of the multi_step_LIF scan: h [T, R, C] -> gI [T, R, C], from the spikes' gradient
-  gs [T, R, C] or, through the vote, from the logits' gradient glogits [R, C // group]."""
+  gs [T, R, C] or, through the vote, from the logits' gradient glogits [R, C // group].
+
+  A window of a recording: gu_T [R, C] is the gradient arriving at u_T,
+  return_gu0 -> (gI, gu0) with gu0 [R, C] = dL/du0.  u0 is accepted for the signature it shares
+  with neuron_backward; this neuron's backward does not read it.  With none of the three the call
+  is the one it was (snnqp_lif_backward)."""
   h = _f32c(h)
   gs = None if gs is None else _f32c(gs)
   glogits = None if glogits is None else _f32c(glogits)
   _require_gpu(h, gs, glogits)
   T, C = h.shape[0], h.shape[-1]
-  R = (h.numel() // (T * C)) if T * C else 0
+  step = tuple(h.shape[1:])
+  state = u0 is not None or gu_T is not None or return_gu0
+  R = (math.prod(step) // C) if C and (T or state) else 0
   gI = torch.empty_like(h)
-  if h.numel() == 0 and (gs is None) != (glogits is None) and (
-      glogits is None or (group > 0 and C % group == 0)):
-    return gI       # an empty upstream has no pointer for the library to tell gs from glogits by
-  L.check(L.lib().snnqp_lif_backward(_ptr(h), _ptr(gs), _ptr(glogits), int(group), T, R, C,
-                                     ctypes.byref(neuron.struct()), int(surrogate), _ptr(gI),
-                                     _stream()))
-  return gI
+  if not state:
+    if h.numel() == 0 and (gs is None) != (glogits is None) and (
+        glogits is None or (group > 0 and C % group == 0)):
+      return gI       # an empty upstream has no pointer for the library to tell gs from glogits by
+    L.check(L.lib().snnqp_lif_backward(_ptr(h), _ptr(gs), _ptr(glogits), int(group), T, R, C,
+                                       ctypes.byref(neuron.struct()), int(surrogate), _ptr(gI),
+                                       _stream()))
+    return gI
+  _window_state("lif_backward", "u0", u0, step, h.device)
+  gu_T = _window_state("lif_backward", "gu_T", gu_T, step, h.device)
+  gu0 = torch.empty(step, dtype=torch.float32, device=h.device) if return_gu0 else None
+  if h.numel() == 0:  # an empty upstream has no pointer to tell gs from glogits by; no step: gu0 = gu_T
+    if (gs is None) == (glogits is None):
+      raise ValueError("lif_backward: exactly one of gs / glogits")
+    if gu0 is not None:
+      gu0.zero_() if gu_T is None else gu0.copy_(gu_T.reshape(step))
+  else:
+    L.check(L.lib().snnqp_lif_backward_state(_ptr(h), _ptr(gs), _ptr(glogits), int(group), T, R, C,
+                                             ctypes.byref(neuron.struct()), int(surrogate),
+                                             _ptr(gu_T), _ptr(gI), _ptr(gu0), _stream()))
+  return (gI, gu0) if return_gu0 else gI
 
 
-def neuron_forward_save(x: torch.Tensor, neuron: Neuron):
+def neuron_forward_save(x: torch.Tensor, neuron: Neuron, u0: Optional[torch.Tensor] = None,
+                        return_state: bool = False):
   """lif_forward_save for the neurons with a parameter (PLIF, LIF; csrc/train_neuron.hip):
-  currents float32 [T, ..., C] -> (h, s), the arithmetic of lif_forward for the same neuron."""
-  x = _f32c(x)
-  _require_gpu(x)
-  T, C = x.shape[0], x.shape[-1]
-  R = (x.numel() // (T * C)) if T * C else 0
-  h = torch.empty_like(x)
-  s = torch.empty_like(x)
-  L.check(L.lib().snnqp_neuron_forward_save(_ptr(x), T, R, C, ctypes.byref(neuron.struct()),
-                                            _ptr(h), _ptr(s), _stream()))
-  return h, s
+  currents float32 [T, ..., C] -> (h, s), the arithmetic of lif_forward for the same neuron.
+  u0 and return_state as lif_forward_save's."""
+  lib = L.lib()
+  return _forward_save("neuron_forward_save", lib.snnqp_neuron_forward_save,
+                       lib.snnqp_neuron_forward_save_state, x, neuron, u0, return_state)
 
 
 def neuron_backward_splits(T: int, R: int, C: int) -> int:
@@ -2146,18 +2196,26 @@ def neuron_backward_workspace_bytes(T: int, R: int, C: int, splits: int, kind: i
 
 def neuron_backward(h: torch.Tensor, x: Optional[torch.Tensor], neuron: Neuron, surrogate: int,
                     gs: Optional[torch.Tensor] = None, glogits: Optional[torch.Tensor] = None,
-                    group: int = 10, splits: Optional[int] = None):
+                    group: int = 10, splits: Optional[int] = None,
+                    u0: Optional[torch.Tensor] = None, gu_T: Optional[torch.Tensor] = None,
+                    return_gu0: bool = False):
   """BPTT of the PLIF / LIF scan: h [T, R, C] and, for PLIF, the currents x the scan consumed ->
   (gI [T, R, C], gparam float64): gparam [1] = sum gh d for PLIF (the gradient of m), [C] =
   sum_{t,r} gh u_{t-1} for LIF (of the decays).  Upstream gs or glogits as lif_backward; the rows
-  are cut into `splits` ranges summed in order (None: neuron_backward_splits)."""
+  are cut into `splits` ranges summed in order (None: neuron_backward_splits).
+
+  A window of a recording: u0 [R, C] is the membrane the forward started from --
+  u_{-1} in the t = 0 term of both sums --, gu_T the gradient arriving at u_T, and return_gu0 ->
+  (gI, gparam, gu0).  With none of the three the call is the one it was (snnqp_neuron_backward)."""
   h = _f32c(h)
   x = None if x is None or neuron.kind == L.NEURON_LIF else _f32c(x)
   gs = None if gs is None else _f32c(gs)
   glogits = None if glogits is None else _f32c(glogits)
   _require_gpu(h, x, gs, glogits)
   T, C = h.shape[0], h.shape[-1]
-  R = (h.numel() // (T * C)) if T * C else 0
+  step = tuple(h.shape[1:])
+  state = u0 is not None or gu_T is not None or return_gu0
+  R = (math.prod(step) // C) if C and (T or state) else 0
   if neuron.kind == L.NEURON_PARAMETRIC_LEAKY_IF and h.numel():
     if x is None or tuple(x.shape) != tuple(h.shape):
       raise ValueError("neuron_backward: PLIF needs the scan's currents x, shaped like h")
@@ -2168,14 +2226,31 @@ def neuron_backward(h: torch.Tensor, x: Optional[torch.Tensor], neuron: Neuron, 
   nbytes = neuron_backward_workspace_bytes(T, R, C, splits, neuron.kind) if known else 0
   gI = torch.empty_like(h)
   gparam = torch.empty((C if neuron.kind == L.NEURON_LIF else 1,), dtype=torch.float64, device=h.device)
-  if h.numel() == 0 and (gs is None) != (glogits is None) and (
-      glogits is None or (group > 0 and C % group == 0)):
-    return gI, gparam.zero_()   # an empty upstream has no pointer to tell gs from glogits by
-  ws = torch.empty(nbytes // 8, dtype=torch.float64, device=h.device)
-  L.check(L.lib().snnqp_neuron_backward(_ptr(h), _ptr(x), _ptr(gs), _ptr(glogits), int(group), T, R, C,
-                                        ctypes.byref(neuron.struct()), int(surrogate), int(splits),
-                                        _ptr(gI), _ptr(gparam), _ptr(ws), nbytes, _stream()))
-  return gI, gparam
+  if not state:
+    if h.numel() == 0 and (gs is None) != (glogits is None) and (
+        glogits is None or (group > 0 and C % group == 0)):
+      return gI, gparam.zero_()   # an empty upstream has no pointer to tell gs from glogits by
+    ws = torch.empty(nbytes // 8, dtype=torch.float64, device=h.device)
+    L.check(L.lib().snnqp_neuron_backward(_ptr(h), _ptr(x), _ptr(gs), _ptr(glogits), int(group), T, R, C,
+                                          ctypes.byref(neuron.struct()), int(surrogate), int(splits),
+                                          _ptr(gI), _ptr(gparam), _ptr(ws), nbytes, _stream()))
+    return gI, gparam
+  u0 = _window_state("neuron_backward", "u0", u0, step, h.device)
+  gu_T = _window_state("neuron_backward", "gu_T", gu_T, step, h.device)
+  gu0 = torch.empty(step, dtype=torch.float32, device=h.device) if return_gu0 else None
+  if h.numel() == 0:  # an empty upstream has no pointer to tell gs from glogits by; no step: gu0 = gu_T
+    if (gs is None) == (glogits is None):
+      raise ValueError("neuron_backward: exactly one of gs / glogits")
+    gparam.zero_()
+    if gu0 is not None:
+      gu0.zero_() if gu_T is None else gu0.copy_(gu_T.reshape(step))
+  else:
+    ws = torch.empty(nbytes // 8, dtype=torch.float64, device=h.device)
+    L.check(L.lib().snnqp_neuron_backward_state(
+        _ptr(h), _ptr(x), _ptr(u0), _ptr(gs), _ptr(glogits), int(group), T, R, C,
+        ctypes.byref(neuron.struct()), int(surrogate), int(splits), _ptr(gu_T), _ptr(gI), _ptr(gu0),
+        _ptr(gparam), _ptr(ws), nbytes, _stream()))
+  return (gI, gparam, gu0) if return_gu0 else (gI, gparam)
 
 
 def dense_weight_grad(x: torch.Tensor, gI: torch.Tensor) -> torch.Tensor:

@@ -18,8 +18,13 @@ from .quant import DuQ
 _PACKED = (ops.PackedSpikes, ops.PackedFrames, ops.GatedSpikes)
 
 
-def check_call(mod, inputs, rng, u_state, online, frames, min_hw=0, gpu=False):
+def check_call(mod, inputs, rng, u_state, online, frames, min_hw=0, gpu=False, carries=False):
   """Refuses what training does not support and returns the input tensor.
+
+  carries: the model trains over windows of a recording (DenseSNN, ConvDenseSNN) and
+  takes a models.StreamState as u_state.  Anything else given as u_state is refused by every
+  model, and a StreamState by a model that does not carry (CextNet: its TCJA gates).  No refusal
+  touches the state.
 
   frames: the conv models -- a uint8 or float32 [B, T, H, W, C] tensor (of at least min_hw x
   min_hw), looked at before the rng, the config or the parameters, and on the GPU (`gpu`) once
@@ -38,8 +43,15 @@ def check_call(mod, inputs, rng, u_state, online, frames, min_hw=0, gpu=False):
   if rng is None:
     raise NotImplementedError("train=True needs an rng (an int seed or a torch.Generator) for "
                               "the dropout %s; the reference splits it unconditionally" % mask)
-  if u_state is not None or online:
-    raise NotImplementedError("training: the online mode and a carried state are not supported")
+  from .models import StreamState
+  if online or (u_state is not None and not isinstance(u_state, StreamState)):
+    raise NotImplementedError("training: the online mode and a carried state that is not a "
+                              "models.StreamState are not supported")
+  if u_state is not None and not carries:
+    raise NotImplementedError(
+        "training %s over windows: its TCJA gates are convolutions over the window's time axis with "
+        "T features, so a window shorter than the configured T has no defined gate (DESIGN.md 15)"
+        % type(mod).__name__)
   if _probing(mod, cfg):
     raise NotImplementedError("training: density probes are not supported")
   if "dropout" not in cfg:
@@ -80,10 +92,19 @@ def _tau_leaf(mod, dyn, kind):
   return leaf["tau"]
 
 
-def conv_block(mod, x, i, bits, pool=2, first=False, real_input=False, wgrad_f64=False):
+def carry_membrane(state, k, u_T):
+  """Block k's u_T of a window into the state's own buffer (whose address stays): the value only --
+  the next window reads it detached (truncated BPTT, the reference's train_step)."""
+  with torch.no_grad():
+    state.membranes[k].copy_(u_T)
+
+
+def conv_block(mod, x, i, bits, pool=2, first=False, real_input=False, wgrad_f64=False, state=None):
   """Conv block i on x [T, B, H, W, Cin]: QuantConv 3x3, BatchNorm on batch statistics, LIF, the
   2x2 max pool (conv_train.ConvBlock, whose arguments the last four are) -> the pooled spikes.
-  Moves the running statistics and sows conv<i>_h, conv<i>_out, bn<i>_mean, bn<i>_var."""
+  Moves the running statistics and sows conv<i>_h, conv<i>_out, bn<i>_mean, bn<i>_var.
+  state: a fitted models.StreamState -- the scan starts from state.membranes[i], a constant of this
+  window's gradient, and leaves u_T there."""
   cfg, C = mod.config, mod.config.channels
   conv = _qconv3x3(cfg, mod.dtype, bits)
   dyn = cfg.neuron_dynamics(dtype=mod.dtype)
@@ -94,9 +115,12 @@ def conv_block(mod, x, i, bits, pool=2, first=False, real_input=False, wgrad_f64
   pk = conv.packed_kernel(cin)
   wq = _transformed_kernel(mod, conv, pk)
   nrn = dyn.neuron(C)
-  y, h, s, mean, var = ct.ConvBlock.apply(
+  y, h, s, mean, var, *u_T = ct.ConvBlock.apply(
       x, wq, norm.scale_param(C), norm.bias_param(C), pk, geom, nrn, surr,
-      float(norm.epsilon), first, pool, real_input, wgrad_f64, _tau_leaf(mod, dyn, kind))
+      float(norm.epsilon), first, pool, real_input, wgrad_f64, _tau_leaf(mod, dyn, kind),
+      None if state is None else state.membranes[i].detach())
+  if state is not None:
+    carry_membrane(state, i, u_T[0])
   norm.update_running(mean, var)
   if mod.is_mutable_collection("intermediates"):
     mod.sow("intermediates", "conv%d_h" % i, h)
@@ -131,20 +155,45 @@ def dense_layer(mod, features, bits, K):
   return dense, dyn, dt.neuron_train_form(dyn, mod.config), dense.packed_kernel(K)
 
 
-def dense_block(mod, x, name, layer, group, mask=None, first=False, real_input=False):
+def dense_block(mod, x, name, layer, group, mask=None, first=False, real_input=False, state=None):
   """A dense block on x [T, B, K]: QuantDense, LIF and, with `group`, the vote
   (dense_train.DenseBlock, whose arguments the last three are) -> the logits, or the spikes of a
   hidden block (group None).  mask (generator, n): draws the block's dropout mask, shaped like
-  x, and sows it as dropout_<n>; None: no mask.  Sows <name>_out and <name>_h."""
+  x, and sows it as dropout_<n>; None: no mask.  Sows <name>_out and <name>_h.
+  state (a fitted models.StreamState, k): the scan starts from state.membranes[k], a constant of
+  this window's gradient, and leaves u_T there; with `group` -> (logits, s), the read-out raster
+  for the state's counts."""
   dense, dyn, (surr, kind), pk = layer
   m = None if mask is None else dt.dropout_mask(x.shape, mod.config.dropout, mask[0], x.device)
   wq = _transformed_kernel(mod, dense, pk)
   nrn = dyn.neuron(dense.features)
-  out, s, h = dt.DenseBlock.apply(x, wq, m, pk, nrn, surr, group, first, real_input,
-                                  _tau_leaf(mod, dyn, kind))
+  out, s, h, *u_T = dt.DenseBlock.apply(
+      x, wq, m, pk, nrn, surr, group, first, real_input, _tau_leaf(mod, dyn, kind),
+      None if state is None else state[0].membranes[state[1]].detach())
+  if state is not None:
+    carry_membrane(*state, u_T[0])
   if mod.is_mutable_collection("intermediates"):
     if m is not None:
       mod.sow("intermediates", "dropout_%d" % mask[1], m)
     mod.sow("intermediates", name + "_out", (out if group is None else s).detach())
     mod.sow("intermediates", name + "_h", h)
+  if state is not None and group is not None:
+    return out, s
   return out
+
+
+def window_state(mod, u_state, shapes, n_out, B, device):
+  """The StreamState of a training call fitted to this model and window before any launch (None:
+  the whole-run call), and the zero logits of a window without a step (else None)."""
+  if u_state is None:
+    return None, None
+  u_state._fit(shapes, n_out, device)
+  return u_state, torch.zeros((B, mod.num_classes), dtype=torch.float32, device=device)
+
+
+def window_done(state, s, logits, steps):
+  """Books a training window as the eval path books one: the read-out raster into the counts, the
+  steps for every row -> (window logits, state)."""
+  ops.vote_accumulate(s.detach(), state.counts)
+  state.advance(steps)
+  return logits, state

@@ -135,12 +135,18 @@ def create_train_state(variables, config, model) -> TrainState:
 
 
 def train_step(state: TrainState, batch, rng, learning_rate_fn, weight_decay, smoothing,
-               loss_type, online=False, burnin=0, return_grads=False):
+               loss_type, online=False, burnin=0, return_grads=False, u_state=None):
   """One offline step (train_utils.py:249-368): loss = loss_type(logits, labels, smoothing) +
   weight_decay * weight_decay_fn(params); gradients by the model's backward (the blocks
   train_forward.py assembles: dense_train.DenseBlock, conv_train.ConvBlock, tcja_train.TcjaGate), averaged over ranks when torch.distributed is initialised; then one update.
   Returns (state, metrics) -- metrics with loss, accuracy, learning_rate and logits --, and the
-  gradient tree as a third element when return_grads."""
+  gradient tree as a third element when return_grads.
+
+  u_state (a models.StreamState; DenseSNN and ConvDenseSNN): the batch is one window
+  of a recording.  The blocks start from the state's membranes, constants of this step's gradient
+  (truncated BPTT, the reference's loss_fn(params, inputs, targets, u_state)), and leave theirs
+  there; still one update per call, and the metrics are the window's -- the vote over the
+  recording so far is u_state.logits()."""
   if online:
     raise NotImplementedError("the online branch of train_step is not supported")
   from .parallel import mean_over_ranks
@@ -148,9 +154,11 @@ def train_step(state: TrainState, batch, rng, learning_rate_fn, weight_decay, sm
   items = _flatten(params)
   leaves = [(path, p.detach().requires_grad_(True)) for path, p in items]
   ptree = _unflatten(leaves)
+  carried = {} if u_state is None else {"u_state": u_state}
   (logits, _), mutated = state.apply_fn(
       {"params": ptree, "batch_stats": state.batch_stats}, batch["dvs_matrix"],
-      trgt=batch["label"], train=True, rng=rng, mutable=["batch_stats"], rngs={"dropout": rng})
+      trgt=batch["label"], train=True, rng=rng, mutable=["batch_stats"], rngs={"dropout": rng},
+      **carried)
   loss = loss_type(logits, batch["label"], smoothing)
   if weight_decay:
     loss = loss + weight_decay * weight_decay_fn(ptree)
@@ -177,6 +185,43 @@ def train_step(state: TrainState, batch, rng, learning_rate_fn, weight_decay, sm
   if return_grads:
     return new_state, metrics, _unflatten([(path, g) for (path, _), g in zip(items, grads)])
   return new_state, metrics
+
+
+def window_rng(rng, k: int):
+  """The rng of window k of a recording whose step was given `rng`.  A torch.Generator is handed on
+  as it is: every window draws from it in turn.  An int seed s gives window 0 the seed s itself --
+  a recording of one window is the train_step of that seed -- and window k > 0 the seed
+  (s + k * 0x9E3779B97F4A7C15) mod 2^63: a function of (s, k) alone, so a run repeats, and the
+  windows of the steps seeded s and s + 1 share no seed."""
+  if isinstance(rng, torch.Generator) or k == 0:
+    return rng
+  return (int(rng) + k * 0x9E3779B97F4A7C15) % (1 << 63)
+
+
+def train_step_windows(state: TrainState, batch, rng, learning_rate_fn, weight_decay, smoothing,
+                       loss_type, window, online=False, burnin=0):
+  """Truncated BPTT over one batch of recordings: batch["dvs_matrix"] [B, T, ...]
+  is cut on T into windows of `window` steps (the last one may be shorter), a fresh
+  models.StreamState carries the membranes and the vote from window to window, and every window is
+  one train_step -- one update, against the recording's labels -- with the rng window_rng gives it.
+  The backward keeps one window's residuals at a time, not the recording's.
+
+  Returns (state, metrics, u_state): the TrainState after the last window, the list of the
+  windows' metrics, and the StreamState, whose logits() are the vote over the whole recording.
+  window >= T is one train_step."""
+  from .models import StreamState
+  window = int(window)
+  if window < 1:
+    raise ValueError("train_step_windows: window must be at least 1 step, got %d" % window)
+  x = batch["dvs_matrix"]
+  T = x.shape[1]
+  u_state, metrics = StreamState(), []
+  for k, t0 in enumerate(range(0, T, window)):
+    part = dict(batch, dvs_matrix=x[:, t0:t0 + window])
+    state, m = train_step(state, part, window_rng(rng, k), learning_rate_fn, weight_decay,
+                          smoothing, loss_type, online=online, burnin=burnin, u_state=u_state)
+    metrics.append(m)
+  return state, metrics, u_state
 
 
 # ---------------------------------------------------------------------------

@@ -27,6 +27,14 @@ alone on both gated stages' shapes, block 0's weight gradient on the float64 and
 timings of each.
 
   python tools/train_step_time.py --cext [--steps 5] [--warmup 2] [--batch 2] [--frames 20] [--hw 128] [--reps 3]
+
+--window W (the dense step and --conv): the recording is trained as windows of W steps with carried
+membranes (train_utils.train_step_windows), ceil(T / W) updates per recording; prints
+the time per recording, and the allocator's level before and its peak
+(torch.cuda.max_memory_allocated()) over one more recording run from a cleared packing cache, and
+nothing else.  Without it the step's line carries the same two figures.
+
+  python tools/train_step_time.py --conv --window 5
 """
 import argparse
 import json
@@ -37,6 +45,36 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
 
 import torch  # noqa: E402
+
+
+def _time_and_peak(fn, steps, warmup):
+  """_time, then the allocator's level before and its peak over one more call (bytes), taken from
+  a cleared packing cache: that cache keeps the packed kernels of up to 128 earlier parameter
+  versions (DuQ's a and c are part of its key and move with every update), so its level grows
+  with the number of updates so far and would hide what one call needs."""
+  from snnquantprune_amd import packing
+  ms = _time(fn, steps, warmup)
+  packing.clear_cache()
+  torch.cuda.synchronize()
+  torch.cuda.reset_peak_memory_stats()
+  before = torch.cuda.memory_allocated()
+  fn()
+  torch.cuda.synchronize()
+  return ms, (before, torch.cuda.max_memory_allocated())
+
+
+def _window_line(workload, args, batch, box, tu):
+  """The --window run of the dense and the conv step: one JSON line."""
+  def step():
+    box[0], _, _ = tu.train_step_windows(box[0], batch, 0, lambda s: 1e-4, 0.0, 0.0, tu.mse_loss,
+                                         window=args.window)
+
+  ms, peak = _time_and_peak(step, args.steps, args.warmup)
+  print(json.dumps({"workload": workload, "batch": args.batch, "frames": args.frames, "window": args.window,
+                    "updates_per_recording": -(-args.frames // args.window),
+                    "hip_recording_ms": round(ms, 3), "hip_memory_before_bytes": peak[0],
+                    "hip_peak_memory_bytes": peak[1],
+                    "samples_per_s": round(args.batch / ms * 1e3, 1)}))
 
 
 def _time(fn, steps, warmup):
@@ -326,11 +364,13 @@ def conv_main(args):
   labels = torch.arange(B, device=dev) % 11
   batch = {"dvs_matrix": x, "label": labels}
   box = [tu.create_train_state(variables, cfg, model)]
+  if args.window:
+    return _window_line("conv_dense_snn_c3_train_windows", args, batch, box, tu)
 
   def hip_step():
     box[0], _ = tu.train_step(box[0], batch, 0, lambda s: 1e-4, 0.0, 0.0, tu.mse_loss)
 
-  hip_ms = _time(hip_step, args.steps, args.warmup)
+  hip_ms, hip_peak = _time_and_peak(hip_step, args.steps, args.warmup)
 
   # the A/B of nn.set_train_conv_mfma in one process: the whole step with the connection of conv1
   # and conv2 on the MFMA currents kernel (on) and on the direct-form kernel (off, the launch of
@@ -397,7 +437,9 @@ def conv_main(args):
 
   eager_ms = _time(eager_step, args.steps, args.warmup)
   print(json.dumps({"workload": "conv_dense_snn_c3_train_step", "batch": B, "frames": T, "hw": HW,
-                    "hip_train_step_ms": round(hip_ms, 3), "eager_torch_train_step_ms": round(eager_ms, 3),
+                    "hip_train_step_ms": round(hip_ms, 3), "hip_memory_before_bytes": hip_peak[0],
+                    "hip_peak_memory_bytes": hip_peak[1],
+                    "eager_torch_train_step_ms": round(eager_ms, 3),
                     "speedup_vs_eager": round(eager_ms / hip_ms, 2),
                     "samples_per_s": round(B / hip_ms * 1e3, 1),
                     "step_conv_mfma_on_ms": [round(t, 3) for t in ab[True]],
@@ -420,7 +462,11 @@ def main():
                   help="--conv: the step with this neuron, --reps timings, and its BPTT scan alone")
   ap.add_argument("--lanes", type=int, nargs="*", default=[0],
                   help="--conv --neuron plif|lif: lanes the scan's `splits` aims at (0: the default)")
+  ap.add_argument("--window", type=int, default=0,
+                  help="the dense step and --conv: train the recording as windows of this many steps")
   args = ap.parse_args()
+  if args.window < 0 or (args.window and (args.cext or args.neuron is not None)):
+    ap.error("--window takes a positive length, for the dense step and for --conv without --neuron")
   dflt = (5, 2, 2) if args.conv or args.cext else (20, 5, 256)
   args.steps = dflt[0] if args.steps is None else args.steps
   args.warmup = dflt[1] if args.warmup is None else args.warmup
@@ -443,11 +489,13 @@ def main():
   batch = {"dvs_matrix": x, "label": labels}
   state = tu.create_train_state(variables, cfg, model)
   box = [state]
+  if args.window:
+    return _window_line("dense_snn_c2_train_windows", args, batch, box, tu)
 
   def hip_step():
     box[0], _ = tu.train_step(box[0], batch, 0, lambda s: 1e-4, 0.0, 0.0, tu.mse_loss)
 
-  hip_ms = _time(hip_step, args.steps, args.warmup)
+  hip_ms, hip_peak = _time_and_peak(hip_step, args.steps, args.warmup)
 
   # the backward kernels alone, on the step's shapes
   nrn = ops.Neuron(1, 2.0, 1.0, 0.0)
@@ -479,7 +527,9 @@ def main():
 
   eager_ms = _time(eager_step, args.steps, args.warmup)
   print(json.dumps({"workload": "dense_snn_c2_train_step", "batch": B, "frames": T,
-                    "hip_train_step_ms": round(hip_ms, 3), "eager_torch_train_step_ms": round(eager_ms, 3),
+                    "hip_train_step_ms": round(hip_ms, 3), "hip_memory_before_bytes": hip_peak[0],
+                    "hip_peak_memory_bytes": hip_peak[1],
+                    "eager_torch_train_step_ms": round(eager_ms, 3),
                     "speedup_vs_eager": round(eager_ms / hip_ms, 2),
                     "samples_per_s": round(B / hip_ms * 1e3, 1),
                     **{k: round(val, 4) for k, val in kern.items()}}))
