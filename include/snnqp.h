@@ -257,7 +257,8 @@ typedef struct {
  * snnqp_neuron_forward_save, snnqp_neuron_backward, snnqp_neuron_backward_splits,
  * snnqp_neuron_backward_workspace_bytes; training over windows of a recording --
  * snnqp_lif_forward_save_state, snnqp_lif_backward_state, snnqp_neuron_forward_save_state,
- * snnqp_neuron_backward_state: new entry points, nothing else moves).
+ * snnqp_neuron_backward_state; training a conv block with rematerialisation --
+ * snnqp_bn_lif_forward_state, snnqp_maxpool2x2_backward_h: new entry points, nothing else moves).
  * A binding compares snnqp_version()
  * with the SNNQP_VERSION it was written against and refuses a library of another version (_lib.py does). */
 #define SNNQP_VERSION 507
@@ -1180,6 +1181,30 @@ int snnqp_conv_input_grad(const float *gI, const float *w, int64_t NB,
  * other position, and a trailing odd row or column, gets 0.  gs [NB][H][W][C]. */
 int snnqp_maxpool2x2_backward(const float *s, const float *gp, int64_t NB, int32_t H, int32_t W,
                               int32_t C, float *gs, snnqp_stream_t stream);
+
+/* ---- training of a conv block with rematerialisation (csrc/train_remat.hip) ------------------
+ * What a block that keeps neither its currents nor h runs chunk by chunk.  All
+ * tensors float32; one lane per element e = r C + c; 64-bit index arithmetic; grids beyond the
+ * launch limits are SNNQP_EINVAL; every refusal is decided on the host before any launch.
+ *
+ * The batch-statistics normalisation and snnqp_lif_forward_save_state in one pass:
+ *   y_t = fl(fl(fl(cur_t - mean[t][c]) mul[t][c]) + bias[c]), then that entry's step on y_t.
+ *   cur    [T][R][C] the raw currents;  mean, mul [T][C] the per-step mean and the multiplier
+ *          fl(fl(1 / sqrt(fl(var + eps))) scale) (computed by the caller);  bias [C]
+ *   u0, u_out  as snnqp_lif_forward_save_state's (u0 null: zeros; may be one buffer)
+ *   h_out, s_out [T][R][C], each nullable: what is not wanted is not written
+ * y is never written.  T == 0 writes u_out = u0 and nothing else.  Null cur, mean, mul or bias
+ * with T R C > 0 is SNNQP_EINVAL.  multi_step_LIF only: a neuron with a parameter is
+ * SNNQP_EUNSUPPORTED, naming snnqp_neuron_forward_save_state, the scan that serves it. */
+int snnqp_bn_lif_forward_state(const float *cur, const float *mean, const float *mul,
+                               const float *bias, int32_t T, int64_t R, int32_t C,
+                               const snnqp_neuron_t *nrn, const float *u0, float *u_out,
+                               float *h_out, float *s_out, snnqp_stream_t stream);
+/* snnqp_maxpool2x2_backward with the pool's input taken as s = ((h - vth) >= 0) ? 1 : 0, the
+ * forward's own compare on h [NB][H][W][C]: the same rule (first maximum in row-major window
+ * order, zeros in a trailing odd row or column), and no spike raster in memory. */
+int snnqp_maxpool2x2_backward_h(const float *h, float vth, const float *gp, int64_t NB, int32_t H,
+                                int32_t W, int32_t C, float *gs, snnqp_stream_t stream);
 
 /* ---- training of CextNet's gated stages (csrc/train_gate.hip) --------------------------------
  * The backward of p = maxpool2x2(y), y[n, h, w, c] = x[n, h, w, c] gate[n, c], with the spatial

@@ -241,6 +241,11 @@ _PROTOTYPES = {
                                       c_void_p]),
     "snnqp_maxpool2x2_backward": (c_int, [c_void_p, c_void_p, c_int64, c_int32, c_int32, c_int32,
                                           c_void_p, c_void_p]),
+    "snnqp_bn_lif_forward_state": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_int32, c_int64,
+                                           c_int32, POINTER(NeuronT), c_void_p, c_void_p, c_void_p,
+                                           c_void_p, c_void_p]),
+    "snnqp_maxpool2x2_backward_h": (c_int, [c_void_p, c_float, c_void_p, c_int64, c_int32, c_int32,
+                                            c_int32, c_void_p, c_void_p]),
     "snnqp_conv_weight_grad_f64": (c_int, [c_void_p, c_void_p, c_int64, POINTER(ConvGeomT), c_void_p,
                                            c_void_p, c_void_p]),
     "snnqp_conv_weight_grad_f64_workspace_bytes": (c_int64, [POINTER(ConvGeomT), c_int64]),

@@ -267,3 +267,180 @@ class ConvBlock(torch.autograd.Function):
     if not ctx.first and ctx.needs_input_grad[0]:
       gx = ops.conv_input_grad(gcur, wq.detach(), geom).reshape(x.shape)
     return gx, gw, gscale, gbias, None, None, None, None, None, None, None, None, None, gtau, gu0
+
+
+# ---- the block with rematerialisation --------------------------------------------
+
+
+def check_remat(W):
+  """config.remat: the steps per chunk, an integer of at least 1."""
+  if isinstance(W, bool) or not isinstance(W, int) or W < 1:
+    raise ValueError("config.remat must be an integer of at least 1 (the steps per chunk), got %r" % (W,))
+  return W
+
+
+def remat_chunks(T: int, W: int):
+  """[(t0, t1), ...]: the steps 0..T cut into chunks of W in order, the last one ragged; W >= T is
+  one chunk, T == 0 none."""
+  check_remat(W)
+  return [(t0, min(t0 + W, T)) for t0 in range(0, T, W)]
+
+
+def _accumulate(acc, part):
+  """The chunks' reductions, added in the order the backward visits them."""
+  return part if acc is None else acc + part
+
+
+class RematConvBlock(torch.autograd.Function):
+  """ConvBlock (pool 2, spike or frame input, float32 weight-gradient chain) that keeps neither
+  its currents nor h: x [T, B, H, W, Cin] is walked in chunks of `chunk` steps, forward and
+  backward, and the backward recomputes each chunk's currents and scan from what the block keeps
+  -- its input (the bit-packed raster from block 1 on, the frames as given for block 0), the
+  per-step statistics, the membrane at the start of every chunk and the parameters.  The chunks'
+  scans are chained exactly: a chunk starts from the membrane the one before left, and its
+  backward scan takes the gu0 of the chunk after as gu_T, so every element-sized tensor is
+  ConvBlock's bit for bit; gw, gscale, gbias and the `tau` sums are each chunk's own reduction,
+  added last chunk first.
+
+  Outputs as ConvBlock's; h and s are the chunks' concatenated and only with want_h (the sown
+  intermediates), else None."""
+
+  @classmethod
+  def apply(cls, x, wq, scale, bias, pk, geom, nrn, surrogate, eps, first, chunk, want_h=False,
+            tau=None, u0=None):
+    check_remat(chunk)
+    return super().apply(x, wq, scale, bias, pk, geom, nrn, surrogate, eps, first, chunk, want_h,
+                         tau, u0)
+
+  @staticmethod
+  def kept_input(x, pk, geom, first):
+    """(what the block keeps of x [T, B, H, W, Cin], how a chunk of it reaches conv_currents): the
+    PackedSpikes [T, B, H, W, Cin] of a spike raster, or block 0's frames as given.  A float32 frame
+    tensor is looked at once, whole, as ConvBlock's single launch looks at it: integer-valued
+    frames go to the integer connection as uint8 ('u8'), others to the float32 one ('real')."""
+    if not first:
+      return ops.pack_bits(x), "bits"
+    if pk.int_weight() is not None and x.dtype == torch.float32:
+      whole = bool(((x == torch.round(x)) & (x >= 0) & (x <= 255)).all())
+      return x, "u8" if whole else "real"
+    return x, "frames"
+
+  @staticmethod
+  def chunk_input(kept, form, geom, t0, t1):
+    """Steps t0..t1 of the kept input as conv_currents takes them, [NB, H, W, Cin]."""
+    xc = kept[t0:t1]
+    if form == "bits":
+      return xc.reshape_leading(-1, geom.H, geom.W)
+    xc = xc.reshape(-1, geom.H, geom.W, geom.Cin)
+    return xc.to(torch.uint8) if form == "u8" else xc
+
+  @staticmethod
+  def chunk_currents(kept, form, pk, geom, t0, t1):
+    """The chunk's raw currents [t1 - t0, B OH OW, C]: the launch of the forward on the same bits,
+    so the backward's tensor is the forward's."""
+    cur = conv_currents(RematConvBlock.chunk_input(kept, form, geom, t0, t1), pk, geom,
+                        real=(form == "real"))
+    return cur.reshape(t1 - t0, -1, geom.Cout)
+
+  @staticmethod
+  def chunk_scan(cur, mean, var, scale, bias, eps, nrn, tau, u, want_h, want_s):
+    """(y, h, s, u_T) of a chunk from the membrane u (None: zeros): the fused kernel for
+    multi_step_LIF (y None: never written), ConvBlock.scan_input and the PLIF / LIF scan with a
+    `tau` leaf."""
+    if tau is None:
+      h, s, u_T = ops.bn_lif_forward(cur, mean, bn_multiplier(var, scale, eps), bias, nrn, u0=u,
+                                     want_h=want_h, want_s=want_s, return_state=True)
+      return None, h, s, u_T
+    y = ConvBlock.scan_input(cur, mean, var, scale, bias, eps)
+    h, s, u_T = ops.neuron_forward_save(y, nrn, u0=u, return_state=True)
+    return y, h, s, u_T
+
+  @staticmethod
+  def forward(ctx, x, wq, scale, bias, pk, geom, nrn, surrogate, eps, first, chunk, want_h, tau, u0):
+    T, B = x.shape[0], x.shape[1]
+    C = geom.Cout
+    OH, OW = geom.out_hw()
+    if u0 is not None and tuple(u0.shape) != (B, OH, OW, C):
+      raise ValueError("RematConvBlock: u0 %s, the block's membranes are %s" % (tuple(u0.shape), (B, OH, OW, C)))
+    kept, form = RematConvBlock.kept_input(x, pk, geom, first)
+    chunks = remat_chunks(T, chunk) or [(0, 0)]
+    # the membrane each chunk starts from: the window's own copy (the caller overwrites the state's
+    # buffer with u_T before the backward runs), then what each chunk hands on
+    u = None if u0 is None else u0.detach().reshape(B * OH * OW, C).clone()
+    starts, means, variances, hs, ss = [], [], [], [], []
+    pooled = torch.empty((T, B, OH // 2, OW // 2, C), dtype=torch.float32, device=x.device)
+    sd, bd = scale.detach(), bias.detach()
+    for t0, t1 in chunks:
+      starts.append(u)
+      cur = RematConvBlock.chunk_currents(kept, form, pk, geom, t0, t1)
+      mean, var = batch_stats(cur)
+      y, h, s, u = RematConvBlock.chunk_scan(cur, mean, var, sd, bd, eps, nrn, tau, u, want_h, True)
+      del cur, y
+      s = s.reshape(t1 - t0, B, OH, OW, C)
+      pooled[t0:t1] = ops.maxpool2x2(s)
+      means.append(mean)
+      variances.append(var)
+      if want_h:
+        hs.append(h.reshape(t1 - t0, B, OH, OW, C))
+        ss.append(s)
+      del h, s
+    mean, var = torch.cat(means), torch.cat(variances)
+    h = torch.cat(hs) if want_h else None
+    s = torch.cat(ss) if want_h else None
+    del hs, ss
+    bits = kept.bits if form == "bits" else kept
+    ctx.save_for_backward(bits, wq, scale, bias, mean, var, tau, *[v for v in starts if v is not None])
+    ctx.zero_start = starts[0] is None
+    ctx.form, ctx.pk, ctx.geom, ctx.nrn, ctx.surrogate, ctx.eps = form, pk, geom, nrn, surrogate, eps
+    ctx.first, ctx.chunks, ctx.window, ctx.x_shape = first, chunks, u0 is not None, tuple(x.shape)
+    ctx.mark_non_differentiable(*[v for v in (h, s, mean, var) if v is not None])
+    u_T = u.reshape(B, OH, OW, C)
+    return (pooled, h, s, mean, var) if u0 is None else (pooled, h, s, mean, var, u_T)
+
+  @staticmethod
+  def backward(ctx, gp, _gh, _gs, _gmean, _gvar, gu_T=None):
+    bits, wq, scale, bias, mean, var, tau, *starts = ctx.saved_tensors
+    if ctx.zero_start:
+      starts = [None] + starts
+    geom, nrn, form = ctx.geom, ctx.nrn, ctx.form
+    T, B = ctx.x_shape[0], ctx.x_shape[1]
+    C = geom.Cout
+    OH, OW = geom.out_hw()
+    kept = ops.PackedSpikes(bits, geom.Cin) if form == "bits" else bits
+    sd, bd = scale.detach(), bias.detach()
+    want_gx = not ctx.first and ctx.needs_input_grad[0]
+    gx = torch.empty(ctx.x_shape, dtype=torch.float32, device=gp.device) if want_gx else None
+    gw = gscale = gbias = gparam = None
+    gu = None if gu_T is None else gu_T.reshape(B * OH * OW, C)
+    gp = gp.contiguous()
+    for k in range(len(ctx.chunks) - 1, -1, -1):
+      t0, t1 = ctx.chunks[k]
+      n = t1 - t0
+      xin = RematConvBlock.chunk_input(kept, form, geom, t0, t1)
+      cur = conv_currents(xin, ctx.pk, geom, real=(form == "real")).reshape(n, B * OH * OW, C)
+      y, h, _, _ = RematConvBlock.chunk_scan(cur, mean[t0:t1], var[t0:t1], sd, bd, ctx.eps, nrn, tau,
+                                             starts[k], True, False)
+      gs = ops.maxpool2x2_backward_h(h.reshape(n, B, OH, OW, C), nrn.v_threshold, gp[t0:t1])
+      gs = gs.reshape(n, B * OH * OW, C)
+      # the chain: this chunk's gu_T is the gu0 of the chunk after (the block's own for the last)
+      want_gu0 = k > 0 or (ctx.window and ctx.needs_input_grad[13])
+      if tau is None:
+        gy, _, gu = scan_backward(h, None, nrn, ctx.surrogate, None, state=(None, gu, want_gu0), gs=gs)
+      else:
+        gy, part, gu = ops.neuron_backward(h, y, nrn, ctx.surrogate, gs=gs, u0=starts[k], gu_T=gu,
+                                           return_gu0=True)
+        gparam = _accumulate(gparam, part)                    # float64, before neuron_param_grad
+      del gs, y, h
+      gcur, gscale_k, gbias_k = bn_backward(gy, cur, mean[t0:t1], var[t0:t1], scale, ctx.eps)
+      del gy, cur
+      gscale, gbias = _accumulate(gscale, gscale_k), _accumulate(gbias, gbias_k)
+      gcur = gcur.reshape(n * B, OH, OW, C)
+      x4 = xin.to_dense() if form == "bits" else xin.to(torch.float32)
+      gw = _accumulate(gw, ops.conv_weight_grad(x4, gcur, geom))
+      del x4, xin
+      if want_gx:
+        gx[t0:t1] = ops.conv_input_grad(gcur, wq.detach(), geom).reshape((n,) + ctx.x_shape[1:])
+      del gcur
+    gtau = None if tau is None else neuron_param_grad(gparam, tau)
+    gu0 = gu.reshape(B, OH, OW, C) if ctx.window and ctx.needs_input_grad[13] else None
+    return gx, gw, gscale, gbias, None, None, None, None, None, None, None, None, gtau, gu0

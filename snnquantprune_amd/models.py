@@ -397,7 +397,8 @@ class DenseSNN(nn.Module):
     from . import dense_train as dt
     from . import train_forward as fw
     cfg = self.config
-    x = fw.check_call(self, inputs, rng, u_state, online, frames=False, carries=True)
+    x = fw.check_call(self, inputs, rng, u_state, online, frames=False, carries=True,
+                      remat="its residuals are weight-sized, not image-sized (DESIGN.md 18.6)")
     hidden = cfg.hidden if "hidden" in cfg else cfg.channels * 2 * 2
     nout = self.num_classes * 10
     B, steps = x.shape[0], x.shape[1]
@@ -490,6 +491,7 @@ class ConvDenseSNN(nn.Module):
     from . import train_forward as fw
     x = fw.check_call(self, inputs, rng, u_state, online, frames=True, carries=True)
     cfg = self.config
+    remat = cfg.remat if "remat" in cfg else None         # steps per chunk, DESIGN.md 19
     nblocks = cfg.num_conv_blocks if "num_conv_blocks" in cfg else 3
     nout = self.num_classes * 10
     B, steps, H, W = x.shape[:4]
@@ -501,7 +503,7 @@ class ConvDenseSNN(nn.Module):
       return empty, state
     x = x.transpose(0, 1).contiguous()                    # models.py:109, [T, B, H, W, C]
     for i in range(nblocks):                              # models.py:111-147
-      x = fw.conv_block(self, x, i, _layer_bits(cfg, i), first=(i == 0), state=state)
+      x = fw.conv_block(self, x, i, _layer_bits(cfg, i), first=(i == 0), state=state, remat=remat)
     x = flatten_channel_major(x)                          # models.py:189-190
     dense = fw.dense_layer(self, nout, _layer_bits(cfg, nblocks), x.shape[-1])
     mask = (dt.generator_of(rng, x.device), 0)
@@ -635,7 +637,9 @@ class CextNet(nn.Module):
     fused kernels are not used."""
     from . import dense_train as dt
     from . import train_forward as fw
-    x = fw.check_call(self, inputs, rng, u_state, online, frames=True, min_hw=32, gpu=True)
+    x = fw.check_call(self, inputs, rng, u_state, online, frames=True, min_hw=32, gpu=True,
+                      remat="its first block's weight gradient runs the float64 chain of DESIGN.md 12.3, "
+                            "and per-chunk roundings of that chain are not served")
     cfg = self.config
     bits = cfg.quant.bits
     x = x.transpose(0, 1).contiguous()                    # models.py:109, [T, B, H, W, C]

@@ -2372,6 +2372,51 @@ def maxpool2x2_backward(s: torch.Tensor, gp: torch.Tensor) -> torch.Tensor:
 
 
 # ---------------------------------------------------------------------------
+# training of a conv block with rematerialisation (csrc/train_remat.hip)
+# ---------------------------------------------------------------------------
+
+
+def bn_lif_forward(cur: torch.Tensor, mean: torch.Tensor, mul: torch.Tensor, bias: torch.Tensor,
+                   neuron: Neuron, u0: Optional[torch.Tensor] = None, want_h: bool = True,
+                   want_s: bool = True, return_state: bool = False):
+  """The batch-statistics normalisation and lif_forward_save in one pass: raw
+  currents cur float32 [T, ..., C], per-step mean and multiplier [T, C] (conv_train.bn_multiplier),
+  bias [C] -> (h, s) float32 like cur, from u0 [..., C] (None: zeros); h or s is None where it is
+  not wanted, and is then not written.  return_state -> (h, s, u_T).  The normalised currents are
+  never written.  multi_step_LIF only."""
+  cur, mean, mul, bias = _f32c(cur), _f32c(mean), _f32c(mul), _f32c(bias)
+  _require_gpu(cur, mean, mul, bias)
+  T, C = cur.shape[0], cur.shape[-1]
+  step = tuple(cur.shape[1:])
+  if tuple(mean.shape) != (T, C) or tuple(mul.shape) != (T, C) or tuple(bias.shape) != (C,):
+    raise ValueError("bn_lif_forward: mean and mul must be [%d, %d] and bias [%d], got %s, %s, %s"
+                     % (T, C, C, tuple(mean.shape), tuple(mul.shape), tuple(bias.shape)))
+  R = (math.prod(step) // C) if C else 0
+  u0 = _window_state("bn_lif_forward", "u0", u0, step, cur.device)
+  h = torch.empty_like(cur) if want_h else None
+  s = torch.empty_like(cur) if want_s else None
+  u_out = torch.empty(step, dtype=torch.float32, device=cur.device) if return_state else None
+  L.check(L.lib().snnqp_bn_lif_forward_state(
+      _ptr(cur), _ptr(mean), _ptr(mul), _ptr(bias), T, R, C, ctypes.byref(neuron.struct()),
+      _ptr(u0), _ptr(u_out), _ptr(h), _ptr(s), _stream()))
+  return (h, s, u_out) if return_state else (h, s)
+
+
+def maxpool2x2_backward_h(h: torch.Tensor, v_threshold: float, gp: torch.Tensor) -> torch.Tensor:
+  """maxpool2x2_backward with the pool's input s = ((h - v_threshold) >= 0) read from the scan's
+  h [..., H, W, C] by the forward's own compare: no spike raster is written."""
+  h, gp = _f32c(h), _f32c(gp)
+  _require_gpu(h, gp)
+  H, W, C = h.shape[-3:]
+  assert tuple(gp.shape) == tuple(h.shape[:-3]) + (H // 2, W // 2, C), (h.shape, gp.shape)
+  NB = h.numel() // (H * W * C) if H * W * C else 0
+  gs = torch.empty_like(h)
+  L.check(L.lib().snnqp_maxpool2x2_backward_h(_ptr(h), float(v_threshold), _ptr(gp), NB, H, W, C,
+                                              _ptr(gs), _stream()))
+  return gs
+
+
+# ---------------------------------------------------------------------------
 # training of CextNet's gated stages (csrc/train_gate.hip)
 # ---------------------------------------------------------------------------
 

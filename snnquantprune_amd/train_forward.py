@@ -18,13 +18,18 @@ from .quant import DuQ
 _PACKED = (ops.PackedSpikes, ops.PackedFrames, ops.GatedSpikes)
 
 
-def check_call(mod, inputs, rng, u_state, online, frames, min_hw=0, gpu=False, carries=False):
+def check_call(mod, inputs, rng, u_state, online, frames, min_hw=0, gpu=False, carries=False,
+               remat=None):
   """Refuses what training does not support and returns the input tensor.
 
   carries: the model trains over windows of a recording (DenseSNN, ConvDenseSNN) and
   takes a models.StreamState as u_state.  Anything else given as u_state is refused by every
   model, and a StreamState by a model that does not carry (CextNet: its TCJA gates).  No refusal
   touches the state.
+
+  remat: None, or why this model does not serve config.remat -- the key is then
+  refused after every other refusal of the call's arguments; a model that serves it (ConvDenseSNN)
+  has its value checked there, conv_train.check_remat.
 
   frames: the conv models -- a uint8 or float32 [B, T, H, W, C] tensor (of at least min_hw x
   min_hw), looked at before the rng, the config or the parameters, and on the GPU (`gpu`) once
@@ -61,6 +66,7 @@ def check_call(mod, inputs, rng, u_state, online, frames, min_hw=0, gpu=False, c
   if qw is not None and getattr(qw, "func", qw) is not DuQ:
     raise NotImplementedError("training supports the DuQ weight quantiser or none, not %r" % (qw,))
   if frames:
+    _check_remat(mod, remat)
     if gpu:
       ops._require_gpu(inputs)
     return inputs
@@ -69,7 +75,18 @@ def check_call(mod, inputs, rng, u_state, online, frames, min_hw=0, gpu=False, c
   x = _as_input(inputs)
   if x.ndim != 3:
     raise ValueError("DenseSNN expects [B, T, K] inputs, got %s" % (tuple(x.shape),))
+  _check_remat(mod, remat)
   return x
+
+
+def _check_remat(mod, why):
+  """config.remat on a model that does not serve it (`why`) is refused; on one that does, its
+  value is checked.  Nothing is launched and no state is looked at."""
+  if "remat" not in mod.config:
+    return
+  if why is not None:
+    raise NotImplementedError("training %s with config.remat: %s" % (type(mod).__name__, why))
+  ct.check_remat(mod.config.remat)
 
 
 def _transformed_kernel(mod, layer, pk):
@@ -99,12 +116,15 @@ def carry_membrane(state, k, u_T):
     state.membranes[k].copy_(u_T)
 
 
-def conv_block(mod, x, i, bits, pool=2, first=False, real_input=False, wgrad_f64=False, state=None):
+def conv_block(mod, x, i, bits, pool=2, first=False, real_input=False, wgrad_f64=False, state=None,
+               remat=None):
   """Conv block i on x [T, B, H, W, Cin]: QuantConv 3x3, BatchNorm on batch statistics, LIF, the
   2x2 max pool (conv_train.ConvBlock, whose arguments the last four are) -> the pooled spikes.
   Moves the running statistics and sows conv<i>_h, conv<i>_out, bn<i>_mean, bn<i>_var.
   state: a fitted models.StreamState -- the scan starts from state.membranes[i], a constant of this
-  window's gradient, and leaves u_T there."""
+  window's gradient, and leaves u_T there.
+  remat: the steps per chunk of conv_train.RematConvBlock (config.remat), which then
+  is the block; it keeps h and the spikes only for the sow."""
   cfg, C = mod.config, mod.config.channels
   conv = _qconv3x3(cfg, mod.dtype, bits)
   dyn = cfg.neuron_dynamics(dtype=mod.dtype)
@@ -115,10 +135,17 @@ def conv_block(mod, x, i, bits, pool=2, first=False, real_input=False, wgrad_f64
   pk = conv.packed_kernel(cin)
   wq = _transformed_kernel(mod, conv, pk)
   nrn = dyn.neuron(C)
-  y, h, s, mean, var, *u_T = ct.ConvBlock.apply(
-      x, wq, norm.scale_param(C), norm.bias_param(C), pk, geom, nrn, surr,
-      float(norm.epsilon), first, pool, real_input, wgrad_f64, _tau_leaf(mod, dyn, kind),
-      None if state is None else state.membranes[i].detach())
+  u0 = None if state is None else state.membranes[i].detach()
+  if remat is None:
+    y, h, s, mean, var, *u_T = ct.ConvBlock.apply(
+        x, wq, norm.scale_param(C), norm.bias_param(C), pk, geom, nrn, surr,
+        float(norm.epsilon), first, pool, real_input, wgrad_f64, _tau_leaf(mod, dyn, kind), u0)
+  else:
+    assert pool == 2 and not real_input and not wgrad_f64, "RematConvBlock: ConvDenseSNN's blocks only"
+    y, h, s, mean, var, *u_T = ct.RematConvBlock.apply(
+        x, wq, norm.scale_param(C), norm.bias_param(C), pk, geom, nrn, surr,
+        float(norm.epsilon), first, remat, mod.is_mutable_collection("intermediates"),
+        _tau_leaf(mod, dyn, kind), u0)
   if state is not None:
     carry_membrane(state, i, u_T[0])
   norm.update_running(mean, var)

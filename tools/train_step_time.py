@@ -35,6 +35,16 @@ the time per recording, and the allocator's level before and its peak
 nothing else.  Without it the step's line carries the same two figures.
 
   python tools/train_step_time.py --conv --window 5
+
+--conv --remat W [--batch B]: the step with config.remat = W -- the conv blocks keep neither their
+currents nor h and recompute them in the backward in chunks of W steps (conv_train.RematConvBlock,
+DESIGN.md 19), one update per recording with the whole-run gradient.  Prints ms per step, the
+allocator's level before the step, its level after the training forward (what the blocks keep;
+taken over one forward and backward of the model on copies of the parameters) and the step's
+peak, from a cleared packing cache, and nothing else.  The --conv line without the flag carries
+the same three figures.
+
+  python tools/train_step_time.py --conv --remat 5 --batch 16
 """
 import argparse
 import json
@@ -61,6 +71,43 @@ def _time_and_peak(fn, steps, warmup):
   fn()
   torch.cuda.synchronize()
   return ms, (before, torch.cuda.max_memory_allocated())
+
+
+def _after_forward(model, state, batch, tu):
+  """The allocator's growth over one training forward of `model` on gradient-carrying copies of the
+  state's parameters, the logits alive: what the blocks keep for the backward (bytes).  The
+  backward then runs, so the graph is whole."""
+  from snnquantprune_amd import packing
+
+  def leaves(tree):
+    return {k: (leaves(t) if isinstance(t, dict) else t.detach().clone().requires_grad_(True))
+            for k, t in tree.items()}
+
+  params = leaves(state.params["params"])
+  packing.clear_cache()
+  torch.cuda.synchronize()
+  before = torch.cuda.memory_allocated()
+  (logits, _), _ = model.apply({"params": params, "batch_stats": state.batch_stats}, batch["dvs_matrix"],
+                               train=True, rng=0, mutable=["batch_stats"])
+  torch.cuda.synchronize()
+  kept = torch.cuda.memory_allocated() - before
+  tu.mse_loss(logits, batch["label"]).backward()
+  torch.cuda.synchronize()
+  return kept
+
+
+def _remat_line(args, model, batch, box, tu):
+  """The --conv --remat run: one JSON line."""
+  def step():
+    box[0], _ = tu.train_step(box[0], batch, 0, lambda s: 1e-4, 0.0, 0.0, tu.mse_loss)
+
+  ms, peak = _time_and_peak(step, args.steps, args.warmup)
+  kept = _after_forward(model, box[0], batch, tu)
+  print(json.dumps({"workload": "conv_dense_snn_c3_train_step", "batch": args.batch, "frames": args.frames,
+                    "hw": args.hw, "remat": args.remat, "chunks": -(-args.frames // args.remat),
+                    "hip_train_step_ms": round(ms, 3), "hip_memory_before_bytes": peak[0],
+                    "hip_memory_after_forward_bytes": peak[0] + kept, "hip_peak_memory_bytes": peak[1],
+                    "samples_per_s": round(args.batch / ms * 1e3, 1)}))
 
 
 def _window_line(workload, args, batch, box, tu):
@@ -357,6 +404,8 @@ def conv_main(args):
   B, T, HW, C, NB = args.batch, args.frames, args.hw, 128, 3
   cfg = syn.make_config(bits=4, prune_percentage=0.9, channels=C, dropout=0.9)
   cfg.optimizer = "adam"
+  if args.remat:
+    cfg.remat = args.remat
   model = models.ConvDenseSNN(num_classes=11, config=cfg)
   v = syn.conv_net_variables(C, 2, NB, HW, 110, True, 0.9)
   variables = nn.tree_from_numpy(v, dev)
@@ -366,11 +415,14 @@ def conv_main(args):
   box = [tu.create_train_state(variables, cfg, model)]
   if args.window:
     return _window_line("conv_dense_snn_c3_train_windows", args, batch, box, tu)
+  if args.remat:
+    return _remat_line(args, model, batch, box, tu)
 
   def hip_step():
     box[0], _ = tu.train_step(box[0], batch, 0, lambda s: 1e-4, 0.0, 0.0, tu.mse_loss)
 
   hip_ms, hip_peak = _time_and_peak(hip_step, args.steps, args.warmup)
+  hip_kept = _after_forward(model, box[0], batch, tu)
 
   # the A/B of nn.set_train_conv_mfma in one process: the whole step with the connection of conv1
   # and conv2 on the MFMA currents kernel (on) and on the direct-form kernel (off, the launch of
@@ -438,6 +490,7 @@ def conv_main(args):
   eager_ms = _time(eager_step, args.steps, args.warmup)
   print(json.dumps({"workload": "conv_dense_snn_c3_train_step", "batch": B, "frames": T, "hw": HW,
                     "hip_train_step_ms": round(hip_ms, 3), "hip_memory_before_bytes": hip_peak[0],
+                    "hip_memory_after_forward_bytes": hip_peak[0] + hip_kept,
                     "hip_peak_memory_bytes": hip_peak[1],
                     "eager_torch_train_step_ms": round(eager_ms, 3),
                     "speedup_vs_eager": round(eager_ms / hip_ms, 2),
@@ -464,7 +517,11 @@ def main():
                   help="--conv --neuron plif|lif: lanes the scan's `splits` aims at (0: the default)")
   ap.add_argument("--window", type=int, default=0,
                   help="the dense step and --conv: train the recording as windows of this many steps")
+  ap.add_argument("--remat", type=int, default=0,
+                  help="--conv: the step with config.remat = this many steps per chunk")
   args = ap.parse_args()
+  if args.remat < 0 or (args.remat and (not args.conv or args.window or args.neuron is not None)):
+    ap.error("--remat takes a positive chunk length, for --conv without --window and --neuron")
   if args.window < 0 or (args.window and (args.cext or args.neuron is not None)):
     ap.error("--window takes a positive length, for the dense step and for --conv without --neuron")
   dflt = (5, 2, 2) if args.conv or args.cext else (20, 5, 256)
