@@ -258,7 +258,8 @@ typedef struct {
  * snnqp_neuron_backward_workspace_bytes; training over windows of a recording --
  * snnqp_lif_forward_save_state, snnqp_lif_backward_state, snnqp_neuron_forward_save_state,
  * snnqp_neuron_backward_state; training a conv block with rematerialisation --
- * snnqp_bn_lif_forward_state, snnqp_maxpool2x2_backward_h: new entry points, nothing else moves).
+ * snnqp_bn_lif_forward_state, snnqp_maxpool2x2_backward_h; magnitude pruning on the device --
+ * snnqp_magnitude_prune, snnqp_magnitude_prune_workspace_bytes: new entry points, nothing else moves).
  * A binding compares snnqp_version()
  * with the SNNQP_VERSION it was written against and refuses a library of another version (_lib.py does). */
 #define SNNQP_VERSION 507
@@ -1232,6 +1233,30 @@ int snnqp_gate_pool_grad_gate(const float *x, const float *gate, const float *gp
 int snnqp_gate_pool_grad_input(const float *x, const float *gate, const float *gp, const float *gm,
                                int64_t NB, int32_t H, int32_t W, int32_t C, float *gx,
                                snnqp_stream_t stream);
+
+/* ---- magnitude pruning on the device (csrc/prune.hip) ------------------------------------------
+ * replaces: the mask selection of update_prune_mask / the global masks,
+ *           examples/train_inpt_spikingjelly.py:147-157, :174-223, when it runs inside the training
+ *           loop (a prune event) instead of once on the host.
+ * w, mask float32 [n], 0 <= k <= n.  An entry is already pruned iff mask[i] == 0 (either zero);
+ * m = their number.  k <= m: nothing is written.  Otherwise the k - m unpruned entries that are
+ * smallest by the key bits(|w[i]|) read as uint32 (-0 equals +0, denormals in order, Inf above
+ * every finite value, NaN above Inf), ties on the key by ascending index, get mask[i] = +0.0f; no
+ * other word of `mask` is written, whatever value it holds.  Only integer compares and counts
+ * decide: the result is a function of (w, mask, k), bitwise the same on every launch.
+ * One stream, no host read, no synchronisation: m is counted and k <= m decided on the device.  A
+ * three-pass radix select (11 / 11 / 10 bits of the key, LDS histograms flushed with integer
+ * atomics into `workspace`) finds the cut; a last pass in which every workgroup owns a contiguous
+ * index range writes the zeros.  `workspace`: snnqp_magnitude_prune_workspace_bytes(n) bytes,
+ * 4-byte aligned, zeroed by the call on `stream`; its contents afterwards mean nothing.
+ * Refused on the host before any launch (SNNQP_EINVAL): n < 0; k < 0 or k > n; n >= 2^32 (the
+ * counters are 32-bit); a null or misaligned w, mask or workspace with n > 0; workspace_bytes below
+ * the query's answer.  n == 0 returns SNNQP_OK and looks at no pointer.  The grid is a function of n
+ * alone, at most 1024 workgroups: it never passes a launch limit. */
+int snnqp_magnitude_prune(const float *w, float *mask, int64_t n, int64_t k, void *workspace,
+                          int64_t workspace_bytes, snnqp_stream_t stream);
+/* Host only.  The bytes of `workspace` for n entries, or SNNQP_EINVAL for n outside [0, 2^32). */
+int64_t snnqp_magnitude_prune_workspace_bytes(int64_t n);
 
 #ifdef __cplusplus
 }

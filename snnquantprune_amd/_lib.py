@@ -253,6 +253,8 @@ _PROTOTYPES = {
                                           c_int32, c_void_p, c_void_p]),
     "snnqp_gate_pool_grad_input": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_int64, c_int32,
                                            c_int32, c_int32, c_void_p, c_void_p]),
+    "snnqp_magnitude_prune": (c_int, [c_void_p, c_void_p, c_int64, c_int64, c_void_p, c_int64, c_void_p]),
+    "snnqp_magnitude_prune_workspace_bytes": (c_int64, [c_int64]),
 }
 
 EXPORTED_SYMBOLS = tuple(_PROTOTYPES)

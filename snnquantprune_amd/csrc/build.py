@@ -14,7 +14,7 @@ SOURCES = ["api.hip", "runtime.hip", "quantize.hip", "spikes.hip", "frames.hip",
            "conv3x3_bits.hip", "conv3x3_currents.hip",
            "dense_mfma.hip", "dense_wide.hip", "dense_fp6.hip", "fseq_gemm.hip", "conv_gated.hip", "dense_gated.hip",
            "train_dense.hip", "train_neuron.hip", "train_conv.hip", "train_gate.hip",
-           "train_remat.hip"]
+           "train_remat.hip", "prune.hip"]
 FLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC",
          "-ffp-contract=off", "-fno-fast-math", "-fno-slp-vectorize", "-Wall",
          "-Wno-unused-function"]

@@ -2455,3 +2455,52 @@ def gate_pool_grad_input(x: torch.Tensor, gate: torch.Tensor, gp: torch.Tensor,
   L.check(L.lib().snnqp_gate_pool_grad_input(_ptr(x), _ptr(gate), _ptr(gp), _ptr(gm), NB, H, W, C,
                                              _ptr(gx), _stream()))
   return gx
+
+
+# ---------------------------------------------------------------------------
+# magnitude pruning (csrc/prune.hip)
+# ---------------------------------------------------------------------------
+
+
+def magnitude_prune(w: torch.Tensor, mask: torch.Tensor, k: int) -> torch.Tensor:
+  """Prunes `mask` in place up to k zeros and returns it: with m entries already pruned
+  (mask == 0), the k - m unpruned entries smallest by the key bits(|w|) read as uint32, ties by
+  ascending flat index, get mask = 0; k <= m writes nothing, and no other value of `mask` is
+  touched.  w, mask: float32 of one shape (flat or shaped), mask contiguous.  On CUDA tensors one
+  launch sequence on the current stream (snnqp_magnitude_prune: no host read, no sync; the
+  workspace comes from torch's allocator and is not kept); on CPU tensors the same rule in torch
+  ops (a stable sort on the key), for the host logic of the training loop.  Either way `mask`
+  counts as written in place (its version moves)."""
+  if w.dtype != torch.float32 or mask.dtype != torch.float32:
+    raise TypeError("magnitude_prune: float32 tensors (w %s, mask %s)" % (w.dtype, mask.dtype))
+  if tuple(w.shape) != tuple(mask.shape) or w.device != mask.device:
+    raise ValueError("magnitude_prune: w %s on %s, mask %s on %s" % (tuple(w.shape), w.device, tuple(mask.shape),
+                                                                     mask.device))
+  if not mask.is_contiguous():
+    raise ValueError("magnitude_prune: mask is written in place and must be contiguous")
+  n, k = mask.numel(), int(k)
+  if not 0 <= k <= n:
+    raise ValueError("magnitude_prune: k = %d outside [0, n = %d]" % (k, n))
+  w = w.detach().contiguous()
+  m_ = mask.detach()
+  if not mask.is_cuda:
+    if k == 0:
+      return mask
+    key = w.reshape(-1).view(torch.int32) & 0x7FFFFFFF             # non-negative: int32 order = uint32 order
+    flat = m_.reshape(-1)
+    idx = torch.nonzero((flat.view(torch.int32) & 0x7FFFFFFF) != 0).reshape(-1)       # ascending
+    more = k - (n - idx.numel())
+    if more > 0:
+      order = torch.sort(key[idx], stable=True).indices[:more]
+      flat[idx[order]] = 0.0
+    return mask
+  nbytes = L.lib().snnqp_magnitude_prune_workspace_bytes(n)
+  if nbytes < 0:
+    L.check(nbytes)
+  ws = torch.empty(nbytes // 4, dtype=torch.int32, device=mask.device)
+  with torch.cuda.device(mask.device):
+    L.check(L.lib().snnqp_magnitude_prune(_ptr(w), _ptr(m_), n, k, _ptr(ws), nbytes, _stream()))
+  # the library wrote through the pointer: what caches by tensor version (packing.get_packed, the
+  # channel and head plans) has to see an in-place write, as it does after a torch op
+  torch.autograd.graph.increment_version(mask)
+  return mask

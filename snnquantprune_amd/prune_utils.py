@@ -13,6 +13,8 @@ They operate on the `params` tree ({'QuantConv_0': {'kernel', 'DuQ_0', 'prune_0'
 
 from __future__ import annotations
 
+from typing import NamedTuple
+
 import numpy as np
 import torch
 
@@ -88,10 +90,14 @@ def update_quant_params(params, init_fn, bits: int):
   return _map_layers(f, params)
 
 
-def prepare_params(params, config):
-  """The sequence of train_inpt_spikingjelly.py:206-230 for a `config.quant`."""
+def prepare_params(params, config, prune: bool = True):
+  """The sequence of train_inpt_spikingjelly.py:206-230 for a `config.quant`.  prune=False leaves
+  the one-shot masks out (a run with `quant.prune_schedule` prunes in its loop) and gives every
+  layer that has none a mask of ones."""
   q = config.quant
-  if q.prune_percentage > 0.:
+  if not prune:
+    params = ones_masks(params)
+  elif q.prune_percentage > 0.:
     if "prune_global" in q and q.prune_global is False:
       params = update_prune_mask(params, q.prune_percentage)
     else:
@@ -99,6 +105,127 @@ def prepare_params(params, config):
   if "start_epoch" not in q or q.start_epoch == -1:
     params = update_quant_params(params, q.init_fn, q.bits)
   return params
+
+
+# ---------------------------------------------------------------------------
+# Gradual magnitude pruning inside the training loop
+# ---------------------------------------------------------------------------
+#
+# `config.quant.prune_schedule = dict(start_epoch=, end_epoch=, every_steps=, initial=0.0)` with the
+# final sparsity `config.quant.prune_percentage`: the cubic schedule of Zhu & Gupta ("To prune, or
+# not to prune", 2017).  The masks are selected on the device (ops.magnitude_prune); nothing here
+# reads a tensor.
+
+PRUNE_SCHEDULE_KEYS = ("start_epoch", "end_epoch", "every_steps", "initial")
+
+
+class PruneSchedule(NamedTuple):
+  """Steps, not epochs: events at t0, t0 + every, ..., t1."""
+  t0: int
+  t1: int
+  every: int
+  initial: float
+
+  def is_event(self, step: int) -> bool:
+    return self.t0 <= step <= self.t1 and (step - self.t0) % self.every == 0
+
+
+def check_prune_schedule(q):
+  """Refuses a `config.quant` whose prune_schedule cannot be run (ValueError); returns the
+  schedule as a plain dict with `initial` filled in.  Looks at the config alone."""
+  sched = dict(q["prune_schedule"])
+  unknown = sorted(set(sched) - set(PRUNE_SCHEDULE_KEYS))
+  if unknown:
+    raise ValueError("quant.prune_schedule: unknown keys %s (known: %s)" % (unknown, list(PRUNE_SCHEDULE_KEYS)))
+  missing = [k for k in PRUNE_SCHEDULE_KEYS[:3] if k not in sched]
+  if missing:
+    raise ValueError("quant.prune_schedule: missing keys %s" % missing)
+  final = float(q.get("prune_percentage", 0.0))
+  if not 0.0 < final <= 1.0:
+    raise ValueError("quant.prune_schedule needs 0 < quant.prune_percentage <= 1 (the final sparsity), got %r" % final)
+  sched.setdefault("initial", 0.0)
+  if int(sched["every_steps"]) != sched["every_steps"] or sched["every_steps"] < 1:
+    raise ValueError("quant.prune_schedule: every_steps = %r, must be an integer >= 1" % (sched["every_steps"],))
+  if not 0.0 <= float(sched["initial"]) <= final:
+    raise ValueError("quant.prune_schedule: initial = %r outside [0, prune_percentage = %r]" % (sched["initial"], final))
+  if sched["start_epoch"] < 0:
+    raise ValueError("quant.prune_schedule: start_epoch = %r < 0" % (sched["start_epoch"],))
+  if sched["end_epoch"] < sched["start_epoch"]:
+    raise ValueError("quant.prune_schedule: end_epoch = %r before start_epoch = %r"
+                     % (sched["end_epoch"], sched["start_epoch"]))
+  return sched
+
+
+def resolve_prune_schedule(q, steps_per_epoch: int) -> PruneSchedule:
+  """The schedule of `config.quant` in steps.  t1 is the last step t0 + j every_steps that is no
+  later than end_epoch * steps_per_epoch: the last event lands exactly on the final sparsity."""
+  sched = check_prune_schedule(q)
+  every = int(sched["every_steps"])
+  t0 = int(sched["start_epoch"] * steps_per_epoch)
+  end = int(sched["end_epoch"] * steps_per_epoch)
+  return PruneSchedule(t0, t0 + (end - t0) // every * every, every, float(sched["initial"]))
+
+
+def sparsity_at(step: int, schedule: PruneSchedule, final: float) -> float:
+  """s(t) = final + (initial - final) (1 - (t - t0) / (t1 - t0))^3 in Python floats, `initial` up
+  to t0 and `final` from t1 on (t1 == t0: `final`).  Non-decreasing in t."""
+  final = float(final)
+  if step >= schedule.t1:
+    return final
+  if step <= schedule.t0:
+    return schedule.initial
+  left = 1.0 - (step - schedule.t0) / (schedule.t1 - schedule.t0)
+  return min(max(final + (schedule.initial - final) * left ** 3, schedule.initial), final)
+
+
+def ones_masks(params):
+  """A mask of ones on every quantised layer that has none (a new tree; existing masks stay)."""
+  def f(x):
+    if "prune_0" in x:
+      return x
+    y = dict(x)
+    y["prune_0"] = {"mask": torch.ones_like(x["kernel"])}
+    return y
+  return _map_layers(f, params)
+
+
+def prune_event(params, sparsity: float, global_: bool = True) -> None:
+  """One prune event at `sparsity`: the masks of the quantised layers of `params`,
+  in tree order, grow to int(count * sparsity) zeros by the rule of ops.magnitude_prune -- over
+  the concatenation of all kernels (global_, one launch sequence) or layer by layer.  The masks
+  are written INTO the leaves the optimiser holds (its moments stay); an entry already pruned stays
+  pruned whatever its kernel value has become.  Everything stays on the kernels' device: no host
+  read, nothing returned.  Every rank of a data-parallel run holds the same kernels and masks and
+  the rule is a function of their values alone, so each rank prunes for itself: no collective."""
+  from . import ops
+  layers = _layers(params)
+  for l in layers:
+    if "prune_0" not in l:
+      raise ValueError("prune_event: a quantised layer without a prune_0/mask leaf")
+  if not layers:
+    return
+  with torch.no_grad():
+    if not global_:
+      for l in layers:
+        mask = l["prune_0"]["mask"]
+        ops.magnitude_prune(l["kernel"].detach().to(torch.float32), mask, int(mask.numel() * sparsity))
+      return
+    w = torch.cat([l["kernel"].detach().to(torch.float32).reshape(-1) for l in layers])
+    m = torch.cat([l["prune_0"]["mask"].detach().reshape(-1) for l in layers])
+    ops.magnitude_prune(w, m, int(m.numel() * sparsity))
+    off = 0
+    for l in layers:
+      mask = l["prune_0"]["mask"]
+      mask.copy_(m[off:off + mask.numel()].reshape(mask.shape))
+      off += mask.numel()
+
+
+def mask_zeros(params):
+  """(zeros, weights) of the masks of `params`: zeros a 0-d int64 tensor on the masks' device (the
+  caller reads it when it logs), weights a Python int."""
+  layers = _layers(params)
+  zeros = sum((l["prune_0"]["mask"] == 0).sum() for l in layers)
+  return zeros, sum(int(l["prune_0"]["mask"].numel()) for l in layers)
 
 
 # ---------------------------------------------------------------------------

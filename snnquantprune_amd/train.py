@@ -19,6 +19,14 @@ CONFIG.py defines get_config() as for eval.py, with the reference's training key
 eval_dataset (event or image sources, input_pipeline.py; images: encoding, image_layout), batch_size, eval_batch_size, num_epochs,
 num_train_steps, steps_per_eval, learning_rate, warmup_epochs, optimizer, weight_decay,
 smoothing, log_every_steps, checkpoint_every_epochs, pretrained, quant.start_epoch.
+
+`quant.prune_schedule = dict(start_epoch=, end_epoch=, every_steps=, initial=0.0)` (optional; this
+port's own key) prunes gradually inside the loop instead of once at load: at the steps
+t0, t0 + every_steps, ..., t1 the masks grow, by magnitude and on the device, to the cubic
+schedule's sparsity, which reaches `quant.prune_percentage` at t1; the event runs in front of the
+step's train_step and is recorded as {"step", "event": "prune", "sparsity", "zeros", "weights"}.
+An evaluation can be `best` only once the event at t1 has run.  Every rank holds the same weights
+and the selection is deterministic, so each rank prunes for itself and no collective is added.
 """
 
 from __future__ import annotations
@@ -97,7 +105,9 @@ def _load_pretrained(path: str, config, device):
   tree = checkpoint.load_torch_checkpoint(path) if path.endswith(".pth") \
       else checkpoint.load_flax_checkpoint(path)
   variables = nn.tree_from_numpy(tree, device)
-  variables["params"] = prune_utils.prepare_params(variables["params"], config)
+  # with a prune schedule the loop prunes: no one-shot masks at load
+  variables["params"] = prune_utils.prepare_params(variables["params"], config,
+                                                   prune="prune_schedule" not in config.quant)
   logging.info("Successfully restored model from: %s", path)
   return variables
 
@@ -105,6 +115,10 @@ def _load_pretrained(path: str, config, device):
 def _run(config, workdir: str, model, source, eval_source, device):
   if "online" in config:
     raise NotImplementedError("the online branch of train_step is not supported")
+  from . import prune_utils
+  scheduled = "prune_schedule" in config.get("quant", {})
+  if scheduled:
+    prune_utils.check_prune_schedule(config.quant)                  # refusals before anything is loaded
   world = int(os.environ.get("WORLD_SIZE", "1"))
   for size in (config.batch_size, config.eval_batch_size):        # train.py:96-98
     if size % world > 0:
@@ -189,13 +203,19 @@ def _run(config, workdir: str, model, source, eval_source, device):
   q = config.get("quant", {})
   quant_step = q.start_epoch * steps_per_epoch if "start_epoch" in q else None
   quant_is_duq = "DuQ" in str(q.get("weight", ""))
+  # Gradual pruning: a prune event is a function of the step and of the kernels and
+  # masks alone, both checkpointed, so a resumed run repeats the events from its checkpoint on
+  # (_Records.rewind) and continues bit for bit.  Every rank prunes its own, identical, copy.
+  prune_sched = prune_utils.resolve_prune_schedule(q, steps_per_epoch) if scheduled else None
 
   def evaluate(step, epochs, record):
     summary, _, _ = eval_pass(state, eval_iter, steps_per_eval, config, world)
     summary = dict(step=step, epoch=epochs, **summary)
-    # the epoch just finished is epochs - 1, counted from 0 as :405 counts it
+    # the epoch just finished is epochs - 1, counted from 0 as :405 counts it; under a prune
+    # schedule a model that is not yet at the final sparsity must not win
     summary["best"] = bool(epochs > 0 and summary["accuracy"] > eval_best
-                           and ("start_epoch" not in q or epochs - 1 > q.start_epoch))
+                           and ("start_epoch" not in q or epochs - 1 > q.start_epoch)
+                           and (prune_sched is None or step > prune_sched.t1))
     if record:
       writer_eval.write(summary)
     return summary
@@ -207,6 +227,13 @@ def _run(config, workdir: str, model, source, eval_source, device):
   train_metrics = []
   last_t, last_step = time.time(), step_offset
   for step in range(step_offset, num_steps):
+    if prune_sched is not None and prune_sched.is_event(step):
+      sparsity = prune_utils.sparsity_at(step, prune_sched, q.prune_percentage)
+      prune_utils.prune_event(state.params["params"], sparsity, q.get("prune_global", True) is not False)
+      zeros, weights = prune_utils.mask_zeros(state.params["params"])
+      zeros = int(zeros)                                            # the event's read, as a log point's
+      logging.info("Prune event at step %d: sparsity %.4f, %d of %d weights pruned", step, sparsity, zeros, weights)
+      writer_train.write({"step": step, "event": "prune", "sparsity": sparsity, "zeros": zeros, "weights": weights})
     if step == quant_step and quant_is_duq:
       logging.info("Quantization start.")
       _start_quantisation(state.params["params"], config)
