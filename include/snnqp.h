@@ -248,7 +248,7 @@ typedef struct {
  * CextNet's gated stages --
  * snnqp_gate_pool_grad_gate, snnqp_gate_pool_grad_input, snnqp_conv_weight_grad_f64,
  * snnqp_conv_weight_grad_f64_workspace_bytes; the batched event front end snnqp_events_bin and its augmenting
- * form snnqp_events_bin_aug with snnqp_event_aug_t; the host-side
+ * form snnqp_events_bin_aug with snnqp_event_aug_t and its mixing form snnqp_events_bin_mix; the host-side
  * query snnqp_conv_float_form; the host-side plan queries snnqp_conv_gated_plan,
  * snnqp_dense_gated_plan, snnqp_dense_wide_plan, snnqp_dense_fp6_plan, snnqp_dense_mfma_plan;
  * streaming inference --
@@ -960,6 +960,38 @@ int snnqp_events_bin_aug(const uint32_t *addr, const int32_t *times, const int64
                          const int32_t *sample, const int32_t *start, int32_t B, int mode, int32_t T,
                          int32_t step_us, int32_t H, int32_t W, float scale, const snnqp_event_aug_t *aug,
                          void *out, int out_type, int32_t *flags, snnqp_stream_t stream);
+/* replaces: nothing in the reference; mixing two recordings (EventMix, the CutMix branch of NDA):
+ *           a box of row b's space-time volume is taken from a partner sample, inside
+ *           snnqp_events_bin_aug's launch, and the events of either that survive are counted.
+ * Arguments, checks, formats and flags are snnqp_events_bin_aug's (aug may be null: the identity), and
+ * sample2  int32 [B], nullable: the partner sample of each row; a value outside [0, S), or a null
+ *          array, leaves the row unmixed: the bytes of snnqp_events_bin_aug and counts[b][1] += 0
+ * start2   int32 [B]: the partner's window origin, mode 1 only
+ * aug2     [B] records, 4-byte aligned, nullable (the identity): row b's partner is decoded under aug2[b]
+ * box      int32 [B][6]: x0, y0, x1, y1, g0, g1 -- final frame pixels and frames, half-open, compared
+ *          as signed 32-bit values, whatever they hold; empty when x1 <= x0, y1 <= y0 or g1 <= g0
+ * counts   int64 [B][2], 8-byte aligned, nullable, zeroed by the caller: counts[b][0] += the events
+ *          of sample[b], counts[b][1] += the events of sample2[b] that reached the count of rule 7
+ *          (before any saturation), over all frames of row b
+ * Frame f of a mixed row b is the sum of two slices, each that of its own untouched sample (number
+ * mode cuts each sample's own equal counts; time mode searches from start[b] and start2[b]):
+ *   - sample[b]'s slice of frame f: every event passes rules 1-6 of aug[b] and is then dropped if
+ *     x0 <= x < x1 and y0 <= y < y1 and g0 <= f < g1;
+ *   - sample2[b]'s slice of frame f, read only when g0 <= f < g1 and aug2[b] does not empty f: every
+ *     event passes rules 1-6 of aug2[b] (rule 5 hashes its index within sample2[b]) and is then
+ *     dropped unless x0 <= x < x1 and y0 <= y < y1.
+ *   7. counted as snnqp_events_bin counts it: the sum is exact before it saturates, the same flags.
+ * Integer adds commute: two launches give the same bytes and the same counts.
+ * SNNQP_EINVAL, on the host, before anything is launched: snnqp_events_bin's refusals, sample2 with a
+ * null box, and in mode 1 sample2 with a null start2.  B == 0 or T == 0 returns SNNQP_OK without a
+ * launch.  Whatever the records and boxes hold, the launch reads them, sample2, start2 and the events
+ * of the two samples' slices, and writes `out`, `flags` and `counts` only. */
+int snnqp_events_bin_mix(const uint32_t *addr, const int32_t *times, const int64_t *offsets, int32_t S,
+                         const int32_t *sample, const int32_t *start, const snnqp_event_aug_t *aug,
+                         const int32_t *sample2, const int32_t *start2, const snnqp_event_aug_t *aug2,
+                         const int32_t *box, int64_t *counts, int32_t B, int mode, int32_t T, int32_t step_us,
+                         int32_t H, int32_t W, float scale, void *out, int out_type, int32_t *flags,
+                         snnqp_stream_t stream);
 /* replaces: the `mnist` branch of examples/input_pipeline.py:286-296 (static images, Poisson-
  *           encoded into num_frames count frames) over a whole batch, in one launch: B rows of a
  *           device-resident uint8 image set -> [B][T][K] counts or spikes.

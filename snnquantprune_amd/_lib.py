@@ -196,6 +196,9 @@ _PROTOTYPES = {
     "snnqp_events_bin_aug": (c_int, [c_void_p, c_void_p, c_void_p, c_int32, c_void_p, c_void_p, c_int32, c_int,
                                      c_int32, c_int32, c_int32, c_int32, c_float, c_void_p, c_void_p, c_int,
                                      c_void_p, c_void_p]),
+    "snnqp_events_bin_mix": (c_int, [c_void_p, c_void_p, c_void_p, c_int32, c_void_p, c_void_p, c_void_p, c_void_p,
+                                     c_void_p, c_void_p, c_void_p, c_void_p, c_int32, c_int, c_int32, c_int32,
+                                     c_int32, c_int32, c_float, c_void_p, c_int, c_void_p, c_void_p]),
     "snnqp_rate_encode": (c_int, [c_void_p, c_int32, c_void_p, c_void_p, c_int32, c_int32, c_int32, c_uint32,
                                   c_uint32, c_void_p, c_int, c_void_p, c_int, c_int64, c_int64, c_void_p]),
     "snnqp_density": (c_int, [c_void_p, c_int, c_int64, c_int64, c_int32, c_void_p, c_void_p]),

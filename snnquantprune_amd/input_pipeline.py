@@ -121,9 +121,24 @@ class EventPlan:
     drop_frames    whole frames: n uniform on 0 .. drop_frames, then f0 on 0 .. T - n
   Integers are 62-bit draws reduced modulo the range, as the origins are.  `augmented_batches`
   yields the batch's ops.EventAugment beside the indices and origins; `batches` yields the pairs.
+
+  Mixing (train split only).  `config.mix = dict(prob=p, size=s[, frames=m])` mixes
+  row b of a batch with row (b + 1) mod per of the same batch -- no second permutation --, which
+  keeps its own origin and its own augmentation record: inside the row's box the partner's events
+  are counted, outside it the row's own.  p and s lie in [0, 1], m is a whole number in 0..T, and
+  the per-rank batch must hold at least 2 rows.  The eval split ignores the key and an absent key
+  draws nothing.  Otherwise every batch -- a skipped one too -- draws after its augmentation, one
+  array of `per` values per line:
+    mixed          1 draw (float64 uniform < p)
+    box            width uniform on 0 .. floor(s * W), height on 0 .. floor(s * H), then x0 on
+                   0 .. W - width, y0 on 0 .. H - height (the cutout's draws)
+    frames         with `frames` only: n uniform on 0 .. m, then g0 on 0 .. T - n; without it the
+                   box spans all T frames
+  `mixed_batches` yields the batch's ops.EventMix as a fourth element.
   """
 
   AUGMENT_KEYS = ("flip_x", "flip_y", "swap_polarity", "shift", "drop_event", "cutout", "drop_frames")
+  MIX_KEYS = ("prob", "size", "frames")
 
   def __init__(self, config, sensor_size, counts_per_rank: int, train: bool, rank: int = 0, world: int = 1):
     self.train = bool(train)
@@ -164,6 +179,41 @@ class EventPlan:
     self.gen.manual_seed(self.seed)
     aug = self._augment_config(_cfg(config, "augment"))            # validated for either split
     self.augment = {k: v for k, v in aug.items() if v} if self.train else {}
+    mix = self._mix_config(_cfg(config, "mix"))                    # validated for either split
+    self.mix = mix if self.train else None
+    if self.mix is not None and self.per < 2:
+      raise ValueError("mix pairs every row with the next row of its batch: batch_size %d over %d processes "
+                       "leaves %d row per process, it needs at least 2" % (total, world, self.per))
+
+  def _mix_config(self, mix):
+    if mix is None:
+      return None
+    form = "mix must be a mapping of prob, size and optionally frames"
+    if not hasattr(mix, "keys"):
+      raise ValueError("%s, got %r" % (form, mix))
+    keys = set(mix.keys())
+    if not {"prob", "size"} <= keys <= set(self.MIX_KEYS):
+      raise ValueError("%s, got the keys %s" % (form, sorted(keys, key=str)))
+    out = {}
+    for k in ("prob", "size"):
+      v = mix[k]
+      try:
+        ok = not isinstance(v, bool) and 0.0 <= float(v) <= 1.0      # (a NaN fails both comparisons)
+      except (TypeError, ValueError):
+        ok = False
+      if not ok:
+        raise ValueError("mix.%s must lie in [0, 1], got %r" % (k, v))
+      out[k] = float(v)
+    if "frames" in keys:
+      v = mix["frames"]
+      try:
+        ok = not isinstance(v, bool) and v == int(v) and 0 <= int(v) <= self.T
+      except (TypeError, ValueError, OverflowError):
+        ok = False
+      if not ok:
+        raise ValueError("mix.frames must be a whole number in 0..%d, got %r" % (self.T, v))
+      out["frames"] = int(v)
+    return out
 
   def _augment_config(self, aug) -> Dict[str, Any]:
     if aug is None:
@@ -227,6 +277,31 @@ class EventPlan:
       kw["frames"] = np.stack([f0, f0 + n], 1)
     return ops.EventAugment(self.per, **kw)
 
+  def draw_mix(self, idx, starts, aug):
+    """The batch's ops.EventMix in the order the class docstring fixes, or None for a plan that does
+    not mix (nothing is drawn then).  The partner of row b is row (b + 1) mod per: its index, its
+    origin and its record of `aug` are the batch's own, rolled by one."""
+    m = self.mix
+    if m is None:
+      return None
+    mixed = self._uniform() < m["prob"]
+    w = self._uniform_int(0, int(np.floor(m["size"] * self.W)))
+    h = self._uniform_int(0, int(np.floor(m["size"] * self.H)))
+    x0, y0 = self._uniform_int(0, self.W - w), self._uniform_int(0, self.H - h)
+    if "frames" in m:
+      n = self._uniform_int(0, m["frames"])
+      g0 = self._uniform_int(0, self.T - n)
+      g1 = g0 + n
+    else:
+      g0, g1 = np.zeros(self.per, np.int64), np.full(self.per, self.T, np.int64)
+    roll = lambda a: np.roll(np.asarray(a), -1, axis=0)                           # noqa: E731
+    aug2 = None if aug is None else ops.EventAugment(
+        self.per, flip_x=roll(aug.flip_x), flip_y=roll(aug.flip_y), swap_polarity=roll(aug.swap_polarity),
+        dx=roll(aug.dx), dy=roll(aug.dy), cutout=roll(aug.cutout), frames=roll(aug.frames),
+        drop_below=roll(aug.drop_below), seed=roll(aug.seed))
+    return ops.EventMix(self.per, partner=np.where(mixed, roll(idx), -1), start=None if starts is None else roll(starts),
+                        box=np.stack([x0, y0, x0 + w, y0 + h, g0, g1], 1), augment=aug2)
+
   def start_range(self, t_min, t_max):
     """[tbegin, tend] of the window origin, both inclusive (:76-77)."""
     t_min, t_max = np.asarray(t_min, np.int64), np.asarray(t_max, np.int64)
@@ -250,6 +325,12 @@ class EventPlan:
   def augmented_batches(self, t_min=None, t_max=None, skip: int = 0):
     """`batches` with each batch's ops.EventAugment as a third element (None when the plan does not
     augment), drawn after the batch's origins -- for a skipped batch too."""
+    for idx, starts, aug, _ in self.mixed_batches(t_min, t_max, skip):
+      yield idx, starts, aug
+
+  def mixed_batches(self, t_min=None, t_max=None, skip: int = 0):
+    """`augmented_batches` with each batch's ops.EventMix as a fourth element (None when the plan
+    does not mix), drawn after the batch's augmentation -- for a skipped batch too."""
     skip = int(skip)
     if skip < 0:
       raise ValueError("skip must be >= 0, got %d" % skip)
@@ -266,10 +347,11 @@ class EventPlan:
         starts = self.draw_starts(np.asarray(t_min)[idx], np.asarray(t_max)[idx]) \
             if self.split_by == "time" else None
         aug = self.draw_augment()
+        mix = self.draw_mix(idx, starts, aug)
         if skip > 0:
           skip -= 1
           continue
-        yield idx, starts, aug
+        yield idx, starts, aug, mix
 
 
 def create_event_split(data, config, train: bool, rank: int = 0, world: int = 1,
@@ -291,12 +373,22 @@ def create_event_split(data, config, train: bool, rank: int = 0, world: int = 1,
   divisor = None if plan.divisor is None else torch.full((), float(plan.divisor), dtype=torch.float32, device=device)
 
   def gen():
-    for idx, starts, aug in plan.augmented_batches(events.t_min, events.t_max, skip):
+    for idx, starts, aug, mix in plan.mixed_batches(events.t_min, events.t_max, skip):
       x = ops.events_bin(events, idx, plan.T, plan.H, plan.W, mode=plan.split_by, start=starts,
-                         step_us=plan.step_us, scale=plan.scale, fmt=plan.fmt, augment=aug)
+                         step_us=plan.step_us, scale=plan.scale, fmt=plan.fmt, augment=aug, mix=mix)
+      if mix is not None:
+        x, counts = x
       if plan.divisor is not None:
         x = x.to(torch.float32) / divisor                          # :134-137
-      yield {"dvs_matrix": x, "label": labels[torch.from_numpy(idx).to(device)]}
+      batch = {"dvs_matrix": x, "label": labels[torch.from_numpy(idx).to(device)]}
+      if mix is not None:
+        # the partner's label (an unmixed row: its own) and the share of the row's own events among
+        # those counted, nA / (nA + nB) in float64, rounded once; 1 where nothing was counted
+        batch["label_mix"] = labels[torch.from_numpy(np.where(mix.partner >= 0, mix.partner, idx)).to(device)]
+        n = counts.to(torch.float64)
+        total = n.sum(1)
+        batch["mix_weight"] = torch.where(total > 0, n[:, 0] / total, torch.ones_like(total)).to(torch.float32)
+      yield batch
   return gen()
 
 
@@ -354,6 +446,8 @@ class ImagePlan:
     aug = _cfg(config, "augment")
     if aug is not None and not (hasattr(aug, "keys") and len(aug.keys()) == 0):
       raise ValueError("augment is for event sources: an image source has no event to flip, shift or drop")
+    if _cfg(config, "mix") is not None:
+      raise ValueError("mix is for event sources: an image source has no events of two recordings to mix")
     total = int(_cfg(config, "batch_size" if train else "eval_batch_size"))
     self.per = total // world
     self.n = int(counts_per_rank)
@@ -438,6 +532,8 @@ def create_split(source, config, train: bool, cache: bool, rank: int = 0, world:
     return create_event_split(load_source(source), config, train, rank, world, device, skip)
   if is_image_source(source):
     return create_image_split(load_source(source), config, train, rank, world, device, skip)
+  if _cfg(config, "mix") is not None:
+    raise ValueError("mix is for event sources: a frame source holds counts, which no longer know their events")
   if train:
     raise NotImplementedError("the training split (shuffle, augmentation) is out of scope")
   data = load_source(source)

@@ -1791,9 +1791,63 @@ class EventAugment:
     return "EventAugment(%d rows)" % self.rows
 
 
+class EventMix:
+  """Per-row mixing of one `events_bin` batch of `rows` rows with a partner sample each
+  (snnqp_events_bin_mix, include/snnqp.h): inside the row's box the partner's events
+  are counted, outside it the row's own.  Host arrays with one entry per row:
+
+    partner   the partner sample, in [0, S) (checked where S is known, in `events_bin`), or -1 for
+              a row that is not mixed
+    start     the partner's window origin, int32; time mode only (None in number mode)
+    box       [rows, 6] (x0, y0, x1, y1, g0, g1), int32: final frame pixels and frames, half-open,
+              0 <= g0 <= g1 (<= T is checked where T is known, in `records`); empty when
+              x1 <= x0, y1 <= y0 or g1 <= g0
+    augment   the partner rows' EventAugment (their flips, shifts, drops ...), or None
+
+  Everything is validated here, on the host; the arrays are kept as int64 attributes."""
+
+  def __init__(self, rows: int, *, partner, start=None, box, augment: Optional[EventAugment] = None):
+    import numpy as np
+    self.rows = B = int(rows)
+    if B < 0:
+      raise ValueError("rows must be >= 0, got %d" % B)
+    self.partner = _event_rows(partner, "partner", B, lo=-1).numpy().astype(np.int64)
+    self.start = None if start is None else _event_rows(start, "mix start", B).numpy().astype(np.int64)
+    a = _host_array(box, "box")
+    if a.shape != (B, 6):
+      raise ValueError("box must have shape %s, (x0, y0, x1, y1, g0, g1) per batch row, got %s" % ((B, 6), a.shape))
+    if a.dtype == np.uint64 and a.size and int(a.max()) > 2 ** 31 - 1:
+      raise ValueError("box must lie in %d..%d, got up to %d" % (-2 ** 31, 2 ** 31 - 1, int(a.max())))
+    a = a.astype(np.int64)
+    if a.size and (int(a.min()) < -2 ** 31 or int(a.max()) > 2 ** 31 - 1):
+      raise ValueError("box must lie in %d..%d, got %d..%d" % (-2 ** 31, 2 ** 31 - 1, int(a.min()), int(a.max())))
+    if np.any(a[:, 4] < 0) or np.any(a[:, 4] > a[:, 5]):
+      raise ValueError("box frames must be (g0, g1) with 0 <= g0 <= g1, got %s" % a[:, 4:].tolist())
+    self.box = a
+    if augment is not None:
+      if not isinstance(augment, EventAugment):
+        raise ValueError("a mix's augment must be an ops.EventAugment, got %r" % (type(augment).__name__,))
+      if augment.rows != B:
+        raise ValueError("a mix's augment must have one record per batch row (%d), got %d" % (B, augment.rows))
+    self.augment = augment
+
+  def records(self, T: int):
+    """(partner int32 [rows], box int32 [rows, 6], the partners' aug records int32 [rows, 12] or
+    None) as the launch reads them.  Refuses a box or a frame range that ends beyond T."""
+    import numpy as np
+    if self.rows and int(self.box[:, 5].max()) > int(T):
+      raise ValueError("box frames must end at or before T = %d, got g1 up to %d" % (T, int(self.box[:, 5].max())))
+    return (self.partner.astype(np.int32), self.box.astype(np.int32),
+            None if self.augment is None else self.augment.records(T))
+
+  def __repr__(self):
+    return "EventMix(%d rows, %d mixed)" % (self.rows, int((self.partner >= 0).sum()))
+
+
 def events_bin(events: EventSet, sample, T: int, H: int, W: int, *, mode, start=None, step_us=None,
                scale: float = 1.0, fmt: Optional[int] = None, flags: Optional[torch.Tensor] = None,
-               out: Optional[torch.Tensor] = None, augment: Optional[EventAugment] = None):
+               out: Optional[torch.Tensor] = None, augment: Optional[EventAugment] = None,
+               mix: Optional[EventMix] = None):
   """One launch (snnqp_events_bin): row b of the batch decodes sample[b] of `events` into T frames of
   H x W x 2 counts.  mode "number": equal-count slices (input_pipeline.py:142-219); mode "time":
   windows of step_us microseconds from start[b], both edges strict (:63-131).  Returns uint8
@@ -1804,7 +1858,11 @@ def events_bin(events: EventSet, sample, T: int, H: int, W: int, *, mode, start=
   [B, T, units] --, every element of it.  `augment`, an EventAugment of B rows, makes it the
   augmenting launch (snnqp_events_bin_aug): flips, shift, cutout, hashed drops, polarity swap and
   emptied frames per row, its records in the same upload as `sample` and `start`; None is the
-  plain launch."""
+  plain launch.  `mix`, an EventMix of B rows, makes it the mixing launch (snnqp_events_bin_mix):
+  inside each mixed row's box the partner sample's events are counted, under the mix's own augment;
+  everything still goes up in that one upload, and the call returns (frames, counts) with counts
+  an int64 [B, 2] device tensor -- the row's own and its partner's events that were counted --,
+  which nothing here reads back."""
   m = EVENT_MODES.get(mode, mode)
   if m not in (0, 1):
     raise ValueError("mode must be 'number' or 'time', got %r" % (mode,))
@@ -1830,6 +1888,17 @@ def events_bin(events: EventSet, sample, T: int, H: int, W: int, *, mode, start=
     if augment.rows != B:
       raise ValueError("augment must have one record per batch row (%d), got %d" % (B, augment.rows))
     records = augment.records(T)
+  if mix is not None:
+    import numpy as np
+    if not isinstance(mix, EventMix):
+      raise ValueError("mix must be an ops.EventMix, got %r" % (type(mix).__name__,))
+    if mix.rows != B:
+      raise ValueError("mix must have one entry per batch row (%d), got %d" % (B, mix.rows))
+    if B and int(mix.partner.max()) >= events.num_samples:
+      raise ValueError("mix partner must lie in -1..%d, got up to %d" % (events.num_samples - 1, int(mix.partner.max())))
+    if m == 1 and mix.start is None:
+      raise ValueError("time mode needs the mix's start: the partners' window origins")
+    partner, box, records2 = mix.records(T)
   _require_gpu(events.addr, flags, out)
   dev = events.device
   packed = fmt in (L.EV1, L.EV4)
@@ -1839,6 +1908,26 @@ def events_bin(events: EventSet, sample, T: int, H: int, W: int, *, mode, start=
     out = torch.empty(shape, dtype=dtype, device=dev)
   elif tuple(out.shape) != shape or out.dtype != dtype or not out.is_contiguous():
     raise ValueError("out must be a contiguous %s tensor of shape %s" % (dtype, shape))
+  if mix is not None:
+    counts = torch.zeros((B, 2), dtype=torch.int64, device=dev)
+    if B and T:
+      parts, at, n = [], {}, 0
+      for name, part in (("rows", rows), ("start", starts), ("aug", None if augment is None else records),
+                         ("partner", partner), ("start2", mix.start if m == 1 else None), ("box", box), ("aug2", records2)):
+        if part is not None:
+          if not isinstance(part, torch.Tensor):
+            part = torch.from_numpy(np.ascontiguousarray(part, dtype=np.int32))
+          parts.append(part.reshape(-1))
+          at[name] = (n, n + part.numel())
+          n += part.numel()
+      both = torch.cat(parts).to(dev)                                              # one upload
+      arg = lambda name: _ptr(both[at[name][0]:at[name][1]]) if name in at else None
+      L.check(L.lib().snnqp_events_bin_mix(_ptr(events._addr_arg), _ptr(events._times_arg), _ptr(events.offsets),
+                                           events.num_samples, arg("rows"), arg("start"), arg("aug"), arg("partner"),
+                                           arg("start2"), arg("aug2"), arg("box"), _ptr(counts), B, m, T,
+                                           int(step_us) if m == 1 else 0, H, W, float(scale), _ptr(out),
+                                           fmt if packed else L.U8, _ptr(flags), _stream()))
+    return (PackedFrames(out, H, W, fmt) if packed else out), counts
   if B and T and augment is not None:
     host = torch.cat([rows] + ([] if starts is None else [starts]) + [torch.from_numpy(records).reshape(-1)])
     both = host.to(dev)                                                          # one upload

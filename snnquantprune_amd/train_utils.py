@@ -36,14 +36,32 @@ def onehot(labels, num_classes):
   return torch.nn.functional.one_hot(labels, num_classes).to(torch.float32)
 
 
+def mixed_targets(labels, labels2, weight, num_classes):
+  """The soft target of mixed recordings: w * onehot(y) + (1 - w) * onehot(y') as
+  float32 [B, classes], w the row's `weight` (the share of its own events among those counted)."""
+  w = torch.as_tensor(weight).to(torch.float32).reshape(-1, 1)
+  a, b = onehot(labels, num_classes), onehot(labels2, num_classes)
+  return w.to(a.device) * a + (1 - w.to(a.device)) * b.to(a.device)
+
+
+def _targets(logits, labels):
+  """The target rows of a loss: the one-hot of integer labels, or a 2-D float `labels` -- a soft
+  target, [B, classes] -- as it is."""
+  if isinstance(labels, torch.Tensor) and labels.dim() == 2 and labels.is_floating_point():
+    if tuple(labels.shape) != tuple(logits.shape):
+      raise ValueError("a soft target must have the logits' shape %s, got %s" % (tuple(logits.shape), tuple(labels.shape)))
+    return labels.to(logits.device)
+  return onehot(labels, logits.shape[1]).to(logits.device)
+
+
 def cross_entropy_loss(logits, labels, smoothing=0):
-  oh = onehot(labels, logits.shape[1]).to(logits.device)
+  oh = _targets(logits, labels)
   oh = oh * (1 - smoothing) + smoothing / oh.shape[1]
   return torch.mean(-(oh * torch.log_softmax(logits, -1)).sum(-1))
 
 
 def mse_loss(logits, labels, smoothing=0, T=1):
-  oh = onehot(labels, logits.shape[1]).to(logits.device)
+  oh = _targets(logits, labels)
   oh = oh * (1 - smoothing) + smoothing / oh.shape[1]
   return torch.mean(torch.square(logits / T - oh))
 
@@ -159,7 +177,12 @@ def train_step(state: TrainState, batch, rng, learning_rate_fn, weight_decay, sm
       {"params": ptree, "batch_stats": state.batch_stats}, batch["dvs_matrix"],
       trgt=batch["label"], train=True, rng=rng, mutable=["batch_stats"], rngs={"dropout": rng},
       **carried)
-  loss = loss_type(logits, batch["label"], smoothing)
+  # a mixed batch (input_pipeline, config.mix): the loss is against the soft target of both labels;
+  # the model's trgt= and the accuracy stay with the row's own label
+  target = batch["label"]
+  if "label_mix" in batch and "mix_weight" in batch:
+    target = mixed_targets(batch["label"], batch["label_mix"], batch["mix_weight"], logits.shape[1]).to(logits.device)
+  loss = loss_type(logits, target, smoothing)
   if weight_decay:
     loss = loss + weight_decay * weight_decay_fn(ptree)
   loss.backward()
@@ -176,6 +199,8 @@ def train_step(state: TrainState, batch, rng, learning_rate_fn, weight_decay, sm
       p.grad = None
   logits = logits.detach()
   metrics = compute_metrics(logits, batch["label"], smoothing, loss_type)
+  if target is not batch["label"]:
+    metrics["loss"] = loss_type(logits, target, smoothing)
   metrics["learning_rate"] = lr
   metrics["logits"] = logits
   # the running statistics the apply returned (each rank keeps its own, as the reference does

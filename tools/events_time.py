@@ -13,8 +13,17 @@ polarity swap with probability 1/2, shifts of up to 8 pixels, a drop probability
 [0, 0.5], a cutout of up to a quarter of a side, up to two emptied frames.  Checks first that an
 identity record gives the plain launch's bytes.
 
+--mix times the mixing launch (ops.events_bin(mix=...), snnqp_events_bin_mix) with
+half the rows mixed with the next row and everything of --augment on for both, against the
+composition that gives the same uint8 frames without it: two augmenting launches (the rows, the
+partners), a box mask over [B, T, H, W] and a saturating add.  Checks first that both give the same
+bytes on the rows without a saturated count, and writes the JSON line to
+profiles/events_mix_time.json as well (--out names another file; the other modes write one only
+when --out is given).
+
   python tools/events_time.py [--batch 64] [--frames 20] [--hw 128] [--events 262144]
-                              [--steps 10] [--warmup 3] [--reps 3] [--hbm-gbs 8000] [--augment]
+                              [--steps 10] [--warmup 3] [--reps 3] [--hbm-gbs 8000] [--augment | --mix]
+                              [--out profiles/events_mix_time.json]
 """
 import argparse
 import json
@@ -52,7 +61,13 @@ def main(argv=None):
   ap.add_argument("--reps", type=int, default=3)
   ap.add_argument("--hbm-gbs", type=float, default=8000.0, help="HBM rate the traffic is set against")
   ap.add_argument("--augment", action="store_true", help="time the augmenting launch beside the plain one")
+  ap.add_argument("--mix", action="store_true", help="time the mixing launch beside two augmenting ones, a mask and an add")
+  ap.add_argument("--out", default=None, help="also write the JSON line to this file (--mix: "
+                  "profiles/events_mix_time.json unless given)")
   args = ap.parse_args(argv)
+  if args.mix and args.out is None:
+    args.out = os.path.join(ROOT, "profiles", "events_mix_time.json")
+  assert not (args.augment and args.mix), "--augment and --mix are two runs"
   assert torch.cuda.is_available(), "events_time.py needs the GPU"
   from snnquantprune_amd import _lib as L
   from snnquantprune_amd import ops
@@ -89,6 +104,8 @@ def main(argv=None):
   def launch_aug(fmt, mode, aug):
     return ops.events_bin(es, rows, T, HW, HW, mode=mode, start=starts, step_us=1000, fmt=fmt, augment=aug)
 
+  if args.mix:
+    return _mix(args, ops, es, rows, starts, draw_augment, rng)
   formats = (("u8", None), ("ev4", L.EV4), ("ev1", L.EV1))
   cands = {}
   if args.augment:
@@ -139,7 +156,69 @@ def main(argv=None):
             min(ms["aug_%s_%s" % (mode, name)]) / min(ms["bin_%s_%s" % (mode, name)]), 3)
     else:
       result.setdefault("speedup_over_loop", {})[name] = round(min(ms["loop_%s" % name]) / min(ms["bin_number_%s" % name]), 2)
-  print(json.dumps(result))
+  _emit(result, args.out)
+
+
+def _emit(result, path):
+  line = json.dumps(result)
+  print(line)
+  if path:
+    os.makedirs(os.path.dirname(os.path.abspath(path)), exist_ok=True)
+    with open(path, "w") as f:
+      f.write(line + "\n")
+
+
+def _mix(args, ops, es, rows, starts, draw_augment, rng):
+  """--mix: the mixing launch against two augmenting launches, a box mask and a saturating add."""
+  B, T, HW = args.batch, args.frames, args.hw
+  dev = es.device
+  aug, aug2 = draw_augment(), draw_augment()
+  partner = np.where(np.arange(B) % 2 == 0, (np.arange(B) + 1) % B, -1)           # half the rows
+  w, h = rng.integers(0, HW // 2 + 1, B), rng.integers(0, HW // 2 + 1, B)
+  x0, y0 = rng.integers(0, HW - w + 1), rng.integers(0, HW - h + 1)
+  n = rng.integers(0, T + 1, B)
+  g0 = rng.integers(0, T - n + 1)
+  box = np.stack([x0, y0, x0 + w, y0 + h, g0, g0 + n], 1)
+  starts2 = [-1] * B
+  rows2 = np.where(partner >= 0, partner, 0).tolist()
+  box_d = torch.from_numpy(box).to(dev)
+  mixed_d = torch.from_numpy(partner >= 0).to(dev)
+  ax, at = torch.arange(HW, device=dev), torch.arange(T, device=dev)
+
+  def launch_mix(mode):
+    m = ops.EventMix(B, partner=partner, start=starts2 if mode == "time" else None, box=box, augment=aug2)
+    return ops.events_bin(es, rows, T, HW, HW, mode=mode, start=starts, step_us=1000, augment=aug, mix=m)
+
+  def composed(mode):
+    a = ops.events_bin(es, rows, T, HW, HW, mode=mode, start=starts, step_us=1000, augment=aug)
+    b = ops.events_bin(es, rows2, T, HW, HW, mode=mode, start=starts2, step_us=1000, augment=aug2)
+    inx = (ax[None] >= box_d[:, 0, None]) & (ax[None] < box_d[:, 2, None])                     # [B, W]
+    iny = (ax[None] >= box_d[:, 1, None]) & (ax[None] < box_d[:, 3, None])                     # [B, H]
+    inf = (at[None] >= box_d[:, 4, None]) & (at[None] < box_d[:, 5, None]) & mixed_d[:, None]  # [B, T]
+    mask = (inf[:, :, None, None] & iny[:, None, :, None] & inx[:, None, None, :])[..., None]
+    total = a.masked_fill(mask, 0).to(torch.int16) + b.masked_fill(~mask, 0)
+    return total.clamp_(max=255).to(torch.uint8)
+
+  cands = {}
+  for mode in ("number", "time"):                       # the same bytes, before any timing
+    got, counts = launch_mix(mode)
+    want = composed(mode)
+    clear = got.reshape(B, -1).amax(1) < 255
+    assert bool(clear.any()) and torch.equal(got[clear], want[clear]), mode
+    assert bool((counts[mixed_d][:, 1] > 0).any()) and bool((counts[~mixed_d][:, 1] == 0).all())
+    cands["mix_%s_u8" % mode] = lambda mode=mode: launch_mix(mode)
+    cands["composed_%s_u8" % mode] = lambda mode=mode: composed(mode)
+  ms = {k: [] for k in cands}
+  for _ in range(args.reps):                            # alternating: every candidate once per round
+    for k, fn in cands.items():
+      ms[k].append(_time(fn, args.steps, args.warmup))
+  result = {"tool": "events_time --mix", "batch": B, "frames": T, "hw": HW, "events_per_sample": args.events,
+            "rows_mixed": int((partner >= 0).sum()), "steps": args.steps, "reps": args.reps,
+            "timing": "HIP events around whole calls (host share included)",
+            "ms": {k: [round(v, 4) for v in vs] for k, vs in ms.items()},
+            "mix_over_composed": {mode: round(min(ms["mix_%s_u8" % mode]) / min(ms["composed_%s_u8" % mode]), 3)
+                                  for mode in ("number", "time")}}
+  _emit(result, args.out)
 
 
 if __name__ == "__main__":
